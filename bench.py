@@ -17,9 +17,11 @@ collective -> "scaling": "weak".  torch.distributed (gloo) is used ONLY for the 
 `--gpus N` (N > 1) without a torch.distributed environment starts the N ranks itself (a `python -m torch.distributed.run`
 child process, before this process touches the GPU) and relays rank 0's line.
 
-The timed region (exactly --steps steps between barrier + sync on both sides) is repeated --regions times; `value` /
-`ms_per_step` are the MEDIAN region, `regions` carries min / median / max.  After the timed regions rank 0 of a 1-GPU run adds
-informational measurements of the other BASELINE configurations (`single_sequence`, `klt_only`, `pipeline_step`).
+The timed region (exactly --steps steps between barrier + sync on both sides) is repeated --regions times (default once; with
+--full five times); `value` / `ms_per_step` are the MEDIAN region, `regions` carries min / median / max.  A plain run does nothing
+else: the CPU baseline, the other BA budget policy, host-handed frames, stage times, rooflines and the second figures of the line run
+with --full only, and --extras (implies --full) adds informational measurements of the other BASELINE configurations
+(`single_sequence`, `klt_only`, `pipeline_step`).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 
 Prints ONE JSON line on rank 0.
 """
@@ -47,9 +49,16 @@ def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--regions", type=int, default=5, help="the K-step timed region is repeated this many times; the median is reported")
-    ap.add_argument("--extras", action="store_true", help="after the headline: the informational single-sequence / KLT-only / pipeline / drop-in measurements "
-                    "(minutes; they go to bench_extras.json, never into the printed line)")
+    ap.add_argument("--regions", type=int, default=None, help="the K-step timed region is repeated this many times; the median is reported "
+                    "(default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: the CPU baseline, five timed regions, the other BA budget "
+                    "policy, host-handed frames, stage times and rooflines, Shi-Tomasi-seeded points, the closed-loop figures (and the side file "
+                    "bench_extras.json).  A plain run sets up, warms up, times --steps steps once and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step handed its caller "
+                    "(points, status, errors, triangulations, BA poses / landmarks / statistics, corners) as DIR/<name>.npy, float32 or float64, "
+                    "at most 64 MB in all")
+    ap.add_argument("--extras", action="store_true", help="(implies --full) after the headline: the informational single-sequence / KLT-only / pipeline / drop-in "
+                    "measurements (minutes; they go to bench_extras.json, never into the printed line)")
     ap.add_argument("--no-extras", action="store_true", help="the headline only: also skip the two second figures of the default line (`host_frames`, "
                     "`closed_loop_w10_256`); what the profiling scripts under tools/ run")
     ap.add_argument("--full-line", action="store_true", help="print the full result object (tens of KB) as the last line instead of the compact one "
@@ -105,6 +114,11 @@ def parse():
     ap.add_argument("--cpu-procs", type=int, default=16, help="CPU-baseline worker processes (one core each), capped by the host's cores")
     ap.add_argument("--cpu-worker", type=int, default=-1, help=argparse.SUPPRESS)     # internal: run as CPU-baseline worker with this seed
     a = ap.parse_args()
+    a.full = a.full or a.extras
+    if a.dump_outputs and a.workload == "pipeline":
+        ap.error("--dump-outputs: workloads A and config5 (the fused frame step)")
+    if a.regions is None:
+        a.regions = 5 if a.full else 1
     if a.ba_iters is None:
         a.ba_iters = 10 if a.workload == "config5" else 30
     return a
@@ -997,7 +1011,7 @@ def measure_extras(device, frame_sets, a, dist, cpu_pipe=None):
     try:
         import subprocess
         cmd = [sys.executable, os.path.abspath(__file__), "--seqs", "96", "--ctxs", "3", "--side-stream", "on", "--host-threads", "3", "--steps", "60",
-               "--warmup", "10", "--regions", "3", "--no-extras", "--no-cpu-baseline", "--ba-iters", "10", "--frames", str(a.frames), "--full-line", "--extras-file", os.devnull]
+               "--warmup", "10", "--regions", "3", "--full", "--no-extras", "--no-cpu-baseline", "--ba-iters", "10", "--frames", str(a.frames), "--full-line", "--extras-file", os.devnull]
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK",
                                                                 "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}      # (a 1-rank torchrun launch)
         pr = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=600, env=env)
@@ -1012,7 +1026,7 @@ def measure_extras(device, frame_sets, a, dist, cpu_pipe=None):
     # run of `--workload config5` is compared with (child process: the workload rebinds the module's shape constants)
     try:
         import subprocess
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", "config5", "--steps", "60", "--warmup", "10", "--regions", "3", "--no-extras",
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", "config5", "--steps", "60", "--warmup", "10", "--regions", "3", "--full", "--no-extras",
                "--no-cpu-baseline", "--full-line", "--extras-file", os.devnull]
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK",
                                                                 "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
@@ -1076,7 +1090,7 @@ def measure_extras(device, frame_sets, a, dist, cpu_pipe=None):
     if a.ba_iters != 10:
         try:
             import subprocess
-            cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(a.steps), "--warmup", "10", "--regions", "3", "--no-extras", "--no-cpu-baseline",
+            cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(a.steps), "--warmup", "10", "--regions", "3", "--full", "--no-extras", "--no-cpu-baseline",
                    "--ba-iters", "10", "--frames", str(a.frames), "--seqs", str(a.seqs), "--full-line", "--extras-file", os.devnull]
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK",
                                                                     "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
@@ -1309,6 +1323,9 @@ def compact_line(full, extras_file=None):
 def emit(full, a):
     """full result object -> side file(s); the compact line (or, --full-line, the object itself) -> the LAST line of stdout"""
     full = _strict(full)
+    if not a.full and not a.extras_file:          # a plain run: the line, no side file
+        print(json.dumps(full, allow_nan=False) if a.full_line else compact_line(full), flush=True)
+        return
     targets = [a.extras_file] if a.extras_file else [os.path.join(ROOT, "bench_extras.json")] + \
         ([os.path.join(ROOT, "gpurun_out", "bench_extras.json")] if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else [])
     written = None
@@ -1347,6 +1364,81 @@ def self_launch(a):
     sys.exit(r.returncode if r.returncode else (0 if line is not None else 1))
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def timed_outputs(seqs):
+    """-> {name: array} of what the last fetched step handed its caller (VoContext.frame_fetch), one row per sequence over the contexts:
+    integers as float32 / float64, the BA statistics one array per field, the corners padded with NaN to the longest list (+ their counts)"""
+    rows = {}
+    for s in seqs:
+        r = s.last
+        one = s.B == 1
+        for k in ("points2d", "status", "err", "X4", "depth1", "reproj", "poses", "landmarks"):
+            # (a solve the budget cut was run again by Group.fetch: its result is under ba_poses / ba_points)
+            v = r.get({"poses": "ba_poses", "landmarks": "ba_points"}.get(k, k))
+            v = r.get(k) if v is None else v
+            if v is not None:
+                v = np.asarray(v)
+                rows.setdefault(k, []).append(v[None] if one else v)
+        if r.get("ba_stats") is not None:
+            st = [r["ba_stats"]] if one else r["ba_stats"]
+            for f in ("cost0", "cost", "lam", "iters", "accepted", "status", "n_obs"):
+                rows.setdefault("ba_" + f, []).append(np.array([x[f] for x in st], np.float64))
+        if r.get("corners") is not None:
+            rows.setdefault("corners", []).extend([r["corners"]] if one else r["corners"])
+    out = {}
+    for k, v in rows.items():
+        if k != "corners":
+            a = np.concatenate(v)
+            out[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    if "corners" in rows:
+        cs = rows["corners"]
+        m = max([len(c) for c in cs] + [1])
+        pad = np.full((len(cs), m, 2), np.nan, np.float32)
+        for b, c in enumerate(cs):
+            pad[b, :len(c)] = c
+        out["corners"], out["corners_count"] = pad, np.array([len(c) for c in cs], np.float32)
+    return out
+
+
+def dump_outputs(d, seqs):
+    """--dump-outputs: DIR/<name>.npy for every output of the last timed step, rows = sequences (`sequence.npy`: their indices).  Above
+    DUMP_MAX_BYTES a fixed, seeded sample of the sequences is written"""
+    out = timed_outputs(seqs)
+    n = len(out["points2d"])
+    total = sum(v.nbytes for v in out.values()) + 8 * n
+    keep = np.arange(n)
+    if total > DUMP_MAX_BYTES:
+        k = max(1, int(n * (DUMP_MAX_BYTES - 65536) // total))          # (room for the files' headers)
+        keep = np.sort(np.random.default_rng(12345).choice(n, k, replace=False))
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "sequence.npy"), keep.astype(np.float64))
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v[keep])
+
+
+def headline_result(a, dist, seqs, frame_sets, region_dt, dt, fps, frames_total, t_setup, c5, n_at_cap, n_trunc):
+    """the result object of a plain run (no --full): the headline and the configuration it was measured in, nothing measured besides"""
+    ba_stats = seqs[0].ba_stats0()
+    return {"metric": ("frames/sec @1920x1080, 5000 KLT pts, 20-frame sharded BA (config 5)" if c5 else
+                       "frames/sec @1241x376, 2000 KLT pts, 10-frame BA window"), "value": round(fps, 2),
+            "unit": "frames/s", "n_gpus": dist.world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(dt / a.steps * 1e3, 4), "higher_is_better": True, "scaling": "strong" if c5 else "weak",
+            "vs_baseline": None, "dtype": "u8/i32 (KLT, Shi-Tomasi) + f64 (DLT, BA)", "data": "synthetic",
+            "config": {"workload": WORKLOAD, "sequences_per_gpu": a.seqs, "batched_contexts_per_gpu": a.ctxs,
+                       "frames_per_step": 1 if c5 else a.seqs * dist.world, "distinct_image_sequences": len(frame_sets),
+                       "frames_source": "resident in HBM (vo_seq_upload)", "tracked_points": "jittered grid (SURVEY 8d's fallback)",
+                       "ba_lm_iteration_budget": a.ba_iters, "ba_lm_iterations_run": ba_stats["iters"],
+                       "stream_layout": seqs[0].c.step_layout(), "launch": "hipGraph replay" if a.graph else "plain",
+                       "ba_solves_stopped_by_lm_max_iters": n_at_cap, "ba_solves_cut_by_the_budget_and_rerun_in_the_timed_region": n_trunc,
+                       "parallelism": ("one sequence, BA landmarks sharded over %d GPU(s)" % dist.world) if c5 else
+                                      ("independent sequences, %d per GPU in %d batched context(s) x %d GPU(s), no collective" % (a.seqs, a.ctxs, dist.world))},
+            "regions": {"n": len(region_dt), "frames_per_s_min": round(frames_total / max(region_dt), 2),
+                        "frames_per_s_median": round(fps, 2), "frames_per_s_max": round(frames_total / min(region_dt), 2)},
+            "roofline": None, "cpu_baseline": None, "setup_s": round(t_setup, 2)}
+
+
 def main():
     global W_IMG, H_IMG, N_PTS, N_NEW, BA_N, BA_W, WORKLOAD, K_CAM
     a = parse()
@@ -1377,7 +1469,7 @@ def main():
         return
     dist = Dist()
     cpu = None
-    if dist.rank == 0 and dist.world == 1 and not a.no_cpu_baseline and a.workload == "A" and a.cpu_worker < 0:
+    if dist.rank == 0 and dist.world == 1 and a.full and not a.no_cpu_baseline and a.workload == "A" and a.cpu_worker < 0:
         # before anything initialises the GPU in this process (child processes are started here)
         n_procs = max(1, min(a.cpu_procs, usable_cores()))
         v, secs, cores, extra = cpu_baseline_parallel(n_procs, a.cpu_frames, a.ba_iters)
@@ -1493,9 +1585,10 @@ def main():
     for _ in range(a.warmup):
         step()
     drain()
-    # ---- timed regions: exactly K steps each, barrier + sync on both sides; KLT kernel bracketed by hipEvents on its stream ----
+    # ---- timed regions: exactly K steps each, barrier + sync on both sides; --full: KLT kernel bracketed by hipEvents on its stream (the roofline) ----
     for s in seqs:
-        s.c.profile_enable((s.c.PROF_KLT,))
+        if a.full:
+            s.c.profile_enable((s.c.PROF_KLT,))
         s.c.sync()
         s.truncated = s.at_cap = 0
         s.iter_hist, s.groups_enq, s.groups_needed, s.n_steps = {}, 0, 0, 0
@@ -1513,12 +1606,15 @@ def main():
         dist.barrier()
         region_dt.append(dist.max(time.perf_counter() - t0))
     dt = float(np.median(region_dt))               # an odd --regions makes this one actual region
+    if a.dump_outputs and dist.rank == 0:
+        dump_outputs(a.dump_outputs, seqs)
     klt_ms, klt_n = 0.0, 0
-    for s in seqs:
-        ms, n = s.c.profile_read(s.c.PROF_KLT)
-        klt_ms += ms
-        klt_n += n
-        s.c.profile_enable(())
+    if a.full:
+        for s in seqs:
+            ms, n = s.c.profile_read(s.c.PROF_KLT)
+            klt_ms += ms
+            klt_n += n
+            s.c.profile_enable(())
     n_trunc = int(dist.sum(float(sum(s.truncated for s in seqs))))
     n_at_cap = int(dist.sum(float(sum(s.at_cap for s in seqs))))
     iter_hist = {}
@@ -1529,7 +1625,7 @@ def main():
     groups_need = sum(s.groups_needed for s in seqs) / max(1, sum(s.n_steps for s in seqs))
     # the same K steps once more with the other budget policy (one region, informational): what the adaptive budget is worth
     other_fps = stationary_fps = None
-    if not c5:
+    if a.full and not c5:
         for s in seqs:
             s.adaptive = not s.adaptive
             s.ba_prm.max_iters = s.ba_iters_cap
@@ -1571,7 +1667,7 @@ def main():
     # ---- the same step with every frame handed over by the host (numpy arrays in page-locked memory -> vo_frame_step_host: upload on a copy stream
     # beside the previous frame's LM chain): 3 regions of exactly K steps, same barriers ----
     host_fig = None
-    if not c5 and not a.no_extras and not a.graph:
+    if a.full and not c5 and not a.no_extras and not a.graph:
         try:
             h2d_bytes = dist.sum(float(sum(s.use_host_frames(True) for s in seqs)))      # all ranks: every GPU has its own link to the host
             for _ in range(max(4, a.warmup)):
@@ -1605,7 +1701,9 @@ def main():
     fps = frames_total / dt
 
     out = None
-    if dist.rank == 0:
+    if dist.rank == 0 and not a.full:
+        out = headline_result(a, dist, seqs, frame_sets, region_dt, dt, fps, frames_total, t_setup, c5, n_at_cap, n_trunc)
+    if dist.rank == 0 and a.full:
         # ---- untimed extras on rank 0: stage breakdown, iteration counts, parity spot check inputs ----
         s0 = seqs[0]
         s0.c.profile_enable((0, 1, 2, 3, 4))
@@ -1702,7 +1800,7 @@ def main():
             out["host_frames"] = host_fig
     # ---- the tracked points seeded by the build's OWN Shi-Tomasi on frame 0 (SURVEY 8d's first choice; the headline tracks its fallback, a jittered
     # grid): 2 000 corners per distinct sequence at the reference's quality level and minimum distance, 3 regions of K steps ----
-    if out is not None and dist.world == 1 and a.workload == "A" and not a.no_extras and not c5:
+    if out is not None and dist.world == 1 and a.full and a.workload == "A" and not a.no_extras and not c5:
         try:
             out["shi_tomasi_seeded_points"] = seeded_points_figure(dist.local_rank, seqs, frame_sets, a, step, drain)
         except Exception as e:      # noqa: BLE001
@@ -1711,7 +1809,7 @@ def main():
     for s in seqs:
         s.c.close()
     try:
-        if out is not None and dist.world == 1 and a.workload == "A" and not a.no_extras:
+        if out is not None and dist.world == 1 and a.full and a.workload == "A" and not a.no_extras:
             # second figure of the line: the coupled loop (Pipeline.step resident on the device) at BASELINE's window and the headline's batch, as a
             # CHILD with a timeout -- whatever it does, the headline built above is printed
             # ... and, in the same child (same scenes), with tables the scene does not fill (8 192 slots per sequence; ~4 200 keypoints tracked): no

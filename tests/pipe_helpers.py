@@ -59,6 +59,48 @@ class ObjectLoop:
                          ba=self.adjuster.last_stats)
 
 
+def describe_arg(x):
+    """an argument as the call trace records it: numbers by value, arrays by dtype and shape, lists by length, other objects by type"""
+    import numbers
+    if isinstance(x, (bool, np.bool_)) or x is None or isinstance(x, str):
+        return repr(x)
+    if isinstance(x, numbers.Integral):
+        return str(int(x))
+    if isinstance(x, numbers.Real):
+        return repr(float(x))
+    if isinstance(x, np.ndarray):
+        return "array<%s>%s" % (x.dtype, list(x.shape))
+    if isinstance(x, (list, tuple)):
+        return "%s[%d]" % ("list" if isinstance(x, list) else "tuple", len(x))
+    return type(x).__name__
+
+
+class CallRecorder:
+    """stands in for the Extractor / BundleAdjuster a caller holds and logs what the caller does with it: every method call (arguments bound
+    to the method's parameter names, so a positional and a keyword argument read alike) and every attribute write, as one line each"""
+
+    def __init__(self, target, tag, log):
+        object.__setattr__(self, "_rec", (target, tag, log))
+
+    def __getattr__(self, name):
+        import inspect
+        target, tag, log = self._rec
+        v = getattr(target, name)
+        if not callable(v) or name.startswith("__"):
+            return v
+
+        def call(*a, **k):
+            b = inspect.signature(v).bind(*a, **k)
+            log.append("%s.%s(%s)" % (tag, name, ", ".join("%s=%s" % (p, describe_arg(x)) for p, x in b.arguments.items())))
+            return v(*a, **k)
+        return call
+
+    def __setattr__(self, name, value):
+        target, tag, log = self._rec
+        log.append("%s.%s = %s" % (tag, name, describe_arg(value)))
+        setattr(target, name, value)
+
+
 # ---------------------------------------------------------------------------------------------------------
 # comparison: object lists vs table state
 # ---------------------------------------------------------------------------------------------------------

@@ -142,15 +142,25 @@ def test_lazy_helpers():
 
 @pytest.mark.parametrize("name,n_steps", [("w4", 12), ("groups", 5)])
 def test_the_references_unmodified_pipeline_step_over_the_lazy_classes(name, n_steps):
-    """build container only: /root/reference/src/pipeline/pipeline.py, imported as it lies, calls the lazy drop-in classes (ref_caller_check.py)"""
+    """the reference's OWN `Pipeline.step` (pipeline.py:92-167, imported as it lies) over the lazy drop-in classes, as the call trace it left
+    (tests/golden/pipe_calls_<name>.json, written by tests/ref_caller_check.py --write): the restated loop makes the same calls on the
+    Extractor / BundleAdjuster, frame by frame and argument by argument, and its lists equal the G5 golden after every frame"""
+    import json
     import os
-    import subprocess
-    import sys
-    if not os.path.isdir("/root/reference/src/pipeline"):
-        pytest.skip("the reference is not on this machine")
-    here = os.path.dirname(os.path.abspath(__file__))
-    r = subprocess.run([sys.executable, os.path.join(here, "ref_caller_check.py"), name, str(n_steps)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and r.stdout.startswith("OK"), r.stdout + r.stderr
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pipe_calls_%s.json" % name)) as f:
+        ref = json.load(f)
+    assert ref["n_steps"] == n_steps and len(ref["calls_per_step"]) == n_steps
+    g = pg.load(name)
+    loop, sc, fos, t0 = _loop(g)
+    trace = []
+    loop.extractor, loop.adjuster = ph.CallRecorder(loop.extractor, "extractor", trace), ph.CallRecorder(loop.adjuster, "adjuster", trace)
+    for s in range(1, n_steps + 1):
+        loop.step(sc["frames"][fos[t0 + s]])
+        assert trace == ref["calls_per_step"][s - 1], "step %d" % s
+        del trace[:]
+        pg.assert_entries(pg.frame(g, s), pg.loop_entries(loop), "reference caller, lazy classes, %s step %d" % (name, s))
+        sess = loop.extractor._lazy
+        assert sess is not None and sess.alive and sess.stats["fast"] == (1 if s == 1 else 1 + 6 * (s - 1)), (s, sess and sess.stats)
 
 
 def test_history_archive_is_indexed_and_bounded_in_bytes():

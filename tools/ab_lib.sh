@@ -8,7 +8,7 @@ for r in $(seq $N); do
   order="a b"; [ $((r % 2)) = 0 ] && order="b a"          # a b b a a b ...: a box warms up over the first runs
   for which in $order; do
     if [ $which = b ]; then export VO_MI355X_LIB=$B; else unset VO_MI355X_LIB; fi
-    out=$(timeout 300 python3 bench.py $ARGS --full-line --extras-file /dev/null 2>/dev/null | tail -1)
+    out=$(timeout 300 python3 bench.py --full $ARGS --full-line --extras-file /dev/null 2>/dev/null | tail -1)
     python3 - "$out" $which <<'P'
 import json, sys
 try:

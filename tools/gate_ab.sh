@@ -2,7 +2,7 @@
 # A/B: the next frame's tracker launch gated behind the first K LM groups of the previous frame's chain (vo_tuning.gate_groups), stream A leaving R
 # compute units free (vo_tuning.reserve_cus).  usage: tools/gate_ab.sh
 run() {
-  out=$(timeout 150 python bench.py --no-extras --no-cpu-baseline --full-line --steps 60 $EXTRA ${1:+--tune $1} 2>/dev/null | tail -1)
+  out=$(timeout 150 python bench.py --full --no-extras --no-cpu-baseline --full-line --steps 60 $EXTRA ${1:+--tune $1} 2>/dev/null | tail -1)
   python - "$out" "$* $EXTRA" <<'P'
 import json, sys
 try:

@@ -1,5 +1,5 @@
 run() {
-  out=$(timeout 200 python3 bench.py --no-extras --no-cpu-baseline --full-line --extras-file /dev/null --steps 60 --regions 5 ${1:+--tune $1} 2>/dev/null | tail -1)
+  out=$(timeout 200 python3 bench.py --full --no-extras --no-cpu-baseline --full-line --extras-file /dev/null --steps 60 --regions 5 ${1:+--tune $1} 2>/dev/null | tail -1)
   python3 - "$out" "$1" <<'P'
 import json, sys
 try:

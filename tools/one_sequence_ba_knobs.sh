@@ -1,7 +1,7 @@
 #!/bin/bash
 # Small batches: the wave-private BA kernels (vo_tuning.ba_kernels = 2) against the lane-per-observation ones (ba_kernels = 1)
 run() {
-  out=$(timeout 150 python bench.py --no-extras --no-cpu-baseline --full-line $EXTRA --tune $1 2>/dev/null | tail -1)
+  out=$(timeout 150 python bench.py --full --no-extras --no-cpu-baseline --full-line $EXTRA --tune $1 2>/dev/null | tail -1)
   python - "$out" "$* $EXTRA" <<'P'
 import json, sys
 d = json.loads(sys.argv[1]); print("%-70s %9.1f frames/s  %.4f ms/step" % (sys.argv[2], d["value"], d["ms_per_step"]))

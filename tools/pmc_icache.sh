@@ -5,7 +5,7 @@ BENCH="$PWD/bench.py"
 ARGS="--steps 4 --warmup 2 --regions 1 --no-extras --no-cpu-baseline --seqs 32 --ctxs 1 --host-threads 1 --side-stream off"
 cd /tmp
 rm -rf $OUT/ic_pmc
-timeout 200 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH GRBM_GUI_ACTIVE --output-format csv -d $OUT/ic_pmc -o p -- python3 $BENCH $ARGS > $OUT/ic_pmc.log 2>&1
+timeout 200 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH GRBM_GUI_ACTIVE --output-format csv -d $OUT/ic_pmc -o p -- python3 $BENCH --full $ARGS > $OUT/ic_pmc.log 2>&1
 cd - > /dev/null
 python3 - <<PY
 import csv, glob

@@ -14,7 +14,7 @@ for CTRS in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_
             "SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS SQ_INSTS_SMEM SQ_INSTS_BRANCH"; do
   i=$((i+1))
   rm -rf $OUT/${TAG}_pmcq$i
-  timeout 200 rocprofv3 --pmc $CTRS --output-format csv -d $OUT/${TAG}_pmcq$i -o p -- python3 $BENCH $ARGS > $OUT/${TAG}_pmcq$i.log 2>&1
+  timeout 200 rocprofv3 --pmc $CTRS --output-format csv -d $OUT/${TAG}_pmcq$i -o p -- python3 $BENCH --full $ARGS > $OUT/${TAG}_pmcq$i.log 2>&1
 done
 cd - > /dev/null
 python3 - <<PY > $OUT/${TAG}_pmc_kernels.txt

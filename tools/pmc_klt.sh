@@ -16,7 +16,7 @@ for CTRS in "TA_TA_BUSY TA_FLAT_READ_WAVEFRONTS GRBM_GUI_ACTIVE" \
             "SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_VMEM_RD SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY"; do
   i=$((i+1))
   rm -rf $OUT/${TAG}_pmck$i
-  timeout 200 rocprofv3 --pmc $CTRS --output-format csv -d $OUT/${TAG}_pmck$i -o p -- python3 $BENCH $ARGS > $OUT/${TAG}_pmck$i.log 2>&1
+  timeout 200 rocprofv3 --pmc $CTRS --output-format csv -d $OUT/${TAG}_pmck$i -o p -- python3 $BENCH --full $ARGS > $OUT/${TAG}_pmck$i.log 2>&1
 done
 cd - > /dev/null
 python3 - <<PY > $OUT/${TAG}_pmc_klt.txt
