@@ -200,6 +200,27 @@ int32_t vo_points_upload(vo_ctx* ctx, const float* p, int32_t n);
 int32_t vo_points_download(vo_ctx* ctx, float* p, uint8_t* status, float* err, int32_t* iters, int32_t n);
 int32_t vo_klt_track_resident(vo_ctx* ctx, int32_t n, const vo_klt_params* prm);  /* async */
 
+/* ---- forward-backward check ------------------------------------------------------------------
+ * What max_bidir_error of extend_tracks / extend_landmarks (extractor.py:44-47,65-68) means once the image order of the second call is
+ * fixed as in the OpenCV sample it copies (notebooks/tracking.py:39-42; the reference tracks forward twice):
+ *   p1, st, err = LK(prev, cur, p0)    unchanged, bit for bit vo_klt_track
+ *   p0r         = LK(cur, prev, p1)    template from the CURRENT frame (image + Scharr), target the previous frame
+ *   fb_err      = max(|p0 - p0r|) over x, y (f32)        ok = fb_err < max_err (max_err rounded to f32 once; NaN fails)
+ * One launch (k_klt_track_fb, one wave per keypoint) runs both passes.
+ *   vo_klt_track_fb   the synchronous form: vo_klt_track's arguments and layout ([batch][n]) plus p0r [batch][n][2], fb_err [batch][n] f32
+ *   vo_set_fb_check   per context; +inf (the default) = off, NaN -> VO_E_INVALID.  Takes effect at the next enqueue.  A finite threshold
+ *                     makes vo_tracks_track and the TRACK stage of vo_pipe_step / vo_pipe_step_host track with the check and AND `ok`
+ *                     into their keep rule: a point that fails it dies exactly like one outside the image (extractor.py:49-53,74-78).
+ *                     Off, they run the plain tracker as before.  vo_klt_track_resident and the fused vo_frame_step_* never check.
+ *   vo_fb_read        synchronous, no step in flight (else VO_E_STATE): ok [batch][n] u8 and fb_err [batch][n] f32 (either may be NULL)
+ *                     of the dense point set of the last track, if it ran with the check (else VO_E_STATE) -- list order of the track
+ *                     table, [landmarks | candidates] in the closed loop; dead slots read ok = 0, fb_err = NaN. */
+int32_t vo_klt_track_fb(vo_ctx* ctx, const float* p0, int32_t n, const vo_klt_params* prm, float* p1, uint8_t* status, float* err,
+                        float* p0r, float* fb_err, int32_t* iters);
+int32_t vo_set_fb_check(vo_ctx* ctx, float max_err);
+int32_t vo_get_fb_check(vo_ctx* ctx, float* max_err);
+int32_t vo_fb_read(vo_ctx* ctx, uint8_t* ok, float* fb_err, int32_t n);
+
 /* ---- Shi-Tomasi re-detection ----------------------------------------------------------------
  * Replaces the exclusion-mask loop + cv2.goodFeaturesToTrack(img, mask=mask, **shitomasi_params)
  * at extractor.py:103-112 on the CURRENT frame.  cur_pts (n_cur x 2 f32, may be NULL) are the
@@ -359,7 +380,8 @@ int32_t vo_match_knn2(vo_ctx* ctx, const float* desc1, int32_t n1, const float* 
  * uv_first, t_first, t_total, a stable tag, and a ring of the last 32 positions by absolute frame index.
  *   vo_tracks_seed    initial tracks born at frame t (t_total = 1, history = [uv]);  pts [batch][n][2]
  *   vo_tracks_track   KLT prev -> cur of every live track, then the reference's rule: keep iff 0 <= x <= W and
- *                     0 <= y <= H (ends included; KLT status ignored, bidirectional test off: pipeline.py:98-100);
+ *                     0 <= y <= H (ends included; KLT status ignored, bidirectional test off: pipeline.py:98-100) -- and, with a
+ *                     finite vo_set_fb_check threshold, the forward-backward check passed (the true bidirectional test);
  *                     survivors: uv, t_total + 1, history append; the others go to the dead list        (async)
  *   vo_tracks_detect  exclusion discs at the live tracks + Shi-Tomasi on the current frame, up to max_new corners per
  *                     sequence appended as tracks born at t (extractor.py:103-132)                      (async)
@@ -383,7 +405,8 @@ int32_t vo_ba_obs_from_tracks(vo_ctx* ctx, int32_t t_now);
  * trajectory) (src/state/state.py:4-10) and Pipeline._landmarks_dead / _landmarks_kp_dead (src/pipeline/pipeline.py:31) -- as
  * device tables, and Pipeline.step (pipeline.py:92-167) as ONE enqueue per frame with every data dependence on the device:
  *   TRACK        pyramid + KLT of all landmark and candidate keypoints, the keep rule and bookkeeping of
- *                Extractor.extend_tracks / extend_landmarks (extractor.py:38-88), what dies goes to the dead lists (pipeline.py:98-103)
+ *                Extractor.extend_tracks / extend_landmarks (extractor.py:38-88), what dies goes to the dead lists (pipeline.py:98-103);
+ *                with a finite vo_set_fb_check threshold the tracking runs the forward-backward check and a point that fails it dies too
  *   POSE         RANSAC-P3P pose from the landmarks' 3-D points and tracked pixels (extractor.py:174-191), non-inliers to the dead
  *                lists (pipeline.py:124-137), pose appended to the trajectory (:140)
  *   TRIANGULATE  Extractor.triangulate_tracks (extractor.py:193-277): candidates with t_total >= min_track_length leave the

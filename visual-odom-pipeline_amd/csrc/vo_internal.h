@@ -98,6 +98,13 @@ struct vo_ctx {
   int32_t* d_iters = nullptr;        // [batch][n x (max_level + 1)]
   int n_resident = 0;
   int iters_stride = 0;              // of the last KLT launch
+  // forward-backward check (vo_klt_fb.hip): threshold of vo_set_fb_check (+inf = off), and the check's rows -- p0r [max_pts][2] f32,
+  // fb_err [max_pts] f32, ok [max_pts] u8 per sequence, fb_seq bytes apart -- in an allocation of their own, made when the check is first
+  // asked for (the result slab goes to the host whole with every fused frame step: it does not grow for a check that step never runs)
+  float fb_max_err = __builtin_inff();
+  uint8_t* d_fb = nullptr;
+  size_t fb_seq = 0, fb_off_err = 0, fb_off_ok = 0;
+  int fb_n = -1;                     // points of the last track if it ran the check, else -1
   // DLT inputs
   float* d_uv0 = nullptr; float* d_uv1 = nullptr;    // [batch][max_pts][2]
   vo_dlt_cam* d_dlt_cam = nullptr;   // [batch]
@@ -224,6 +231,11 @@ int32_t vo_st_prepare(vo_ctx* c, const vo_st_params* prm);
 // the resident entry points with the per-sequence counters named by the caller (device arrays [batch], null = uniform): d_counts = live
 // points of each sequence (KLT input / exclusion discs), d_limit = cap on the corners each sequence's re-detection needs
 int32_t vo_klt_track_resident_counts(vo_ctx* c, int32_t n, const vo_klt_params* prm, const int32_t* d_counts);
+// the same tracking with the forward-backward check (k_klt_track_fb): the ok flags land in vo_fb_ok(c) [batch][fb_seq bytes]
+int32_t vo_klt_track_resident_fb(vo_ctx* c, int32_t n, const vo_klt_params* prm, const int32_t* d_counts);
+inline bool vo_fb_on(const vo_ctx* c) { return !(c->fb_max_err == __builtin_inff()); }     // +inf = off
+inline const uint8_t* vo_fb_ok(const vo_ctx* c) { return c->d_fb + c->fb_off_ok; }
+void vo_fb_destroy(vo_ctx* c);
 int32_t vo_shi_tomasi_resident_counts(vo_ctx* c, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm, const int32_t* d_counts,
                                       const int32_t* d_limit);
 

@@ -19,205 +19,10 @@
 //   DPP neighbour exchange -- the texture addresser issued 28 cache accesses per load instruction and was busy 91 % of the
 //   kernel: the kernel was bound by it, not by the vector ALUs; profiles/r02_pmc_klt_*.txt.)
 //   The template (I, Ix, Iy at 16 pixels per lane) lives in 24 VGPRs across all iterations.
-#include "vo_internal.h"
+#include "vo_klt_lk.h"
 
 #include <stdlib.h>
 #include <string.h>
-
-#define W_BITS 14
-
-struct klt_level_args {
-  const uint8_t* imgI;    // sequence 0; sequence b at + b * seq_px pixels
-  const uint32_t* derI;   // (4 Ix | 4 Iy << 16) per pixel
-  const uint8_t* imgJ;
-  size_t seq_px;
-  int w, h, pitch;
-};
-
-struct klt_args {
-  klt_level_args lv[VO_MAX_LEVELS];
-  size_t slab_seq;        // byte stride between the sequences' point / status / err arrays
-  size_t iters_seq;       // int32 stride between the sequences' iteration tables
-  int top, win, max_count, n, iters_stride;
-  int xcd_remap;             // batch % 8 == 0: keep every sequence on ONE XCD (see k_klt_track)
-  float min_eig_num;         // minEig < threshold  <=>  numerator < min_eig_num  (klt_min_eig_numerator: no division per level)
-  float eps_lo, eps_hi;      // |delta|^2 in float below / above these decides the convergence test; in between: float64
-  double eps2;
-};
-
-// Window loads go through buffer instructions: address = descriptor base (the level's image: scalar registers) + ONE per-lane
-// offset that is fixed for the level (vector register) + the wave-uniform window origin advanced per row (scalar register).
-// With global_load the compiler kept the row advance in vector registers: one v_add per image load and a 64-bit
-// v_lshl_add_u64 more per derivative load -- 8 / 24 vector instructions per LK iteration / template in a kernel that is bound
-// by vector-instruction issue (tools/vmem_probe.hip).  Unaligned dwords are fine (same rules as global_load).
-typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t klt_rsrc(const void* base) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, -1, 0x00020000);   // raw, 4 GB range, no swizzle
-}
-
-// every lane receives the value of the lane 16 further up (the same column pair of the next row group; lanes 48..63 wrap
-// around to rows that only masked pixels use): ds_bpermute_b32, the LDS crossbar -- no vector-ALU or memory-pipe slot
-__device__ __forceinline__ uint32_t row_next(uint32_t v, int lane) {
-  return (uint32_t)__builtin_amdgcn_ds_bpermute(((lane + 16) & 63) << 2, (int)v);
-}
-
-// exact wave-wide sum of an int32 per lane whose total fits in int32; result uniform
-__device__ __forceinline__ int wave_sum_i32(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112 /* row_shr:2 */, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114 /* row_shr:4 */, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118 /* row_shr:8 */, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142 /* row_bcast:15 */, 0xa, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143 /* row_bcast:31 */, 0xc, 0xf, false);
-  return __builtin_amdgcn_readlane(v, 63);
-}
-
-// exact wave-wide sum of arbitrary int32 per lane (the total needs up to 36 bits), returned as the float nearest
-// to the exact integer: the two 16-bit-split partial sums are combined in float64 (exact, < 2^53) and rounded ONCE,
-// which is bit-identical to converting the 64-bit integer sum to float (what the CPU oracle does) and far cheaper
-// than the software int64 -> float conversion.
-__device__ __forceinline__ float wave_sum_exact_f32(int v) {
-  const int lo = wave_sum_i32(v & 0xFFFF);
-  const int hi = wave_sum_i32(v >> 16);
-  return (float)((double)hi * 65536.0 + (double)lo);
-}
-
-// Four (two) wave-wide int32 sums at once as a reduce-scatter: after two quad exchanges lane l holds the quad sum of value
-// number l & 3, the remaining steps (row rotations, row swaps) are multiples of 4 lanes and keep that assignment -- 15 + 4
-// instructions instead of 4 x 7.  Totals must fit int32 (callers pass 16-bit halves).
-template <int CTRL>
-__device__ __forceinline__ int klt_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-
-__device__ __forceinline__ int klt_rows_sum(int z) {            // sum over the 16 quads, class (lane & 3) preserved
-  z += klt_dpp<0x124>(z);                                       // row_ror:4
-  z += klt_dpp<0x128>(z);                                       // row_ror:8
-  {
-    const auto r = __builtin_amdgcn_permlane16_swap((unsigned)z, (unsigned)z, false, false);
-    z = (int)r[0] + (int)r[1];
-  }
-  {
-    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)z, (unsigned)z, false, false);
-    z = (int)r[0] + (int)r[1];
-  }
-  return z;
-}
-
-__device__ __forceinline__ void wave_sum4_i32(int a, int b, int c, int d, int lane, int& sa, int& sb, int& sc, int& sd) {
-  const bool odd = lane & 1, up = lane & 2;
-  const int x = (odd ? b : a) + klt_dpp<0xB1>(odd ? a : b);     // quad_perm [1,0,3,2]: even lanes sum a, odd lanes sum b (pairs)
-  const int y = (odd ? d : c) + klt_dpp<0xB1>(odd ? c : d);     //                      even lanes sum c, odd lanes sum d
-  int z = (up ? y : x) + klt_dpp<0x4E>(up ? x : y);             // quad_perm [2,3,0,1]: lane & 3 = 0, 1, 2, 3 <-> a, b, c, d (quads)
-  z = klt_rows_sum(z);
-  sa = __builtin_amdgcn_readlane(z, 0); sb = __builtin_amdgcn_readlane(z, 1);
-  sc = __builtin_amdgcn_readlane(z, 2); sd = __builtin_amdgcn_readlane(z, 3);
-}
-
-__device__ __forceinline__ void wave_sum2_i32(int a, int b, int lane, int& sa, int& sb) {
-  const bool odd = lane & 1;
-  int z = (odd ? b : a) + klt_dpp<0xB1>(odd ? a : b);           // even lanes sum a, odd lanes sum b (pairs)
-  z += klt_dpp<0x4E>(z);                                        // quads
-  z = klt_rows_sum(z);
-  sa = __builtin_amdgcn_readlane(z, 0); sb = __builtin_amdgcn_readlane(z, 1);
-}
-
-// Two / three wave-wide sums whose QUAD partial sums still fit int32 (callers guarantee |per-lane value| < 2^29): the first
-// two butterfly stages run on the full 32-bit values as a reduce-scatter (lane & 1 selects the value), and only the 16 quad
-// sums are split into 16-bit halves -- the spare lane class of every quad carries the high halves, so ONE row reduction
-// delivers low and high totals of both values (15 vector instructions instead of 21 for the four pre-split halves).
-__device__ __forceinline__ void wave_sum2_wide(int a, int b, int lane, int& la, int& ha, int& lb, int& hb) {
-  const bool odd = lane & 1, up = lane & 2;
-  int z = (odd ? b : a) + klt_dpp<0xB1>(odd ? a : b);           // pairs: even lanes a, odd lanes b
-  z += klt_dpp<0x4E>(z);                                        // quads: lanes 0, 2 hold a's quad sum, lanes 1, 3 b's
-  int w = up ? (z >> 16) : (z & 0xFFFF);                        // lane & 3 = 0: lo a, 1: lo b, 2: hi a, 3: hi b
-  w = klt_rows_sum(w);
-  la = __builtin_amdgcn_readlane(w, 0); lb = __builtin_amdgcn_readlane(w, 1);
-  ha = __builtin_amdgcn_readlane(w, 2); hb = __builtin_amdgcn_readlane(w, 3);
-}
-
-__device__ __forceinline__ void wave_sum3_wide(int a, int b, int c, int lane, int& la, int& ha, int& lb, int& hb, int& lc, int& hc) {
-  const bool odd = lane & 1, up = lane & 2;
-  const int x = (odd ? b : a) + klt_dpp<0xB1>(odd ? a : b);     // pairs: even lanes a, odd lanes b
-  const int y = c + klt_dpp<0xB1>(c);                           // pairs of c in every lane
-  const int z = (up ? y : x) + klt_dpp<0x4E>(up ? x : y);       // quads: lane & 3 = 0: a, 1: b, 2 and 3: c
-  const int w0 = klt_rows_sum(((lane & 3) == 3) ? (z >> 16) : (z & 0xFFFF));   // lo a, lo b, lo c, hi c
-  const int w1 = klt_rows_sum(z >> 16);                                        // hi a, hi b
-  la = __builtin_amdgcn_readlane(w0, 0); lb = __builtin_amdgcn_readlane(w0, 1);
-  lc = __builtin_amdgcn_readlane(w0, 2); hc = __builtin_amdgcn_readlane(w0, 3);
-  ha = __builtin_amdgcn_readlane(w1, 0); hb = __builtin_amdgcn_readlane(w1, 1);
-}
-
-// float nearest to the exact integer hi * 2^16 + lo (lo < 2^20).  It fits int32 whenever |hi| < 2^14 -- always, except for
-// gross mismatches -- and then ONE v_cvt_f32_i32 rounds it exactly like the float64 route (5 quarter-rate instructions).
-__device__ __forceinline__ float klt_combine(int hi, int lo) {
-  if ((unsigned)(hi + 16384) < 32768u) return (float)(hi * 65536 + lo);
-  return (float)((double)hi * 65536.0 + (double)lo);
-}
-
-// cvRound(x) for 0 <= x <= 2^14: adding 1.5 * 2^23 leaves round-to-nearest-even(x) in the low mantissa bits (one float add and one
-// integer subtract at full rate instead of v_rndne_f32 + v_cvt_i32_f32 at quarter rate)
-__device__ __forceinline__ int klt_round(float x) { return __float_as_int(x + 12582912.f) - 0x4B400000; }
-
-// the four bilinear weights as packed 16-bit pairs wt = iw00 | iw01 << 16, wb = iw10 | iw11 << 16.  The rounded values sit in
-// the low 16 bits of the magic-number sums (weights <= 2^14), so the byte gathers take them from there directly
-__device__ __forceinline__ void lk_weights(float a, float b, uint32_t& wt, uint32_t& wb) {
-  const uint32_t r00 = (uint32_t)__float_as_int((1.f - a) * (1.f - b) * (float)(1 << W_BITS) + 12582912.f);
-  const uint32_t r01 = (uint32_t)__float_as_int(a * (1.f - b) * (float)(1 << W_BITS) + 12582912.f);
-  const uint32_t r10 = (uint32_t)__float_as_int((1.f - a) * b * (float)(1 << W_BITS) + 12582912.f);
-  const uint32_t iw11 = (uint32_t)(1 << W_BITS) + 3u * 0x4B400000u - (r00 + r01 + r10);
-  wt = __builtin_amdgcn_perm(r01, r00, 0x05040100u);
-  wb = __builtin_amdgcn_perm(iw11, r10, 0x05040100u);
-}
-
-__device__ __forceinline__ float uniform_f(float v) {
-  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
-}
-
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-
-// D = a.lo * b.lo + a.hi * b.hi + c  (signed 16-bit halves) -> v_dot2c_i32_i16
-__device__ __forceinline__ int dot2(uint32_t a, uint32_t b, int c) {
-  return __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b), c, false);
-}
-// The same product with the accumulator taken from a THIRD operand (VOP3P v_dot2_i32_i16): hipcc selects the two-address
-// v_dot2c form for the plain builtin and then needs a v_mov to preload every rounding constant / zero (16 per LK iteration);
-// the clamp bit exists only in the three-address encoding, so asking for it selects that form.  No sum here comes near
-// the int32 range (|taps| <= 255 * 2^14), so the saturation never acts and the value is the plain dot product.
-__device__ __forceinline__ int dot2k(uint32_t a, uint32_t b, int c) {
-  return __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b), c, true);
-}
-// (lo16(a) | lo16(b) << 16) -> one v_perm_b32
-__device__ __forceinline__ uint32_t pack_lo(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }
-__device__ __forceinline__ uint32_t pack_hi(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
-// bytes (k, k+1) of a dword widened to two 16-bit halves
-__device__ __forceinline__ uint32_t bytes01(uint32_t t) { return __builtin_amdgcn_perm(0u, t, 0x0c010c00u); }
-__device__ __forceinline__ uint32_t bytes12(uint32_t t) { return __builtin_amdgcn_perm(0u, t, 0x0c020c01u); }
-__device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) {
-  return __builtin_bit_cast(uint32_t, __builtin_bit_cast(s16x2, a) - __builtin_bit_cast(s16x2, b));
-}
-__device__ __forceinline__ uint32_t pk_abs(uint32_t a) {
-  const s16x2 v = __builtin_bit_cast(s16x2, a);
-  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(v, -v));
-}
-
-// bilinear samples (5 fractional bits) of the two pixels a lane owns in one step, packed (v0 | v1 << 16).
-// T/B: top / bottom row dwords (3 useful bytes each); wt = iw00 | iw01 << 16, wb = iw10 | iw11 << 16.
-__device__ __forceinline__ uint32_t sample2(uint32_t T, uint32_t B, uint32_t wt, uint32_t wb) {
-  const int s0 = dot2(bytes01(B), wb, dot2k(bytes01(T), wt, 1 << (W_BITS - 5 - 1)));
-  const int s1 = dot2(bytes12(B), wb, dot2k(bytes12(T), wt, 1 << (W_BITS - 5 - 1)));
-  // (s >> 9) of both sums packed: bytes 1..2 of each sum are s >> 8 (0 <= s < 2^24), one packed 16-bit shift finishes --
-  // two instructions instead of two shifts and a pack
-  typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-  const u16x2 h = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm((uint32_t)s1, (uint32_t)s0, 0x06050201u));
-  return __builtin_bit_cast(uint32_t, h >> (unsigned short)(W_BITS - 5 - 8));
-}
-
-// interpolated derivative of one pixel, times 2^16: top pair / bottom pair already gathered as (left | right << 16).  The
-// derivative image holds 4 x Scharr (vo_frame.hip), so the sum is 4 (s + 2^13) and the value OpenCV keeps, (s + 2^13) >> 14, is its
-// UPPER HALF: the byte gather that packs two pixels reads it from there (and zeroes masked pixels): one instruction per pixel pair
-// instead of two shifts, a pack and a mask
-__device__ __forceinline__ uint32_t deriv1(uint32_t top, uint32_t bot, uint32_t wt, uint32_t wb) {
-  return (uint32_t)dot2(bot, wb, dot2k(top, wt, 1 << (W_BITS + 1)));
-}
 
 // WAVES = minimum waves per SIMD the register allocation must allow (6: 79 VGPRs, no scratch -- the default; 5: 81; 4 and 5 measured 3 % and 2 % slower)
 template <int WAVES>
@@ -709,13 +514,13 @@ static float klt_min_eig_numerator(float thr, float c) {
   return from_ord(hi);
 }
 
-static int32_t klt_launch(vo_ctx* c, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* counts) {
+// the argument checks and the argument block of a tracker launch (also k_klt_track_fb's forward pass, vo_klt_fb.hip); nothing to fill for n = 0
+int32_t vo_klt_make_args(vo_ctx* c, int n, const vo_klt_params* prm, klt_args& A) {
   VO_CHECK(c, c->n_pushed >= 2, VO_E_STATE, "need two pushed frames");
   VO_CHECK(c, n >= 0 && n <= c->max_pts, VO_E_CAPACITY, "n exceeds max_pts");
   VO_CHECK(c, prm && prm->win >= 3 && prm->win <= VO_MAX_WIN && (prm->win & 1), VO_E_INVALID, "win must be odd, 3..31");
   VO_CHECK(c, prm->max_level >= 0 && prm->max_level < VO_MAX_LEVELS, VO_E_INVALID, "bad max_level");
   if (n == 0) return VO_OK;
-  klt_args A;
   const vo_frame& P = c->fr[c->cur ^ 1];
   const vo_frame& C = c->fr[c->cur];
   // effective top level: levels available in the frame store, truncated by this call's window rule
@@ -739,6 +544,13 @@ static int32_t klt_launch(vo_ctx* c, int n, const vo_klt_params* prm, size_t off
   A.iters_stride = prm->max_level + 1;
   A.slab_seq = c->slab_seq; A.iters_seq = (size_t)c->max_pts * VO_MAX_LEVELS;
   c->iters_stride = A.iters_stride;
+  return VO_OK;
+}
+
+static int32_t klt_launch(vo_ctx* c, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* counts) {
+  c->fb_n = -1;                         // the last track ran without the forward-backward check (vo_fb_read)
+  klt_args A;
+  { const int32_t r = vo_klt_make_args(c, n, prm, A); if (r != VO_OK || n == 0) return r; }
   {
     vo_prof_scope prof(c, VO_PROF_KLT);   // brackets exactly this launch (bench.py roofline figure)
     const int waves = c->tune.klt_waves > 0 ? c->tune.klt_waves : 6;

@@ -69,6 +69,7 @@ struct vo_pipe_ws {
   hipEvent_t ev[VO_PIPE_INFLIGHT] = {};
   hipEvent_t ev_track = nullptr;                 // the side stream's pyramid + KLT of a step are done
   long enq = 0, fetched = 0;
+  bool fb_active = false;                        // the last TRACK ran the forward-backward check (vo_set_fb_check): both halves of the keep rule use its flags
   bool lm_half_pending = false;                  // a TRACK | TRACK_CANDIDATES call has tracked every keypoint and applied the candidates' half only:
                                                  // the landmarks' half (TRACK_LANDMARKS alone) may follow -- and only then
 };
@@ -216,7 +217,7 @@ template <int CH>
 // with the landmarks)
 __global__ void __launch_bounds__(PIPE_TPB) k_pipe_extend(pipe_ptrs Pall, const float* __restrict__ pts, size_t slab_seq, int W, int H,
                                                           float* __restrict__ pnp_X, float* __restrict__ pnp_uv, int pnp_cap, int which,
-                                                          uint8_t* __restrict__ keep_out) {
+                                                          uint8_t* __restrict__ keep_out, const uint8_t* __restrict__ fb_ok, size_t fb_seq) {
   extern __shared__ int32_t s_dyn[];
   __shared__ int s_w[16];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -232,6 +233,9 @@ __global__ void __launch_bounds__(PIPE_TPB) k_pipe_extend(pipe_ptrs Pall, const 
   int32_t* const s_fl = s_fk + P.N;
   int32_t* const s_src = s_fl + P.N;
   const float2* p1 = reinterpret_cast<const float2*>(vo_seq(pts, slab_seq, b));
+  // the forward-backward check's flags of the tracked set (null: the check is off): a point that fails it dies like one outside the image
+  const uint8_t* const fbk = fb_ok ? fb_ok + (size_t)b * fb_seq : nullptr;
+  auto good = [&](int j) { return !fbk || fbk[j] != 0; };
   pnp_X += (size_t)b * pnp_cap * 3; pnp_uv += (size_t)b * pnp_cap * 2;
   // ---- trip 1: counters ----
   const int nl = P.cnt[C_NLM], nc = P.cnt[C_NCAND], nd0 = P.cnt[C_NDEAD];
@@ -257,12 +261,12 @@ __global__ void __launch_bounds__(PIPE_TPB) k_pipe_extend(pipe_ptrs Pall, const 
     q[c] = make_float2(0.f, 0.f);
     if ((which & 2) && j < nl) {
       L[c] = P.lm_L[j]; K[c] = P.lm_K[j]; ksh[c] = P.lm_ksh[j] != 0; q[c] = p1[j];
-      keep[c] = pipe_inside(q[c], W, H); die[c] = !keep[c];
+      keep[c] = pipe_inside(q[c], W, H) && good(j); die[c] = !keep[c];
       keep_out[(size_t)b * pnp_cap + j] = keep[c] ? 1 : 0;      // which landmark entries survived (vo_pipe_inliers_read until the POSE stage overwrites it)
     }
     if (!SPLIT) {
       KC[c] = 0; keepc[c] = false; qc[c] = make_float2(0.f, 0.f);
-      if ((which & 1) && j < nc) { KC[c] = P.cand[j]; qc[c] = p1[nl + j]; keepc[c] = pipe_inside(qc[c], W, H); }
+      if ((which & 1) && j < nc) { KC[c] = P.cand[j]; qc[c] = p1[nl + j]; keepc[c] = pipe_inside(qc[c], W, H) && good(nl + j); }
     }
   }
   // ---- trip 3: every row field the phases below need, and the heads of the free lists ----
@@ -316,7 +320,7 @@ __global__ void __launch_bounds__(PIPE_TPB) k_pipe_extend(pipe_ptrs Pall, const 
       for (int c = 0; c < CH; c++) {
         const int j = tid * CH + c;
         kc[c] = 0; kp[c] = false; pc[c] = make_float2(0.f, 0.f);
-        if (j < nc) { kc[c] = P.cand[j]; pc[c] = p1[nl + j]; kp[c] = pipe_inside(pc[c], W, H); }
+        if (j < nc) { kc[c] = P.cand[j]; pc[c] = p1[nl + j]; kp[c] = pipe_inside(pc[c], W, H) && good(nl + j); }
       }
 #pragma unroll
       for (int c = 0; c < CH; c++) {
@@ -1498,7 +1502,9 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
       const size_t fr = (size_t)c->width * c->height;
       r = vo_build_pyramid(c, c->d_seq + (size_t)frame_idx * fr, fr * c->seq_n, nullptr);
     }
-    if (r == VO_OK) r = vo_klt_track_resident_counts(c, w->N, &prm.klt, w->d_dn + DN_PTS * B);
+    w->fb_active = vo_fb_on(c);                      // vo_set_fb_check: track with the forward-backward check
+    if (r == VO_OK) r = w->fb_active ? vo_klt_track_resident_fb(c, w->N, &prm.klt, w->d_dn + DN_PTS * B)
+                                     : vo_klt_track_resident_counts(c, w->N, &prm.klt, w->d_dn + DN_PTS * B);
     c->stream = main_stream;
     if (track_side) {                                  // joined on every path
       const hipError_t e1 = hipEventRecord(w->ev_track, c->stream2);
@@ -1512,7 +1518,8 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
     const size_t lds = sizeof(int32_t) * ((w->N > 4 * PIPE_TPB ? 0 : (size_t)w->R) + 3 * (size_t)w->N);     // (above 4 096 slots the row words are global)
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, dim3(c->batch), dim3(PIPE_TPB), lds, c->stream, P, vo_slab<const float>(c, vo_off_p(c)), c->slab_seq,
-                         c->width, c->height, pv.X, pv.uv, pv.cap, halves, const_cast<uint8_t*>(pv.mask));
+                         c->width, c->height, pv.X, pv.uv, pv.cap, halves, const_cast<uint8_t*>(pv.mask),
+                         (w->fb_active && w->N > 0) ? vo_fb_ok(c) : nullptr, c->fb_seq);
     };
     if (w->N <= PIPE_TPB) launch(k_pipe_extend<1>);
     else if (w->N <= 2 * PIPE_TPB) launch(k_pipe_extend<2>);

@@ -11,7 +11,8 @@
 // Semantics follow /root/reference/src/extractor/extractor.py:
 //   vo_tracks_track    = extend_tracks / extend_landmarks (:38-88): KLT prev -> cur of every live track, keep iff
 //                        0 <= x <= W and 0 <= y <= H (both ends inclusive; KLT status is ignored, the bidirectional
-//                        test is disabled by max_bidir_error = inf: pipeline.py:98-100), survivors get uv, t_total + 1
+//                        test is disabled by max_bidir_error = inf: pipeline.py:98-100; a finite vo_set_fb_check threshold adds the
+//                        true forward-backward check, vo_klt_fb.hip), survivors get uv, t_total + 1
 //                        and a history entry, the others are reported dead;
 //   vo_tracks_detect   = extract(..., 'shi-tomasi') (:90-132): exclusion discs at the live tracks, goodFeaturesToTrack,
 //                        every corner becomes Keypoint(t_first = t, t_total = 1, uv_first = uv = corner, history = [corner]);
@@ -117,7 +118,9 @@ __device__ __forceinline__ int trk_scan(int flag, int* s_w /* 16 */, int& total)
 // ---- extend: keep rule, ordered in-place compaction of every column of the table, counters, history, dead list ----
 // One workgroup per sequence walks the list in chunks of 1024: a chunk is read completely into registers before any of
 // its survivors is written, and survivors only move towards the front, so nothing unread is overwritten.
-__global__ void __launch_bounds__(1024) k_trk_extend(trk_ptrs P, float* __restrict__ pts, size_t slab_seq, int t, int W, int H) {
+// fb_ok (or null = the check is off): the forward-backward check's flags of the tracked set (vo_klt_fb.hip), fb_seq bytes per sequence
+__global__ void __launch_bounds__(1024) k_trk_extend(trk_ptrs P, float* __restrict__ pts, size_t slab_seq, int t, int W, int H,
+                                                     const uint8_t* __restrict__ fb_ok, size_t fb_seq) {
   __shared__ int s_w[16];
   const int b = blockIdx.x, tid = threadIdx.x;
   float2* p = reinterpret_cast<float2*>(vo_seq(pts, slab_seq, b));
@@ -138,7 +141,8 @@ __global__ void __launch_bounds__(1024) k_trk_extend(trk_ptrs P, float* __restri
       for (int h = 0; h < VO_TRK_HIST; h++) hrow[h] = trk_hist_row(P, b, h)[i];
     }
     // 0 <= x <= W and 0 <= y <= H, ends included; NaN fails like in Python
-    const int keep = (valid && pi.x >= 0.f && pi.x <= (float)W && pi.y >= 0.f && pi.y <= (float)H) ? 1 : 0;
+    const int keep = (valid && pi.x >= 0.f && pi.x <= (float)W && pi.y >= 0.f && pi.y <= (float)H &&
+                      (!fb_ok || fb_ok[(size_t)b * fb_seq + i])) ? 1 : 0;
     int kept, died;
     const int pos = trk_scan(keep, s_w, kept);
     const int dpos = trk_scan(valid && !keep, s_w, died);
@@ -227,12 +231,13 @@ extern "C" int32_t vo_tracks_track(vo_ctx* c, int32_t t, const vo_klt_params* pr
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   VO_CHECK(c, c->trk && c->d_pt_counts, VO_E_STATE, "vo_tracks_seed first");
   vo_trk_ws* tw = c->trk;
+  const bool fb = vo_fb_on(c);           // vo_set_fb_check: the forward-backward check joins the keep rule
   if (tw->n_hi > 0) {
-    const int32_t r = vo_klt_track_resident(c, tw->n_hi, prm);
+    const int32_t r = fb ? vo_klt_track_resident_fb(c, tw->n_hi, prm, c->d_pt_counts) : vo_klt_track_resident(c, tw->n_hi, prm);
     if (r != VO_OK) return r;
   }
   hipLaunchKernelGGL(k_trk_extend, dim3(c->batch), dim3(1024), 0, c->stream, trk_make(tw), vo_slab<float>(c, vo_off_p(c)),
-                     c->slab_seq, t, c->width, c->height);
+                     c->slab_seq, t, c->width, c->height, (fb && tw->n_hi > 0) ? vo_fb_ok(c) : nullptr, c->fb_seq);
   VO_HIP(c, hipGetLastError());
   return VO_OK;
 }

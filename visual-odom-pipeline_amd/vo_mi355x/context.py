@@ -174,6 +174,42 @@ class VoContext:
             return self._out(p1), self._out(st), self._out(err), self._out(it)
         return self._out(p1), self._out(st), self._out(err)
 
+    def klt_track_fb(self, p0, params=None, return_iters=False):
+        """klt_track with the forward-backward check in the same launch (vo_klt_track_fb): p1, status, err exactly as klt_track, plus
+        p0r (n,2) f32 = the backward track of p1 (current -> previous frame) and fb_err (n,) f32 = max(|p0 - p0r|) over x, y.  The ok flags
+        (fb_err < the context's threshold) come from fb_read(n)."""
+        p0, n = self._npts(p0)
+        B = self.batch
+        prm = params if params is not None else self.klt_params()
+        p1 = np.zeros((B, n, 2), np.float32)
+        st = np.zeros((B, n), np.uint8)
+        err = np.zeros((B, n), np.float32)
+        p0r = np.zeros((B, n, 2), np.float32)
+        fb_err = np.zeros((B, n), np.float32)
+        it = np.full((B, n, prm.max_level + 1), -1, np.int32)
+        self._ck(self._L.vo_klt_track_fb(self._h, ptr(p0, C.c_float), n, C.byref(prm), ptr(p1, C.c_float), ptr(st, C.c_uint8),
+                                         ptr(err, C.c_float), ptr(p0r, C.c_float), ptr(fb_err, C.c_float), ptr(it, C.c_int32)))
+        out = (self._out(p1), self._out(st), self._out(err), self._out(p0r), self._out(fb_err))
+        return out + (self._out(it),) if return_iters else out
+
+    def set_fb_check(self, max_err=np.inf):
+        """threshold of the forward-backward check (vo_set_fb_check): a finite value makes tracks_track and the closed loop's TRACK stage
+        drop every point with fb_err >= max_err (or NaN); np.inf (the default) turns it off.  Rounded to float32 once."""
+        self._ck(self._L.vo_set_fb_check(self._h, C.c_float(float(max_err))))
+
+    def get_fb_check(self):
+        v = C.c_float(0.0)
+        self._ck(self._L.vo_get_fb_check(self._h, C.byref(v)))
+        return v.value
+
+    def fb_read(self, n):
+        """(ok (n,) bool, fb_err (n,) f32) of the last track's dense point set, if it ran with the check [leading batch dim if batch > 1]"""
+        B = self.batch
+        ok = np.zeros((B, n), np.uint8)
+        fb_err = np.zeros((B, n), np.float32)
+        self._ck(self._L.vo_fb_read(self._h, ptr(ok, C.c_uint8), ptr(fb_err, C.c_float), n))
+        return self._out(ok.astype(bool)), self._out(fb_err)
+
     def points_upload(self, p):
         p, n = self._npts(p)
         self._ck(self._L.vo_points_upload(self._h, ptr(p, C.c_float), n))

@@ -26,10 +26,19 @@ class DMatch:
 
 
 class Extractor:
-    def __init__(self, cfg=None, min_kp_dist=10, ctx=None, device=0, max_pts=8192, lazy=None, lazy_backend=None):
+    def __init__(self, cfg=None, min_kp_dist=10, ctx=None, device=0, max_pts=8192, lazy=None, lazy_backend=None, bidir="reference"):
         """lazy (default: on unless VO_LAZY=0): once a frame has come through the reference's call order (pipeline.py:98-156) the state moves
         into device tables and the lists this class hands out are views of them (vo_mi355x/lazy.py); lazy_backend: test hook
-        (ctx, K, params, width, height) -> backend, default the GPU one.  max_pts: keypoints per call AND the capacity of those tables (<= 8192)."""
+        (ctx, K, params, width, height) -> backend, default the GPU one.  max_pts: keypoints per call AND the capacity of those tables (<= 8192).
+        bidir: what a finite max_bidir_error of extend_tracks / extend_landmarks means.  "reference" (default): the reference's check, whose
+        second KLT call tracks FORWARD again from p1 (extractor.py:45,66).  "backward": the true forward-backward check,
+        LK(cur, prev, p1) as in the OpenCV sample the reference copies (notebooks/tracking.py:39-42), both passes in one vo_klt_track_fb
+        launch; a keypoint whose round trip misses its start by max_bidir_error or more (max over x, y; float32) is dropped / goes to the dead
+        lists like one outside the image.  max_bidir_error = inf is the plain path in both modes.  A lazy session serves only the infinite
+        threshold: a call with a finite one takes the plain path (the session ends there), as it always has."""
+        if bidir not in ("reference", "backward"):
+            raise ValueError("bidir must be 'reference' or 'backward'")
+        self._bidir = bidir
         from . import lazy as _lz
         self._cfg = cfg
         self._lazy_on = _lz.enabled() if lazy is None else bool(lazy)
@@ -77,17 +86,22 @@ class Extractor:
         if not self._same(self._dev_cur, img):
             self._push(img)
 
+    def _klt_prm(self):
+        return self._ctx.klt_params(win=self._lk_params["winSize"][0], max_level=self._lk_params["maxLevel"],
+                                    max_count=self._lk_params["criteria"][1], epsilon=self._lk_params["criteria"][2])
+
     def _klt(self, p0):
-        c = self._ctx
-        prm = c.klt_params(win=self._lk_params["winSize"][0], max_level=self._lk_params["maxLevel"],
-                           max_count=self._lk_params["criteria"][1], epsilon=self._lk_params["criteria"][2])
-        return c.klt_track(p0, prm)
+        return self._ctx.klt_track(p0, self._klt_prm())
 
     def _track(self, im_curr, p0, max_bidir_error):
-        """p1 and the reference's 'bidirectional' flag.  The reference's second pass tracks FORWARD again from
+        """p1 and the 'bidirectional' flag.  bidir="reference": the reference's second pass tracks FORWARD again from
         p1 (extractor.py:45,66); with an infinite threshold its result cannot change `good` (NaN aside), so it
-        is skipped then."""
+        is skipped then.  bidir="backward" with a finite threshold: the forward-backward check (vo_klt_track_fb)."""
         self._ensure_pair(self._im_prev, im_curr)
+        if self._bidir == "backward" and max_bidir_error != np.inf:
+            c = self._ctx
+            p1, _st, _err, _p0r, fb_err = c.klt_track_fb(p0, self._klt_prm())
+            return p1, fb_err < np.float32(max_bidir_error)
         p1, _st, _err = self._klt(p0)
         if np.isinf(max_bidir_error):
             good = ~np.isnan(p1).any(axis=1)

@@ -45,10 +45,14 @@ class ResidentPipeline:
     solve).  An enqueued iteration whose solve has already stopped exits at once but still costs its four launches (~16 us per frame for
     one sequence, ~45 us for a batch of 32), so a caller that tracks one camera may pass the few iterations a warm-started window needs
     (2-3 typical; e.g. ba_budget=6) and watch rec["ba_done"]: 0 flags a solve the budget cut (set_ba_budget raises it between frames).
-    resurrect=False leaves dead landmarks dead (not the reference; see include/vo_mi355x.h)."""
+    resurrect=False leaves dead landmarks dead (not the reference; see include/vo_mi355x.h).
+    fb_max_error: threshold of the forward-backward KLT check (the context's vo_set_fb_check).  Finite: the TRACK stage tracks every keypoint
+    back to the previous frame as well, and a landmark or candidate whose round trip misses its start by fb_max_error or more (max over x, y)
+    dies like one that left the image; ctx.fb_read(n) returns the flags after a fetch.  np.inf (the default): off, the reference's behaviour."""
 
     def __init__(self, ctx, K, ba_window=4, min_track_length=3, mask_radius=7, max_new=1000, max_reproj_err=2.0, min_bearing_angle=0.5,
-                 ba_max_iters=50, ba_budget=None, ba_ftol=1e-3, ba_xtol=1e-3, pnp_blind_batches=4, pnp_seed=0, min_kp_dist=7, resurrect=True):
+                 ba_max_iters=50, ba_budget=None, ba_ftol=1e-3, ba_xtol=1e-3, pnp_blind_batches=4, pnp_seed=0, min_kp_dist=7, resurrect=True,
+                 fb_max_error=np.inf):
         self.ctx, self._L = ctx, ctx._L
         B = ctx.batch
         K = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (B, 3, 3)))
@@ -64,6 +68,8 @@ class ResidentPipeline:
         p.st.min_distance = float(min_kp_dist)
         self.params = p
         ctx._ck(self._L.vo_pipe_create(ctx._h, K.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p)))
+        if not (fb_max_error == np.inf and ctx.get_fb_check() == np.inf):     # (off on a context that never set it: no call at all)
+            ctx.set_fb_check(fb_max_error)
         self.N, self.R, self.B = ctx.max_pts, 4 * ctx.max_pts, B
         self.ba_window = ba_window
         self._inflight = 0
