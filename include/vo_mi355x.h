@@ -71,16 +71,36 @@ typedef struct {
   double  harris_k;          /* 0.04 (OpenCV default) */
 } vo_st_params;
 
+/* Robust loss of the bundle adjustment, scipy.optimize.least_squares' names (vo_ba_params.loss).  With C = f_scale (huber_delta),
+ * s = |e|^2 the squared pixel error of an observation and z = s / C^2, the cost is 1/2 C^2 sum rho(z) and the IRLS weight w = rho'(z):
+ *   HUBER    z if z <= 1, else 2 sqrt(z) - 1          w = 1 or 1 / sqrt(z)
+ *   LINEAR   z                                         w = 1   (runs the Huber kernels with an unreachable knee; C plays no part)
+ *   SOFT_L1  2 (sqrt(1 + z) - 1)                       w = 1 / sqrt(1 + z)
+ *   CAUCHY   log1p(z)                                  w = 1 / (1 + z)
+ *   ARCTAN   atan(z)                                   w = 1 / (1 + z^2)
+ * The Jacobians, the Schur complement, the Cholesky factorisation and the LM logic are the same for every loss; SOFT_L1, CAUCHY and ARCTAN
+ * run kernel sets of their own (k_ba_build_wr / k_ba_update_wr, k_ba_build_r / k_ba_update_r) beside the Huber ones.  scipy's rho''
+ * rescaling of the Jacobian is not copied: the IRLS fixed point sum w J^T e = 0 is the point scipy's TRF converges to. */
+enum {
+  VO_LOSS_HUBER = 0,         /* the default: a zero-filled vo_ba_params is the reference's loss */
+  VO_LOSS_LINEAR = 1,
+  VO_LOSS_SOFT_L1 = 2,
+  VO_LOSS_CAUCHY = 3,
+  VO_LOSS_ARCTAN = 4
+};
+
 /* BundleAdjuster configuration, src/bundle_adjuster/bundle_adjuster.py:8-16 and
- * src/pipeline/pipeline.py:28-29 (xtol = ftol = 1e-3, loss 'huber', f_scale 1) */
+ * src/pipeline/pipeline.py:28-29 (xtol = ftol = 1e-3, loss 'huber', f_scale 1).
+ * Every entry point that takes it (vo_ba_adjust, vo_ba_solve_resident, vo_frame_step*, vo_pipe_create / vo_pipe_params.ba) returns
+ * VO_E_INVALID with nothing enqueued for an unknown loss code or a huber_delta that is <= 0 or NaN. */
 typedef struct {
   int32_t max_iters;         /* LM iterations (linearise + solve + evaluate) cap, e.g. 50 */
-  int32_t _pad;
+  int32_t loss;              /* VO_LOSS_*, default VO_LOSS_HUBER (0) */
   double  ftol;              /* 1e-3 */
   double  xtol;              /* 1e-3 */
   double  gtol;              /* 1e-8 (scipy default) */
   double  lambda0;           /* initial Marquardt damping, 1e-4 */
-  double  huber_delta;       /* 1.0 px */
+  double  huber_delta;       /* scipy's f_scale C for every loss (the name is the Huber knee's), 1.0 px */
   double  lambda_min;        /* floor of the damping, 1e-3.  The reference fixes no gauge, so the normal equations
                                 have a 7-dimensional near-null space; without a floor the Nielsen schedule drives
                                 lambda to ~1e-5 after two good steps and then spends 4-6 iterations on rejected
@@ -293,6 +313,11 @@ int32_t vo_ba_fetch(vo_ctx* ctx, double* poses_out, double* points_out, vo_ba_st
 int32_t vo_ba_probe(vo_ctx* ctx, double lambda, double huber_delta, double* residual, int32_t* n_obs,
                     double* cost, double* Hpp, double* gp, double* Hll, double* gl, double* S,
                     double* rhs, double* dposes, double* dpoints);
+/* the same probe with the weights and cost of any loss (VO_LOSS_*, f_scale = C); vo_ba_probe is its VO_LOSS_HUBER case.
+ * An unknown loss or an f_scale <= 0 / NaN: VO_E_INVALID, nothing enqueued. */
+int32_t vo_ba_probe_loss(vo_ctx* ctx, double lambda, int32_t loss, double f_scale, double* residual, int32_t* n_obs,
+                         double* cost, double* Hpp, double* gp, double* Hll, double* gl, double* S,
+                         double* rhs, double* dposes, double* dpoints);
 
 /* ---- landmark-sharded bundle adjustment of ONE problem (BASELINE config 5) -------
  * The reference has no multi-device path (single Python process, src/pipeline/pipeline.py:155-156 calls adjust once

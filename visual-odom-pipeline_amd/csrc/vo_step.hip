@@ -335,6 +335,7 @@ static int32_t frame_step(vo_ctx* c, int32_t frame_idx, const uint8_t* const* ho
   if (ba) s.ba = *ba; else vo_ba_default_params(&s.ba);
   if (s.do_dlt) VO_CHECK(c, c->dlt_n > 0, VO_E_STATE, "vo_dlt_upload first");
   if (s.do_ba) VO_CHECK(c, vo_ba_ready(c), VO_E_STATE, "vo_ba_upload first");
+  if (s.do_ba) { const int32_t rc = vo_ba_check_params(c, &s.ba); if (rc != VO_OK) return rc; }
   if (s.do_st) { int32_t r = vo_st_prepare(c, &s.st); if (r != VO_OK) return r; }    // allocations happen outside any capture
 
   // up to two steps may be in flight: step t + 1 is enqueued while the host still reads step t's (pinned) results.

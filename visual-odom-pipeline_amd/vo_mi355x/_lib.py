@@ -36,8 +36,21 @@ class StParams(C.Structure):
                 ("min_distance", C.c_double), ("use_harris", C.c_int32), ("_pad", C.c_int32), ("harris_k", C.c_double)]
 
 
+# vo_ba_params.loss: include/vo_mi355x.h VO_LOSS_*, under scipy.optimize.least_squares' names
+LOSSES = {"huber": 0, "linear": 1, "soft_l1": 2, "cauchy": 3, "arctan": 4}
+
+
+def loss_code(loss):
+    """scipy's loss name -> VO_LOSS_* code; ValueError for an unknown name, NotImplementedError for a callable"""
+    if callable(loss):
+        raise NotImplementedError("a callable loss is not supported by the HIP bundle adjustment; use one of %s" % sorted(LOSSES))
+    if loss not in LOSSES:
+        raise ValueError("loss must be one of %s, got %r" % (sorted(LOSSES), loss))
+    return LOSSES[loss]
+
+
 class BaParams(C.Structure):
-    _fields_ = [("max_iters", C.c_int32), ("_pad", C.c_int32), ("ftol", C.c_double), ("xtol", C.c_double),
+    _fields_ = [("max_iters", C.c_int32), ("loss", C.c_int32), ("ftol", C.c_double), ("xtol", C.c_double),
                 ("gtol", C.c_double), ("lambda0", C.c_double), ("huber_delta", C.c_double), ("lambda_min", C.c_double)]
 
 
@@ -196,6 +209,8 @@ SIGNATURES = {
     "vo_pipe_inliers_read": (C.c_int32, [_ctx, _u8p, C.c_int32]),
     "vo_ba_probe": (C.c_int32, [_ctx, C.c_double, C.c_double, _f64p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p,
                                 _f64p, _f64p, _f64p, _f64p]),
+    "vo_ba_probe_loss": (C.c_int32, [_ctx, C.c_double, C.c_int32, C.c_double, _f64p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p,
+                                     _f64p, _f64p, _f64p, _f64p]),
 }
 
 _lib = None

@@ -60,12 +60,27 @@ class BundleAdjuster:
             poses[s, 3:] = H[:3, 3]
         return poses, points, obs, n_live, [p[0] for p in stay_out], [p[1] for p in stay_out]
 
+    def _solve_loss(self, obs, N, W):
+        """the loss the reference's least_squares call would use (:180-194): method 'lm' runs 'linear' when the residuals outnumber the
+        variables and is refused by scipy otherwise; a name scipy does not know is a ValueError, a callable loss is not supported"""
+        from ._lib import loss_code
+        loss_code(self._loss)
+        if self._method == 'lm':
+            # one residual per observation (the norm, :18-65; the sparsity pattern has one row each, :85-124) against 3 N + 6 W variables
+            n_res, n_var = int(np.count_nonzero(~np.isnan(obs[..., 0]))), 3 * N + 6 * W
+            if n_res <= n_var:
+                raise ValueError("Method 'lm' doesn't work when the number of residuals is less than the number of variables.")
+            return 'linear'
+        return self._loss
+
     def adjust(self, state, landmarks_dead, landmarks_kp_dead, K, t_now):
         from . import lazy as _lz
+        from ._lib import loss_code
+        loss_code(self._loss)                                     # (an unknown name or a callable fails before anything is touched)
         sess = _lz.session_of(state, landmarks_kp_dead)
         if sess is not None:          # the lists are views of the device tables (lazy.py): resurrection, solve and write-back happen there
             r = sess.adjust(state, landmarks_dead, landmarks_kp_dead, K, t_now, self._window_size, self._ftol, self._xtol, self._max_iters) \
-                if self._loss == 'huber' else sess._fail("adjust: loss")
+                if self._loss == 'huber' and self._method != 'lm' else sess._fail("adjust: loss")
             if r is not NotImplemented:
                 state, dead_l, dead_k, self.last_stats = r
                 return state, dead_l, dead_k
@@ -80,8 +95,11 @@ class BundleAdjuster:
         N, W = len(lms), self._window_size
         if N > 0 and not np.isnan(obs[..., 0]).all():
             c = self._context()
-            delta = 1.0 if self._loss == 'huber' else 1e30       # 'linear' loss == Huber with an unreachable knee
-            prm = c.ba_params(max_iters=self._max_iters, ftol=self._ftol, xtol=self._xtol, huber_delta=delta)
+            loss = self._solve_loss(obs, N, W)
+            if loss in ('huber', 'linear'):                       # 'linear' loss == Huber with an unreachable knee (any context's ba_params)
+                prm = c.ba_params(max_iters=self._max_iters, ftol=self._ftol, xtol=self._xtol, huber_delta=1.0 if loss == 'huber' else 1e30)
+            else:
+                prm = c.ba_params(max_iters=self._max_iters, ftol=self._ftol, xtol=self._xtol, loss=loss)
             poses, points, self.last_stats = c.ba_adjust(np.asarray(K, np.float64), poses, points, obs, prm)
         # positions back into the landmark objects, every landmark its own (3, 1) array (:197-201)
         fresh = np.ascontiguousarray(points, np.float64).reshape(N, 3, 1).copy()

@@ -468,11 +468,13 @@ class VoContext:
         return out
 
     # -- BA -------------------------------------------------------------------------------------
-    def ba_params(self, max_iters=50, ftol=1e-3, xtol=1e-3, gtol=1e-8, lambda0=1e-4, huber_delta=1.0, lambda_min=1e-3):
+    def ba_params(self, max_iters=50, ftol=1e-3, xtol=1e-3, gtol=1e-8, lambda0=1e-4, huber_delta=1.0, lambda_min=1e-3, loss='huber'):
+        """loss: scipy's name ('huber', 'linear', 'soft_l1', 'cauchy', 'arctan'); huber_delta is scipy's f_scale for every loss"""
         p = BaParams()
         self._L.vo_ba_default_params(C.byref(p))
         p.max_iters, p.ftol, p.xtol, p.gtol, p.lambda0, p.huber_delta = max_iters, ftol, xtol, gtol, lambda0, huber_delta
         p.lambda_min = lambda_min
+        p.loss = _lib.loss_code(loss)
         return p
 
     @staticmethod
@@ -737,8 +739,9 @@ class VoContext:
         self._ck(self._L.vo_ba_gather_points(self._h, ptr(out, C.c_double)))
         return out
 
-    def ba_probe(self, lam=1e-4, huber_delta=1.0):
-        """Parity probe of problem 0 at the uploaded x0: residuals, normal equations, reduced system, one LM step."""
+    def ba_probe(self, lam=1e-4, huber_delta=1.0, loss='huber'):
+        """Parity probe of problem 0 at the uploaded x0: residuals, normal equations, reduced system, one LM step.
+        loss: scipy's name, huber_delta its f_scale."""
         W, N = self._ba_shape
         res = np.zeros(W * N)
         n_obs = C.c_int32(0)
@@ -748,7 +751,7 @@ class VoContext:
         S, rhs = np.zeros((6 * W, 6 * W)), np.zeros(6 * W)
         dp, dl = np.zeros((W, 6)), np.zeros((N, 3))
         d = C.c_double
-        self._ck(self._L.vo_ba_probe(self._h, lam, huber_delta, ptr(res, d), C.byref(n_obs), C.byref(cost),
+        self._ck(self._L.vo_ba_probe_loss(self._h, lam, _lib.loss_code(loss), huber_delta, ptr(res, d), C.byref(n_obs), C.byref(cost),
                                      ptr(Hpp, d), ptr(gp, d), ptr(Hll, d), ptr(gl, d), ptr(S, d), ptr(rhs, d),
                                      ptr(dp, d), ptr(dl, d)))
         return dict(residual=res[:n_obs.value].copy(), cost=cost.value, Hpp=Hpp, gp=gp, Hll=Hll, gl=gl, S=S, rhs=rhs,

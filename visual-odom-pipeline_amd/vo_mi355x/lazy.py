@@ -763,7 +763,7 @@ def seed_after_adjust(adjuster, state, dead_l, dead_k, K, t_now):
     """Called at the end of a plain `adjust`.  If the frame came through the reference's call order on ONE drop-in Extractor that owns a device
     context holding the frame, the caller's objects move into device tables: the state's lists are rewritten in place with proxies and the
     two dead lists come back as lists of proxies (None: nothing changed)."""
-    if not enabled() or adjuster._loss != 'huber':
+    if not enabled() or adjuster._loss != 'huber' or adjuster._method == 'lm':      # (the session solves the Huber / trf case only)
         return None
     cands = [e for e in _EXTRACTORS if e._lazy_on and e._frame_is_reference_order() and e._dev_cur is not None]
     if len(cands) != 1:
