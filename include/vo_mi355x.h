@@ -531,7 +531,9 @@ int32_t vo_pipe_step(vo_ctx* ctx, int32_t frame_idx, int32_t stages);
 /* the same step with the frame handed over by the host, as the reference's loop does (Pipeline.step(img): src/pipeline/pipeline.py:98,171-172):
  * frames[b] = the new image of sequence b (rows of `stride` bytes).  Upload on the copy stream (see vo_frame_step_host: one gather launch for
  * page-locked images), pyramid + tracking on the side stream behind it -- the overlap of a resident frame.  `stages` must contain VO_PIPE_TRACK.
- * Page-locked images must stay untouched until the step has been fetched. */
+ * In flight: up to VO_PIPE_INFLIGHT steps, host and resident ones together, as vo_pipe_step.  Every image a step was given, whatever memory holds
+ * it (page-locked, registered or pageable), must stay allocated and untouched until vo_pipe_fetch has returned that step.  A refused call
+ * (VO_E_STATE: no frame in the store, steps in flight on the gated layout, VO_PIPE_INFLIGHT steps in flight) enqueues nothing. */
 int32_t vo_pipe_step_host(vo_ctx* ctx, const uint8_t* const* frames, int32_t stride, int32_t stages);
 int32_t vo_pipe_fetch(vo_ctx* ctx, vo_pipe_record* rec /* [batch] */);        /* waits for the OLDEST step not fetched yet */
 int32_t vo_pipe_set_ba_budget(vo_ctx* ctx, int32_t budget);
@@ -598,9 +600,11 @@ int32_t vo_frame_fetch(vo_ctx* ctx, int32_t n_pts, float* p, uint8_t* status, fl
  * src/pipeline/pipeline.py:98,171-172): frames[b] = this step's image of sequence b, `height` rows of `stride` bytes (>= width), uint8.  The
  * upload runs on a copy stream of its own into a device buffer double-buffered by step parity, the pyramid of the step waits for it by an event:
  * with two steps in flight the upload of frame t + 1 overlaps the bundle adjustment of frame t.  Images that follow each other in host memory (a
- * [batch][height][width] array) travel as one copy.  Pinned memory (vo_host_alloc, or registered by the caller) is read by DMA asynchronously and
- * must stay untouched until vo_frame_fetch has returned this step; pageable memory is consumed before the call returns (staged by the runtime:
- * slower).  Results are bit-identical to vo_frame_step_resident on the same frames.  Plain launches (a captured graph bakes its source in). */
+ * [batch][height][width] array) travel as one copy.  Pinned memory (vo_host_alloc, or registered by the caller) is read by the GPU while the
+ * step runs; pageable memory is staged by the runtime (slower).  In flight: up to 2 steps, as vo_frame_step_resident.  Every image a step was
+ * given, of any memory kind, must stay allocated and untouched until vo_frame_fetch has returned that step (when a pageable source has been
+ * read is up to the runtime, not promised here).  Results are bit-identical to vo_frame_step_resident on the same frames.  Plain launches (a
+ * captured graph bakes its source in). */
 int32_t vo_frame_step_host(vo_ctx* ctx, const uint8_t* const* frames, int32_t stride, int32_t n_pts, int32_t do_dlt, int32_t do_ba,
                            int32_t do_st, int32_t mask_radius, const vo_klt_params* klt,
                            const vo_st_params* st, const vo_ba_params* ba);                    /* async */

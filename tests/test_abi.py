@@ -45,6 +45,14 @@ def test_struct_layouts_match_header():
     assert b.ftol == 1e-3 and b.xtol == 1e-3 and b.huber_delta == 1.0
 
 
+def test_python_mirrors_of_the_pipe_constants_match_header():
+    """resident.INFLIGHT bounds how long step_host keeps a step's images referenced: it must be the library's in-flight limit"""
+    from vo_mi355x import resident
+    txt = open(os.path.join(ROOT, "include", "vo_mi355x.h")).read()
+    assert int(re.search(r"#define VO_PIPE_INFLIGHT (\d+)", txt).group(1)) == resident.INFLIGHT
+    assert int(re.search(r"#define VO_PIPE_HIST (\d+)", txt).group(1)) == resident.HIST
+
+
 def test_the_library_reads_no_tuning_from_the_environment():
     """rounds 1-5 shipped 23 getenv switches; forced forms now go through vo_set_tuning.  What is left: VO_BLOCKING_SYNC (how a host thread
     waits) and the VO_STEP_TRACE debug trace."""

@@ -90,7 +90,9 @@ struct vo_ctx {
   hipEvent_t ev_raw_free[2] = {nullptr, nullptr};   // the pyramid has read d_host_raw[k] (recorded on the ctx stream, awaited by stream_h2d)
   bool raw_free_recorded[2] = {false, false};
   int pipe_host_slot = 0;                           // vo_pipe_step_host alternates the two buffers on its own count
-  const uint8_t** h_ptr_tab = nullptr;              // page-locked [2][batch]: device-visible addresses of a step's images (read by k_gather_frames)
+  // page-locked [VO_HOST_TAB_SLOTS][batch]: device-visible addresses of a step's images, read by k_gather_frames WHILE it runs -- so one slot per
+  // step that can be in flight (vo_host_tab_slot), never one per d_host_raw half
+  const uint8_t** h_ptr_tab = nullptr;
   uint8_t* d_seq = nullptr;          // preloaded sequences [batch][seq_n][h][w] (vo_seq_upload)
   int seq_n = 0;
   // tracked point sets live in the result slab (off_pa / off_pb, ping-pong selected by p_parity)
@@ -211,7 +213,14 @@ static inline int vo_div_up(int a, int b) { return (a + b - 1) / b; }
 // cross-unit internals used by the fused frame step (vo_step.hip)
 int32_t vo_build_pyramid(vo_ctx* c, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx);
 // a step's `batch` images from the host into d_host_raw[slot] on the copy stream (vo_step.hip); ev_h2d[slot] is recorded behind it
-int32_t vo_host_frames_upload(vo_ctx* c, const uint8_t* const* frames, int32_t stride, int slot);
+// tab_slot: the row of h_ptr_tab this step's pointers go to (vo_host_tab_slot_frame / vo_host_tab_slot_pipe)
+int32_t vo_host_frames_upload(vo_ctx* c, const uint8_t* const* frames, int32_t stride, int slot, int tab_slot);
+// The pointer table's rows: [0, 2) the frame step (vo_frame_step_host admits 2 in flight), by steps_enq & 1; [2, 2 + VO_PIPE_INFLIGHT) the closed
+// loop (vo_pipe_step_host admits VO_PIPE_INFLIGHT), by pipe->enq % VO_PIPE_INFLIGHT.  A row is written again only once the step that used it
+// has been fetched, and a fetched step's gather is done (its pyramid waited for ev_h2d before it ran).  The two paths never share a row.
+#define VO_HOST_TAB_SLOTS (2 + VO_PIPE_INFLIGHT)
+inline int vo_host_tab_slot_frame(long steps_enq) { return (int)(steps_enq & 1); }
+inline int vo_host_tab_slot_pipe(long pipe_enq) { return 2 + (int)(pipe_enq % VO_PIPE_INFLIGHT); }
 int32_t vo_ba_enqueue_pub_copy(vo_ctx* c, int half);     // half: which pinned mirror (0 / 1)
 void vo_ba_unpack_pub(vo_ctx* c, int half, double* poses_out, double* points_out, vo_ba_stats* stats);   // arrays over the batch
 bool vo_ba_ready(const vo_ctx* c);

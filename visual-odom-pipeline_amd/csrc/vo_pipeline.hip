@@ -1410,6 +1410,28 @@ extern "C" int32_t vo_pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages) {
   return pipe_step_entry(c, frame_idx < 0 ? -1 : frame_idx, stages);
 }
 
+// every check that can refuse a step, before anything of it is enqueued: vo_pipe_step_host runs them ahead of the upload, so a refused call
+// leaves no gather in flight and no buffer or pointer-table slot taken
+static int32_t pipe_step_admit(vo_ctx* c, int32_t frame_idx, int32_t stages) {
+  VO_CHECK(c, c->pipe, VO_E_STATE, "vo_pipe_create first");
+  VO_CHECK(c, c->pipe->enq - c->pipe->fetched < VO_PIPE_INFLIGHT, VO_E_STATE, "vo_pipe_fetch the oldest step first");
+  if (c->stream_reserve > 0 || c->ba_wide_groups > 0)
+    VO_CHECK(c, c->pipe->enq == c->pipe->fetched && c->steps_enq == c->steps_fetched, VO_E_STATE, "steps in flight on the gated stream layout");
+  const int halves = (stages & (VO_PIPE_TRACK_CANDIDATES | VO_PIPE_TRACK_LANDMARKS)) ? (((stages & VO_PIPE_TRACK_CANDIDATES) ? 1 : 0) | ((stages & VO_PIPE_TRACK_LANDMARKS) ? 2 : 0)) : 3;
+  // the landmarks' half on its own reads the positions a TRACK | TRACK_CANDIDATES call left in the point buffer: without that call before it
+  // k_pipe_extend would take stale positions for tracked ones
+  if (!(stages & VO_PIPE_TRACK) && (stages & VO_PIPE_TRACK_LANDMARKS))
+    VO_CHECK(c, halves == 2 && c->pipe->lm_half_pending, VO_E_STATE, "VO_PIPE_TRACK_LANDMARKS alone needs a VO_PIPE_TRACK | VO_PIPE_TRACK_CANDIDATES call before it");
+  if (!(stages & VO_PIPE_TRACK) && (stages & VO_PIPE_TRACK_CANDIDATES))
+    return vo_fail(c, VO_E_STATE, "pipe_step: VO_PIPE_TRACK_CANDIDATES without VO_PIPE_TRACK (the candidates' half follows the tracking in the same call)");
+  if (stages & VO_PIPE_TRACK) {
+    const bool has_frame = frame_idx >= 0 || frame_idx == PIPE_FRAME_FROM_HOST;
+    if (frame_idx >= 0) VO_CHECK(c, c->d_seq && frame_idx < c->seq_n, VO_E_STATE, "no resident sequence / bad frame index");
+    VO_CHECK(c, c->n_pushed + (has_frame ? 1 : 0) >= 2, VO_E_STATE, "tracking needs two frames in the frame store");
+  }
+  return VO_OK;
+}
+
 // the same step with this frame's images handed over by the host (Pipeline.step(img), pipeline.py:98,171-172): the upload runs on the copy stream
 // (k_gather_frames for page-locked images), the pyramid + tracking of the step on the side stream behind it, exactly like a resident frame
 extern "C" int32_t vo_pipe_step_host(vo_ctx* c, const uint8_t* const* frames, int32_t stride, int32_t stages) {
@@ -1418,24 +1440,28 @@ extern "C" int32_t vo_pipe_step_host(vo_ctx* c, const uint8_t* const* frames, in
   VO_CHECK(c, frames != nullptr && stride >= c->width, VO_E_INVALID, "bad frame pointers / stride");
   VO_CHECK(c, (stages & VO_PIPE_TRACK) != 0, VO_E_INVALID, "a step that takes a frame tracks it (VO_PIPE_TRACK)");
   for (int b = 0; b < c->batch; b++) VO_CHECK(c, frames[b] != nullptr, VO_E_INVALID, "null frame pointer");
-  VO_CHECK(c, c->pipe->enq - c->pipe->fetched < VO_PIPE_INFLIGHT, VO_E_STATE, "vo_pipe_fetch the oldest step first");
+  { const int32_t ra = pipe_step_admit(c, PIPE_FRAME_FROM_HOST, stages); if (ra != VO_OK) return ra; }
   VO_HIP(c, hipSetDevice(c->device));
-  c->pipe_host_slot ^= 1;
-  { const int32_t ru = vo_host_frames_upload(c, frames, stride, c->pipe_host_slot); if (ru != VO_OK) return ru; }
-  return pipe_step_entry(c, PIPE_FRAME_FROM_HOST, stages);
+  // d_host_raw: the two halves in turn (ev_raw_free orders each); the pointers: this step's own row of the table, free since the step
+  // VO_PIPE_INFLIGHT before it was fetched
+  const int half = c->pipe_host_slot ^ 1;
+  { const int32_t ru = vo_host_frames_upload(c, frames, stride, half, vo_host_tab_slot_pipe(c->pipe->enq)); if (ru != VO_OK) return ru; }
+  c->pipe_host_slot = half;
+  const int32_t r = pipe_step_entry(c, PIPE_FRAME_FROM_HOST, stages);
+  // (error path) the step does not count, so its pointer-table row goes to the next one: let the gather finish reading it first
+  if (r != VO_OK) (void)hipStreamSynchronize(c->stream_h2d);
+  return r;
 }
 
 static int32_t pipe_step_entry(vo_ctx* c, int32_t frame_idx, int32_t stages) {
-  VO_CHECK(c, c->pipe, VO_E_STATE, "vo_pipe_create first");
-  VO_CHECK(c, c->pipe->enq - c->pipe->fetched < VO_PIPE_INFLIGHT, VO_E_STATE, "vo_pipe_fetch the oldest step first");
+  { const int32_t ra = pipe_step_admit(c, frame_idx, stages); if (ra != VO_OK) return ra; }
   VO_HIP(c, hipSetDevice(c->device));
   // the closed loop's chain (PnP, the adjustment) lives on the ctx stream: it gets every compute unit (the pipelined frame step of a batch
   // confines that stream to 224 of them for its tracker launches, vo_set_side_stream)
   // -- the layout stays what vo_set_side_stream made it: it is SUSPENDED here and the next vo_frame_step_* puts it back (vo_step_layout reports
   // what is in effect at the moment).  vo_set_side_stream / vo_set_tuning refuse while pipe steps are in flight, so a masked stream is never met
   // with steps of this loop still on it
-  if (c->stream_reserve > 0 || c->ba_wide_groups > 0) {
-    VO_CHECK(c, c->pipe->enq == c->pipe->fetched && c->steps_enq == c->steps_fetched, VO_E_STATE, "steps in flight on the gated stream layout");
+  if (c->stream_reserve > 0 || c->ba_wide_groups > 0) {      // (nothing in flight: pipe_step_admit)
     const int32_t rr = vo_main_stream_reserve(c, 0);
     if (rr != VO_OK) return rr;
     c->ba_wide_groups = 0; c->ba_wide_recorded = false; c->layout_suspended = true;
@@ -1471,17 +1497,10 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
   const bool side = c->side_stream != 0 && c->stream2 != nullptr;
   hipStream_t const main_stream = c->stream;
   const int halves = (stages & (VO_PIPE_TRACK_CANDIDATES | VO_PIPE_TRACK_LANDMARKS)) ? (((stages & VO_PIPE_TRACK_CANDIDATES) ? 1 : 0) | ((stages & VO_PIPE_TRACK_LANDMARKS) ? 2 : 0)) : 3;
-  // the landmarks' half on its own reads the positions a TRACK | TRACK_CANDIDATES call left in the point buffer: without that call before it
-  // k_pipe_extend would take stale positions for tracked ones
-  if (!(stages & VO_PIPE_TRACK) && (stages & VO_PIPE_TRACK_LANDMARKS))
-    VO_CHECK(c, halves == 2 && w->lm_half_pending, VO_E_STATE, "VO_PIPE_TRACK_LANDMARKS alone needs a VO_PIPE_TRACK | VO_PIPE_TRACK_CANDIDATES call before it");
-  if (!(stages & VO_PIPE_TRACK) && (stages & VO_PIPE_TRACK_CANDIDATES))
-    return vo_fail(c, VO_E_STATE, "pipe_step: VO_PIPE_TRACK_CANDIDATES without VO_PIPE_TRACK (the candidates' half follows the tracking in the same call)");
+  // (the stage combinations, the frame store and the resident sequence were checked by pipe_step_admit)
   if (stages & (VO_PIPE_TRACK | VO_PIPE_TRACK_LANDMARKS)) w->lm_half_pending = (stages & VO_PIPE_TRACK) && halves == 1;
   if (stages & VO_PIPE_TRACK) {
     const bool from_host = frame_idx == PIPE_FRAME_FROM_HOST, has_frame = frame_idx >= 0 || from_host;
-    if (frame_idx >= 0) VO_CHECK(c, c->d_seq && frame_idx < c->seq_n, VO_E_STATE, "no resident sequence / bad frame index");
-    VO_CHECK(c, c->n_pushed + (has_frame ? 1 : 0) >= 2, VO_E_STATE, "tracking needs two frames in the frame store");
     const bool track_side = side && has_frame;
     r = VO_OK;
     if (track_side && main_dirty) {

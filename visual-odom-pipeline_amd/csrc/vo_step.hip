@@ -236,22 +236,51 @@ __global__ __launch_bounds__(256) void k_gather_frames(const uint8_t* const* __r
 
 // the upload of a host-frame step on the copy stream into d_host_raw[half].  Page-locked images: the gather kernel; pageable ones: a copy per
 // image (runs of images that follow each other in host memory -- a [batch][h][w] array -- go as ONE copy), which the runtime stages
-int32_t vo_host_frames_upload(vo_ctx* c, const uint8_t* const* frames, int32_t stride, int half) {
+// first use: the copy stream, the pointer table, both halves and their events -- made into locals and handed to the context only when every one
+// of them exists (a failure part way leaves no null resource behind for the next call to take as made)
+static int32_t host_frames_setup(vo_ctx* c) {
   const size_t fr = (size_t)c->width * c->height;
-  if (!c->stream_h2d) {
-    VO_HIP(c, hipStreamCreateWithFlags(&c->stream_h2d, hipStreamNonBlocking));
-    VO_HIP(c, hipHostMalloc((void**)&c->h_ptr_tab, 2 * sizeof(void*) * (size_t)c->batch, hipHostMallocDefault));
-    for (int k = 0; k < 2; k++) {
-      VO_HIP(c, hipMalloc((void**)&c->d_host_raw[k], fr * c->batch));
-      VO_HIP(c, hipEventCreateWithFlags(&c->ev_h2d[k], hipEventDisableTiming));
-      VO_HIP(c, hipEventCreateWithFlags(&c->ev_raw_free[k], hipEventDisableTiming));
-    }
+  hipStream_t st = nullptr;
+  const uint8_t** tab = nullptr;
+  uint8_t* raw[2] = {nullptr, nullptr};
+  hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
+  // One row of pointers per step that can be in flight (VO_HOST_TAB_SLOTS, vo_internal.h): k_gather_frames reads its row while it runs, and a row
+  // is written again only after the step that used it has been fetched -- whose pyramid waited for ev_h2d, i.e. for the gather to end.  So the
+  // enqueue path never waits on the host for a row
+  hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&tab, VO_HOST_TAB_SLOTS * sizeof(void*) * (size_t)c->batch, hipHostMallocDefault);
+  for (int k = 0; k < 2 && e == hipSuccess; k++) {
+    e = hipMalloc((void**)&raw[k], fr * c->batch);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_h2d[k], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_free[k], hipEventDisableTiming);
   }
+  if (e != hipSuccess) {
+    for (int k = 0; k < 2; k++) {
+      if (raw[k]) (void)hipFree(raw[k]);
+      if (ev_h2d[k]) (void)hipEventDestroy(ev_h2d[k]);
+      if (ev_free[k]) (void)hipEventDestroy(ev_free[k]);
+    }
+    if (tab) (void)hipHostFree(tab);
+    if (st) (void)hipStreamDestroy(st);
+    VO_HIP(c, e);
+  }
+  c->h_ptr_tab = tab;
+  for (int k = 0; k < 2; k++) { c->d_host_raw[k] = raw[k]; c->ev_h2d[k] = ev_h2d[k]; c->ev_raw_free[k] = ev_free[k]; c->raw_free_recorded[k] = false; }
+  c->stream_h2d = st;                         // last: the key of the first-use test
+  return VO_OK;
+}
+
+// the upload of a host-frame step on the copy stream into d_host_raw[half], its image pointers in row tab_slot of h_ptr_tab.  Page-locked images:
+// the gather kernel; pageable ones: a copy per image (runs of images that follow each other in host memory -- a [batch][h][w] array -- go as ONE
+// copy), which the runtime stages
+int32_t vo_host_frames_upload(vo_ctx* c, const uint8_t* const* frames, int32_t stride, int half, int tab_slot) {
+  const size_t fr = (size_t)c->width * c->height;
+  if (!c->stream_h2d) { const int32_t rs = host_frames_setup(c); if (rs != VO_OK) return rs; }
   // the pyramid of the step that used this half two steps ago has read it (that step has been fetched, so this wait never blocks in practice)
   if (c->raw_free_recorded[half]) VO_HIP(c, hipStreamWaitEvent(c->stream_h2d, c->ev_raw_free[half], 0));
   uint8_t* const dst = c->d_host_raw[half];
   // device-visible addresses of the images, if every one of them is page-locked
-  const uint8_t** tab = c->h_ptr_tab + (size_t)half * c->batch;
+  const uint8_t** tab = c->h_ptr_tab + (size_t)tab_slot * c->batch;
   bool pinned = true;
   for (int b = 0; b < c->batch && pinned; b++) {
     hipPointerAttribute_t at;
@@ -345,14 +374,18 @@ static int32_t frame_step(vo_ctx* c, int32_t frame_idx, const uint8_t* const* ho
   VO_CHECK(c, c->steps_enq - c->steps_fetched < 2, VO_E_STATE, "vo_frame_fetch the previous step(s) first");
   c->main_dirty = true;
   const int half = (int)(c->steps_enq & 1);
-  if (host_frames) { const int32_t ru = vo_host_frames_upload(c, host_frames, stride, half); if (ru != VO_OK) return ru; }
+  if (host_frames) { const int32_t ru = vo_host_frames_upload(c, host_frames, stride, half, vo_host_tab_slot_frame(c->steps_enq)); if (ru != VO_OK) return ru; }
   const bool graph_ok = c->use_graph && c->prof.mask == 0 && c->n_pushed >= 2 && !host_frames;     // (host frames: plain launches)
   if (!graph_ok) {
     bool recorded = false;
     c->in_step = true;
     const int32_t r = step_enqueue(c, s, nullptr, frame_idx, half, &recorded);
     c->in_step = false;
-    if (r != VO_OK) return r;
+    if (r != VO_OK) {
+      // (error path) the step does not count, so its pointer-table row goes to the next one: let the gather finish reading it first
+      if (host_frames) (void)hipStreamSynchronize(c->stream_h2d);
+      return r;
+    }
     if (!recorded) VO_HIP(c, hipEventRecord(c->ev_step[half], c->stream));
     c->steps_enq++;
     return VO_OK;

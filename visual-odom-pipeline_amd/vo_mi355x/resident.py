@@ -16,6 +16,7 @@ Object identity is part of the reference's behaviour (BundleAdjuster.adjust appe
 without copying them, bundle_adjuster.py:142-147): the tables are rows of Keypoint / Landmark OBJECTS plus ordered lists of row
 indices, and `seed` / `objects` translate between the two forms keeping who-shares-what.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -25,6 +26,7 @@ from ._lib import PipeParams, PipeRecord
 from .state import Keypoint, Landmark, State, Trajectory
 
 HIST = 32
+INFLIGHT = 4          # VO_PIPE_INFLIGHT: steps that may be enqueued before the oldest is fetched
 TRACK, POSE, TRIANGULATE, ADJUST, DETECT, ALL = 1, 2, 4, 8, 16, 31
 TRACK_CANDIDATES, TRACK_LANDMARKS, KEEP_FREE_LISTS = 32, 64, 128      # the halves of TRACK's bookkeeping as the reference calls them (include/vo_mi355x.h)
 LOST, CAPACITY, GROUPS = 1, 2, 4
@@ -74,6 +76,7 @@ class ResidentPipeline:
         self.N, self.R, self.B = ctx.max_pts, 4 * ctx.max_pts, B
         self.ba_window = ba_window
         self._inflight = 0
+        self._host_refs = collections.deque()             # per step in flight, oldest first: the arrays step_host was given (None: a resident step)
         ctx._ba_shape = (ba_window, ctx.max_pts)          # VoContext.ba_probe reads the resident problem the ADJUST stage builds
 
     # ---- tables ---------------------------------------------------------------------------------
@@ -97,21 +100,25 @@ class ResidentPipeline:
         """enqueue one frame (frame_idx of the uploaded sequence, or -1: the caller has pushed it); returns at once"""
         self.ctx._ck(self._L.vo_pipe_step(self.ctx._h, int(frame_idx), int(stages)))
         self._inflight += 1
+        self._host_refs.append(None)
 
     def step_host(self, frames, stages=ALL):
         """enqueue one frame whose images the HOST hands over (one uint8 [h, w] array per sequence, or the tuple `VoContext.host_frames` returns):
         Pipeline.step(img) of the reference (pipeline.py:98,171-172).  The upload runs on the copy stream, pyramid + tracking on the side stream.
-        Arrays over page-locked memory (`VoContext.host_alloc`) must stay untouched until the step has been fetched (they are kept referenced)."""
+        The arrays, of any memory kind, must stay untouched until the step has been fetched; they are kept referenced until then (up to
+        INFLIGHT steps' worth)."""
         ptrs, stride, frames = frames if isinstance(frames, tuple) and len(frames) == 3 and isinstance(frames[1], int) else self.ctx.host_frames(frames)
         self.ctx._ck(self._L.vo_pipe_step_host(self.ctx._h, ptrs, int(stride), int(stages)))
         self._inflight += 1
-        self._host_refs = (getattr(self, "_host_refs", []) + [frames])[-4:]
+        self._host_refs.append(frames)
 
     def fetch(self):
         """records of the OLDEST step in flight: list of dicts, one per sequence (a dict when batch == 1)"""
         rec = (PipeRecord * self.B)()
         self.ctx._ck(self._L.vo_pipe_fetch(self.ctx._h, rec))
         self._inflight -= 1
+        if self._host_refs:
+            self._host_refs.popleft()                     # that step is done with its images
         out = []
         for r in rec:
             d = {n: getattr(r, n) for n in _RECORD_FIELDS}
@@ -127,6 +134,8 @@ class ResidentPipeline:
         rec = (PipeRecord * self.B)()
         self.ctx._ck(self._L.vo_pipe_fetch(self.ctx._h, rec))
         self._inflight -= 1
+        if self._host_refs:
+            self._host_refs.popleft()                     # that step is done with its images
         return rec
 
     # ---- read-backs of the object boundary (lazy.py): the lists in one copy, object rows by index, the consensus mask -------------
