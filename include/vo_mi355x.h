@@ -92,7 +92,10 @@ enum {
 /* BundleAdjuster configuration, src/bundle_adjuster/bundle_adjuster.py:8-16 and
  * src/pipeline/pipeline.py:28-29 (xtol = ftol = 1e-3, loss 'huber', f_scale 1).
  * Every entry point that takes it (vo_ba_adjust, vo_ba_solve_resident, vo_frame_step*, vo_pipe_create / vo_pipe_params.ba) returns
- * VO_E_INVALID with nothing enqueued for an unknown loss code or a huber_delta that is <= 0 or NaN. */
+ * VO_E_INVALID with nothing enqueued for an unknown loss code or a huber_delta that is <= 0 or NaN, and for SOFT_L1, CAUCHY and ARCTAN
+ * a huber_delta outside [VO_BA_F_SCALE_MIN, VO_BA_F_SCALE_MAX] (+inf included), where C^2 or 1 / C^2 would overflow. */
+#define VO_BA_F_SCALE_MIN 1e-150
+#define VO_BA_F_SCALE_MAX 1e150
 typedef struct {
   int32_t max_iters;         /* LM iterations (linearise + solve + evaluate) cap, e.g. 50 */
   int32_t loss;              /* VO_LOSS_*, default VO_LOSS_HUBER (0) */
@@ -314,7 +317,7 @@ int32_t vo_ba_probe(vo_ctx* ctx, double lambda, double huber_delta, double* resi
                     double* cost, double* Hpp, double* gp, double* Hll, double* gl, double* S,
                     double* rhs, double* dposes, double* dpoints);
 /* the same probe with the weights and cost of any loss (VO_LOSS_*, f_scale = C); vo_ba_probe is its VO_LOSS_HUBER case.
- * An unknown loss or an f_scale <= 0 / NaN: VO_E_INVALID, nothing enqueued. */
+ * An unknown loss, an f_scale <= 0 / NaN, or a robust loss's f_scale outside [VO_BA_F_SCALE_MIN, VO_BA_F_SCALE_MAX]: VO_E_INVALID, nothing enqueued. */
 int32_t vo_ba_probe_loss(vo_ctx* ctx, double lambda, int32_t loss, double f_scale, double* residual, int32_t* n_obs,
                          double* cost, double* Hpp, double* gp, double* Hll, double* gl, double* S,
                          double* rhs, double* dposes, double* dpoints);

@@ -274,3 +274,113 @@ def solve(K, poses0, points0, obs, max_iters=50, lam0=1e-4, ftol=1e-3, xtol=1e-3
                 status = 4
                 break
     return dict(poses=poses, points=points, cost=F, cost0=F0, iters=it, accepted=n_acc, status=status, lam=lam)
+
+
+# ---- every robust loss of scipy.optimize.least_squares (the library's vo_ba_params.loss) ----------------------------------------------
+# s = |e|^2, z = s / C^2 with C = f_scale; cost = 1/2 sum C^2 rho(z), IRLS weight w = rho'(z).  The Jacobian blocks, the Schur step and the
+# LM schedule are the ones above; 'huber' is the functions above themselves (bit for bit).
+LOSSES = ("huber", "linear", "soft_l1", "cauchy", "arctan")
+
+
+def loss_rho(s, loss, C=1.0):
+    """C^2 rho(s / C^2): the cost term of one observation (before the 1/2)"""
+    if loss == "huber":
+        return huber_rho(s, C)
+    d2 = C * C
+    z = s / d2
+    if loss == "linear":
+        return s
+    if loss == "soft_l1":
+        return d2 * 2.0 * z / (np.sqrt(1.0 + z) + 1.0)
+    if loss == "cauchy":
+        return d2 * np.log1p(z)
+    if loss == "arctan":
+        return d2 * np.arctan(z)
+    raise ValueError(loss)
+
+
+def loss_weight(s, loss, C=1.0):
+    """rho'(z)"""
+    if loss == "huber":
+        return huber_weight(s, C)
+    z = s / (C * C)
+    if loss == "linear":
+        return np.ones_like(s)
+    if loss == "soft_l1":
+        return 1.0 / np.sqrt(1.0 + z)
+    if loss == "cauchy":
+        return 1.0 / (1.0 + z)
+    if loss == "arctan":
+        return 1.0 / (1.0 + z * z)
+    raise ValueError(loss)
+
+
+def loss_cost(K, poses, points, obs, loss="huber", C=1.0):
+    if loss == "huber":
+        return cost(K, poses, points, obs, C)
+    r = residual_norm(K, poses, points, obs)
+    return 0.5 * loss_rho(r * r, loss, C).sum()
+
+
+def loss_normal_equations(K, poses, points, obs, loss="huber", C=1.0):
+    if loss == "huber":
+        return normal_equations(K, poses, points, obs, C)
+    e, Jp, Jl, m = jacobian_blocks(K, poses, points, obs)
+    s = (e * e).sum(-1)
+    w = loss_weight(s, loss, C) * m
+    Hpp = np.einsum('wn,wnka,wnkb->wab', w, Jp, Jp)
+    Hpl = np.einsum('wn,wnka,wnkb->wnab', w, Jp, Jl)
+    Hll = np.einsum('wn,wnka,wnkb->nab', w, Jl, Jl)
+    gp = np.einsum('wn,wnka,wnk->wa', w, Jp, e)
+    gl = np.einsum('wn,wnka,wnk->na', w, Jl, e)
+    c = 0.5 * (loss_rho(s, loss, C) * m).sum()
+    return dict(Hpp=Hpp, Hpl=Hpl, Hll=Hll, gp=gp, gl=gl, cost=c)
+
+
+def loss_solve(K, poses0, points0, obs, loss="huber", C=1.0, max_iters=50, lam0=1e-4, ftol=1e-3, xtol=1e-3, gtol=1e-8, lam_min=1e-3):
+    """solve() with the loss as a parameter (the same statements in the same order: 'huber' gives solve()'s bits).
+    margin: the smallest relative distance of any decision taken to its threshold (gtol, the acceptance test Ft < F with gain ratio > 0,
+    ftol, xtol) -- a solver that rounds differently can only decide otherwise where it is ~1e-16; a scene whose margin is tiny is marginal."""
+    poses, points = np.array(poses0, np.float64), np.array(points0, np.float64)
+    lam, nu = lam0, 2.0
+    F = loss_cost(K, poses, points, obs, loss, C)
+    F0 = F
+    status, it, n_acc = 0, 0, 0
+    margin = np.inf
+    rel = lambda a, b: abs(a - b) / max(abs(b), 1e-300)
+    for it in range(1, max_iters + 1):
+        ne = loss_normal_equations(K, poses, points, obs, loss, C)
+        ginf = max(np.abs(ne['gp']).max(), np.abs(ne['gl']).max())
+        margin = min(margin, rel(ginf, gtol))
+        if ginf < gtol:
+            status = 1; it -= 1
+            break
+        dp, dl, pred = lm_step(ne, lam)
+        tp, tl = poses + dp, points + dl
+        Ft = loss_cost(K, tp, tl, obs, loss, C)
+        step = np.sqrt((dp * dp).sum() + (dl * dl).sum())
+        xn = np.sqrt((poses * poses).sum() + (points * points).sum())
+        r = (F - Ft) / pred if pred > 0 else -1.0
+        margin = min(margin, rel(Ft, F), rel(step, xtol * (xtol + xn)))
+        if Ft < F and r > 0:
+            dF = F - Ft
+            poses, points, F = tp, tl, Ft
+            n_acc += 1
+            lam = lam * max(1.0 / 3.0, 1.0 - (2.0 * r - 1.0) ** 3); nu = 2.0
+            lam = max(lam, lam_min)
+            margin = min(margin, rel(dF, ftol * F))
+            if dF < ftol * F:
+                status = 2
+                break
+            if step < xtol * (xtol + xn):
+                status = 3
+                break
+        else:
+            if step < xtol * (xtol + xn):
+                status = 3
+                break
+            lam *= nu; nu *= 2.0
+            if lam > 1e12:
+                status = 4
+                break
+    return dict(poses=poses, points=points, cost=F, cost0=F0, iters=it, accepted=n_acc, status=status, lam=lam, margin=margin)

@@ -62,14 +62,21 @@ class OracleContext:
             e.append(np.linalg.norm(uv - p[:, :2] / p[:, 2:3], axis=1))
         return X4, depth1, (e[0] + e[1]) / 2
 
-    def ba_params(self, max_iters=50, ftol=1e-3, xtol=1e-3, gtol=1e-8, lambda0=1e-4, huber_delta=1.0, lambda_min=1e-3):
+    def ba_params(self, max_iters=50, ftol=1e-3, xtol=1e-3, gtol=1e-8, lambda0=1e-4, huber_delta=1.0, lambda_min=1e-3, loss="huber"):
+        if loss not in bo.LOSSES:
+            raise ValueError("unknown loss %r" % (loss,))
         return SimpleNamespace(max_iters=max_iters, ftol=ftol, xtol=xtol, gtol=gtol, lambda0=lambda0, huber_delta=huber_delta,
-                               lambda_min=lambda_min)
+                               lambda_min=lambda_min, loss=loss)
 
     def ba_adjust(self, K, poses, points, obs, params=None):
         prm = params or self.ba_params()
-        r = bo.solve(K, poses, points, obs, max_iters=prm.max_iters, lam0=prm.lambda0, ftol=prm.ftol, xtol=prm.xtol,
-                     gtol=prm.gtol, delta=prm.huber_delta, lam_min=prm.lambda_min)
+        loss = getattr(prm, "loss", "huber")
+        if loss == "huber":
+            r = bo.solve(K, poses, points, obs, max_iters=prm.max_iters, lam0=prm.lambda0, ftol=prm.ftol, xtol=prm.xtol,
+                         gtol=prm.gtol, delta=prm.huber_delta, lam_min=prm.lambda_min)
+        else:
+            r = bo.loss_solve(K, poses, points, obs, loss, prm.huber_delta, max_iters=prm.max_iters, lam0=prm.lambda0, ftol=prm.ftol,
+                              xtol=prm.xtol, gtol=prm.gtol, lam_min=prm.lambda_min)
         return r["poses"], r["points"], dict(cost0=r["cost0"], cost=r["cost"], lam=r["lam"], iters=r["iters"],
                                              accepted=r["accepted"], status=r["status"], n_obs=int(bo.valid_mask(obs).sum()))
 

@@ -110,11 +110,12 @@ def cpython_set_order(keys):
 
 class Params:
     def __init__(self, ba_window=4, min_track_length=3, mask_radius=7, max_new=1000, max_reproj_err=2.0, min_bearing_angle=0.5,
-                 ba_max_iters=50, ba_ftol=1e-3, ba_xtol=1e-3, pnp_seed=0, min_distance=7, resurrect=True):
+                 ba_max_iters=50, ba_ftol=1e-3, ba_xtol=1e-3, pnp_seed=0, min_distance=7, resurrect=True, ba_loss="huber", ba_f_scale=1.0):
         self.ba_window, self.min_track_length, self.mask_radius, self.max_new = ba_window, min_track_length, mask_radius, max_new
         self.max_reproj_err, self.min_bearing_angle = max_reproj_err, min_bearing_angle
         self.ba_max_iters, self.ba_ftol, self.ba_xtol, self.pnp_seed, self.min_distance = ba_max_iters, ba_ftol, ba_xtol, pnp_seed, min_distance
         self.resurrect = resurrect       # False: dead landmarks stay dead (not the reference; see vo_pipe_params.resurrect)
+        self.ba_loss, self.ba_f_scale = ba_loss, ba_f_scale    # the ADJUST stage's robust loss and its f_scale (scipy's names)
 
 
 class PipeModel:
@@ -395,7 +396,7 @@ class PipeModel:
         N, W = len(points), prm.ba_window
         self.info["ba"] = None
         if N > 0 and not np.isnan(obs[..., 0]).all():
-            bp = self.ctx.ba_params(max_iters=prm.ba_max_iters, ftol=prm.ba_ftol, xtol=prm.ba_xtol)
+            bp = self.ctx.ba_params(max_iters=prm.ba_max_iters, ftol=prm.ba_ftol, xtol=prm.ba_xtol, huber_delta=prm.ba_f_scale, loss=prm.ba_loss)
             poses, points, self.info["ba"] = self.ctx.ba_adjust(self.K, poses, points, obs, bp)
         for i in range(N):                 # in list order: entries sharing a landmark object -- the last one wins (:197-201)
             self.l_p[self.lm_L[i]] = points[i]

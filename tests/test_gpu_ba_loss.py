@@ -102,14 +102,15 @@ def test_bad_loss_and_f_scale_are_rejected(ctx):
     W, N = obs.shape[:2]
     f64 = lambda a: np.ascontiguousarray(a, np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double))
     po, pt = np.zeros((W, 6)), np.zeros((N, 3))
-    for loss, fs in ((5, 1.0), (-1, 1.0), (3, 0.0), (3, -1.0), (2, float("nan"))):
+    # (a robust loss's f_scale outside [1e-150, 1e150], +inf included: C^2 or 1 / C^2 would overflow -- tests/test_gpu_ba_loss_forms.py)
+    for loss, fs in ((5, 1.0), (-1, 1.0), (3, 0.0), (3, -1.0), (2, float("nan")), (3, float("inf")), (4, 1e200), (2, 1e-200), (4, 5e-324)):
         p = ctx.ba_params(max_iters=5)
         p.loss, p.huber_delta = loss, fs
         r = L.vo_ba_adjust(ctx._h, f64(K), f64(poses), f64(points), f64(obs), W, N, ctypes.byref(p), f64(po), f64(pt), None)
         assert r == -1, (loss, fs, r)                                # VO_E_INVALID
         assert not po.any() and not pt.any()
     ctx.ba_upload(K, poses, points, obs)
-    for loss, fs in ((7, 1.0), (3, 0.0), (3, float("nan"))):
+    for loss, fs in ((7, 1.0), (3, 0.0), (3, float("nan")), (4, float("inf")), (2, 2e150), (3, 1e-151)):
         with pytest.raises(_lib.VoError):
             ctx._ck(L.vo_ba_probe_loss(ctx._h, 1e-4, loss, fs, None, None, None, None, None, None, None, None, None, None, None))
     with pytest.raises(ValueError):

@@ -412,6 +412,15 @@ __device__ __forceinline__ double ba_atan(double z) {
 //   cauchy   log1p(z),  w = 1 / (1 + z)
 //   arctan   atan(z),   w = 1 / (1 + z^2)
 // The weights come from v_rsq / v_rcp + Newton steps like the rest of the solver; log1p and atan (ba_log1p, ba_atan) feed the cost sums only.
+// vo_ba_check_params keeps C in [VO_BA_F_SCALE_MIN, VO_BA_F_SCALE_MAX] for these losses (C^2 and 1 / C^2 finite and normal); z is still
+// unbounded (a point close to a camera plane), so it is capped below inf (rsqrt_nr / rcp_nr of inf are NaN), and arctan's weight takes
+// z <= ~2^511: every weight finite and >= 0, every cost term finite.
+// The caps clamp the high word of z >= 0 as an unsigned integer: one v_min_u32 with a literal, where an f64 constant for v_min_f64 would
+// take two scalar registers in every robust build / update kernel.
+__device__ __forceinline__ double ba_cap_hi(double x, unsigned hi_max) {
+  const unsigned hi = min((unsigned)__double2hiint(x), hi_max);
+  return __hiloint2double((int)hi, __double2loint(x));
+}
 template <int LOSS>
 __device__ __forceinline__ void ba_loss(double s, double delta, double d2, double id2, double& w, double& rho) {
   if constexpr (LOSS == VO_LOSS_HUBER) {
@@ -420,7 +429,7 @@ __device__ __forceinline__ void ba_loss(double s, double delta, double d2, doubl
     w = inl ? 1.0 : delta * irs;
     rho = inl ? s : 2.0 * delta * (s * irs) - d2;
   } else {
-    const double z = s * id2, opz = 1.0 + z;
+    const double z = ba_cap_hi(s * id2, 0x7FEFFFFFu), opz = 1.0 + z;     // (a residual far beyond f_scale: z ~ 1.8e308, not inf)
     if constexpr (LOSS == VO_LOSS_SOFT_L1) {
       w = rsqrt_nr(opz);
       rho = 2.0 * s * rcp_nr(fma(opz, w, 1.0));          // opz w = sqrt(1 + z)
@@ -429,7 +438,8 @@ __device__ __forceinline__ void ba_loss(double s, double delta, double d2, doubl
       rho = d2 * ba_log1p(z);
     } else {
       static_assert(LOSS == VO_LOSS_ARCTAN, "a robust loss");
-      w = rcp_nr(fma(z, z, 1.0));
+      const double zw = ba_cap_hi(z, 0x5FE00000u);          // (z <= ~2^511, z^2 finite: w ~ 2^-1022 where 1 / (1 + z^2) is below it)
+      w = rcp_nr(fma(zw, zw, 1.0));
       rho = d2 * ba_atan(z);
     }
   }
@@ -1668,6 +1678,9 @@ static ba_ptrs ba_make_ptrs_dbg(vo_ctx* c) { ba_ptrs P = ba_make_ptrs(c); P.dbg 
 int32_t vo_ba_check_params(vo_ctx* c, const vo_ba_params* p) {
   VO_CHECK(c, p->loss >= VO_LOSS_HUBER && p->loss <= VO_LOSS_ARCTAN, VO_E_INVALID, "unknown loss (VO_LOSS_*)");
   VO_CHECK(c, p->huber_delta > 0.0, VO_E_INVALID, "huber_delta (f_scale) must be > 0");     // (NaN fails the comparison)
+  // soft_l1 / cauchy / arctan divide by C^2 and scale by it: outside this range C^2 or 1 / C^2 overflows (rho = inf * 0, rcp_nr(inf): NaN)
+  VO_CHECK(c, p->loss < VO_LOSS_SOFT_L1 || (p->huber_delta >= VO_BA_F_SCALE_MIN && p->huber_delta <= VO_BA_F_SCALE_MAX), VO_E_INVALID,
+           "f_scale of a robust loss must be in [1e-150, 1e150]");
   return VO_OK;
 }
 
