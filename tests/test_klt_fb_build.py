@@ -1,7 +1,12 @@
 """CPU-only: what hipcc makes of the tracker kernels (gfx950 cross-compile, no GPU needed).
 
-k_klt_track_fb (csrc/vo_klt_fb.hip: forward + backward LK in one launch) must run without scratch at >= 5 waves per SIMD, and moving the LK
-helpers into csrc/vo_klt_lk.h for it must leave k_klt_track<4|5|6> exactly where they were: 79 / 81 VGPRs, 88 SGPRs, no scratch, occupancy 6 / 5."""
+k_klt_track (csrc/vo_klt.hip) and k_klt_track_fb (csrc/vo_klt_fb.hip: forward + backward LK in one launch) call ONE per-point LK body,
+klt_lk_point (csrc/vo_klt_lk.h).  k_klt_track_fb must run without scratch at >= 5 waves per SIMD, and sharing the body must leave
+k_klt_track<4|5|6> where they were: 79 / 81 VGPRs, 88 SGPRs, no scratch, occupancy 6 / 5, and -- stronger than the register pin -- the
+same count of every vector, buffer, LDS and global instruction as the build of the commit before the body was shared
+(tests/golden/klt_parent_opcodes.json)."""
+import collections
+import json
 import os
 import re
 import shutil
@@ -26,6 +31,23 @@ def _flags():
     m = re.search(r"^CXXFLAGS \?=(.*?)(?<!\\)\n", mk, flags=re.M | re.S)
     flags = m.group(1).replace("\\\n", " ").replace("$(ARCH)", "gfx950").split()
     return [f for f in flags if f != "-fPIC"]
+
+
+def _opcodes(src, kernel, tmp_path):
+    """opcode -> count over the device assembly of the one kernel whose mangled name contains `kernel`"""
+    asm = tmp_path / "k.s"
+    out = subprocess.run([_hipcc()] + _flags() + ["--cuda-device-only", "-S", src, "-o", str(asm)], cwd=CSRC, capture_output=True, text=True,
+                         timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = asm.read_text().split("\n")
+    (start,) = [i for i, l in enumerate(lines) if re.match(r"_Z\w*%s\w*:" % kernel, l)]
+    end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith(".Lfunc_end"))
+    h = collections.Counter()
+    for l in lines[start + 1:end]:
+        m = re.match(r"\s+([a-z][a-z0-9_]+)(\s|$)", l)
+        if m:
+            h[m.group(1)] += 1
+    return h
 
 
 def _resources(src, tmp_path):
@@ -59,3 +81,18 @@ def test_klt_track_resources_unchanged(tmp_path):
     for wv, (vgpr, occ) in want.items():
         (r,) = [v for k, v in res.items() if re.search(r"k_klt_trackILi%dE" % wv, k)]
         assert (r["VGPRs"], r["TotalSGPRs"], r["ScratchSize"], r["Occupancy"]) == (vgpr, 88, 0, occ), (wv, r)
+
+
+@pytest.mark.parametrize("src,kernel,name", [("vo_klt.hip", "k_klt_trackILi6E", "k_klt_track<6>"),
+                                             ("vo_klt_fb.hip", "k_klt_track_fbILi6E", "k_klt_track_fb<6>")])
+def test_klt_vector_and_memory_opcodes_equal_the_parents(src, kernel, name, tmp_path):
+    """every v_*, buffer_*, ds_* and global_* opcode as often as in the parent commit's build of the same kernel (a committed histogram,
+    never the tree under test); scalar opcodes are reported, not asserted"""
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "klt_parent_opcodes.json")))[name]
+    got = _opcodes(src, kernel, tmp_path)
+    pinned = ("v_", "buffer_", "ds_", "global_")
+    assert sum(1 for k in want if k.startswith(pinned)) > 50 and any(k.startswith("buffer_load") for k in want), "fixture"
+    diff = {k: (want.get(k, 0), got.get(k, 0)) for k in sorted(set(want) | set(got)) if want.get(k, 0) != got.get(k, 0)}
+    scalar = {k: v for k, v in diff.items() if not k.startswith(pinned)}
+    vector = {k: v for k, v in diff.items() if k.startswith(pinned)}
+    assert not vector, "%s (parent, now): %s; scalar differences (not asserted): %s" % (name, vector, scalar)

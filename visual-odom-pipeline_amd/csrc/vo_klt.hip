@@ -7,18 +7,7 @@
 // normal matrix / mismatch vector summed EXACTLY in integers (oracle/vo_oracle.c acc_mode = 1), so
 // results are bit-identical to the CPU oracle independent of summation order.
 //
-// Lane <-> window mapping (window <= 31x31, read footprint 32 rows x 34 bytes):
-//   lane = r*16 + cp,  cp = 0..15 (column pair), r = 0..3;  step s = 0..7 covers window row 8r + s,
-//   columns 2cp and 2cp+1.  One unaligned dword load per lane per step fetches the 3 bytes the two
-//   bilinear footprints need from the top row; the bottom row of step s is the SAME lane's top row of
-//   step s + 1 (already in a register, its byte gathers are shared), only step 7 takes it from the
-//   lane 16 further up (row group r + 1, step 0: one ds_bpermute per iteration).  => 8 dword loads per
-//   lane per LK iteration for a 1 KB window, served by L1/L2 (a pyramid level is <= 0.6 MB; HBM sees it once).
-//   The 16 lanes of a row group read 34 CONSECUTIVE bytes, so a load instruction touches 4 rows = 4-8 cache lines and each
-//   quad of lanes one line.  (With lane = cp*4 + r -- a quad = four different rows, chosen in round 1 for a one-instruction
-//   DPP neighbour exchange -- the texture addresser issued 28 cache accesses per load instruction and was busy 91 % of the
-//   kernel: the kernel was bound by it, not by the vector ALUs; profiles/r02_pmc_klt_*.txt.)
-//   The template (I, Ix, Iy at 16 pixels per lane) lives in 24 VGPRs across all iterations.
+// The per-point body (klt_lk_point) and its lane <-> window mapping are in vo_klt_lk.h, shared with k_klt_track_fb (vo_klt_fb.hip).
 #include "vo_klt_lk.h"
 
 #include <stdlib.h>
@@ -52,189 +41,10 @@ __global__ void __launch_bounds__(64, WAVES) k_klt_track(klt_args A, const float
   p0 = vo_seq(p0, A.slab_seq, bseq); p1 = vo_seq(p1, A.slab_seq, bseq);
   status = vo_seq(status, A.slab_seq, bseq); err = vo_seq(err, A.slab_seq, bseq);
   unsigned long long* dbgk = (pt == A.n / 2 && bseq == 0 && dbg) ? dbg + 24 : nullptr;   // diagnostic stamps of one wave
-  VO_STAMP(dbgk, 0);
-  const int cp = lane & 15, r = lane >> 4;
-  const int win = A.win;
-  const float half = (float)(win - 1) * 0.5f;
-  const float FLT_SCALE = 1.f / (float)(1 << 20);
-
   const float p0x = uniform_f(p0[2 * pt]), p0y = uniform_f(p0[2 * pt + 1]);
-  float outx = 0.f, outy = 0.f;   // nextPts[pt]
-  int st = 1;
-  float errv = 0.f;
-
-  // validity of the lane's two columns as 16-bit masks (lo = column 2cp, hi = column 2cp + 1)
-  const uint32_t colmask = ((2 * cp < win) ? 0x0000FFFFu : 0u) | ((2 * cp + 1 < win) ? 0xFFFF0000u : 0u);
-  const uint32_t colones = colmask & 0x00010001u;
-  // v_perm selector "upper halves of (a, b)" with the constant-zero code 0x0c for the columns outside the window
-  const uint32_t colsel = (0x07060302u & colmask) | (0x0c0c0c0cu & ~colmask);
-
-  for (int level = A.top; level >= 0; level--) {
-    klt_level_args L = A.lv[level];
-    L.imgI += (size_t)bseq * L.seq_px; L.derI += (size_t)bseq * L.seq_px; L.imgJ += (size_t)bseq * L.seq_px;
-    const float scale = __int_as_float((127 - level) << 23);       // 2^-level, exactly what 1.f / (float)(1 << level) gives (no division)
-    float prevx = p0x * scale, prevy = p0y * scale;
-    float nextx, nexty;
-    if (level == A.top) { nextx = prevx; nexty = prevy; }
-    else { nextx = outx * 2.f; nexty = outy * 2.f; }
-    outx = nextx; outy = nexty;
-    int n_it = -1;
-
-    prevx -= half; prevy -= half;
-    const float fpx = floorf(prevx), fpy = floorf(prevy);        // (float)(int)floorf(x) == floorf(x): the fraction needs no int -> float convert
-    const int ipx = (int)fpx, ipy = (int)fpy;
-    if (ipx < -win || ipx >= L.w || ipy < -win || ipy >= L.h) {
-      if (level == 0) { st = 0; errv = 0.f; }
-      if (iters && lane == 0) iters[pt * A.iters_stride + level] = n_it;
-      continue;
-    }
-    const uint32_t lane_off = (uint32_t)(8 * r * L.pitch + 2 * cp);    // the lane's corner of the 32 x 34 footprint
-    uint32_t wt, wb;
-    lk_weights(prevx - fpx, prevy - fpy, wt, wb);
-
-    // ---- template: packed pairs of I (5 frac bits), Ix, Iy for the lane's 16 pixels; exact A11, A12, A22 ----
-    uint32_t tI[8], tX[8], tY[8];
-    {
-      uint32_t T[8], D0[8], D1[8], D2[8];
-      // addresses = level base (scalar registers) + a 32-bit offset: the wave-uniform window origin, advanced per row on the
-      // scalar unit, plus ONE per-lane offset that is fixed for the level (it was a chain of 64-bit vector adds per row)
-      const uint32_t uo = (uint32_t)(ipy + VO_PAD) * (uint32_t)L.pitch + (uint32_t)(ipx + VO_PAD);
-      const __amdgpu_buffer_rsrc_t rI = klt_rsrc(L.imgI), rD = klt_rsrc(L.derI);
-#pragma unroll
-      for (int s = 0; s < 8; s++) {
-        const uint32_t o = uo + (uint32_t)s * (uint32_t)L.pitch;          // wave-uniform
-        T[s] = __builtin_amdgcn_raw_buffer_load_b32(rI, (int)lane_off, (int)o, 0);
-        // three consecutive pixels: one 12-byte load.  (8 bytes + the neighbour lane's first pixel through a DPP row shift was
-        // measured: the same kernel time -- the data path is not priced per byte.)
-        const u32x3 d3 = __builtin_amdgcn_raw_buffer_load_b96(rD, (int)(lane_off * 4u), (int)(o * 4u), 0);
-        D0[s] = d3[0]; D1[s] = d3[1]; D2[s] = d3[2];
-      }
-      // row 8r + 8 = step 0 of row group r + 1 (lanes of r == 3 receive a row that only masked pixels use)
-      const uint32_t T8 = row_next(T[0], lane), D08 = row_next(D0[0], lane), D18 = row_next(D1[0], lane), D28 = row_next(D2[0], lane);
-      int a11 = 0, a12 = 0, a22 = 0;
-#pragma unroll
-      for (int s = 0; s < 8; s++) {
-        const uint32_t B = (s < 7) ? T[(s + 1) & 7] : T8;
-        const uint32_t E0 = (s < 7) ? D0[(s + 1) & 7] : D08;
-        const uint32_t E1 = (s < 7) ? D1[(s + 1) & 7] : D18;
-        const uint32_t E2 = (s < 7) ? D2[(s + 1) & 7] : D28;
-        tI[s] = sample2(T[s], B, wt, wb);
-        const uint32_t x0 = deriv1(pack_lo(D0[s], D1[s]), pack_lo(E0, E1), wt, wb);
-        const uint32_t y0 = deriv1(pack_hi(D0[s], D1[s]), pack_hi(E0, E1), wt, wb);
-        const uint32_t x1 = deriv1(pack_lo(D1[s], D2[s]), pack_lo(E1, E2), wt, wb);
-        const uint32_t y1 = deriv1(pack_hi(D1[s], D2[s]), pack_hi(E1, E2), wt, wb);
-        const uint32_t sel = (8 * r + s < win) ? colsel : 0x0c0c0c0cu;    // rows / columns outside the window contribute nothing
-        const uint32_t xp = __builtin_amdgcn_perm(x1, x0, sel), yp = __builtin_amdgcn_perm(y1, y0, sel);
-        tX[s] = xp; tY[s] = yp;
-        // the first step starts the three sums from an inline zero (three-address form: no preload)
-        a11 = s ? dot2(xp, xp, a11) : dot2k(xp, xp, 0);
-        a12 = s ? dot2(xp, yp, a12) : dot2k(xp, yp, 0);
-        a22 = s ? dot2(yp, yp, a22) : dot2k(yp, yp, 0);
-      }
-      float A11, A12, A22;
-      {
-        // per lane 16 products of two int16 derivatives (|Scharr| <= 4080): < 2^28.01, a quad's sum < 2^30.01
-        int l11, h11, l12, h12, l22, h22;
-        wave_sum3_wide(a11, a12, a22, lane, l11, h11, l12, h12, l22, h22);
-        A11 = klt_combine(h11, l11) * FLT_SCALE; A12 = klt_combine(h12, l12) * FLT_SCALE; A22 = klt_combine(h22, l22) * FLT_SCALE;
-      }
-      if (level == A.top) VO_STAMP(dbgk, 1);   // first template
-      float D = A11 * A22 - A12 * A12;
-      // minEig = num / (2 win^2) < minEigThreshold, decided on the numerator (threshold pre-divided exactly on the host)
-      const float num = A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12);
-      if (num < A.min_eig_num || D < 1.1920929e-07f) {
-        if (level == 0) st = 0;
-        if (iters && lane == 0) iters[pt * A.iters_stride + level] = n_it;
-        continue;
-      }
-      D = 1.f / D;
-
-      nextx -= half; nexty -= half;
-      const __amdgpu_buffer_rsrc_t rJ = klt_rsrc(L.imgJ);
-      float pdx = 0.f, pdy = 0.f;
-      int j = 0;
-      for (; j < A.max_count; j++) {
-        const float fnx = floorf(nextx), fny = floorf(nexty);
-        const int inx = (int)fnx, iny = (int)fny;
-        if (inx < -win || inx >= L.w || iny < -win || iny >= L.h) {
-          if (level == 0) st = 0;
-          break;
-        }
-        uint32_t jt, jb;
-        lk_weights(nextx - fnx, nexty - fny, jt, jb);
-        uint32_t Tj[8];
-        const uint32_t uj = (uint32_t)(iny + VO_PAD) * (uint32_t)L.pitch + (uint32_t)(inx + VO_PAD);
-#pragma unroll
-        for (int s = 0; s < 8; s++) Tj[s] = __builtin_amdgcn_raw_buffer_load_b32(rJ, (int)lane_off, (int)(uj + (uint32_t)s * (uint32_t)L.pitch), 0);
-        const uint32_t Tj8 = row_next(Tj[0], lane);
-        int b1 = 0, b2 = 0;
-#pragma unroll
-        for (int s = 0; s < 8; s++) {
-          const uint32_t B = (s < 7) ? Tj[(s + 1) & 7] : Tj8;
-          const uint32_t d = pk_sub(sample2(Tj[s], B, jt, jb), tI[s]);   // (diff0 | diff1 << 16), |diff| <= 8160
-          b1 = s ? dot2(d, tX[s], b1) : dot2k(d, tX[0], 0);
-          b2 = s ? dot2(d, tY[s], b2) : dot2k(d, tY[0], 0);
-        }
-        // per lane 16 products |diff| <= 8160 (255 << 5) times |derivative| <= 4080: < 2^28.99, a quad's sum < 2^30.99
-        int l1, h1, l2, h2;
-        wave_sum2_wide(b1, b2, lane, l1, h1, l2, h2);
-        const float fb1 = klt_combine(h1, l1) * FLT_SCALE;
-        const float fb2 = klt_combine(h2, l2) * FLT_SCALE;
-        const float dx = (A12 * fb2 - A22 * fb1) * D;
-        const float dy = (A12 * fb1 - A11 * fb2) * D;
-        nextx += dx; nexty += dy;
-        outx = nextx + half; outy = nexty + half;
-        // |delta|^2 <= eps^2 is OpenCV's float64 test; its float32 value is within 2^-22 of it, so only a value between the
-        // two guard constants needs the float64 evaluation
-        const float d2 = dx * dx + dy * dy;
-        bool conv;
-        if (d2 < A.eps_lo) conv = true;
-        else if (d2 > A.eps_hi) conv = false;
-        else conv = (double)dx * (double)dx + (double)dy * (double)dy <= A.eps2;
-        if (conv) { j++; break; }
-        // fabs((double)x) < 0.01 for a float x  <=>  fabsf(x) <= (float)0.01: 0.01 lies strictly between that float and the next
-        if (j > 0 && fabsf(dx + pdx) <= 0.01f && fabsf(dy + pdy) <= 0.01f) {
-          outx -= dx * 0.5f; outy -= dy * 0.5f;
-          j++;
-          break;
-        }
-        pdx = dx; pdy = dy;
-        if (level == A.top && j == 0) VO_STAMP(dbgk, 2);   // first LK iteration
-      }
-      n_it = j;
-      if (level == A.top) VO_STAMP(dbgk, 3);   // top level done
-      if (level == 1) VO_STAMP(dbgk, 4);       // levels top-1 .. 1 done
-      if (iters && lane == 0) iters[pt * A.iters_stride + level] = n_it;
-
-      if (st && level == 0) {
-        const float nx = outx - half, ny = outy - half;
-        const float fnx = floorf(nx), fny = floorf(ny);
-        const int inx = (int)fnx, iny = (int)fny;
-        if (inx < -win || inx >= L.w || iny < -win || iny >= L.h) {
-          st = 0;
-        } else {
-          uint32_t jt, jb;
-          lk_weights(nx - fnx, ny - fny, jt, jb);
-          uint32_t Tj[8];
-          const uint32_t uj = (uint32_t)(iny + VO_PAD) * (uint32_t)L.pitch + (uint32_t)(inx + VO_PAD);
-#pragma unroll
-          for (int s = 0; s < 8; s++) Tj[s] = __builtin_amdgcn_raw_buffer_load_b32(rJ, (int)lane_off, (int)(uj + (uint32_t)s * (uint32_t)L.pitch), 0);
-          const uint32_t Tj8 = row_next(Tj[0], lane);
-          int e = 0;
-#pragma unroll
-          for (int s = 0; s < 8; s++) {
-            const uint32_t B = (s < 7) ? Tj[(s + 1) & 7] : Tj8;
-            const uint32_t d = pk_abs(pk_sub(sample2(Tj[s], B, jt, jb), tI[s]));
-            const uint32_t ones = (8 * r + s < win) ? colones : 0u;
-            e = s ? dot2(d, ones, e) : dot2k(d, ones, 0);
-          }
-          const int ierr = wave_sum_i32(e);
-          errv = (float)ierr * 1.f / (float)(32 * win * win);
-        }
-      }
-    }
-  }
-  VO_STAMP(dbgk, 5);
+  float outx, outy, errv;
+  int st;
+  klt_lk_point(A, A.lv, bseq, pt, lane, p0x, p0y, iters, dbgk, outx, outy, st, errv);
   if (lane == 0) {
     p1[2 * pt] = outx; p1[2 * pt + 1] = outy;
     status[pt] = (uint8_t)st;
