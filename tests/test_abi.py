@@ -68,6 +68,27 @@ def test_the_library_reads_no_tuning_from_the_environment():
     assert tuple(re.findall(r"int32_t\s+(\w+);", body)) == _lib.TUNING_FIELDS
 
 
+def test_no_stage_picks_its_stream_from_swapped_context_state():
+    """Enqueue functions take their stream as an argument: the ctx stream is assigned where the context is created and where it is re-created
+    with a CU mask, nowhere else, and the fields that carried per-call arguments of a stage through the context are gone.
+    A source scan of the pattern this code base used (`c->stream = ...` inside a function defined in column 0): a swap through another spelling of
+    the context (`ctx->stream`, `std::swap`) would get past it."""
+    src = os.path.join(ROOT, "visual-odom-pipeline_amd", "csrc")
+    assigned_in = set()
+    for f in sorted(os.listdir(src)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        txt = open(os.path.join(src, f)).read()
+        for name in ("in_step", "ba_wait_before_publish", "ba_wide_event", "vo_ba_set_live"):
+            assert not re.search(r"\b%s\b" % name, txt), (f, name)
+        for m in re.finditer(r"c\s*->\s*stream\s*=(?!=)", txt):
+            # the enclosing function: the last definition that starts in column 0 before the match
+            heads = re.findall(r"^(?:extern \"C\" |static )?[A-Za-z_][\w \*:<>]*?\b(\w+)\s*\([^;{]*\)\s*\{", txt[:m.start()], flags=re.M)
+            assigned_in.add(heads[-1] if heads else f)
+    assert assigned_in <= {"vo_ctx_create_batched", "vo_main_stream_reserve"}, assigned_in
+    assert "vo_main_stream_reserve" in assigned_in          # (the pattern still finds an assignment where there is one)
+
+
 def test_no_cpu_fallback_without_a_device():
     """On a box without a GPU the product must fail loudly, not compute on the CPU."""
     from vo_mi355x import _lib, VoContext, VoError

@@ -24,7 +24,7 @@
 // group, camera sums are cross-group shuffles + one LDS pass, so every observation is linearised exactly once
 // per kernel and nothing is re-read from HBM.
 //
-// One LM iteration = 3 launches on the ctx stream (state double-buffered by iteration parity):
+// One LM iteration = 3 launches on the stream of the enqueue (state double-buffered by iteration parity):
 //   k_ba_build  : [decide previous step]; per workgroup (1024 lanes = 64 or 32 landmarks): linearise, H_ll/g_l,
 //                 damped 3x3 inverse factor L_j, camera partial sums (H_pp, g_p, cost); the workgroup's slice of
 //                 Y^ = [H_pl L | L^T g_l] is staged in LDS ((3 PPB) x RP panel, 120 KB) and its Gram matrix
@@ -152,7 +152,6 @@ struct vo_ba_ws {
   double* d_x0_own = nullptr; double* d_obs_own = nullptr;
   double* d_bank_x0 = nullptr; double* d_bank_obs = nullptr;
   int bank_n = 0, bank_sel = 0;
-  const int32_t* d_nlive = nullptr; int nlive_stride = 0;     // vo_ba_set_live
   // wave-private kernels (vo_ba_wave.h): windows of <= 10 slots
   int v2 = 0, v2_rt = 0, v2_spl = 0, v2_lpp = 8;
   size_t v2_lds = 0;
@@ -1585,7 +1584,6 @@ extern "C" int32_t vo_ba_upload_bank(vo_ctx* c, const double* K, const double* p
   b->d_x0_own = b->d_x0; b->d_obs_own = b->d_obs;
   b->d_x0 = b->d_bank_x0; b->d_obs = b->d_bank_obs;
   b->bank_n = n_problems; b->bank_sel = 0;
-  b->d_nlive = nullptr; b->nlive_stride = 0;      // a dense uploaded problem: every slot counts
   b->uploaded = true;
   return VO_OK;
 }
@@ -1603,7 +1601,8 @@ extern "C" int32_t vo_ba_select_problem(vo_ctx* c, int32_t k) {
   return VO_OK;
 }
 
-static ba_ptrs ba_make_ptrs(const vo_ctx* c) {
+// o: the options of the enqueue the pointers are for (all zero outside the step orchestrators)
+static ba_ptrs ba_make_ptrs(const vo_ctx* c, const vo_ba_enqueue_opts& o) {
   vo_ba_ws* b = c->ba;
   ba_ptrs P;
   P.K = b->d_K; P.obs = b->d_obs; P.x0 = b->d_x0; P.xa = b->d_x[0]; P.xb = b->d_x[1]; P.aux = b->d_aux;
@@ -1652,7 +1651,7 @@ static ba_ptrs ba_make_ptrs(const vo_ctx* c) {
   P.s_evalpart = (size_t)b->nblk * BA_EVAL_VALS; P.s_tilesum = b->red_stride; P.s_posesum = b->red_stride;
   P.s_cams = 2 * W * BA_CAM;
   P.sharded = c->ba_sharded; P.rank = c->comm_rank; P.n_ranks = c->comm_ranks; P.batch = c->batch;
-  P.n_live = b->d_nlive; P.s_nlive = b->nlive_stride;
+  P.n_live = o.d_live; P.s_nlive = o.live_stride;       // closed loop: d_live[b * live_stride] landmark slots of problem b are in use (null: all N)
   {
     // the solve sums the partial sets itself when that is ONE trip per thread (lower triangle of [S rhs] + camera sums <= 1 024 values: windows
     // of <= 6 slots; <= 32 sets) and no exchange between shards needs the reduced packet; vo_tuning.ba_fold = 1 / 2 overrides (A/B).  Measured
@@ -1667,12 +1666,7 @@ static ba_ptrs ba_make_ptrs(const vo_ctx* c) {
   return P;
 }
 
-// closed loop: counts[b * stride] landmark slots of problem b are in use (device memory, read by every launch; null: all N)
-void vo_ba_set_live(vo_ctx* c, const int32_t* d_counts, int stride) {
-  if (!c->ba) return;
-  c->ba->d_nlive = d_counts; c->ba->nlive_stride = stride;
-}
-static ba_ptrs ba_make_ptrs_dbg(vo_ctx* c) { ba_ptrs P = ba_make_ptrs(c); P.dbg = c->d_dbg; return P; }
+static ba_ptrs ba_make_ptrs_dbg(vo_ctx* c) { ba_ptrs P = ba_make_ptrs(c, {}); P.dbg = c->d_dbg; return P; }
 
 // the loss fields of a vo_ba_params: a known code and a positive f_scale
 int32_t vo_ba_check_params(vo_ctx* c, const vo_ba_params* p) {
@@ -1713,108 +1707,118 @@ extern "C" int32_t vo_ba_upload(vo_ctx* c, const double* K, const double* poses,
   VO_HIP(c, hipMemcpy2DAsync(b->d_x0, sizeof(double) * nx, poses, sizeof(double) * 6 * W, sizeof(double) * 6 * W, B, hipMemcpyHostToDevice, c->stream));
   VO_HIP(c, hipMemcpy2DAsync(b->d_x0 + 6 * W, sizeof(double) * nx, points, sizeof(double) * 3 * N, sizeof(double) * 3 * N, B, hipMemcpyHostToDevice, c->stream));
   VO_HIP(c, hipStreamSynchronize(c->stream));
-  b->d_nlive = nullptr; b->nlive_stride = 0;      // a dense uploaded problem: every slot counts
   b->uploaded = true;
   return VO_OK;
 }
 
 template <int LOSS>
-static int32_t ba_launch_iter_t(vo_ctx* c, const ba_ptrs& P, const ba_params_dev& prm, int it, double probe_lambda,
+static int32_t ba_launch_iter_t(vo_ctx* c, hipStream_t q, const ba_ptrs& P, const ba_params_dev& prm, int it, double probe_lambda,
                                 double* probe_S, double* hpp_out, double* probe_dl) {
   vo_ba_ws* b = c->ba;
   const int B = c->batch;
   if (b->v2) {
     const dim3 g(b->v2_g0 * B);
     const int g0 = b->v2_g0, gc = b->v2_gcap;
-    if (b->v2_spl == 2 && b->v2_lpp == 5) hipLaunchKernelGGL((k_ba_build_w<4, 2, 5, LOSS>), g, dim3(256), b->v2_lds, c->stream, P, prm, it, probe_lambda, g0, gc);
-    else if (b->v2_spl == 2) hipLaunchKernelGGL((k_ba_build_w<4, 2, 8, LOSS>), g, dim3(256), b->v2_lds, c->stream, P, prm, it, probe_lambda, g0, gc);
-    else if (b->v2_rt == 4) hipLaunchKernelGGL((k_ba_build_w<4, 1, 8, LOSS>), g, dim3(256), b->v2_lds, c->stream, P, prm, it, probe_lambda, g0, gc);
-    else if (b->v2_rt == 3) hipLaunchKernelGGL((k_ba_build_w<3, 1, 8, LOSS>), g, dim3(256), b->v2_lds, c->stream, P, prm, it, probe_lambda, g0, gc);
-    else if (b->v2_rt == 2 && b->v2_lpp == 4) hipLaunchKernelGGL((k_ba_build_w<2, 1, 4, LOSS>), g, dim3(256), b->v2_lds, c->stream, P, prm, it, probe_lambda, g0, gc);
-    else if (b->v2_rt == 2) hipLaunchKernelGGL((k_ba_build_w<2, 1, 8, LOSS>), g, dim3(256), b->v2_lds, c->stream, P, prm, it, probe_lambda, g0, gc);
-    else if (b->v2_lpp == 4) hipLaunchKernelGGL((k_ba_build_w<1, 1, 4, LOSS>), g, dim3(256), b->v2_lds, c->stream, P, prm, it, probe_lambda, g0, gc);
-    else hipLaunchKernelGGL((k_ba_build_w<1, 1, 8, LOSS>), g, dim3(256), b->v2_lds, c->stream, P, prm, it, probe_lambda, g0, gc);
-  } else if (b->tpb == 256 && b->LPP == 8) hipLaunchKernelGGL((k_ba_build<256, 8, LOSS>), dim3(P.nset, B), dim3(256), b->build_lds, c->stream, P, prm, it, probe_lambda);
-  else if (b->tpb == 256) hipLaunchKernelGGL((k_ba_build<256, 0, LOSS>), dim3(P.nset, B), dim3(256), b->build_lds, c->stream, P, prm, it, probe_lambda);
-  else if (b->tpb == 512) hipLaunchKernelGGL((k_ba_build<512, 0, LOSS>), dim3(b->nblk, B), dim3(512), b->build_lds, c->stream, P, prm, it, probe_lambda);
-  else hipLaunchKernelGGL((k_ba_build<1024, 0, LOSS>), dim3(b->nblk, B), dim3(1024), b->build_lds, c->stream, P, prm, it, probe_lambda);
-  if constexpr (LOSS != VO_LOSS_HUBER) hipLaunchKernelGGL(k_ba_cost_r<LOSS>, dim3(B), dim3(256), 0, c->stream, P, prm, it);
-  if (!P.fold) hipLaunchKernelGGL(k_ba_reduce, dim3(vo_div_up(b->n_tiles * 256 + b->W * BA_POSE_VALS + 1, 64), B), dim3(256), 0, c->stream, P, it);
+    if (b->v2_spl == 2 && b->v2_lpp == 5) hipLaunchKernelGGL((k_ba_build_w<4, 2, 5, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
+    else if (b->v2_spl == 2) hipLaunchKernelGGL((k_ba_build_w<4, 2, 8, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
+    else if (b->v2_rt == 4) hipLaunchKernelGGL((k_ba_build_w<4, 1, 8, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
+    else if (b->v2_rt == 3) hipLaunchKernelGGL((k_ba_build_w<3, 1, 8, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
+    else if (b->v2_rt == 2 && b->v2_lpp == 4) hipLaunchKernelGGL((k_ba_build_w<2, 1, 4, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
+    else if (b->v2_rt == 2) hipLaunchKernelGGL((k_ba_build_w<2, 1, 8, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
+    else if (b->v2_lpp == 4) hipLaunchKernelGGL((k_ba_build_w<1, 1, 4, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
+    else hipLaunchKernelGGL((k_ba_build_w<1, 1, 8, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
+  } else if (b->tpb == 256 && b->LPP == 8) hipLaunchKernelGGL((k_ba_build<256, 8, LOSS>), dim3(P.nset, B), dim3(256), b->build_lds, q, P, prm, it, probe_lambda);
+  else if (b->tpb == 256) hipLaunchKernelGGL((k_ba_build<256, 0, LOSS>), dim3(P.nset, B), dim3(256), b->build_lds, q, P, prm, it, probe_lambda);
+  else if (b->tpb == 512) hipLaunchKernelGGL((k_ba_build<512, 0, LOSS>), dim3(b->nblk, B), dim3(512), b->build_lds, q, P, prm, it, probe_lambda);
+  else hipLaunchKernelGGL((k_ba_build<1024, 0, LOSS>), dim3(b->nblk, B), dim3(1024), b->build_lds, q, P, prm, it, probe_lambda);
+  if constexpr (LOSS != VO_LOSS_HUBER) hipLaunchKernelGGL(k_ba_cost_r<LOSS>, dim3(B), dim3(256), 0, q, P, prm, it);
+  if (!P.fold) hipLaunchKernelGGL(k_ba_reduce, dim3(vo_div_up(b->n_tiles * 256 + b->W * BA_POSE_VALS + 1, 64), B), dim3(256), 0, q, P, it);
   if (P.sharded) {
     // exchange 1: every shard's reduced packet -> the sum over all shards of all ranks, in every entry
-    hipLaunchKernelGGL(k_ba_xsum, dim3(vo_div_up((int)b->red_stride, 256)), dim3(256), 0, c->stream, P, it);
-    const int32_t r = vo_comm_allreduce_f64(c, b->d_tilesum, b->red_stride * B);
+    hipLaunchKernelGGL(k_ba_xsum, dim3(vo_div_up((int)b->red_stride, 256)), dim3(256), 0, q, P, it);
+    const int32_t r = vo_comm_allreduce_f64(c, q, b->d_tilesum, b->red_stride * B);
     if (r != VO_OK) return r;
   }
-  hipLaunchKernelGGL(k_ba_solve, dim3(B), dim3(BA_SOLVE_THREADS), b->solve_lds, c->stream, P, prm, it, probe_S, hpp_out);
+  hipLaunchKernelGGL(k_ba_solve, dim3(B), dim3(BA_SOLVE_THREADS), b->solve_lds, q, P, prm, it, probe_S, hpp_out);
   if (b->v2) {
-    if (b->v2_spl == 2 && b->v2_lpp == 5) hipLaunchKernelGGL((k_ba_update_w<2, 5, LOSS>), dim3(b->v2_g0 * B), dim3(256), 0, c->stream, P, prm, it, probe_dl, b->v2_g0, b->v2_gcap);
-    else if (b->v2_spl == 2) hipLaunchKernelGGL((k_ba_update_w<2, 8, LOSS>), dim3(b->v2_g0 * B), dim3(256), 0, c->stream, P, prm, it, probe_dl, b->v2_g0, b->v2_gcap);
-    else if (b->v2_lpp == 4) hipLaunchKernelGGL((k_ba_update_w<1, 4, LOSS>), dim3(b->v2_g0 * B), dim3(256), 0, c->stream, P, prm, it, probe_dl, b->v2_g0, b->v2_gcap);
-    else hipLaunchKernelGGL((k_ba_update_w<1, 8, LOSS>), dim3(b->v2_g0 * B), dim3(256), 0, c->stream, P, prm, it, probe_dl, b->v2_g0, b->v2_gcap);
-  } else if (b->tpb == 256 && b->LPP == 8) hipLaunchKernelGGL((k_ba_update<256, 8, LOSS>), dim3(b->nblk, B), dim3(256), 0, c->stream, P, prm, it, probe_dl);
-  else if (b->tpb == 256) hipLaunchKernelGGL((k_ba_update<256, 0, LOSS>), dim3(b->nblk, B), dim3(256), 0, c->stream, P, prm, it, probe_dl);
-  else if (b->tpb == 512) hipLaunchKernelGGL((k_ba_update<512, 0, LOSS>), dim3(b->nblk, B), dim3(512), 0, c->stream, P, prm, it, probe_dl);
-  else hipLaunchKernelGGL((k_ba_update<1024, 0, LOSS>), dim3(b->nblk, B), dim3(1024), 0, c->stream, P, prm, it, probe_dl);
+    if (b->v2_spl == 2 && b->v2_lpp == 5) hipLaunchKernelGGL((k_ba_update_w<2, 5, LOSS>), dim3(b->v2_g0 * B), dim3(256), 0, q, P, prm, it, probe_dl, b->v2_g0, b->v2_gcap);
+    else if (b->v2_spl == 2) hipLaunchKernelGGL((k_ba_update_w<2, 8, LOSS>), dim3(b->v2_g0 * B), dim3(256), 0, q, P, prm, it, probe_dl, b->v2_g0, b->v2_gcap);
+    else if (b->v2_lpp == 4) hipLaunchKernelGGL((k_ba_update_w<1, 4, LOSS>), dim3(b->v2_g0 * B), dim3(256), 0, q, P, prm, it, probe_dl, b->v2_g0, b->v2_gcap);
+    else hipLaunchKernelGGL((k_ba_update_w<1, 8, LOSS>), dim3(b->v2_g0 * B), dim3(256), 0, q, P, prm, it, probe_dl, b->v2_g0, b->v2_gcap);
+  } else if (b->tpb == 256 && b->LPP == 8) hipLaunchKernelGGL((k_ba_update<256, 8, LOSS>), dim3(b->nblk, B), dim3(256), 0, q, P, prm, it, probe_dl);
+  else if (b->tpb == 256) hipLaunchKernelGGL((k_ba_update<256, 0, LOSS>), dim3(b->nblk, B), dim3(256), 0, q, P, prm, it, probe_dl);
+  else if (b->tpb == 512) hipLaunchKernelGGL((k_ba_update<512, 0, LOSS>), dim3(b->nblk, B), dim3(512), 0, q, P, prm, it, probe_dl);
+  else hipLaunchKernelGGL((k_ba_update<1024, 0, LOSS>), dim3(b->nblk, B), dim3(1024), 0, q, P, prm, it, probe_dl);
   if (P.sharded) {
     // exchange 2: the 4 step statistics the next decision needs
-    hipLaunchKernelGGL(k_ba_xstat, dim3(1), dim3(256), 0, c->stream, P, it);
-    const int32_t r = vo_comm_allreduce_f64(c, b->d_xstat, (size_t)BA_EVAL_VALS * B);
+    hipLaunchKernelGGL(k_ba_xstat, dim3(1), dim3(256), 0, q, P, it);
+    const int32_t r = vo_comm_allreduce_f64(c, q, b->d_xstat, (size_t)BA_EVAL_VALS * B);
     if (r != VO_OK) return r;
   }
   return VO_OK;
 }
 
 // one LM iteration with the kernel set of the loss (prm.loss: ba_dev_params has turned VO_LOSS_LINEAR into the Huber set)
-static int32_t ba_launch_iter(vo_ctx* c, const ba_ptrs& P, const ba_params_dev& prm, int it, double probe_lambda,
+static int32_t ba_launch_iter(vo_ctx* c, hipStream_t q, const ba_ptrs& P, const ba_params_dev& prm, int it, double probe_lambda,
                               double* probe_S, double* hpp_out, double* probe_dl) {
   switch (prm.loss) {
-    case VO_LOSS_SOFT_L1: return ba_launch_iter_t<VO_LOSS_SOFT_L1>(c, P, prm, it, probe_lambda, probe_S, hpp_out, probe_dl);
-    case VO_LOSS_CAUCHY: return ba_launch_iter_t<VO_LOSS_CAUCHY>(c, P, prm, it, probe_lambda, probe_S, hpp_out, probe_dl);
-    case VO_LOSS_ARCTAN: return ba_launch_iter_t<VO_LOSS_ARCTAN>(c, P, prm, it, probe_lambda, probe_S, hpp_out, probe_dl);
-    default: return ba_launch_iter_t<VO_LOSS_HUBER>(c, P, prm, it, probe_lambda, probe_S, hpp_out, probe_dl);
+    case VO_LOSS_SOFT_L1: return ba_launch_iter_t<VO_LOSS_SOFT_L1>(c, q, P, prm, it, probe_lambda, probe_S, hpp_out, probe_dl);
+    case VO_LOSS_CAUCHY: return ba_launch_iter_t<VO_LOSS_CAUCHY>(c, q, P, prm, it, probe_lambda, probe_S, hpp_out, probe_dl);
+    case VO_LOSS_ARCTAN: return ba_launch_iter_t<VO_LOSS_ARCTAN>(c, q, P, prm, it, probe_lambda, probe_S, hpp_out, probe_dl);
+    default: return ba_launch_iter_t<VO_LOSS_HUBER>(c, q, P, prm, it, probe_lambda, probe_S, hpp_out, probe_dl);
   }
 }
 
 // enqueue `n_it` LM iterations starting at iteration index `it0`
-static int32_t ba_enqueue_iters(vo_ctx* c, const ba_params_dev& prm, int it0, int n_it) {
-  vo_prof_scope prof(c, VO_PROF_BA);
-  const ba_ptrs P = ba_make_ptrs(c);
+static int32_t ba_enqueue_iters(vo_ctx* c, hipStream_t q, const ba_params_dev& prm, int it0, int n_it, const vo_ba_enqueue_opts& o) {
+  vo_prof_scope prof(c, q, VO_PROF_BA);
+  const ba_ptrs P = ba_make_ptrs(c, o);
   for (int it = it0; it < it0 + n_it; it++) {
-    const int32_t r = ba_launch_iter(c, P, prm, it, -1.0, nullptr, nullptr, nullptr);
+    const int32_t r = ba_launch_iter(c, q, P, prm, it, -1.0, nullptr, nullptr, nullptr);
     if (r != VO_OK) return r;
     // pipelined frame step: the groups in which (nearly) every problem of the batch still runs are over -- the next frame's tracker may start
-    if (c->ba_wide_event && it - it0 + 1 == c->ba_wide_groups) VO_HIP(c, hipEventRecord(c->ba_wide_event, c->stream));
+    if (o.wide_event && it - it0 + 1 == o.wide_groups) VO_HIP(c, hipEventRecord(o.wide_event, q));
   }
-  if (c->ba_wide_event && n_it < c->ba_wide_groups) VO_HIP(c, hipEventRecord(c->ba_wide_event, c->stream));
+  if (o.wide_event && n_it < o.wide_groups) VO_HIP(c, hipEventRecord(o.wide_event, q));
   VO_HIP(c, hipGetLastError());
   return VO_OK;
 }
 
-static void ba_launch_finalize(vo_ctx* c, const ba_ptrs& P, const ba_params_dev& d, int n_it, ba_state* st_out, int st_stride) {
+static void ba_launch_finalize(vo_ctx* c, hipStream_t q, const ba_ptrs& P, const ba_params_dev& d, int n_it, ba_state* st_out, int st_stride) {
   vo_ba_ws* b = c->ba;
-  hipLaunchKernelGGL(k_ba_finalize, dim3(c->batch, 8), dim3(256), 0, c->stream, P, d, n_it, b->d_pub, b->pub_bytes, st_out, st_stride);
+  hipLaunchKernelGGL(k_ba_finalize, dim3(c->batch, 8), dim3(256), 0, q, P, d, n_it, b->d_pub, b->pub_bytes, st_out, st_stride);
+}
+
+// what refuses a resident solve (nothing is enqueued then).  Run twice on the public path: vo_ba_solve_resident refuses before it touches the
+// device or waits for the side streams, and vo_ba_enqueue_solve checks for the frame step, which hands it the caller's parameters unseen
+static int32_t ba_solve_admit(vo_ctx* c, const vo_ba_params* prm) {
+  VO_CHECK(c, c->ba && c->ba->uploaded, VO_E_STATE, "vo_ba_upload first");
+  VO_CHECK(c, prm->max_iters >= 0 && prm->max_iters <= 1000, VO_E_INVALID, "bad max_iters");
+  return vo_ba_check_params(c, prm);
+}
+
+int32_t vo_ba_enqueue_solve(vo_ctx* c, hipStream_t q, const vo_ba_params* prm, const vo_ba_enqueue_opts& o) {
+  { const int32_t ra = ba_solve_admit(c, prm); if (ra != VO_OK) return ra; }
+  const ba_params_dev d = ba_dev_params(prm);
+  int32_t r = ba_enqueue_iters(c, q, d, 0, prm->max_iters, o);
+  if (r != VO_OK) return r;
+  vo_ba_ws* b = c->ba;
+  const ba_ptrs P = ba_make_ptrs(c, o);
+  // pipelined frame step: the copy of the PREVIOUS solution runs on another stream; it must have left d_pub before this one lands there
+  if (o.wait_before_publish) VO_HIP(c, hipStreamWaitEvent(q, o.wait_before_publish, 0));
+  ba_launch_finalize(c, q, P, d, prm->max_iters, b->d_state + (prm->max_iters & 1), 2);
+  VO_HIP(c, hipGetLastError());
+  return VO_OK;
 }
 
 extern "C" int32_t vo_ba_solve_resident(vo_ctx* c, const vo_ba_params* prm) {
   if (!c) return VO_E_INVALID;
   vo_ba_params def;
   if (!prm) { vo_ba_default_params(&def); prm = &def; }
-  VO_CHECK(c, c->ba && c->ba->uploaded, VO_E_STATE, "vo_ba_upload first");
-  VO_CHECK(c, prm->max_iters >= 0 && prm->max_iters <= 1000, VO_E_INVALID, "bad max_iters");
-  { const int32_t rc = vo_ba_check_params(c, prm); if (rc != VO_OK) return rc; }
+  { const int32_t ra = ba_solve_admit(c, prm); if (ra != VO_OK) return ra; }
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  const ba_params_dev d = ba_dev_params(prm);
-  int32_t r = ba_enqueue_iters(c, d, 0, prm->max_iters);
-  if (r != VO_OK) return r;
-  vo_ba_ws* b = c->ba;
-  const ba_ptrs P = ba_make_ptrs(c);
-  // pipelined frame step: the copy of the PREVIOUS solution runs on another stream; it must have left d_pub before this one lands there
-  if (c->ba_wait_before_publish) VO_HIP(c, hipStreamWaitEvent(c->stream, c->ba_wait_before_publish, 0));
-  ba_launch_finalize(c, P, d, prm->max_iters, b->d_state + (prm->max_iters & 1), 2);
-  VO_HIP(c, hipGetLastError());
-  return VO_OK;
+  return vo_ba_enqueue_solve(c, c->stream, prm, {});
 }
 
 // ---- closed-loop pipeline hooks: the problem (x0, obs) is written by a device kernel every frame ----
@@ -1839,13 +1843,13 @@ int32_t vo_ba_get_view(vo_ctx* c, vo_ba_view* v) {
   v->x_stride = (size_t)6 * b->W + 3 * (size_t)b->N; v->obs_stride = (size_t)2 * b->W * b->N; v->W = b->W; v->N = b->N;
   return VO_OK;
 }
-int32_t vo_ba_enqueue_budget(vo_ctx* c, const vo_ba_params* prm, int it0, int n_it) {
+int32_t vo_ba_enqueue_budget(vo_ctx* c, hipStream_t q, const vo_ba_params* prm, int it0, int n_it, const vo_ba_enqueue_opts& o) {
   VO_CHECK(c, c->ba && c->ba->uploaded, VO_E_STATE, "vo_ba_reserve first");
   { const int32_t rc = vo_ba_check_params(c, prm); if (rc != VO_OK) return rc; }
   const ba_params_dev d = ba_dev_params(prm);
-  if (n_it > 0) { const int32_t r = ba_enqueue_iters(c, d, it0, n_it); if (r != VO_OK) return r; }
-  const ba_ptrs P = ba_make_ptrs(c);
-  ba_launch_finalize(c, P, d, it0 + n_it, c->ba->d_state + ((it0 + n_it) & 1), 2);
+  if (n_it > 0) { const int32_t r = ba_enqueue_iters(c, q, d, it0, n_it, o); if (r != VO_OK) return r; }
+  const ba_ptrs P = ba_make_ptrs(c, o);
+  ba_launch_finalize(c, q, P, d, it0 + n_it, c->ba->d_state + ((it0 + n_it) & 1), 2);
   VO_HIP(c, hipGetLastError());
   return VO_OK;
 }
@@ -1856,9 +1860,9 @@ static void ba_fill_stats(const ba_state& s, int n_obs, vo_ba_stats* st) {
 }
 
 // internal: enqueue the D2H copy of the published results into the pinned mirror (used by the frame step)
-int32_t vo_ba_enqueue_pub_copy(vo_ctx* c, int half) {
+int32_t vo_ba_enqueue_pub_copy(vo_ctx* c, hipStream_t q, int half) {
   vo_ba_ws* b = c->ba;
-  VO_HIP(c, hipMemcpyAsync(b->h_pub + (size_t)half * b->pub_bytes * c->batch, b->d_pub, b->pub_bytes * c->batch, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP(c, hipMemcpyAsync(b->h_pub + (size_t)half * b->pub_bytes * c->batch, b->d_pub, b->pub_bytes * c->batch, hipMemcpyDeviceToHost, q));
   return VO_OK;
 }
 
@@ -1880,7 +1884,7 @@ extern "C" int32_t vo_ba_fetch(vo_ctx* c, double* poses_out, double* points_out,
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   // its own pinned mirror: a frame step still in flight keeps the two halves vo_frame_fetch reads
-  int32_t r = vo_ba_enqueue_pub_copy(c, 2);
+  int32_t r = vo_ba_enqueue_pub_copy(c, c->stream, 2);
   if (r != VO_OK) return r;
   VO_HIP(c, hipStreamSynchronize(c->stream));
   vo_ba_unpack_pub(c, 2, poses_out, points_out, stats);
@@ -1913,7 +1917,7 @@ extern "C" int32_t vo_ba_gather_points(vo_ctx* c, double* points_all) {
   // points part of the published x of every problem -> packed send buffer
   VO_HIP(c, hipMemcpy2DAsync(send, sizeof(double) * 3 * b->N, b->d_pub + VO_BA_PUB_HEADER + sizeof(double) * 6 * b->W, b->pub_bytes,
                              sizeof(double) * 3 * b->N, B, hipMemcpyDeviceToDevice, c->stream));
-  const int32_t r = vo_comm_allgather_f64(c, send, recv, cnt);
+  const int32_t r = vo_comm_allgather_f64(c, c->stream, send, recv, cnt);
   if (r != VO_OK) return r;
   VO_HIP(c, hipMemcpyAsync(b->h_gather, recv, sizeof(double) * cnt * R, hipMemcpyDeviceToHost, c->stream));
   VO_HIP(c, hipStreamSynchronize(c->stream));
@@ -1935,7 +1939,7 @@ extern "C" int32_t vo_ba_adjust(vo_ctx* c, const double* K, const double* poses,
   if (r != VO_OK) return r;
   vo_ba_ws* b = c->ba;
   const ba_params_dev d = ba_dev_params(prm);
-  const ba_ptrs P = ba_make_ptrs(c);
+  const ba_ptrs P = ba_make_ptrs(c, {});
   const int B = c->batch;
   // iterations are enqueued in chunks; between chunks the host peeks at the states to stop early
   const int CH = 4;
@@ -1944,18 +1948,18 @@ extern "C" int32_t vo_ba_adjust(vo_ctx* c, const double* K, const double* poses,
   do {
     const int n = (prm->max_iters - it < CH) ? prm->max_iters - it : CH;
     if (n > 0) {
-      r = ba_enqueue_iters(c, d, it, n);
+      r = ba_enqueue_iters(c, c->stream, d, it, n, {});
       if (r != VO_OK) return r;
       it += n;
     }
-    ba_launch_finalize(c, P, d, it, b->d_state + (it & 1), 2);
+    ba_launch_finalize(c, c->stream, P, d, it, b->d_state + (it & 1), 2);
     VO_HIP(c, hipMemcpy2DAsync(b->h_state, sizeof(ba_state), b->d_state + (it & 1), 2 * sizeof(ba_state), sizeof(ba_state), B,
                                hipMemcpyDeviceToHost, c->stream));
     VO_HIP(c, hipStreamSynchronize(c->stream));
     all_done = true;
     for (int q = 0; q < B; q++) all_done = all_done && b->h_state[q].done;
   } while (!all_done && it < prm->max_iters);
-  r = vo_ba_enqueue_pub_copy(c, 2);
+  r = vo_ba_enqueue_pub_copy(c, c->stream, 2);
   if (r != VO_OK) return r;
   VO_HIP(c, hipStreamSynchronize(c->stream));
   vo_ba_unpack_pub(c, 2, poses_out, points_out, stats);
@@ -1996,7 +2000,7 @@ extern "C" int32_t vo_ba_probe_loss(vo_ctx* c, double lambda, int32_t loss, doub
   const ba_params_dev d = ba_dev_params(&prm);
   const ba_ptrs P = ba_make_ptrs_dbg(c);
   hipLaunchKernelGGL(k_ba_residual, dim3(vo_div_up(N, 128), c->batch), dim3(128), 0, c->stream, P, b->d_x0, d.delta, b->d_res);
-  { const int32_t r = ba_launch_iter(c, P, d, 0, lambda, b->d_S, b->d_Hpp, b->d_dl); if (r != VO_OK) return r; }
+  { const int32_t r = ba_launch_iter(c, c->stream, P, d, 0, lambda, b->d_S, b->d_Hpp, b->d_dl); if (r != VO_OK) return r; }
   VO_HIP(c, hipGetLastError());
   VO_HIP(c, hipStreamSynchronize(c->stream));
   // ---- copy out ----

@@ -1,8 +1,8 @@
 // Communicator for the ONE exchange step of the path: the shared-landmark bundle-adjustment reduction of a single
 // sequence whose landmarks are sharded over the GPUs of a node (BASELINE config 5).  One process per
 // GPU; the collectives are RCCL's (all-reduce of the packed [Gram tiles | camera sums | max-gradient slots] and of the
-// 4 step statistics per LM iteration, all-gather of the adjusted points once per adjust), enqueued on the ctx stream
-// so that they order with the kernels of the iteration and need no host synchronisation.
+// 4 step statistics per LM iteration, all-gather of the adjusted points once per adjust), enqueued on the stream the
+// caller names -- the one of the iteration's kernels -- so that they order with them and need no host synchronisation.
 //
 // librccl is opened lazily with dlopen: a process that never creates a communicator never loads it.
 #include "vo_internal.h"
@@ -93,21 +93,21 @@ extern "C" int32_t vo_comm_destroy(vo_ctx* c) {
   return VO_OK;
 }
 
-// in-place sum over the ranks, on the ctx stream; a no-op without a communicator
-int32_t vo_comm_allreduce_f64(vo_ctx* c, double* buf, size_t count) {
+// in-place sum over the ranks, on stream q; a no-op without a communicator
+int32_t vo_comm_allreduce_f64(vo_ctx* c, hipStream_t q, double* buf, size_t count) {
   if (!c->comm) return VO_OK;
-  const ncclResult_t r = rccl()->AllReduce(buf, buf, count, ncclDouble, ncclSum, static_cast<ncclComm_t>(c->comm), c->stream);
+  const ncclResult_t r = rccl()->AllReduce(buf, buf, count, ncclDouble, ncclSum, static_cast<ncclComm_t>(c->comm), q);
   if (r != ncclSuccess) return rccl_fail(c, "ncclAllReduce", r);
   return VO_OK;
 }
 
 // recv [n_ranks][count] <- send [count] of every rank; a device copy without a communicator
-int32_t vo_comm_allgather_f64(vo_ctx* c, const double* send, double* recv, size_t count) {
+int32_t vo_comm_allgather_f64(vo_ctx* c, hipStream_t q, const double* send, double* recv, size_t count) {
   if (!c->comm) {
-    VO_HIP(c, hipMemcpyAsync(recv, send, count * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    VO_HIP(c, hipMemcpyAsync(recv, send, count * sizeof(double), hipMemcpyDeviceToDevice, q));
     return VO_OK;
   }
-  const ncclResult_t r = rccl()->AllGather(send, recv, count, ncclDouble, static_cast<ncclComm_t>(c->comm), c->stream);
+  const ncclResult_t r = rccl()->AllGather(send, recv, count, ncclDouble, static_cast<ncclComm_t>(c->comm), q);
   if (r != ncclSuccess) return rccl_fail(c, "ncclAllGather", r);
   return VO_OK;
 }

@@ -140,9 +140,11 @@ static int32_t dlt_set_cams(vo_ctx* c, const float* P0, const float* P1, const d
   return VO_OK;
 }
 
-static int32_t dlt_launch(vo_ctx* c, int n) {
-  vo_prof_scope prof(c, VO_PROF_DLT);
-  hipLaunchKernelGGL(k_dlt, dim3(vo_div_up(n, 64), c->batch), dim3(64), 0, c->stream, c->d_dlt_cam, n, c->dlt_stats,
+// the uploaded pairs and cameras (vo_dlt_upload): n = c->dlt_n pairs per sequence.  The caller has checked n > 0 (vo_dlt_resident, frame_step:
+// VO_E_STATE "vo_dlt_upload first"); an empty grid would come back as a launch error instead
+int32_t vo_dlt_enqueue(vo_ctx* c, hipStream_t q, int n) {
+  vo_prof_scope prof(c, q, VO_PROF_DLT);
+  hipLaunchKernelGGL(k_dlt, dim3(vo_div_up(n, 64), c->batch), dim3(64), 0, q, c->d_dlt_cam, n, c->dlt_stats,
                      (size_t)c->max_pts * 2, c->slab_seq, c->d_uv0, c->d_uv1, vo_slab<float>(c, c->off_X4),
                      vo_slab<double>(c, c->off_depth), vo_slab<double>(c, c->off_reproj), nullptr, nullptr, 1);
   VO_HIP(c, hipGetLastError());
@@ -151,9 +153,9 @@ static int32_t dlt_launch(vo_ctx* c, int n) {
 
 // closed-loop pipeline: cameras (cams_per_seq per sequence), their per-point selection and the pixel pairs were written by device
 // kernels; counts[b] pairs are valid; X4 keeps the row stride n_hi
-int32_t vo_dlt_enqueue_counts(vo_ctx* c, int n_hi, const int32_t* d_counts, const vo_dlt_cam* d_cams, const int32_t* d_cam_sel, int cams_per_seq) {
-  vo_prof_scope prof(c, VO_PROF_DLT);
-  hipLaunchKernelGGL(k_dlt, dim3(vo_div_up(n_hi, 64), c->batch), dim3(64), 0, c->stream, d_cams, n_hi, 1,
+int32_t vo_dlt_enqueue_counts(vo_ctx* c, hipStream_t q, int n_hi, const int32_t* d_counts, const vo_dlt_cam* d_cams, const int32_t* d_cam_sel, int cams_per_seq) {
+  vo_prof_scope prof(c, q, VO_PROF_DLT);
+  hipLaunchKernelGGL(k_dlt, dim3(vo_div_up(n_hi, 64), c->batch), dim3(64), 0, q, d_cams, n_hi, 1,
                      (size_t)c->max_pts * 2, c->slab_seq, c->d_uv0, c->d_uv1, vo_slab<float>(c, c->off_X4),
                      vo_slab<double>(c, c->off_depth), vo_slab<double>(c, c->off_reproj), d_counts, d_cam_sel, cams_per_seq);
   VO_HIP(c, hipGetLastError());
@@ -190,7 +192,7 @@ extern "C" int32_t vo_triangulate_dlt(vo_ctx* c, const float* P0, const float* P
   if (r != VO_OK) return r;
   r = dlt_upload_uv(c, uv0, uv1, n);
   if (r != VO_OK) return r;
-  r = dlt_launch(c, n);
+  r = vo_dlt_enqueue(c, c->stream, n);
   if (r != VO_OK) return r;
   r = dlt_download(c, n, X4, depth1, reproj);
   if (r != VO_OK) return r;
@@ -220,7 +222,7 @@ extern "C" int32_t vo_dlt_resident(vo_ctx* c) {
   VO_CHECK(c, c->dlt_n > 0, VO_E_STATE, "vo_dlt_upload first");
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  return dlt_launch(c, c->dlt_n);
+  return vo_dlt_enqueue(c, c->stream, c->dlt_n);
 }
 
 extern "C" int32_t vo_dlt_fetch(vo_ctx* c, float* X4, double* depth1, double* reproj) {

@@ -262,15 +262,15 @@ static hipEvent_t prof_event(vo_ctx* c) {
   return p.pool[p.used++];
 }
 
-vo_prof_scope::vo_prof_scope(vo_ctx* c_, int region_) : c(c_), region(region_) {
+vo_prof_scope::vo_prof_scope(vo_ctx* c_, hipStream_t q_, int region_) : c(c_), q(q_), region(region_) {
   if (!((c->prof.mask >> region) & 1)) return;
   e0 = prof_event(c); e1 = prof_event(c);
-  if (e0) (void)hipEventRecord(e0, c->stream);
+  if (e0) (void)hipEventRecord(e0, q);
 }
 
 vo_prof_scope::~vo_prof_scope() {
   if (!e0 || !e1) return;
-  (void)hipEventRecord(e1, c->stream);
+  (void)hipEventRecord(e1, q);
   c->prof.pairs[region].push_back(std::make_pair(e0, e1));
 }
 
@@ -504,8 +504,8 @@ extern "C" int32_t vo_sync(vo_ctx* c) {
 // ------------------------------------------------------------------------------------------------
 // frames
 // ------------------------------------------------------------------------------------------------
-int32_t vo_build_pyramid(vo_ctx* c, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx) {
-  vo_prof_scope prof(c, VO_PROF_FRAME);
+int32_t vo_build_pyramid(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx) {
+  vo_prof_scope prof(c, q, VO_PROF_FRAME);
   c->cur ^= 1;
   vo_frame& F = c->fr[c->cur];
   const int B = c->batch;
@@ -518,10 +518,10 @@ int32_t vo_build_pyramid(vo_ctx* c, const uint8_t* d_raw_img, size_t raw_seq_str
       bil_args A;
       A.maxk = c->bil_maxk;
       for (int k = 0; k < 49; k++) { A.dx[k] = c->bil_dx[k]; A.dy[k] = c->bil_dy[k]; A.sw[k] = c->bil_sw[k]; }
-      hipLaunchKernelGGL(k_pad_level0_bilateral, grid1, dim3(256), 0, c->stream, d_raw_img, raw_seq_stride, d_frame_idx, L.w,
+      hipLaunchKernelGGL(k_pad_level0_bilateral, grid1, dim3(256), 0, q, d_raw_img, raw_seq_stride, d_frame_idx, L.w,
                          L.h, F.img[0], c->lvl_px[0], L.pitch, L.ph, A, c->d_bil_cw);
     } else {
-      hipLaunchKernelGGL(k_pad_level0, grid, dim3(256), 0, c->stream, d_raw_img, raw_seq_stride, d_frame_idx, L.w, L.h,
+      hipLaunchKernelGGL(k_pad_level0, grid, dim3(256), 0, q, d_raw_img, raw_seq_stride, d_frame_idx, L.w, L.h,
                          F.img[0], c->lvl_px[0], L.pitch, L.ph, remap);
     }
   }
@@ -535,7 +535,7 @@ int32_t vo_build_pyramid(vo_ctx* c, const uint8_t* d_raw_img, size_t raw_seq_str
       dst = F.img[l + 1]; dw = D.w; dh = D.h; dpitch = D.pitch; dpx = c->lvl_px[l + 1];
       nb_down = vo_div_up(vo_div_up(D.w + 2 * VO_PAD, 4) * D.ph, 256);
     }
-    hipLaunchKernelGGL(k_scharr_pyrdown, dim3(nb_scharr + nb_down, B), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL(k_scharr_pyrdown, dim3(nb_scharr + nb_down, B), dim3(256), 0, q,
                        F.img[l], c->lvl_px[l], L.w, L.h, L.pitch, F.der[l], nb_scharr, dst, dpx, dw, dh, dpitch, remap);
   }
   VO_HIP(c, hipGetLastError());
@@ -563,7 +563,7 @@ extern "C" int32_t vo_frame_push(vo_ctx* c, const uint8_t* img, int32_t stride) 
   else for (size_t y = 0; y < rows; y++) memcpy(c->h_raw + y * c->width, img + y * (size_t)stride, c->width);
   VO_HIP(c, hipMemcpyAsync(c->d_raw, c->h_raw, bytes, hipMemcpyHostToDevice, c->stream));
   VO_HIP(c, hipEventRecord(c->ev_raw, c->stream));
-  return vo_build_pyramid(c, c->d_raw, (size_t)c->width * c->height, nullptr);
+  return vo_build_pyramid(c, c->stream, c->d_raw, (size_t)c->width * c->height, nullptr);
 }
 
 // frames: [batch][n_frames][height][width] uint8
@@ -588,7 +588,7 @@ extern "C" int32_t vo_frame_push_resident(vo_ctx* c, int32_t idx) {
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   const size_t fr = (size_t)c->width * c->height;
-  return vo_build_pyramid(c, c->d_seq + (size_t)idx * fr, fr * c->seq_n, nullptr);
+  return vo_build_pyramid(c, c->stream, c->d_seq + (size_t)idx * fr, fr * c->seq_n, nullptr);
 }
 
 extern "C" int32_t vo_pyramid_level_size(vo_ctx* c, int32_t level, int32_t* w, int32_t* h) {

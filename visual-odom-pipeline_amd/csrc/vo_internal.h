@@ -53,10 +53,8 @@ struct vo_ctx {
   hipEvent_t ev_ba[2] = {nullptr, nullptr};     // the BA of the step using half k has published its solution (d_pub)
   hipEvent_t ev_copy1[2] = {nullptr, nullptr};  // the KLT results of the step using half k have left the device (copy on stream A)
   hipEvent_t ev_pub[2] = {nullptr, nullptr};    // ... and the copy of it (on stream2) has left the device: the next k_ba_finalize may overwrite d_pub
-  hipEvent_t ba_wait_before_publish = nullptr;  // set by the pipelined step around vo_ba_solve_resident
   hipEvent_t ev_ba_wide[2] = {nullptr, nullptr}; // pipelined step: the first `ba_wide_groups` LM groups of the step using half k have run (recorded on stream C);
                                                 // the NEXT step's tracker launch waits for it -- the wide groups get the whole chip, the tail groups run beside the tracker
-  hipEvent_t ba_wide_event = nullptr;           // set by the pipelined step around vo_ba_solve_resident: record after `ba_wide_groups` groups
   int ba_wide_groups = 0;                       // 0: no gating
   bool ba_wide_recorded = false;
   int stream_reserve = 0;                        // compute units `stream` leaves free (CU mask of its queue; vo_set_side_stream)
@@ -69,7 +67,6 @@ struct vo_ctx {
   float* d_bil_cw = nullptr;         // [256] colour weights
   int side_stream = 1;               // vo_set_side_stream
   vo_tuning tune = {};               // forced forms (vo_set_tuning); all zero = the library's rules
-  bool in_step = false;              // inside vo_frame_step_resident: its stage calls must not wait for the side streams (vo_quiesce_side)
   bool main_dirty = true;            // an entry point other than vo_pipe_step may have enqueued work on `stream` since the last pipe step (set by
                                      // vo_quiesce_side, which every such entry point calls): the next pipe step orders its side streams behind it
   int batch = 1;
@@ -198,10 +195,10 @@ __device__ __forceinline__ void vo_xcd_assign(unsigned id, unsigned nblk, int re
   }
 }
 
-// RAII bracket: records an event pair on the ctx stream around a region when profiling is on
+// RAII bracket: records an event pair on stream q around a region when profiling is on
 struct vo_prof_scope {
-  vo_ctx* c; int region; hipEvent_t e0 = nullptr, e1 = nullptr;
-  vo_prof_scope(vo_ctx* c_, int region_);
+  vo_ctx* c; hipStream_t q; int region; hipEvent_t e0 = nullptr, e1 = nullptr;
+  vo_prof_scope(vo_ctx* c_, hipStream_t q_, int region_);
   ~vo_prof_scope();
 };
 
@@ -210,8 +207,9 @@ struct vo_prof_scope {
 
 static inline int vo_div_up(int a, int b) { return (a + b - 1) / b; }
 
-// cross-unit internals used by the fused frame step (vo_step.hip)
-int32_t vo_build_pyramid(vo_ctx* c, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx);
+// cross-unit internals used by the fused frame step (vo_step.hip).  Every function that enqueues takes the stream q its launches, copies, event
+// records and profile brackets go to, and never waits for the side streams: that (vo_quiesce_side) is the extern "C" entry points' business
+int32_t vo_build_pyramid(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx);
 // a step's `batch` images from the host into d_host_raw[slot] on the copy stream (vo_step.hip); ev_h2d[slot] is recorded behind it
 // tab_slot: the row of h_ptr_tab this step's pointers go to (vo_host_tab_slot_frame / vo_host_tab_slot_pipe)
 int32_t vo_host_frames_upload(vo_ctx* c, const uint8_t* const* frames, int32_t stride, int slot, int tab_slot);
@@ -221,7 +219,7 @@ int32_t vo_host_frames_upload(vo_ctx* c, const uint8_t* const* frames, int32_t s
 #define VO_HOST_TAB_SLOTS (2 + VO_PIPE_INFLIGHT)
 inline int vo_host_tab_slot_frame(long steps_enq) { return (int)(steps_enq & 1); }
 inline int vo_host_tab_slot_pipe(long pipe_enq) { return 2 + (int)(pipe_enq % VO_PIPE_INFLIGHT); }
-int32_t vo_ba_enqueue_pub_copy(vo_ctx* c, int half);     // half: which pinned mirror (0 / 1)
+int32_t vo_ba_enqueue_pub_copy(vo_ctx* c, hipStream_t q, int half);     // half: which pinned mirror (0 / 1)
 void vo_ba_unpack_pub(vo_ctx* c, int half, double* poses_out, double* points_out, vo_ba_stats* stats);   // arrays over the batch
 bool vo_ba_ready(const vo_ctx* c);
 double* vo_ba_obs_device(vo_ctx* c, int* n_slots, int* n_pts);   // resident observation table [batch][W][N][2] of the uploaded problem
@@ -237,20 +235,20 @@ bool vo_blocking_sync();             // environment VO_BLOCKING_SYNC=1: events a
 int32_t vo_main_stream_reserve(vo_ctx* c, int reserve);               // the ctx stream re-created with / without a CU mask (vo_set_side_stream(c, 2) of a batch)
 hipError_t vo_stream_create(hipStream_t* st, int reserve_cus);      // reserve_cus > 0: the queue never uses the last `reserve_cus` bits of the CU mask
 int32_t vo_st_prepare(vo_ctx* c, const vo_st_params* prm);
-// the resident entry points with the per-sequence counters named by the caller (device arrays [batch], null = uniform): d_counts = live
+// the resident enqueues with the per-sequence counters named by the caller (device arrays [batch], null = uniform): d_counts = live
 // points of each sequence (KLT input / exclusion discs), d_limit = cap on the corners each sequence's re-detection needs
-int32_t vo_klt_track_resident_counts(vo_ctx* c, int32_t n, const vo_klt_params* prm, const int32_t* d_counts);
+int32_t vo_klt_track_resident_counts(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts);
 // the same tracking with the forward-backward check (k_klt_track_fb): the ok flags land in vo_fb_ok(c) [batch][fb_seq bytes]
-int32_t vo_klt_track_resident_fb(vo_ctx* c, int32_t n, const vo_klt_params* prm, const int32_t* d_counts);
+int32_t vo_klt_track_resident_fb(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts);
 inline bool vo_fb_on(const vo_ctx* c) { return !(c->fb_max_err == __builtin_inff()); }     // +inf = off
 inline const uint8_t* vo_fb_ok(const vo_ctx* c) { return c->d_fb + c->fb_off_ok; }
 void vo_fb_destroy(vo_ctx* c);
-int32_t vo_shi_tomasi_resident_counts(vo_ctx* c, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm, const int32_t* d_counts,
+int32_t vo_shi_tomasi_resident_counts(vo_ctx* c, hipStream_t q, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm, const int32_t* d_counts,
                                       const int32_t* d_limit);
 
-// collectives on the ctx stream (vo_comm.hip); identity / device copy without a communicator
-int32_t vo_comm_allreduce_f64(vo_ctx* c, double* buf, size_t count);
-int32_t vo_comm_allgather_f64(vo_ctx* c, const double* send, double* recv, size_t count);
+// collectives on stream q (vo_comm.hip); identity / device copy without a communicator
+int32_t vo_comm_allreduce_f64(vo_ctx* c, hipStream_t q, double* buf, size_t count);
+int32_t vo_comm_allgather_f64(vo_ctx* c, hipStream_t q, const double* send, double* recv, size_t count);
 
 void vo_trk_destroy(vo_ctx* c);
 void vo_pipe_destroy(vo_ctx* c);
@@ -269,16 +267,25 @@ static_assert(sizeof(ba_state) <= VO_BA_PUB_HEADER, "the publish buffer's header
 struct vo_ba_view { double* x0; double* obs; const uint8_t* pub; size_t pub_bytes; size_t x_stride; size_t obs_stride; int W, N; };
 int32_t vo_ba_reserve(vo_ctx* c, const double* K_host, int W, int N);
 int32_t vo_ba_get_view(vo_ctx* c, vo_ba_view* v);
-void vo_ba_set_live(vo_ctx* c, const int32_t* d_counts, int stride);   // landmark slots in use per problem (device counters), or null
 int32_t vo_ba_check_params(vo_ctx* c, const vo_ba_params* prm);   // loss code and f_scale: VO_OK or VO_E_INVALID (nothing enqueued)
-int32_t vo_ba_enqueue_budget(vo_ctx* c, const vo_ba_params* prm, int it0, int n_it);   // iterations it0 .. it0 + n_it - 1, then publish
+// what one enqueue of the bundle adjustment is told beside its parameters; all zero = none of it
+struct vo_ba_enqueue_opts {
+  hipEvent_t wait_before_publish;   // k_ba_finalize waits for it (pipelined frame step: the copy of the previous solution has left d_pub)
+  hipEvent_t wide_event;            // recorded behind the first `wide_groups` LM groups (pipelined frame step: the next tracker launch waits for it)
+  int wide_groups;
+  const int32_t* d_live;            // closed loop: d_live[b * live_stride] landmark slots of problem b are in use (device counters); null = all N
+  int live_stride;
+};
+int32_t vo_ba_enqueue_solve(vo_ctx* c, hipStream_t q, const vo_ba_params* prm, const vo_ba_enqueue_opts& o);   // vo_ba_solve_resident's enqueue
+int32_t vo_ba_enqueue_budget(vo_ctx* c, hipStream_t q, const vo_ba_params* prm, int it0, int n_it, const vo_ba_enqueue_opts& o);   // iterations it0 .. it0 + n_it - 1, then publish
 // 3D-2D pose: correspondences written on the device, counts[b] of them per sequence
 struct vo_pnp_view { float* X; float* uv; const uint8_t* mask; const double* out; const int32_t* ctrl; size_t ctrl_stride; int cap; };
 int32_t vo_pnp_reserve(vo_ctx* c, const double* K_host);
 int32_t vo_pnp_get_view(vo_ctx* c, vo_pnp_view* v);
-int32_t vo_pnp_enqueue_counts(vo_ctx* c, const vo_pnp_params* prm, int blind_batches, const int32_t* d_counts);
+int32_t vo_pnp_enqueue_counts(vo_ctx* c, hipStream_t q, const vo_pnp_params* prm, int blind_batches, const int32_t* d_counts);
 // triangulation of up to n_hi pairs per sequence (c->d_uv0 / d_uv1), counts[b] valid; point i of sequence b uses cams[b][cam_sel[b][i]]
-int32_t vo_dlt_enqueue_counts(vo_ctx* c, int n_hi, const int32_t* d_counts, const vo_dlt_cam* d_cams, const int32_t* d_cam_sel, int cams_per_seq);
+int32_t vo_dlt_enqueue_counts(vo_ctx* c, hipStream_t q, int n_hi, const int32_t* d_counts, const vo_dlt_cam* d_cams, const int32_t* d_cam_sel, int cams_per_seq);
+int32_t vo_dlt_enqueue(vo_ctx* c, hipStream_t q, int n);     // the uploaded pairs (vo_dlt_resident's enqueue), n = c->dlt_n > 0: the caller's check
 void vo_pnp_destroy(vo_ctx* c);
 void vo_ess_destroy(vo_ctx* c);
 void vo_match_destroy(vo_ctx* c);

@@ -357,14 +357,14 @@ int32_t vo_klt_make_args(vo_ctx* c, int n, const vo_klt_params* prm, klt_args& A
   return VO_OK;
 }
 
-static int32_t klt_launch(vo_ctx* c, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* counts) {
+static int32_t klt_launch(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* counts) {
   c->fb_n = -1;                         // the last track ran without the forward-backward check (vo_fb_read)
   klt_args A;
   { const int32_t r = vo_klt_make_args(c, n, prm, A); if (r != VO_OK || n == 0) return r; }
   {
-    vo_prof_scope prof(c, VO_PROF_KLT);   // brackets exactly this launch (bench.py roofline figure)
+    vo_prof_scope prof(c, q, VO_PROF_KLT);   // brackets exactly this launch (bench.py roofline figure)
     const int waves = c->tune.klt_waves > 0 ? c->tune.klt_waves : 6;
-#define VO_KLT_LAUNCH(WV) hipLaunchKernelGGL(k_klt_track<WV>, dim3(n, c->batch), dim3(64), 0, c->stream, A,                \
+#define VO_KLT_LAUNCH(WV) hipLaunchKernelGGL(k_klt_track<WV>, dim3(n, c->batch), dim3(64), 0, q, A,                \
                        vo_slab<const float>(c, off_in), vo_slab<float>(c, off_out), vo_slab<uint8_t>(c, c->off_status),     \
                        vo_slab<float>(c, c->off_err), c->d_iters, c->d_dbg, counts)
 #ifdef VO_EXPERIMENTS
@@ -372,7 +372,7 @@ static int32_t klt_launch(vo_ctx* c, int n, const vo_klt_params* prm, size_t off
     const int pair = c->tune.klt_pair;
     if (pair) {
       const int npair = (n + 1) / 2;
-#define VO_KLT_LAUNCH2(WV) hipLaunchKernelGGL(k_klt_track2<WV>, dim3(npair, c->batch), dim3(64), 0, c->stream, A,            \
+#define VO_KLT_LAUNCH2(WV) hipLaunchKernelGGL(k_klt_track2<WV>, dim3(npair, c->batch), dim3(64), 0, q, A,            \
                        vo_slab<const float>(c, off_in), vo_slab<float>(c, off_out), vo_slab<uint8_t>(c, c->off_status),     \
                        vo_slab<float>(c, c->off_err), c->d_iters, counts)
       if (pair == 3) VO_KLT_LAUNCH2(3); else if (pair == 5) VO_KLT_LAUNCH2(5); else VO_KLT_LAUNCH2(4);
@@ -406,7 +406,7 @@ extern "C" int32_t vo_klt_track(vo_ctx* c, const float* p0, int32_t n, const vo_
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   const size_t off_in = vo_off_p(c), off_out = vo_off_p_next(c);
   VO_HIP(c, slab_h2d(c, off_in, p0, sizeof(float) * 2 * n));
-  int32_t r = klt_launch(c, n, prm, off_in, off_out, nullptr);
+  int32_t r = klt_launch(c, c->stream, n, prm, off_in, off_out, nullptr);
   if (r != VO_OK) return r;
   VO_HIP(c, slab_d2h(c, p1, off_out, sizeof(float) * 2 * n));
   VO_HIP(c, slab_d2h(c, status, c->off_status, n));
@@ -452,16 +452,18 @@ extern "C" int32_t vo_points_download(vo_ctx* c, float* p, uint8_t* status, floa
 
 extern "C" int32_t vo_klt_track_resident(vo_ctx* c, int32_t n, const vo_klt_params* prm) {
   if (!c) return VO_E_INVALID;
-  return vo_klt_track_resident_counts(c, n, prm, c->d_pt_counts);      // (non-null only while a vo_tracks_* table is seeded)
-}
-
-int32_t vo_klt_track_resident_counts(vo_ctx* c, int32_t n, const vo_klt_params* prm, const int32_t* d_counts) {
-  vo_klt_params def;
-  if (!prm) { vo_klt_default_params(&def); prm = &def; }
+  // (checked here too: a refused call neither touches the device nor waits for the side streams; the enqueue form checks for the step orchestrators)
   VO_CHECK(c, n >= 0 && n <= c->n_resident, VO_E_INVALID, "n exceeds the resident point set");
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  int32_t r = klt_launch(c, n, prm, vo_off_p(c), vo_off_p_next(c), d_counts);
+  return vo_klt_track_resident_counts(c, c->stream, n, prm, c->d_pt_counts);      // (non-null only while a vo_tracks_* table is seeded)
+}
+
+int32_t vo_klt_track_resident_counts(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts) {
+  vo_klt_params def;
+  if (!prm) { vo_klt_default_params(&def); prm = &def; }
+  VO_CHECK(c, n >= 0 && n <= c->n_resident, VO_E_INVALID, "n exceeds the resident point set");
+  int32_t r = klt_launch(c, q, n, prm, vo_off_p(c), vo_off_p_next(c), d_counts);
   if (r != VO_OK) return r;
   c->p_parity ^= 1;   // tracked positions become the resident set
   return VO_OK;

@@ -89,7 +89,7 @@ void vo_fb_destroy(vo_ctx* c) {
   c->d_fb = nullptr;
 }
 
-static int32_t fb_launch(vo_ctx* c, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* counts) {
+static int32_t fb_launch(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* counts) {
   c->fb_n = -1;
   klt_args A;
   { const int32_t r = vo_klt_make_args(c, n, prm, A); if (r != VO_OK) return r; }
@@ -105,8 +105,8 @@ static int32_t fb_launch(vo_ctx* c, int n, const vo_klt_params* prm, size_t off_
   F.fb_seq = c->fb_seq; F.off_err = c->fb_off_err; F.off_ok = c->fb_off_ok;
   F.max_err = c->fb_max_err;
   {
-    vo_prof_scope prof(c, VO_PROF_KLT);
-    hipLaunchKernelGGL(k_klt_track_fb<6>, dim3(n, c->batch), dim3(64), 0, c->stream, A, F, vo_slab<const float>(c, off_in),
+    vo_prof_scope prof(c, q, VO_PROF_KLT);
+    hipLaunchKernelGGL(k_klt_track_fb<6>, dim3(n, c->batch), dim3(64), 0, q, A, F, vo_slab<const float>(c, off_in),
                        vo_slab<float>(c, off_out), vo_slab<uint8_t>(c, c->off_status), vo_slab<float>(c, c->off_err), c->d_iters, counts, c->d_fb);
   }
   VO_HIP(c, hipGetLastError());
@@ -131,7 +131,7 @@ extern "C" int32_t vo_klt_track_fb(vo_ctx* c, const float* p0, int32_t n, const 
   const size_t off_in = vo_off_p(c), off_out = vo_off_p_next(c);
   VO_HIP(c, hipMemcpy2DAsync(c->d_slab + off_in, c->slab_seq, p0, sizeof(float) * 2 * n, sizeof(float) * 2 * n, c->batch,
                              hipMemcpyHostToDevice, c->stream));
-  const int32_t r = fb_launch(c, n, prm, off_in, off_out, nullptr);
+  const int32_t r = fb_launch(c, c->stream, n, prm, off_in, off_out, nullptr);
   if (r != VO_OK) return r;
   VO_HIP(c, rows_d2h(c, p1, c->d_slab + off_out, c->slab_seq, sizeof(float) * 2 * n));
   VO_HIP(c, rows_d2h(c, status, c->d_slab + c->off_status, c->slab_seq, n));
@@ -148,13 +148,11 @@ extern "C" int32_t vo_klt_track_fb(vo_ctx* c, const float* p0, int32_t n, const 
 }
 
 // the resident form (vo_tracks_track, the closed loop's TRACK stage): vo_klt_track_resident_counts with the check
-int32_t vo_klt_track_resident_fb(vo_ctx* c, int32_t n, const vo_klt_params* prm, const int32_t* d_counts) {
+int32_t vo_klt_track_resident_fb(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts) {
   vo_klt_params def;
   if (!prm) { vo_klt_default_params(&def); prm = &def; }
   VO_CHECK(c, n >= 0 && n <= c->n_resident, VO_E_INVALID, "n exceeds the resident point set");
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  const int32_t r = fb_launch(c, n, prm, vo_off_p(c), vo_off_p_next(c), d_counts);
+  const int32_t r = fb_launch(c, q, n, prm, vo_off_p(c), vo_off_p_next(c), d_counts);
   if (r != VO_OK) return r;
   c->p_parity ^= 1;   // tracked positions become the resident set
   return VO_OK;

@@ -1150,7 +1150,6 @@ void vo_pipe_destroy(vo_ctx* c) {
   if (w->ev_track) (void)hipEventDestroy(w->ev_track);
   delete w;
   c->pipe = nullptr;
-  vo_ba_set_live(c, nullptr, 0);       // (the counters the bundle adjustment looked at are gone)
 }
 
 extern "C" int32_t vo_pipe_default_params(vo_pipe_params* p) {
@@ -1357,20 +1356,19 @@ extern "C" int32_t vo_pipe_inliers_read(vo_ctx* c, uint8_t* mask, int32_t n) {
 }
 
 // entries per thread of the list kernels: the lists hold at most max_pts entries
-#define PIPE_DISPATCH_LDS(KERNEL, LDS, ...)                                                                                          \
+#define PIPE_DISPATCH_LDS(KERNEL, LDS, Q, ...)                                                                                       \
   do {                                                                                                                               \
-    if (w->N <= PIPE_TPB) hipLaunchKernelGGL(KERNEL<1>, dim3(c->batch), dim3(PIPE_TPB), LDS, c->stream, __VA_ARGS__);                 \
-    else if (w->N <= 2 * PIPE_TPB) hipLaunchKernelGGL(KERNEL<2>, dim3(c->batch), dim3(PIPE_TPB), LDS, c->stream, __VA_ARGS__);        \
-    else if (w->N <= 4 * PIPE_TPB) hipLaunchKernelGGL(KERNEL<4>, dim3(c->batch), dim3(PIPE_TPB), LDS, c->stream, __VA_ARGS__);        \
-    else hipLaunchKernelGGL(KERNEL<8>, dim3(c->batch), dim3(PIPE_TPB), LDS, c->stream, __VA_ARGS__);                                  \
+    if (w->N <= PIPE_TPB) hipLaunchKernelGGL(KERNEL<1>, dim3(c->batch), dim3(PIPE_TPB), LDS, Q, __VA_ARGS__);                         \
+    else if (w->N <= 2 * PIPE_TPB) hipLaunchKernelGGL(KERNEL<2>, dim3(c->batch), dim3(PIPE_TPB), LDS, Q, __VA_ARGS__);                \
+    else if (w->N <= 4 * PIPE_TPB) hipLaunchKernelGGL(KERNEL<4>, dim3(c->batch), dim3(PIPE_TPB), LDS, Q, __VA_ARGS__);                \
+    else hipLaunchKernelGGL(KERNEL<8>, dim3(c->batch), dim3(PIPE_TPB), LDS, Q, __VA_ARGS__);                                          \
   } while (0)
-#define PIPE_DISPATCH(KERNEL, ...) PIPE_DISPATCH_LDS(KERNEL, 0, __VA_ARGS__)
 
-static void pipe_launch_spawn(vo_ctx* c, int do_detect, int rebuild = 1) {
+static void pipe_launch_spawn(vo_ctx* c, hipStream_t q, int do_detect, int rebuild = 1) {
   vo_pipe_ws* w = c->pipe;
   vo_pnp_view pv;
   (void)vo_pnp_get_view(c, &pv);
-  PIPE_DISPATCH_LDS(k_pipe_spawn, 2 * sizeof(uint32_t) * (size_t)((w->R + 3) / 4), pipe_make(w), do_detect, vo_slab<const uint32_t>(c, c->off_st_scalars),
+  PIPE_DISPATCH_LDS(k_pipe_spawn, 2 * sizeof(uint32_t) * (size_t)((w->R + 3) / 4), q, pipe_make(w), do_detect, vo_slab<const uint32_t>(c, c->off_st_scalars),
                      vo_slab<const float>(c, c->off_st_out), vo_slab<float>(c, vo_off_p(c)), c->slab_seq, w->prm.max_new, pv.out, pv.ctrl,
                 pv.ctrl_stride, w->d_rec, rebuild);
 }
@@ -1382,10 +1380,10 @@ extern "C" int32_t vo_pipe_commit(vo_ctx* c) {
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   vo_pipe_ws* w = c->pipe;
   hipLaunchKernelGGL(k_pipe_dense, dim3(c->batch), dim3(PIPE_TPB), 0, c->stream, pipe_make(w), vo_slab<float>(c, vo_off_p(c)), c->slab_seq, 1);
-  pipe_launch_spawn(c, 0);                      // free lists (and a record of the seeded state)
+  pipe_launch_spawn(c, c->stream, 0);           // free lists (and a record of the seeded state)
   { vo_ba_view bv; const int32_t rb = vo_ba_get_view(c, &bv); if (rb != VO_OK) return rb;
     const pipe_ptrs P = pipe_make(w);
-    PIPE_DISPATCH(k_pipe_writeback, P, 0, bv.pub, bv.pub_bytes, bv.x0, bv.x_stride, bv.W, w->d_rec); }
+    PIPE_DISPATCH_LDS(k_pipe_writeback, 0, c->stream, P, 0, bv.pub, bv.pub_bytes, bv.x0, bv.x_stride, bv.W, w->d_rec); }
   VO_HIP(c, hipGetLastError());
   VO_HIP(c, hipStreamSynchronize(c->stream));
   return VO_OK;
@@ -1469,12 +1467,7 @@ static int32_t pipe_step_entry(vo_ctx* c, int32_t frame_idx, int32_t stages) {
   const bool dirty = c->main_dirty;               // something other than a pipe step has used the ctx stream since the last one
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   c->main_dirty = false;
-  hipStream_t const main_stream = c->stream;
-  c->in_step = true;                              // the stage calls below must not wait for the side streams on the host
-  const int32_t r = pipe_step(c, frame_idx, stages, dirty);
-  c->in_step = false;
-  c->stream = main_stream;                        // (an early return may have left the side stream selected)
-  return r;
+  return pipe_step(c, frame_idx, stages, dirty);
 }
 
 static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main_dirty) {
@@ -1495,7 +1488,6 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
   // flight.  The main stream waits for the side stream twice per step (before extend, before the record leaves), so after every call
   // it is downstream of all side work.  A frame the caller pushed itself (frame_idx < 0) is tracked on the main stream as before.
   const bool side = c->side_stream != 0 && c->stream2 != nullptr;
-  hipStream_t const main_stream = c->stream;
   const int halves = (stages & (VO_PIPE_TRACK_CANDIDATES | VO_PIPE_TRACK_LANDMARKS)) ? (((stages & VO_PIPE_TRACK_CANDIDATES) ? 1 : 0) | ((stages & VO_PIPE_TRACK_LANDMARKS) ? 2 : 0)) : 3;
   // (the stage combinations, the frame store and the resident sequence were checked by pipe_step_admit)
   if (stages & (VO_PIPE_TRACK | VO_PIPE_TRACK_LANDMARKS)) w->lm_half_pending = (stages & VO_PIPE_TRACK) && halves == 1;
@@ -1511,21 +1503,19 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
     }
     // (the pyramid on a stream of its own, ahead of the side stream's re-detection: measured, slower -- every cross-stream event costs more
     //  than the five launches it would overlap; one context of 96 sequences 37.5 k against 39.0 k frames/s, one sequence 2 320 against 2 715)
-    if (track_side) c->stream = c->stream2;
+    hipStream_t const tq = track_side ? c->stream2 : c->stream;      // the stream of the pyramid and the tracker
     if (from_host) {
       const int slot = c->pipe_host_slot;
-      const hipError_t ew = hipStreamWaitEvent(c->stream, c->ev_h2d[slot], 0);
-      if (ew != hipSuccess) { c->stream = main_stream; VO_HIP(c, ew); }
-      r = vo_build_pyramid(c, c->d_host_raw[slot], (size_t)c->width * c->height, nullptr);
-      if (r == VO_OK && hipEventRecord(c->ev_raw_free[slot], c->stream) == hipSuccess) c->raw_free_recorded[slot] = true;
+      VO_HIP(c, hipStreamWaitEvent(tq, c->ev_h2d[slot], 0));
+      r = vo_build_pyramid(c, tq, c->d_host_raw[slot], (size_t)c->width * c->height, nullptr);
+      if (r == VO_OK && hipEventRecord(c->ev_raw_free[slot], tq) == hipSuccess) c->raw_free_recorded[slot] = true;
     } else if (frame_idx >= 0) {
       const size_t fr = (size_t)c->width * c->height;
-      r = vo_build_pyramid(c, c->d_seq + (size_t)frame_idx * fr, fr * c->seq_n, nullptr);
+      r = vo_build_pyramid(c, tq, c->d_seq + (size_t)frame_idx * fr, fr * c->seq_n, nullptr);
     }
     w->fb_active = vo_fb_on(c);                      // vo_set_fb_check: track with the forward-backward check
-    if (r == VO_OK) r = w->fb_active ? vo_klt_track_resident_fb(c, w->N, &prm.klt, w->d_dn + DN_PTS * B)
-                                     : vo_klt_track_resident_counts(c, w->N, &prm.klt, w->d_dn + DN_PTS * B);
-    c->stream = main_stream;
+    if (r == VO_OK) r = w->fb_active ? vo_klt_track_resident_fb(c, tq, w->N, &prm.klt, w->d_dn + DN_PTS * B)
+                                     : vo_klt_track_resident_counts(c, tq, w->N, &prm.klt, w->d_dn + DN_PTS * B);
     if (track_side) {                                  // joined on every path
       const hipError_t e1 = hipEventRecord(w->ev_track, c->stream2);
       const hipError_t e2 = hipStreamWaitEvent(c->stream, w->ev_track, 0);
@@ -1536,88 +1526,63 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
   // the keep rule / bookkeeping on the tracked point set: with TRACK, or alone (VO_PIPE_TRACK_LANDMARKS after a TRACK | VO_PIPE_TRACK_CANDIDATES call)
   if ((stages & VO_PIPE_TRACK) || (stages & (VO_PIPE_TRACK_CANDIDATES | VO_PIPE_TRACK_LANDMARKS))) {
     const size_t lds = sizeof(int32_t) * ((w->N > 4 * PIPE_TPB ? 0 : (size_t)w->R) + 3 * (size_t)w->N);     // (above 4 096 slots the row words are global)
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(c->batch), dim3(PIPE_TPB), lds, c->stream, P, vo_slab<const float>(c, vo_off_p(c)), c->slab_seq,
-                         c->width, c->height, pv.X, pv.uv, pv.cap, halves, const_cast<uint8_t*>(pv.mask),
-                         (w->fb_active && w->N > 0) ? vo_fb_ok(c) : nullptr, c->fb_seq);
-    };
-    if (w->N <= PIPE_TPB) launch(k_pipe_extend<1>);
-    else if (w->N <= 2 * PIPE_TPB) launch(k_pipe_extend<2>);
-    else if (w->N <= 4 * PIPE_TPB) launch(k_pipe_extend<4>);
-    else launch(k_pipe_extend<8>);
+    PIPE_DISPATCH_LDS(k_pipe_extend, lds, c->stream, P, vo_slab<const float>(c, vo_off_p(c)), c->slab_seq, c->width, c->height, pv.X, pv.uv, pv.cap,
+                      halves, const_cast<uint8_t*>(pv.mask), (w->fb_active && w->N > 0) ? vo_fb_ok(c) : nullptr, c->fb_seq);
   }
   if (stages & VO_PIPE_POSE) {
-    r = vo_pnp_enqueue_counts(c, &prm.pnp, prm.pnp_blind_batches, w->d_dn + DN_PNP * B);
+    r = vo_pnp_enqueue_counts(c, c->stream, &prm.pnp, prm.pnp_blind_batches, w->d_dn + DN_PNP * B);
     if (r != VO_OK) return r;
   }
   if (stages & (VO_PIPE_POSE | VO_PIPE_TRIANGULATE))
   {
     const size_t lds = sizeof(int32_t) * 3 * (size_t)w->N;
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(c->batch), dim3(PIPE_TPB), lds, c->stream, P, (stages & VO_PIPE_POSE) ? 1 : 0, (stages & VO_PIPE_TRIANGULATE) ? 1 : 0,
-                         pv.mask, pv.out, pv.cap, prm.min_track_length, c->d_uv0, c->d_uv1, (size_t)c->max_pts * 2, w->d_cams, w->d_cam_sel);
-    };
-    if (w->N <= PIPE_TPB) launch(k_pipe_prune<1>);
-    else if (w->N <= 2 * PIPE_TPB) launch(k_pipe_prune<2>);
-    else if (w->N <= 4 * PIPE_TPB) launch(k_pipe_prune<4>);
-    else launch(k_pipe_prune<8>);
+    PIPE_DISPATCH_LDS(k_pipe_prune, lds, c->stream, P, (stages & VO_PIPE_POSE) ? 1 : 0, (stages & VO_PIPE_TRIANGULATE) ? 1 : 0, pv.mask, pv.out, pv.cap,
+                      prm.min_track_length, c->d_uv0, c->d_uv1, (size_t)c->max_pts * 2, w->d_cams, w->d_cam_sel);
   }
   if (stages & VO_PIPE_TRIANGULATE) {
-    r = vo_dlt_enqueue_counts(c, w->N, w->d_dn + DN_RIPE * B, w->d_cams, w->d_cam_sel, PIPE_HIST);
+    r = vo_dlt_enqueue_counts(c, c->stream, w->N, w->d_dn + DN_RIPE * B, w->d_cams, w->d_cam_sel, PIPE_HIST);
     if (r != VO_OK) return r;
   }
   if (stages & (VO_PIPE_TRIANGULATE | VO_PIPE_ADJUST))
   {
     const size_t lds = sizeof(int32_t) * 3 * (size_t)w->N + (size_t)w->R;
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(c->batch), dim3(PIPE_TPB), lds, c->stream, P, (stages & VO_PIPE_TRIANGULATE) ? 1 : 0, (stages & VO_PIPE_ADJUST) ? 1 : 0,
-                         vo_slab<const float>(c, c->off_X4), vo_slab<const double>(c, c->off_depth), vo_slab<const double>(c, c->off_reproj), c->slab_seq,
-                         w->N, prm.max_reproj_err, prm.min_bearing_angle, w->d_cam_sel, bv.W, prm.resurrect, bv.x0, bv.obs, bv.x_stride, bv.obs_stride, bv.N,
-                         vo_slab<float>(c, vo_off_p(c)), c->slab_seq);
-    };
-    if (w->N <= PIPE_TPB) launch(k_pipe_promote<1>);
-    else if (w->N <= 2 * PIPE_TPB) launch(k_pipe_promote<2>);
-    else if (w->N <= 4 * PIPE_TPB) launch(k_pipe_promote<4>);
-    else launch(k_pipe_promote<8>);
+    PIPE_DISPATCH_LDS(k_pipe_promote, lds, c->stream, P, (stages & VO_PIPE_TRIANGULATE) ? 1 : 0, (stages & VO_PIPE_ADJUST) ? 1 : 0,
+                      vo_slab<const float>(c, c->off_X4), vo_slab<const double>(c, c->off_depth), vo_slab<const double>(c, c->off_reproj), c->slab_seq,
+                      w->N, prm.max_reproj_err, prm.min_bearing_angle, w->d_cam_sel, bv.W, prm.resurrect, bv.x0, bv.obs, bv.x_stride, bv.obs_stride, bv.N,
+                      vo_slab<float>(c, vo_off_p(c)), c->slab_seq);
     if (w->N > 2 * PIPE_TPB)     // (the CH >= 4 kernels leave the problem / point-set phase to a wide launch)
       hipLaunchKernelGGL(k_pipe_problem, dim3(vo_div_up(w->N, 256), c->batch), dim3(256), 0, c->stream, P, (stages & VO_PIPE_ADJUST) ? 1 : 0, bv.W, bv.x0, bv.obs,
                          bv.x_stride, bv.obs_stride, bv.N, vo_slab<float>(c, vo_off_p(c)), c->slab_seq);
   }
   else if (halves & 2)   // (after the candidates' half alone the buffer still holds the tracked positions the landmarks' half will read)
     hipLaunchKernelGGL(k_pipe_dense, dim3(B), dim3(PIPE_TPB), 0, c->stream, P, vo_slab<float>(c, vo_off_p(c)), c->slab_seq, 0);
+  // the adjustment counts the landmark slots in use by the loop's own counters: an option of ITS enqueues, so that any other entry point that solves
+  // on the shared BA workspace (vo_ba_solve_resident on a problem written through vo_ba_obs_device) sees every slot
+  vo_ba_enqueue_opts ba_live = {};
+  ba_live.d_live = (const int32_t*)w->tab[VO_PIPE_COUNTS] + C_NLM; ba_live.live_stride = PIPE_NCNT;
   if (side) {
     // re-detection + spawn on the side stream behind promote / dense; adjustment + write-back on the main stream
     VO_HIP(c, hipEventRecord(c->ev_fork, c->stream));
     VO_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-    c->stream = c->stream2;
-    r = (stages & VO_PIPE_DETECT) ? vo_shi_tomasi_resident_counts(c, w->N, prm.mask_radius, &prm.st, w->d_dn + DN_PTS * B, w->d_dn + DN_ROOM * B) : VO_OK;
-    if (r == VO_OK) pipe_launch_spawn(c, (stages & VO_PIPE_DETECT) ? 1 : 0, (stages & VO_PIPE_KEEP_FREE_LISTS) ? 0 : 1);
-    c->stream = main_stream;
-    if (r == VO_OK && (stages & VO_PIPE_ADJUST)) {
-      // the live-slot counters are scoped to THIS enqueue: any other entry point that solves on the shared BA workspace afterwards
-      // (vo_ba_solve_resident on a problem written through vo_ba_obs_device) must see every slot again
-      vo_ba_set_live(c, (const int32_t*)w->tab[VO_PIPE_COUNTS] + C_NLM, PIPE_NCNT);
-      r = vo_ba_enqueue_budget(c, &prm.ba, 0, prm.ba_budget);
-      vo_ba_set_live(c, nullptr, 0);
-    }
-    if (r == VO_OK) PIPE_DISPATCH(k_pipe_writeback, P, (stages & VO_PIPE_ADJUST) ? 1 : 0, bv.pub, bv.pub_bytes, bv.x0, bv.x_stride, bv.W, w->d_rec);
+    r = (stages & VO_PIPE_DETECT) ? vo_shi_tomasi_resident_counts(c, c->stream2, w->N, prm.mask_radius, &prm.st, w->d_dn + DN_PTS * B, w->d_dn + DN_ROOM * B) : VO_OK;
+    if (r == VO_OK) pipe_launch_spawn(c, c->stream2, (stages & VO_PIPE_DETECT) ? 1 : 0, (stages & VO_PIPE_KEEP_FREE_LISTS) ? 0 : 1);
+    if (r == VO_OK && (stages & VO_PIPE_ADJUST)) r = vo_ba_enqueue_budget(c, c->stream, &prm.ba, 0, prm.ba_budget, ba_live);
+    if (r == VO_OK) PIPE_DISPATCH_LDS(k_pipe_writeback, 0, c->stream, P, (stages & VO_PIPE_ADJUST) ? 1 : 0, bv.pub, bv.pub_bytes, bv.x0, bv.x_stride, bv.W, w->d_rec);
     const hipError_t e1 = hipEventRecord(c->ev_join, c->stream2);
     const hipError_t e2 = hipStreamWaitEvent(c->stream, c->ev_join, 0);     // joined on every path: nothing is left running on the side stream
     if (r != VO_OK) return r;
     VO_HIP(c, e1); VO_HIP(c, e2);
   } else {
     if (stages & VO_PIPE_ADJUST) {
-      vo_ba_set_live(c, (const int32_t*)w->tab[VO_PIPE_COUNTS] + C_NLM, PIPE_NCNT);
-      r = vo_ba_enqueue_budget(c, &prm.ba, 0, prm.ba_budget);
-      vo_ba_set_live(c, nullptr, 0);
+      r = vo_ba_enqueue_budget(c, c->stream, &prm.ba, 0, prm.ba_budget, ba_live);
       if (r != VO_OK) return r;
     }
     if (stages & VO_PIPE_DETECT) {
-      r = vo_shi_tomasi_resident_counts(c, w->N, prm.mask_radius, &prm.st, w->d_dn + DN_PTS * B, w->d_dn + DN_ROOM * B);
+      r = vo_shi_tomasi_resident_counts(c, c->stream, w->N, prm.mask_radius, &prm.st, w->d_dn + DN_PTS * B, w->d_dn + DN_ROOM * B);
       if (r != VO_OK) return r;
     }
-    PIPE_DISPATCH(k_pipe_writeback, P, (stages & VO_PIPE_ADJUST) ? 1 : 0, bv.pub, bv.pub_bytes, bv.x0, bv.x_stride, bv.W, w->d_rec);
-    pipe_launch_spawn(c, (stages & VO_PIPE_DETECT) ? 1 : 0, (stages & VO_PIPE_KEEP_FREE_LISTS) ? 0 : 1);
+    PIPE_DISPATCH_LDS(k_pipe_writeback, 0, c->stream, P, (stages & VO_PIPE_ADJUST) ? 1 : 0, bv.pub, bv.pub_bytes, bv.x0, bv.x_stride, bv.W, w->d_rec);
+    pipe_launch_spawn(c, c->stream, (stages & VO_PIPE_DETECT) ? 1 : 0, (stages & VO_PIPE_KEEP_FREE_LISTS) ? 0 : 1);
   }
   VO_HIP(c, hipGetLastError());
   const int slot = (int)(w->enq % VO_PIPE_INFLIGHT);

@@ -757,23 +757,23 @@ static int32_t pnp_alloc(vo_ctx* c, int n) {
 }
 
 // k: index of the batch within its search (0: the small first batch); first: the control block is reset by this batch's own kernels
-static void pnp_enqueue_batch(vo_ctx* c, const vo_pnp_params* prm, int k, const int32_t* counts = nullptr, int first = 0) {
+static void pnp_enqueue_batch(vo_ctx* c, hipStream_t q, const vo_pnp_params* prm, int k, const int32_t* counts = nullptr, int first = 0) {
   vo_pnp_ws* w = c->pnp;
   const unsigned B = (unsigned)c->batch;
   const double thr2 = prm->reproj_err * prm->reproj_err;
   const int nb = k == 0 ? PNP_FIRST_BATCH : PNP_BATCH;
-  hipLaunchKernelGGL(k_pnp_solve, dim3((nb + 63) / 64, B), dim3(64), 0, c->stream, w->d_K, w->d_X, w->d_uv, w->cap, w->n, (unsigned)prm->seed,
+  hipLaunchKernelGGL(k_pnp_solve, dim3((nb + 63) / 64, B), dim3(64), 0, q, w->d_K, w->d_X, w->d_uv, w->cap, w->n, (unsigned)prm->seed,
                      w->d_hyp, w->d_ctrl, counts, first, nb);
-  hipLaunchKernelGGL(k_pnp_score, dim3(nb, B), dim3(PNP_SCORE_THREADS), 0, c->stream, w->d_K, w->d_X, w->d_uv, w->cap, w->n, thr2, w->d_hyp, counts);
-  hipLaunchKernelGGL(k_pnp_select, dim3(B), dim3(PNP_BATCH), 0, c->stream, w->d_hyp, w->d_ctrl, w->n, prm->confidence, prm->max_iters, counts, first, nb);
+  hipLaunchKernelGGL(k_pnp_score, dim3(nb, B), dim3(PNP_SCORE_THREADS), 0, q, w->d_K, w->d_X, w->d_uv, w->cap, w->n, thr2, w->d_hyp, counts);
+  hipLaunchKernelGGL(k_pnp_select, dim3(B), dim3(PNP_BATCH), 0, q, w->d_hyp, w->d_ctrl, w->n, prm->confidence, prm->max_iters, counts, first, nb);
 }
 
-static int32_t pnp_enqueue_refine(vo_ctx* c, const vo_pnp_params* prm, const int32_t* counts = nullptr) {
+static int32_t pnp_enqueue_refine(vo_ctx* c, hipStream_t q, const vo_pnp_params* prm, const int32_t* counts = nullptr) {
   vo_pnp_ws* w = c->pnp;
   const size_t B = c->batch;
   const int n_most = counts ? w->cap : w->n;          // (device-side counts never exceed the capacity)
   auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(PNP_REFINE_THREADS), 0, c->stream, w->d_K, w->d_X, w->d_uv, w->cap, w->n,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(PNP_REFINE_THREADS), 0, q, w->d_K, w->d_X, w->d_uv, w->cap, w->n,
                        prm->reproj_err * prm->reproj_err, w->d_ctrl, w->d_mask, w->d_out, counts);
   };
   if (n_most <= 4 * PNP_REFINE_THREADS) launch(k_pnp_refine<4>);
@@ -781,8 +781,8 @@ static int32_t pnp_enqueue_refine(vo_ctx* c, const vo_pnp_params* prm, const int
   else launch(k_pnp_refine<0>);
   VO_HIP(c, hipGetLastError());
   if (counts) return VO_OK;       // closed-loop pipeline: the results are consumed on the device
-  VO_HIP(c, hipMemcpyAsync(w->h_out, w->d_out, sizeof(double) * 8 * B, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP(c, hipMemcpyAsync(w->h_ctrl, w->d_ctrl, sizeof(pnp_ctrl) * B, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP(c, hipMemcpyAsync(w->h_out, w->d_out, sizeof(double) * 8 * B, hipMemcpyDeviceToHost, q));
+  VO_HIP(c, hipMemcpyAsync(w->h_ctrl, w->d_ctrl, sizeof(pnp_ctrl) * B, hipMemcpyDeviceToHost, q));
   return VO_OK;
 }
 
@@ -802,10 +802,10 @@ int32_t vo_pnp_get_view(vo_ctx* c, vo_pnp_view* v) {
   v->ctrl_stride = sizeof(pnp_ctrl) / sizeof(int32_t); v->cap = w->cap;
   return VO_OK;
 }
-int32_t vo_pnp_enqueue_counts(vo_ctx* c, const vo_pnp_params* prm, int blind_batches, const int32_t* d_counts) {
+int32_t vo_pnp_enqueue_counts(vo_ctx* c, hipStream_t q, const vo_pnp_params* prm, int blind_batches, const int32_t* d_counts) {
   VO_CHECK(c, c->pnp, VO_E_STATE, "vo_pnp_reserve first");
-  for (int k = 0; k < blind_batches; k++) pnp_enqueue_batch(c, prm, k, d_counts, k == 0 ? 1 : 0);     // (blind_batches >= 1: vo_pipe_create)
-  return pnp_enqueue_refine(c, prm, d_counts);
+  for (int k = 0; k < blind_batches; k++) pnp_enqueue_batch(c, q, prm, k, d_counts, k == 0 ? 1 : 0);     // (blind_batches >= 1: vo_pipe_create)
+  return pnp_enqueue_refine(c, q, prm, d_counts);
 }
 
 // resident form: the correspondences stay in HBM (vo_pnp_upload), a solve is enqueued per frame without any host
@@ -843,8 +843,8 @@ extern "C" int32_t vo_pnp_solve_resident(vo_ctx* c, const vo_pnp_params* prm, in
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   vo_pnp_ws* w = c->pnp;
   hipLaunchKernelGGL(k_pnp_init, dim3((unsigned)c->batch), dim3(1), 0, c->stream, w->d_ctrl, prm->max_iters);
-  for (int k = 0; k < blind_batches; k++) pnp_enqueue_batch(c, prm, k);
-  return pnp_enqueue_refine(c, prm);
+  for (int k = 0; k < blind_batches; k++) pnp_enqueue_batch(c, c->stream, prm, k);
+  return pnp_enqueue_refine(c, c->stream, prm);
 }
 
 extern "C" int32_t vo_pnp_fetch(vo_ctx* c, double* rvec, double* tvec, uint8_t* inlier_mask, vo_pnp_stats* stats) {
@@ -886,14 +886,14 @@ extern "C" int32_t vo_pnp_ransac(vo_ctx* c, const double* K, const float* pts3d,
   // batches of 32, then 256 hypotheses per sequence until every sequence has reached its iteration bound (typically one or
   // two batches: the bound is 33 iterations at 70 % inliers, 145 at 50 %)
   for (int guard = 0; guard < (prm->max_iters + PNP_BATCH - 1) / PNP_BATCH + 1; guard++) {
-    pnp_enqueue_batch(c, prm, guard);
+    pnp_enqueue_batch(c, c->stream, prm, guard);
     VO_HIP(c, hipMemcpyAsync(w->h_ctrl, w->d_ctrl, sizeof(pnp_ctrl) * B, hipMemcpyDeviceToHost, c->stream));
     VO_HIP(c, hipStreamSynchronize(c->stream));
     bool all = true;
     for (size_t b = 0; b < B; b++) all = all && w->h_ctrl[b].done;
     if (all) break;
   }
-  r = pnp_enqueue_refine(c, prm);
+  r = pnp_enqueue_refine(c, c->stream, prm);
   if (r != VO_OK) return r;
   r = vo_pnp_fetch(c, rvec, tvec, inlier_mask, stats);
   if (r != VO_OK) return r;

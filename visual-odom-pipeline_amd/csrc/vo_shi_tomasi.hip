@@ -1057,7 +1057,7 @@ void vo_st_destroy(vo_ctx* c) {
   c->st = nullptr;
 }
 
-static int32_t st_init(vo_ctx* c) {
+static int32_t st_init(vo_ctx* c, hipStream_t q) {
   if (c->st) return VO_OK;
   vo_st_ws* s = new vo_st_ws();
   c->st = s;
@@ -1068,7 +1068,7 @@ static int32_t st_init(vo_ctx* c) {
   s->d_scalars = vo_slab<uint32_t>(c, c->off_st_scalars);
   VO_HIP(c, hipMalloc((void**)&s->d_cand, sizeof(unsigned long long) * ST_CAND_STRIDE * B));
   VO_HIP(c, hipMalloc((void**)&s->d_nraw, sizeof(uint32_t) * B));
-  VO_HIP(c, hipMemsetAsync(s->d_nraw, 0, sizeof(uint32_t) * B, c->stream));
+  VO_HIP(c, hipMemsetAsync(s->d_nraw, 0, sizeof(uint32_t) * B, q));
   s->n_blockmax = vo_div_up(c->width, 256 - 32) * c->height;                     // upper bound over both eigenvalue paths (1-row bands)
   VO_HIP(c, hipMalloc((void**)&s->d_blockmax, sizeof(float) * (size_t)s->n_blockmax * B));
   s->d_out = vo_slab<float>(c, c->off_st_out);
@@ -1106,7 +1106,7 @@ void vo_st_flags_restore(vo_ctx* c, int saved) { if (c->st && saved >= 0) { c->s
 int vo_st_launch_state(const vo_ctx* c) { return c->st ? (c->st->mask_clean ? 1 : 0) | (c->tune.st_keep_eig ? 2 : 0) : 0; }   // decides which kernels a resident launch enqueues
 // all allocations a launch with these parameters needs (called outside any graph capture)
 int32_t vo_st_prepare(vo_ctx* c, const vo_st_params* prm) {
-  int32_t r = st_init(c);
+  int32_t r = st_init(c, c->stream);
   if (r != VO_OK) return r;
   vo_st_ws* s = c->st;
   const bool fused = !c->tune.st_two_kernels && prm && prm->block_size == 31 && c->height > 31 && c->width > 31;
@@ -1124,7 +1124,7 @@ extern "C" int32_t vo_st_default_params(vo_st_params* p) {
 // pts: sequence-0 pointer of the exclusion-disc centres, pts_seq: byte stride between sequences
 // keep: store the eigenvalue map and leave the exclusion mask in place (vo_shi_tomasi_read); otherwise the fused kernel writes
 // no map and hands the mask back clean, which saves the k_st_mask_init launch of the next call
-static int32_t st_launch(vo_ctx* c, const float* d_pts, size_t pts_seq, int n_cur, int mask_radius, const uint8_t* d_user_mask,
+static int32_t st_launch(vo_ctx* c, hipStream_t q, const float* d_pts, size_t pts_seq, int n_cur, int mask_radius, const uint8_t* d_user_mask,
                          const vo_st_params* prm, const int32_t* counts, bool keep, const int32_t* limit_dev = nullptr) {
   VO_CHECK(c, c->n_pushed >= 1, VO_E_STATE, "no frame pushed");
   VO_CHECK(c, prm->block_size >= 1 && prm->block_size <= 31 && (prm->block_size & 1), VO_E_INVALID,
@@ -1132,7 +1132,7 @@ static int32_t st_launch(vo_ctx* c, const float* d_pts, size_t pts_seq, int n_cu
   VO_CHECK(c, mask_radius >= 0 && mask_radius <= ST_MAX_RADIUS, VO_E_INVALID, "mask_radius must be 0..31");
   VO_CHECK(c, prm->max_corners <= ST_OUT_CAP, VO_E_CAPACITY, "max_corners exceeds 4096");
   vo_st_ws* s = c->st;
-  vo_prof_scope prof(c, VO_PROF_ST);
+  vo_prof_scope prof(c, q, VO_PROF_ST);
   const int W = c->width, H = c->height, r = prm->block_size / 2, B = c->batch;
   const vo_frame& F = c->fr[c->cur];
   const double scale_d = 1.0 / ((double)(1 << 2) * prm->block_size * 255.0);
@@ -1143,18 +1143,18 @@ static int32_t st_launch(vo_ctx* c, const float* d_pts, size_t pts_seq, int n_cu
   int n_blockmax;
   if (fused) {
     if (keep || d_user_mask || !s->mask_clean)
-      hipLaunchKernelGGL(k_st_mask_init, dim3(vo_div_up((int)(((size_t)W * H + 15) / 16), 256), B), dim3(256), 0, c->stream, s->d_mask, d_user_mask,
+      hipLaunchKernelGGL(k_st_mask_init, dim3(vo_div_up((int)(((size_t)W * H + 15) / 16), 256), B), dim3(256), 0, q, s->d_mask, d_user_mask,
                          (size_t)W * H, s->d_scalars, c->slab_seq);
   } else {
     if (!s->d_h) VO_HIP(c, hipMalloc((void**)&s->d_h, (size_t)W * H * 3 * sizeof(int32_t) * B));
-    hipLaunchKernelGGL(k_st_sobel_hsum, dim3(vo_div_up(W, ST_HS_COLS), H, B), dim3(256), 0, c->stream, F.img[0], c->lvl_px[0],
+    hipLaunchKernelGGL(k_st_sobel_hsum, dim3(vo_div_up(W, ST_HS_COLS), H, B), dim3(256), 0, q, F.img[0], c->lvl_px[0],
                        c->lv[0].pitch, W, H, r, s->d_h, s->d_mask, d_user_mask, s->d_scalars, c->slab_seq);
   }
   if (n_cur > 0) {
     disc_rows rows;
     circle_rows(mask_radius, &rows);
     const int total = n_cur * (2 * mask_radius + 1);
-    hipLaunchKernelGGL(k_st_discs, dim3(vo_div_up(total, 256), B), dim3(256), 0, c->stream, d_pts, pts_seq, n_cur, mask_radius,
+    hipLaunchKernelGGL(k_st_discs, dim3(vo_div_up(total, 256), B), dim3(256), 0, q, d_pts, pts_seq, n_cur, mask_radius,
                        rows, s->d_mask, W, H, counts);
   }
   if (fused) {
@@ -1183,18 +1183,18 @@ static int32_t st_launch(vo_ctx* c, const float* d_pts, size_t pts_seq, int n_cu
     const bool nms_fused = !c->tune.st_separate_nms;
     const int xcd_remap = (!c->tune.xcd_remap_off && B % 8 == 0) ? 1 : 0;
     const bool restore = !keep && !d_user_mask && nms_fused;
-    hipLaunchKernelGGL(k_st_eig_fused<15>, dim3(gx, gy, B), dim3(256), 0, c->stream, F.img[0], c->lvl_px[0], c->lv[0].pitch, W, H, rb, s2,
+    hipLaunchKernelGGL(k_st_eig_fused<15>, dim3(gx, gy, B), dim3(256), 0, q, F.img[0], c->lvl_px[0], c->lv[0].pitch, W, H, rb, s2,
                        s->d_mask, (keep || !nms_fused) ? s->d_eig : nullptr, s->d_blockmax, prm->quality_level, s->d_cand, s->d_nraw,
                        restore ? 1 : 0, nms_fused ? 1 : 0, xcd_remap);
     if (!nms_fused)
-      hipLaunchKernelGGL(k_st_nms, dim3(vo_div_up(W - 2, 256), vo_div_up(H - 2, ST_NMS_ROWS), B), dim3(256), 0, c->stream, s->d_eig,
+      hipLaunchKernelGGL(k_st_nms, dim3(vo_div_up(W - 2, 256), vo_div_up(H - 2, ST_NMS_ROWS), B), dim3(256), 0, q, s->d_eig,
                          s->d_mask, W, H, prm->quality_level, s->d_blockmax, n_blockmax, s->d_cand, s->d_scalars, c->slab_seq, s->d_nraw);
     s->mask_clean = restore; s->eig_valid = keep || !nms_fused;
   } else {
     n_blockmax = vo_div_up(W, 256) * vo_div_up(H, ST_ROWS);
-    hipLaunchKernelGGL(k_st_vsum_eig, dim3(vo_div_up(W, 256), vo_div_up(H, ST_ROWS), B), dim3(256), 0, c->stream, s->d_h,
+    hipLaunchKernelGGL(k_st_vsum_eig, dim3(vo_div_up(W, 256), vo_div_up(H, ST_ROWS), B), dim3(256), 0, q, s->d_h,
                        s->d_mask, W, H, r, s2, s->d_eig, s->d_blockmax, prm->use_harris ? 1 : 0, prm->harris_k);
-    hipLaunchKernelGGL(k_st_nms, dim3(vo_div_up(W - 2, 256), vo_div_up(H - 2, ST_NMS_ROWS), B), dim3(256), 0, c->stream, s->d_eig,
+    hipLaunchKernelGGL(k_st_nms, dim3(vo_div_up(W - 2, 256), vo_div_up(H - 2, ST_NMS_ROWS), B), dim3(256), 0, q, s->d_eig,
                        s->d_mask, W, H, prm->quality_level, s->d_blockmax, n_blockmax, s->d_cand, s->d_scalars, c->slab_seq, s->d_nraw);
     s->mask_clean = false; s->eig_valid = true;
   }
@@ -1208,11 +1208,11 @@ static int32_t st_launch(vo_ctx* c, const float* d_pts, size_t pts_seq, int n_cu
   // the short-chunk instance keeps min(cap - accepted, ...) keys per pass: with a corner limit near its capacity the last corners would come
   // one tiny chunk -- and one rescan of the raw list -- at a time, so limits above half of it take the large instance
   if (limit_dev && (prm->max_corners > 0 && prm->max_corners <= ST_CAP_CLOSED_LOOP / 2))
-    hipLaunchKernelGGL(k_st_select<ST_CAP_CLOSED_LOOP>, dim3(B), dim3(1024), st_sel_lds(ST_CAP_CLOSED_LOOP), c->stream, s->d_cand,
+    hipLaunchKernelGGL(k_st_select<ST_CAP_CLOSED_LOOP>, dim3(B), dim3(1024), st_sel_lds(ST_CAP_CLOSED_LOOP), q, s->d_cand,
                        s->d_scalars, W, H, cell, gw, gh, md2, use_dist, prm->max_corners, s->d_out, c->slab_seq, c->d_dbg,
                        s->d_blockmax, n_blockmax, prm->quality_level, s->d_nraw, limit_dev);
   else
-    hipLaunchKernelGGL(k_st_select<ST_CAND_CAP>, dim3(B), dim3(1024), st_sel_lds(ST_CAND_CAP), c->stream, s->d_cand,
+    hipLaunchKernelGGL(k_st_select<ST_CAND_CAP>, dim3(B), dim3(1024), st_sel_lds(ST_CAND_CAP), q, s->d_cand,
                        s->d_scalars, W, H, cell, gw, gh, md2, use_dist, prm->max_corners, s->d_out, c->slab_seq, c->d_dbg,
                        s->d_blockmax, n_blockmax, prm->quality_level, s->d_nraw, limit_dev);
   VO_HIP(c, hipGetLastError());
@@ -1247,7 +1247,7 @@ extern "C" int32_t vo_shi_tomasi(vo_ctx* c, const float* cur_pts, int32_t n_cur,
   VO_CHECK(c, n_cur >= 0 && n_cur <= c->max_pts && (n_cur == 0 || cur_pts), VO_E_CAPACITY, "bad cur_pts");
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  int32_t r = st_init(c);
+  int32_t r = st_init(c, c->stream);
   if (r != VO_OK) return r;
   vo_st_ws* s = c->st;
   const size_t pts_seq = sizeof(float) * 2 * (size_t)c->max_pts;
@@ -1255,27 +1255,29 @@ extern "C" int32_t vo_shi_tomasi(vo_ctx* c, const float* cur_pts, int32_t n_cur,
     VO_HIP(c, hipMemcpy2DAsync(s->d_pts, pts_seq, cur_pts, sizeof(float) * 2 * n_cur, sizeof(float) * 2 * n_cur, c->batch,
                                hipMemcpyHostToDevice, c->stream));
   if (mask) VO_HIP(c, hipMemcpyAsync(s->d_user_mask, mask, (size_t)c->width * c->height * c->batch, hipMemcpyHostToDevice, c->stream));
-  r = st_launch(c, s->d_pts, pts_seq, n_cur, mask_radius, mask ? s->d_user_mask : nullptr, prm, nullptr, true);
+  r = st_launch(c, c->stream, s->d_pts, pts_seq, n_cur, mask_radius, mask ? s->d_user_mask : nullptr, prm, nullptr, true);
   if (r != VO_OK) return r;
   return st_fetch(c, out_pts, n_out);
 }
 
 extern "C" int32_t vo_shi_tomasi_resident(vo_ctx* c, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm) {
   if (!c) return VO_E_INVALID;
-  return vo_shi_tomasi_resident_counts(c, n_cur, mask_radius, prm, c->d_pt_counts, nullptr);   // (counts: non-null only while a vo_tracks_* table is seeded)
+  // (checked here too: a refused call neither touches the device nor waits for the side streams; the enqueue form checks for the step orchestrators)
+  VO_CHECK(c, n_cur >= 0 && n_cur <= c->n_resident, VO_E_INVALID, "n_cur exceeds the resident point set");
+  VO_HIP(c, hipSetDevice(c->device));
+  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
+  return vo_shi_tomasi_resident_counts(c, c->stream, n_cur, mask_radius, prm, c->d_pt_counts, nullptr);   // (counts: non-null only while a vo_tracks_* table is seeded)
 }
 
-int32_t vo_shi_tomasi_resident_counts(vo_ctx* c, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm, const int32_t* d_counts,
+int32_t vo_shi_tomasi_resident_counts(vo_ctx* c, hipStream_t q, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm, const int32_t* d_counts,
                                       const int32_t* d_limit) {
   vo_st_params def;
   if (!prm) { vo_st_default_params(&def); prm = &def; }
   VO_CHECK(c, n_cur >= 0 && n_cur <= c->n_resident, VO_E_INVALID, "n_cur exceeds the resident point set");
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  int32_t r = st_init(c);
+  int32_t r = st_init(c, q);
   if (r != VO_OK) return r;
   const bool dev_limit = !c->tune.st_host_limit;                                                           // (vo_tuning: A/B, read per call -- tests compare both)
-  return st_launch(c, vo_slab<const float>(c, vo_off_p(c)), c->slab_seq, n_cur, mask_radius, nullptr, prm, d_counts,
+  return st_launch(c, q, vo_slab<const float>(c, vo_off_p(c)), c->slab_seq, n_cur, mask_radius, nullptr, prm, d_counts,
                    c->tune.st_keep_eig != 0, dev_limit ? d_limit : nullptr);
 }
 

@@ -44,8 +44,8 @@ extern "C" void vo_debug_step_trace_dump(int first_step, int n_steps) {
 }
 
 int32_t vo_quiesce_side(vo_ctx* c) {
-  if (!c->in_step) c->main_dirty = true;                    // (vo_pipe_step clears it: see there)
-  if (c->side_stream != 2 || c->in_step) return VO_OK;      // layouts 0 / 1 join their side stream inside the step
+  c->main_dirty = true;                                     // (vo_pipe_step clears it: see there)
+  if (c->side_stream != 2) return VO_OK;                    // layouts 0 / 1 join their side stream inside the step
   if (c->stream2) VO_HIP(c, hipStreamSynchronize(c->stream2));
   if (c->stream3) VO_HIP(c, hipStreamSynchronize(c->stream3));
   return VO_OK;
@@ -60,7 +60,7 @@ struct step_cfg {
   vo_ba_params ba;
 };
 
-// enqueue everything of one frame on the ctx stream (also used under stream capture); *recorded: ev_step[half] has been recorded
+// enqueue everything of one frame (also used under stream capture: then all of it on the ctx stream); *recorded: ev_step[half] has been recorded
 // frame_idx < 0: the frames of this step arrive from the host in c->d_host_raw[half] (vo_frame_step_host: the upload runs on the copy stream,
 // ev_h2d[half] says when it is there)
 static bool step_trace_on() { static const bool on = getenv("VO_STEP_TRACE") != nullptr; return on; }
@@ -73,10 +73,10 @@ static int32_t step_enqueue(vo_ctx* c, const step_cfg& s, const int32_t* d_frame
   const size_t fr = (size_t)c->width * c->height;
   if (frame_idx < 0) {
     VO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_h2d[half], 0));
-    r = vo_build_pyramid(c, c->d_host_raw[half], fr, nullptr);
+    r = vo_build_pyramid(c, c->stream, c->d_host_raw[half], fr, nullptr);
     if (r == VO_OK) { VO_HIP(c, hipEventRecord(c->ev_raw_free[half], c->stream)); c->raw_free_recorded[half] = true; }
-  } else if (d_frame_idx) r = vo_build_pyramid(c, c->d_seq, fr * c->seq_n, d_frame_idx);
-  else r = vo_build_pyramid(c, c->d_seq + (size_t)frame_idx * fr, fr * c->seq_n, nullptr);
+  } else if (d_frame_idx) r = vo_build_pyramid(c, c->stream, c->d_seq, fr * c->seq_n, d_frame_idx);
+  else r = vo_build_pyramid(c, c->stream, c->d_seq + (size_t)frame_idx * fr, fr * c->seq_n, nullptr);
   if (r != VO_OK) return r;
   if (trace_a && c->side_stream == 2) trace_push(g_tb, c->stream, 6000);
   // pipelined layout: the tracker's launch takes every free wave slot for its whole duration, the previous frame's LM chain would stand still
@@ -84,7 +84,7 @@ static int32_t step_enqueue(vo_ctx* c, const step_cfg& s, const int32_t* d_frame
   // overlaps the chain's narrow tail groups, which run on the compute units stream A's CU mask leaves free (vo_set_side_stream)
   if (c->side_stream == 2 && s.do_ba && !d_frame_idx && c->ba_wide_groups > 0 && c->ba_wide_recorded)
     VO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_ba_wide[half ^ 1], 0));
-  r = vo_klt_track_resident(c, s.n_pts, &s.klt);
+  r = vo_klt_track_resident_counts(c, c->stream, s.n_pts, &s.klt, c->d_pt_counts);     // (counts: non-null only while a vo_tracks_* table is seeded)
   if (r != VO_OK) return r;
   if (trace_a && c->side_stream == 2) trace_push(g_tb, c->stream, 6000);
   uint8_t* const h_dst = c->h_slab + (size_t)half * c->slab_bytes;
@@ -106,32 +106,28 @@ static int32_t step_enqueue(vo_ctx* c, const step_cfg& s, const int32_t* d_frame
     else VO_HIP(c, hipMemcpy2DAsync(h_dst, c->slab_seq, c->d_slab, c->slab_seq, part1, c->batch, hipMemcpyDeviceToHost, c->stream));
     VO_HIP(c, hipEventRecord(c->ev_copy1[half], c->stream));
     if (trace_a) trace_push(g_ta, c->stream, 4000);
-    hipStream_t main_stream = c->stream;
-    c->stream = c->stream3;
     const bool trace = trace_a;                                        // debug: GPU-side timeline of stream C, printed by vo_debug_step_trace_dump
     if (trace) trace_push(g_tr, c->stream3, 4000);
     // C carries nothing but the LM iterations and k_ba_finalize: the copy of the solution goes to B (behind ev_ba), so that the next
     // frame's iterations follow this frame's directly; k_ba_finalize of the next step waits for that copy (ev_pub) -- long done by then
-    c->ba_wait_before_publish = c->pub_copy_pending ? c->ev_pub[half ^ 1] : nullptr;
-    c->ba_wide_event = c->ba_wide_groups > 0 ? c->ev_ba_wide[half] : nullptr;
-    r = vo_ba_solve_resident(c, &s.ba);
-    c->ba_wait_before_publish = nullptr;
-    if (c->ba_wide_event && r == VO_OK) c->ba_wide_recorded = true;
-    c->ba_wide_event = nullptr;
+    vo_ba_enqueue_opts bo = {};
+    bo.wait_before_publish = c->pub_copy_pending ? c->ev_pub[half ^ 1] : nullptr;
+    bo.wide_event = c->ba_wide_groups > 0 ? c->ev_ba_wide[half] : nullptr;
+    bo.wide_groups = c->ba_wide_groups;
+    r = vo_ba_enqueue_solve(c, c->stream3, &s.ba, bo);
+    if (bo.wide_event && r == VO_OK) c->ba_wide_recorded = true;
     hipError_t e = hipEventRecord(c->ev_ba[half], c->stream3);
     if (trace) trace_push(g_tr, c->stream3, 4000);
-    c->stream = c->stream2;
-    if (r == VO_OK && s.do_st) r = vo_shi_tomasi_resident(c, s.n_pts, s.mask_radius, &s.st);
-    if (r == VO_OK && s.do_dlt) r = vo_dlt_resident(c);
+    if (r == VO_OK && s.do_st) r = vo_shi_tomasi_resident_counts(c, c->stream2, s.n_pts, s.mask_radius, &s.st, c->d_pt_counts, nullptr);
+    if (r == VO_OK && s.do_dlt) r = vo_dlt_enqueue(c, c->stream2, c->dlt_n);
     if (e == hipSuccess) e = (c->batch == 1) ? hipMemcpyAsync(h_dst + part1, c->d_slab + part1, c->slab_seq - part1, hipMemcpyDeviceToHost, c->stream2)
                                              : hipMemcpy2DAsync(h_dst + part1, c->slab_seq, c->d_slab + part1, c->slab_seq, c->slab_seq - part1, c->batch,
                                                                 hipMemcpyDeviceToHost, c->stream2);
     if (e == hipSuccess) e = hipStreamWaitEvent(c->stream2, c->ev_copy1[half], 0);
     if (e == hipSuccess) e = hipStreamWaitEvent(c->stream2, c->ev_ba[half], 0);
-    if (r == VO_OK && e == hipSuccess) r = vo_ba_enqueue_pub_copy(c, half);      // on B (c->stream is stream2 here)
+    if (r == VO_OK && e == hipSuccess) r = vo_ba_enqueue_pub_copy(c, c->stream2, half);
     if (e == hipSuccess) e = hipEventRecord(c->ev_pub[half], c->stream2);
     c->pub_copy_pending = true;
-    c->stream = main_stream;
     if (e == hipSuccess) e = hipEventRecord(c->ev_step[half], c->stream2);
     if (r != VO_OK) return r;
     VO_HIP(c, e);
@@ -158,21 +154,18 @@ static int32_t step_enqueue(vo_ctx* c, const step_cfg& s, const int32_t* d_frame
     VO_HIP(c, hipEventRecord(c->ev_fork, c->stream));
     VO_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
     forked = true;
-    hipStream_t main_stream = c->stream;
-    c->stream = c->stream2;
-    r = vo_shi_tomasi_resident(c, s.n_pts, s.mask_radius, &s.st);
+    r = vo_shi_tomasi_resident_counts(c, c->stream2, s.n_pts, s.mask_radius, &s.st, c->d_pt_counts, nullptr);
     // the triangulation does not feed this frame's bundle adjustment (the BA problem is resident): beside a BA it goes to
     // the side branch too, off the KLT -> BA critical path (48 us of latency-bound work per step)
-    if (r == VO_OK && dlt_side) r = vo_dlt_resident(c);
-    c->stream = main_stream;
+    if (r == VO_OK && dlt_side) r = vo_dlt_enqueue(c, c->stream2, c->dlt_n);
     if (r != VO_OK) { (void)join(); return r; }
   }
-  if (s.do_dlt && !dlt_side) { r = vo_dlt_resident(c); if (r != VO_OK) { (void)join(); return r; } }
-  if (s.do_ba) { r = vo_ba_solve_resident(c, &s.ba); if (r != VO_OK) { (void)join(); return r; } }
+  if (s.do_dlt && !dlt_side) { r = vo_dlt_enqueue(c, c->stream, c->dlt_n); if (r != VO_OK) { (void)join(); return r; } }
+  if (s.do_ba) { r = vo_ba_enqueue_solve(c, c->stream, &s.ba, {}); if (r != VO_OK) { (void)join(); return r; } }
   if (fork) VO_HIP(c, join());
-  else if (s.do_st) { r = vo_shi_tomasi_resident(c, s.n_pts, s.mask_radius, &s.st); if (r != VO_OK) return r; }
+  else if (s.do_st) { r = vo_shi_tomasi_resident_counts(c, c->stream, s.n_pts, s.mask_radius, &s.st, c->d_pt_counts, nullptr); if (r != VO_OK) return r; }
   VO_HIP(c, hipMemcpyAsync(h_dst, c->d_slab, c->slab_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (s.do_ba) { r = vo_ba_enqueue_pub_copy(c, half); if (r != VO_OK) return r; }
+  if (s.do_ba) { r = vo_ba_enqueue_pub_copy(c, c->stream, half); if (r != VO_OK) return r; }
   c->step_off_p[half] = vo_off_p(c);
   return VO_OK;
 }
@@ -378,9 +371,7 @@ static int32_t frame_step(vo_ctx* c, int32_t frame_idx, const uint8_t* const* ho
   const bool graph_ok = c->use_graph && c->prof.mask == 0 && c->n_pushed >= 2 && !host_frames;     // (host frames: plain launches)
   if (!graph_ok) {
     bool recorded = false;
-    c->in_step = true;
     const int32_t r = step_enqueue(c, s, nullptr, frame_idx, half, &recorded);
-    c->in_step = false;
     if (r != VO_OK) {
       // (error path) the step does not count, so its pointer-table row goes to the next one: let the gather finish reading it first
       if (host_frames) (void)hipStreamSynchronize(c->stream_h2d);
@@ -405,9 +396,7 @@ static int32_t frame_step(vo_ctx* c, int32_t frame_idx, const uint8_t* const* ho
     const int cur0 = c->cur, pushed0 = c->n_pushed, parity0 = c->p_parity, st0 = vo_st_flags_save(c);
     VO_HIP(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     bool recorded = false;
-    c->in_step = true;
     const int32_t r = step_enqueue(c, s, c->d_frame_idx, frame_idx, half, &recorded);
-    c->in_step = false;
     const hipError_t e = hipStreamEndCapture(c->stream, &g);
     if (r != VO_OK || e != hipSuccess) {
       // nothing was launched: undo what the enqueue functions did to the host-side frame / point parities and launch flags

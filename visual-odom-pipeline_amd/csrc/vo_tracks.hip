@@ -228,12 +228,13 @@ extern "C" int32_t vo_tracks_seed(vo_ctx* c, const float* pts, int32_t n, int32_
 // KLT prev -> cur of every live track (the frame store must hold both frames), then the reference's pruning and bookkeeping
 extern "C" int32_t vo_tracks_track(vo_ctx* c, int32_t t, const vo_klt_params* prm) {
   if (!c) return VO_E_INVALID;
-  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   VO_CHECK(c, c->trk && c->d_pt_counts, VO_E_STATE, "vo_tracks_seed first");
+  VO_HIP(c, hipSetDevice(c->device));
+  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   vo_trk_ws* tw = c->trk;
   const bool fb = vo_fb_on(c);           // vo_set_fb_check: the forward-backward check joins the keep rule
   if (tw->n_hi > 0) {
-    const int32_t r = fb ? vo_klt_track_resident_fb(c, tw->n_hi, prm, c->d_pt_counts) : vo_klt_track_resident(c, tw->n_hi, prm);
+    const int32_t r = fb ? vo_klt_track_resident_fb(c, c->stream, tw->n_hi, prm, c->d_pt_counts) : vo_klt_track_resident(c, tw->n_hi, prm);
     if (r != VO_OK) return r;
   }
   hipLaunchKernelGGL(k_trk_extend, dim3(c->batch), dim3(1024), 0, c->stream, trk_make(tw), vo_slab<float>(c, vo_off_p(c)),
