@@ -244,6 +244,40 @@ int32_t vo_set_fb_check(vo_ctx* ctx, float max_err);
 int32_t vo_get_fb_check(vo_ctx* ctx, float* max_err);
 int32_t vo_fb_read(vo_ctx* ctx, uint8_t* ok, float* fb_err, int32_t n);
 
+/* ---- motion-predicted initial flow -----------------------------------------------------------
+ * The reference only ever calls cv2.calcOpticalFlowPyrLK with flags = 0 (extractor.py:44,65): every point starts at its previous position.
+ * This is OpenCV's other documented mode, OPTFLOW_USE_INITIAL_FLOW (video/lkpyramid.cpp): the caller hands a guess g per point, and with
+ * `top` the highest pyramid level actually used (after truncation)
+ *   at level == top:   nextPt = g * (float)(1.0 / (1 << top))    per component, f32
+ *   everything else as vo_klt_track: the template is taken at p0 / 2^level in the previous frame; the propagation to the lower levels, the
+ *   out-of-range and min-eigenvalue skips (a skipped top level hands the scaled guess down as it hands prevPt down), the exits, status,
+ *   err and iters are unchanged.
+ *   A guess with a component that is not finite (OpenCV leaves that undefined): the point starts from p0.
+ *   g == p0 gives the unseeded tracker's bits: the same f32 expression on the same value.
+ * Kernels k_klt_seeded / k_klt_seeded_fb (one wave per keypoint; the forward pass is seeded, the backward pass LK(cur, prev, p1) is not).
+ *   vo_klt_track_init      vo_klt_track with guess [batch][n][2] f32; synchronous, the same layouts.  guess == NULL: exactly vo_klt_track.
+ *   vo_klt_track_fb_init   vo_klt_track_fb likewise.
+ *   vo_set_klt_predict     per context: VO_KLT_PREDICT_OFF (0, the default) or VO_KLT_PREDICT_CONST_VELOCITY (1); anything else ->
+ *                          VO_E_INVALID.  Takes effect at the next enqueue.  On, vo_tracks_track and the TRACK stage of vo_pipe_step /
+ *                          vo_pipe_step_host write a guess per point of the tracked set on the device and run the seeded kernel (with a
+ *                          finite vo_set_fb_check threshold the seeded forward-backward kernel).  The predictor, f32 per component:
+ *                              g = uv + (uv - prev);   prev missing or not finite: g = uv;   no clamping -- a guess outside the image
+ *                              meets the tracker's own out-of-range rules
+ *                          uv = the point the tracker starts from; prev = the track's position one frame earlier: the track table's ring
+ *                          entry of frame t - 2 (missing for a track born at t - 1), the closed loop's history entry hist_len - 2 of the
+ *                          keypoint row behind the entry (LM_K[i] for a landmark, CAND[i - n_landmarks] for a candidate; missing when
+ *                          hist_len < 2).  vo_klt_track_resident and the fused vo_frame_step_* never predict: they have no history.
+ *   vo_klt_guess_read      synchronous, no step in flight (else VO_E_STATE): guess [batch][n][2] f32, what the last track started from,
+ *                          if a predictor ran for it (else VO_E_STATE) -- the tracker's point order; dead slots read NaN. */
+enum { VO_KLT_PREDICT_OFF = 0, VO_KLT_PREDICT_CONST_VELOCITY = 1 };
+int32_t vo_klt_track_init(vo_ctx* ctx, const float* p0, const float* guess, int32_t n, const vo_klt_params* prm,
+                          float* p1, uint8_t* status, float* err, int32_t* iters);
+int32_t vo_klt_track_fb_init(vo_ctx* ctx, const float* p0, const float* guess, int32_t n, const vo_klt_params* prm, float* p1, uint8_t* status,
+                             float* err, float* p0r, float* fb_err, int32_t* iters);
+int32_t vo_set_klt_predict(vo_ctx* ctx, int32_t mode);
+int32_t vo_get_klt_predict(vo_ctx* ctx, int32_t* mode);
+int32_t vo_klt_guess_read(vo_ctx* ctx, float* guess, int32_t n);
+
 /* ---- Shi-Tomasi re-detection ----------------------------------------------------------------
  * Replaces the exclusion-mask loop + cv2.goodFeaturesToTrack(img, mask=mask, **shitomasi_params)
  * at extractor.py:103-112 on the CURRENT frame.  cur_pts (n_cur x 2 f32, may be NULL) are the

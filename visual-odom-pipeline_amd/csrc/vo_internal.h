@@ -104,6 +104,11 @@ struct vo_ctx {
   uint8_t* d_fb = nullptr;
   size_t fb_seq = 0, fb_off_err = 0, fb_off_ok = 0;
   int fb_n = -1;                     // points of the last track if it ran the check, else -1
+  // motion-predicted start of the tracker (vo_klt_seed.hip): mode of vo_set_klt_predict, and the guesses [batch][max_pts][2] f32 in the
+  // tracker's point order -- an allocation of its own, made when a guess is first needed (a context that never asks has none)
+  int klt_predict = VO_KLT_PREDICT_OFF;
+  float* d_guess = nullptr;
+  int guess_n = -1;                  // points of the last track if a predictor wrote its start positions, else -1
   // DLT inputs
   float* d_uv0 = nullptr; float* d_uv1 = nullptr;    // [batch][max_pts][2]
   vo_dlt_cam* d_dlt_cam = nullptr;   // [batch]
@@ -243,6 +248,13 @@ int32_t vo_klt_track_resident_fb(vo_ctx* c, hipStream_t q, int32_t n, const vo_k
 inline bool vo_fb_on(const vo_ctx* c) { return !(c->fb_max_err == __builtin_inff()); }     // +inf = off
 inline const uint8_t* vo_fb_ok(const vo_ctx* c) { return c->d_fb + c->fb_off_ok; }
 void vo_fb_destroy(vo_ctx* c);
+// motion prediction (vo_klt_seed.hip).  vo_guess_reserve: the guess rows exist afterwards.  vo_klt_track_resident_seeded: the resident
+// tracking started at the guesses a predictor kernel has just written to c->d_guess on q (k_klt_seeded, or k_klt_seeded_fb with fb)
+inline bool vo_predict_on(const vo_ctx* c) { return c->klt_predict != VO_KLT_PREDICT_OFF; }
+inline size_t vo_guess_seq(const vo_ctx* c) { return sizeof(float) * 2 * (size_t)c->max_pts; }      // bytes per sequence
+int32_t vo_guess_reserve(vo_ctx* c);
+int32_t vo_klt_track_resident_seeded(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts, bool fb);
+void vo_guess_destroy(vo_ctx* c);
 int32_t vo_shi_tomasi_resident_counts(vo_ctx* c, hipStream_t q, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm, const int32_t* d_counts,
                                       const int32_t* d_limit);
 

@@ -359,6 +359,7 @@ int32_t vo_klt_make_args(vo_ctx* c, int n, const vo_klt_params* prm, klt_args& A
 
 static int32_t klt_launch(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* counts) {
   c->fb_n = -1;                         // the last track ran without the forward-backward check (vo_fb_read)
+  c->guess_n = -1;                      // ... and without a predicted start (vo_klt_guess_read)
   klt_args A;
   { const int32_t r = vo_klt_make_args(c, n, prm, A); if (r != VO_OK || n == 0) return r; }
   {

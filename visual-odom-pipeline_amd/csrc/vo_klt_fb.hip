@@ -14,14 +14,6 @@
 
 #include <math.h>
 
-// the backward pass's levels: template image + derivatives of the current frame, target = the previous frame
-struct klt_fb_args {
-  klt_level_args bw[VO_MAX_LEVELS];
-  size_t fb_seq;                 // byte stride between the sequences' rows of the check
-  size_t off_err, off_ok;        // fb_err and ok rows (p0r at 0)
-  float max_err;
-};
-
 // WAVES = minimum waves per SIMD the register allocation must allow: ONE instantiation, 6 (k_klt_track's default; 80 VGPRs, no scratch)
 template <int WAVES>
 __global__ void __launch_bounds__(64, WAVES) k_klt_track_fb(klt_args A, klt_fb_args F, const float* __restrict__ p0, float* __restrict__ p1,
@@ -75,7 +67,7 @@ __global__ void __launch_bounds__(64, WAVES) k_klt_track_fb(klt_args A, klt_fb_a
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static int32_t fb_reserve(vo_ctx* c) {
+int32_t vo_fb_reserve(vo_ctx* c) {
   if (c->d_fb) return VO_OK;
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t M = (size_t)c->max_pts;
@@ -89,13 +81,8 @@ void vo_fb_destroy(vo_ctx* c) {
   c->d_fb = nullptr;
 }
 
-static int32_t fb_launch(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* counts) {
-  c->fb_n = -1;
-  klt_args A;
-  { const int32_t r = vo_klt_make_args(c, n, prm, A); if (r != VO_OK) return r; }
-  if (n == 0) { c->fb_n = 0; return VO_OK; }
-  { const int32_t r = fb_reserve(c); if (r != VO_OK) return r; }
-  klt_fb_args F;
+// the backward pass's argument block for the forward block A (the check's rows must exist: vo_fb_reserve)
+void vo_klt_fb_make_args(const vo_ctx* c, const klt_args& A, klt_fb_args& F) {
   const vo_frame& P = c->fr[c->cur ^ 1];
   const vo_frame& C = c->fr[c->cur];
   for (int l = 0; l <= A.top; l++) {
@@ -104,6 +91,16 @@ static int32_t fb_launch(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* p
   }
   F.fb_seq = c->fb_seq; F.off_err = c->fb_off_err; F.off_ok = c->fb_off_ok;
   F.max_err = c->fb_max_err;
+}
+
+static int32_t fb_launch(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* counts) {
+  c->fb_n = -1; c->guess_n = -1;
+  klt_args A;
+  { const int32_t r = vo_klt_make_args(c, n, prm, A); if (r != VO_OK) return r; }
+  if (n == 0) { c->fb_n = 0; return VO_OK; }
+  { const int32_t r = vo_fb_reserve(c); if (r != VO_OK) return r; }
+  klt_fb_args F;
+  vo_klt_fb_make_args(c, A, F);
   {
     vo_prof_scope prof(c, q, VO_PROF_KLT);
     hipLaunchKernelGGL(k_klt_track_fb<6>, dim3(n, c->batch), dim3(64), 0, q, A, F, vo_slab<const float>(c, off_in),
@@ -163,7 +160,7 @@ extern "C" int32_t vo_set_fb_check(vo_ctx* c, float max_err) {
   VO_CHECK(c, max_err == max_err, VO_E_INVALID, "NaN threshold (+inf turns the check off)");
   if (!(max_err == __builtin_inff())) {       // the rows of the check exist before the first enqueue that needs them
     VO_HIP(c, hipSetDevice(c->device));
-    const int32_t r = fb_reserve(c);
+    const int32_t r = vo_fb_reserve(c);
     if (r != VO_OK) return r;
   }
   c->fb_max_err = max_err;

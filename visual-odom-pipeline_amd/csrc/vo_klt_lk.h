@@ -1,5 +1,6 @@
 // Lucas-Kanade pieces shared by the tracker kernels: the argument blocks, the cross-lane sums and the packed bilinear / derivative taps
-// (vo_klt.hip: k_klt_track; vo_klt_fb.hip: k_klt_track_fb) and, built from them, the per-point LK body klt_lk_point that both kernels call.
+// (vo_klt.hip: k_klt_track; vo_klt_fb.hip: k_klt_track_fb; vo_klt_seed.hip: their seeded forms) and, built from them, the per-point LK body
+// klt_lk_point that all of them call.
 // All of it is inlined into the kernels.
 #pragma once
 #include "vo_internal.h"
@@ -23,6 +24,14 @@ struct klt_args {
   float min_eig_num;         // minEig < threshold  <=>  numerator < min_eig_num  (klt_min_eig_numerator: no division per level)
   float eps_lo, eps_hi;      // |delta|^2 in float below / above these decides the convergence test; in between: float64
   double eps2;
+};
+
+// the backward pass's levels of the forward-backward kernels: template image + derivatives of the current frame, target = the previous frame
+struct klt_fb_args {
+  klt_level_args bw[VO_MAX_LEVELS];
+  size_t fb_seq;                 // byte stride between the sequences' rows of the check
+  size_t off_err, off_ok;        // fb_err and ok rows (p0r at 0)
+  float max_err;
 };
 
 // Window loads go through buffer instructions: address = descriptor base (the level's image: scalar registers) + ONE per-lane
@@ -218,10 +227,14 @@ __device__ __forceinline__ uint32_t deriv1(uint32_t top, uint32_t bot, uint32_t 
 // Pyramidal LK of the keypoint (p0x, p0y) (wave-uniform) through levels A.top .. 0 with template lv[l].imgI / derI and target lv[l].imgJ.
 // Results are wave-uniform: outx, outy = nextPts, st = status, errv = the error before the status mask.  iters (this sequence's table)
 // gets the iterations per level, or null.  dbgk: where the six diagnostic stamps of one wave go (k_klt_track), or null; a literal nullptr folds them away.
+// SEEDED (OpenCV's OPTFLOW_USE_INITIAL_FLOW; vo_klt_seed.hip): the top level starts at the guess (gx, gy) (wave-uniform, finite: the callers
+// replace a non-finite guess by p0) scaled like p0 instead of at p0 itself; nothing else changes, so (gx, gy) = (p0x, p0y) gives the unseeded
+// bits.  The unseeded instantiation does not see the two values.
 // ------------------------------------------------------------------------------------------------
+template <bool SEEDED = false>
 __device__ __forceinline__ void klt_lk_point(const klt_args& A, const klt_level_args (&lv)[VO_MAX_LEVELS], int bseq, int pt, int lane,
                                              float p0x, float p0y, int32_t* iters, unsigned long long* dbgk,
-                                             float& outx, float& outy, int& st, float& errv) {
+                                             float& outx, float& outy, int& st, float& errv, float gx = 0.f, float gy = 0.f) {
   VO_STAMP(dbgk, 0);
   const int cp = lane & 15, r = lane >> 4;
   const int win = A.win;
@@ -244,7 +257,10 @@ __device__ __forceinline__ void klt_lk_point(const klt_args& A, const klt_level_
     const float scale = __int_as_float((127 - level) << 23);       // 2^-level, exactly what 1.f / (float)(1 << level) gives (no division)
     float prevx = p0x * scale, prevy = p0y * scale;
     float nextx, nexty;
-    if (level == A.top) { nextx = prevx; nexty = prevy; }
+    if (level == A.top) {
+      if (SEEDED) { nextx = gx * scale; nexty = gy * scale; }
+      else { nextx = prevx; nexty = prevy; }
+    }
     else { nextx = outx * 2.f; nexty = outy * 2.f; }
     outx = nextx; outy = nexty;
     int n_it = -1;
@@ -408,3 +424,6 @@ __device__ __forceinline__ void klt_lk_point(const klt_args& A, const klt_level_
 
 // the argument checks and block of a tracker launch (vo_klt.hip); nothing is filled for n = 0
 int32_t vo_klt_make_args(vo_ctx* c, int n, const vo_klt_params* prm, klt_args& A);
+// the forward-backward check's rows (allocated on first use) and the backward pass's argument block (vo_klt_fb.hip)
+int32_t vo_fb_reserve(vo_ctx* c);
+void vo_klt_fb_make_args(const vo_ctx* c, const klt_args& A, klt_fb_args& F);

@@ -1,0 +1,245 @@
+// Pyramidal LK with a caller-supplied start per point: OpenCV's OPTFLOW_USE_INITIAL_FLOW (video/lkpyramid.cpp).  The reference only calls
+// cv2.calcOpticalFlowPyrLK(..., flags = 0) (src/extractor/extractor.py:44,65): the top pyramid level starts at the point's previous position.
+// Here it starts at a guess g,
+//   level == top:  nextPt = g * (float)(1.0 / (1 << top))      (top = the highest level actually used)
+// and everything else is the unseeded tracker: template at p0 / 2^level, propagation, skips, exits, status, err, iters.  A guess with a
+// component that is not finite starts from p0 (OpenCV leaves that undefined); g == p0 gives k_klt_track's bits.
+//   k_klt_seeded      k_klt_track with the guess
+//   k_klt_seeded_fb   k_klt_track_fb with the guess for the FORWARD pass; the backward pass LK(cur, prev, p1) starts at p1 as before
+// Both are one wave per keypoint around klt_lk_point<true> (vo_klt_lk.h), with k_klt_track's XCD remap and dead-slot rules.  In a translation
+// unit of their own: co-compiled kernels perturb each other's register allocation, and k_klt_track / k_klt_track_fb are pinned.
+//
+// The guesses of the resident paths come from two small predictor kernels (vo_tracks.hip: k_trk_predict, vo_pipeline.hip: k_pipe_predict),
+// constant velocity from the track's own history: g = uv + (uv - prev), or uv without a finite prev.  They write c->d_guess
+// [batch][max_pts][2] f32 in the tracker's point order on the tracker's stream, right before the launch here.
+#include "vo_klt_lk.h"
+
+#include <math.h>
+
+// the guess of point pt as two wave-uniform floats; not finite -> p0
+__device__ __forceinline__ void klt_guess(const float* __restrict__ guess, int pt, float p0x, float p0y, float& gx, float& gy) {
+  gx = uniform_f(guess[2 * pt]); gy = uniform_f(guess[2 * pt + 1]);
+  if (!(fabsf(gx) < __builtin_inff()) || !(fabsf(gy) < __builtin_inff())) { gx = p0x; gy = p0y; }
+}
+
+// WAVES = minimum waves per SIMD the register allocation must allow: one instantiation each, 5 (84 / 90 VGPRs, no scratch).  At 6 the
+// allocator's 80 registers leave 12 bytes per lane in scratch: the guess keeps the top level's start apart from the template position
+template <int WAVES>
+__global__ void __launch_bounds__(64, WAVES) k_klt_seeded(klt_args A, const float* __restrict__ p0, const float* __restrict__ guess, size_t guess_seq,
+                                                   float* __restrict__ p1, uint8_t* __restrict__ status, float* __restrict__ err,
+                                                   int32_t* __restrict__ iters, const int32_t* __restrict__ counts) {
+  int pt = blockIdx.x, bseq = blockIdx.y;
+  if (A.xcd_remap) {             // one sequence per XCD (k_klt_track)
+    const unsigned id = blockIdx.y * gridDim.x + blockIdx.x;
+    const unsigned q = id >> 3;
+    bseq = (int)(id & 7u) + 8 * (int)(q / (unsigned)A.n);
+    pt = (int)(q % (unsigned)A.n);
+  }
+  if (pt >= A.n) return;
+  const int lane = threadIdx.x;
+  if (iters) iters += (size_t)bseq * A.iters_seq;
+  const bool dead = counts && pt >= counts[bseq];    // track table: this sequence has fewer live points
+  if (iters && lane < A.iters_stride && (dead || lane > A.top)) iters[pt * A.iters_stride + lane] = -1;
+  if (dead) return;
+  p0 = vo_seq(p0, A.slab_seq, bseq); p1 = vo_seq(p1, A.slab_seq, bseq);
+  status = vo_seq(status, A.slab_seq, bseq); err = vo_seq(err, A.slab_seq, bseq);
+  guess = vo_seq(guess, guess_seq, bseq);
+  const float p0x = uniform_f(p0[2 * pt]), p0y = uniform_f(p0[2 * pt + 1]);
+  float gx, gy;
+  klt_guess(guess, pt, p0x, p0y, gx, gy);
+  float outx, outy, errv;
+  int st;
+  klt_lk_point<true>(A, A.lv, bseq, pt, lane, p0x, p0y, iters, nullptr, outx, outy, st, errv, gx, gy);
+  if (lane == 0) {
+    p1[2 * pt] = outx; p1[2 * pt + 1] = outy;
+    status[pt] = (uint8_t)st;
+    err[pt] = st ? errv : 0.f;
+  }
+}
+
+template <int WAVES>
+__global__ void __launch_bounds__(64, WAVES) k_klt_seeded_fb(klt_args A, klt_fb_args F, const float* __restrict__ p0, const float* __restrict__ guess,
+                                                      size_t guess_seq, float* __restrict__ p1, uint8_t* __restrict__ status,
+                                                      float* __restrict__ err, int32_t* __restrict__ iters, const int32_t* __restrict__ counts,
+                                                      uint8_t* __restrict__ fb) {
+  int pt = blockIdx.x, bseq = blockIdx.y;
+  if (A.xcd_remap) {             // one sequence per XCD (k_klt_track)
+    const unsigned id = blockIdx.y * gridDim.x + blockIdx.x;
+    const unsigned q = id >> 3;
+    bseq = (int)(id & 7u) + 8 * (int)(q / (unsigned)A.n);
+    pt = (int)(q % (unsigned)A.n);
+  }
+  if (pt >= A.n) return;
+  const int lane = threadIdx.x;
+  if (iters) iters += (size_t)bseq * A.iters_seq;
+  fb += (size_t)bseq * F.fb_seq;
+  float* const p0r = reinterpret_cast<float*>(fb);
+  float* const fb_err = reinterpret_cast<float*>(fb + F.off_err);
+  uint8_t* const ok = fb + F.off_ok;
+  const bool dead = counts && pt >= counts[bseq];
+  if (iters && lane < A.iters_stride && (dead || lane > A.top)) iters[pt * A.iters_stride + lane] = -1;
+  if (dead) {                                        // a dead slot is never good (its check reads as NaN)
+    if (lane == 0) { p0r[2 * pt] = p0r[2 * pt + 1] = fb_err[pt] = __builtin_nanf(""); ok[pt] = 0; }
+    return;
+  }
+  p0 = vo_seq(p0, A.slab_seq, bseq); p1 = vo_seq(p1, A.slab_seq, bseq);
+  status = vo_seq(status, A.slab_seq, bseq); err = vo_seq(err, A.slab_seq, bseq);
+  guess = vo_seq(guess, guess_seq, bseq);
+  const float p0x = uniform_f(p0[2 * pt]), p0y = uniform_f(p0[2 * pt + 1]);
+  float gx, gy;
+  klt_guess(guess, pt, p0x, p0y, gx, gy);
+  float outx, outy, errv;
+  int st;
+  klt_lk_point<true>(A, A.lv, bseq, pt, lane, p0x, p0y, iters, nullptr, outx, outy, st, errv, gx, gy);
+  if (lane == 0) {
+    p1[2 * pt] = outx; p1[2 * pt + 1] = outy;
+    status[pt] = (uint8_t)st;
+    err[pt] = st ? errv : 0.f;
+  }
+  // backward from the tracked position whatever its status, unseeded (k_klt_track_fb)
+  float rx, ry, rerr;
+  int rst;
+  klt_lk_point(A, F.bw, bseq, pt, lane, outx, outy, nullptr, nullptr, rx, ry, rst, rerr);
+  if (lane == 0) {
+    const float ex = fabsf(p0x - rx), ey = fabsf(p0y - ry);
+    const float e = (ex != ex || ey != ey) ? __builtin_nanf("") : (ex >= ey ? ex : ey);     // numpy's max: NaN propagates
+    p0r[2 * pt] = rx; p0r[2 * pt + 1] = ry;
+    fb_err[pt] = e;
+    ok[pt] = (e < F.max_err) ? 1 : 0;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+int32_t vo_guess_reserve(vo_ctx* c) {
+  if (c->d_guess) return VO_OK;
+  VO_HIP(c, hipMalloc((void**)&c->d_guess, vo_guess_seq(c) * (size_t)c->batch));
+  return VO_OK;
+}
+
+void vo_guess_destroy(vo_ctx* c) {
+  if (c->d_guess) (void)hipFree(c->d_guess);
+  c->d_guess = nullptr;
+}
+
+// the seeded launch on q with the guesses in c->d_guess; fb: with the forward-backward check (k_klt_seeded_fb)
+static int32_t seeded_launch(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* counts, bool fb) {
+  c->fb_n = -1; c->guess_n = -1;
+  klt_args A;
+  { const int32_t r = vo_klt_make_args(c, n, prm, A); if (r != VO_OK) return r; }
+  if (n == 0) { if (fb) c->fb_n = 0; return VO_OK; }
+  VO_CHECK(c, c->d_guess, VO_E_STATE, "no guesses");
+  if (fb) {
+    { const int32_t r = vo_fb_reserve(c); if (r != VO_OK) return r; }
+    klt_fb_args F;
+    vo_klt_fb_make_args(c, A, F);
+    vo_prof_scope prof(c, q, VO_PROF_KLT);
+    hipLaunchKernelGGL(k_klt_seeded_fb<5>, dim3(n, c->batch), dim3(64), 0, q, A, F, vo_slab<const float>(c, off_in), c->d_guess, vo_guess_seq(c),
+                       vo_slab<float>(c, off_out), vo_slab<uint8_t>(c, c->off_status), vo_slab<float>(c, c->off_err), c->d_iters, counts, c->d_fb);
+  } else {
+    vo_prof_scope prof(c, q, VO_PROF_KLT);
+    hipLaunchKernelGGL(k_klt_seeded<5>, dim3(n, c->batch), dim3(64), 0, q, A, vo_slab<const float>(c, off_in), c->d_guess, vo_guess_seq(c),
+                       vo_slab<float>(c, off_out), vo_slab<uint8_t>(c, c->off_status), vo_slab<float>(c, c->off_err), c->d_iters, counts);
+  }
+  VO_HIP(c, hipGetLastError());
+  if (fb) c->fb_n = n;
+  return VO_OK;
+}
+
+static hipError_t rows_h2d(vo_ctx* c, uint8_t* d, size_t d_stride, const void* h, size_t row_bytes) {
+  return hipMemcpy2DAsync(d, d_stride, h, row_bytes, row_bytes, c->batch, hipMemcpyHostToDevice, c->stream);
+}
+static hipError_t rows_d2h(vo_ctx* c, void* h, const uint8_t* d, size_t d_stride, size_t row_bytes) {
+  return hipMemcpy2DAsync(h, row_bytes, d, d_stride, row_bytes, c->batch, hipMemcpyDeviceToHost, c->stream);
+}
+
+// the synchronous forms' common body; p0r / fb_err non-null: with the check
+static int32_t track_init(vo_ctx* c, const float* p0, const float* guess, int32_t n, const vo_klt_params* prm, float* p1, uint8_t* status,
+                          float* err, float* p0r, float* fb_err, int32_t* iters, bool fb) {
+  vo_klt_params def;
+  if (!prm) { vo_klt_default_params(&def); prm = &def; }
+  VO_CHECK(c, n >= 0 && n <= c->max_pts, VO_E_CAPACITY, "n exceeds max_pts");
+  if (n == 0) return VO_OK;
+  VO_CHECK(c, p0 && p1 && status && err && (!fb || (p0r && fb_err)), VO_E_INVALID, "null buffer");
+  VO_HIP(c, hipSetDevice(c->device));
+  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
+  { const int32_t rg = vo_guess_reserve(c); if (rg != VO_OK) return rg; }
+  const size_t off_in = vo_off_p(c), off_out = vo_off_p_next(c);
+  VO_HIP(c, rows_h2d(c, c->d_slab + off_in, c->slab_seq, p0, sizeof(float) * 2 * n));
+  VO_HIP(c, rows_h2d(c, reinterpret_cast<uint8_t*>(c->d_guess), vo_guess_seq(c), guess, sizeof(float) * 2 * n));
+  const int32_t r = seeded_launch(c, c->stream, n, prm, off_in, off_out, nullptr, fb);
+  if (r != VO_OK) return r;
+  VO_HIP(c, rows_d2h(c, p1, c->d_slab + off_out, c->slab_seq, sizeof(float) * 2 * n));
+  VO_HIP(c, rows_d2h(c, status, c->d_slab + c->off_status, c->slab_seq, n));
+  VO_HIP(c, rows_d2h(c, err, c->d_slab + c->off_err, c->slab_seq, sizeof(float) * n));
+  if (fb) {
+    VO_HIP(c, rows_d2h(c, p0r, c->d_fb, c->fb_seq, sizeof(float) * 2 * n));
+    VO_HIP(c, rows_d2h(c, fb_err, c->d_fb + c->fb_off_err, c->fb_seq, sizeof(float) * n));
+  }
+  if (iters) {
+    const size_t row = sizeof(int32_t) * (size_t)n * (prm->max_level + 1);
+    VO_HIP(c, rows_d2h(c, iters, reinterpret_cast<const uint8_t*>(c->d_iters), sizeof(int32_t) * (size_t)c->max_pts * VO_MAX_LEVELS, row));
+  }
+  VO_HIP(c, hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+extern "C" int32_t vo_klt_track_init(vo_ctx* c, const float* p0, const float* guess, int32_t n, const vo_klt_params* prm,
+                                     float* p1, uint8_t* status, float* err, int32_t* iters) {
+  if (!c) return VO_E_INVALID;
+  if (!guess) return vo_klt_track(c, p0, n, prm, p1, status, err, iters);
+  return track_init(c, p0, guess, n, prm, p1, status, err, nullptr, nullptr, iters, false);
+}
+
+extern "C" int32_t vo_klt_track_fb_init(vo_ctx* c, const float* p0, const float* guess, int32_t n, const vo_klt_params* prm, float* p1,
+                                        uint8_t* status, float* err, float* p0r, float* fb_err, int32_t* iters) {
+  if (!c) return VO_E_INVALID;
+  if (!guess) return vo_klt_track_fb(c, p0, n, prm, p1, status, err, p0r, fb_err, iters);
+  return track_init(c, p0, guess, n, prm, p1, status, err, p0r, fb_err, iters, true);
+}
+
+// the resident form (vo_tracks_track, the closed loop's TRACK stage) behind a predictor kernel on q
+int32_t vo_klt_track_resident_seeded(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts, bool fb) {
+  vo_klt_params def;
+  if (!prm) { vo_klt_default_params(&def); prm = &def; }
+  VO_CHECK(c, n >= 0 && n <= c->n_resident, VO_E_INVALID, "n exceeds the resident point set");
+  const int32_t r = seeded_launch(c, q, n, prm, vo_off_p(c), vo_off_p_next(c), d_counts, fb);
+  if (r != VO_OK) return r;
+  c->guess_n = n;     // the predictor's guesses of this track stay in c->d_guess (vo_klt_guess_read)
+  c->p_parity ^= 1;   // tracked positions become the resident set
+  return VO_OK;
+}
+
+extern "C" int32_t vo_set_klt_predict(vo_ctx* c, int32_t mode) {
+  if (!c) return VO_E_INVALID;
+  VO_CHECK(c, mode == VO_KLT_PREDICT_OFF || mode == VO_KLT_PREDICT_CONST_VELOCITY, VO_E_INVALID, "unknown prediction mode");
+  if (mode != VO_KLT_PREDICT_OFF) {           // the guess rows exist before the first enqueue that needs them
+    VO_HIP(c, hipSetDevice(c->device));
+    const int32_t r = vo_guess_reserve(c);
+    if (r != VO_OK) return r;
+  }
+  c->klt_predict = mode;
+  return VO_OK;
+}
+
+extern "C" int32_t vo_get_klt_predict(vo_ctx* c, int32_t* mode) {
+  if (!c || !mode) return VO_E_INVALID;
+  *mode = c->klt_predict;
+  return VO_OK;
+}
+
+extern "C" int32_t vo_klt_guess_read(vo_ctx* c, float* guess, int32_t n) {
+  if (!c) return VO_E_INVALID;
+  VO_CHECK(c, !vo_pipe_busy(c) && c->steps_enq == c->steps_fetched, VO_E_STATE, "steps in flight: fetch them first");
+  VO_CHECK(c, c->guess_n >= 0, VO_E_STATE, "the last track did not predict");
+  VO_CHECK(c, n >= 0 && n <= c->guess_n, VO_E_INVALID, "n exceeds the points of the last track");
+  VO_HIP(c, hipSetDevice(c->device));
+  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
+  if (n > 0) {
+    VO_CHECK(c, guess, VO_E_INVALID, "null buffer");
+    VO_HIP(c, rows_d2h(c, guess, reinterpret_cast<const uint8_t*>(c->d_guess), vo_guess_seq(c), sizeof(float) * 2 * n));
+  }
+  VO_HIP(c, hipStreamSynchronize(c->stream));
+  return VO_OK;
+}

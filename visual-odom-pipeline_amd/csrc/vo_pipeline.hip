@@ -1135,6 +1135,33 @@ __global__ void __launch_bounds__(PIPE_TPB) k_pipe_dense(pipe_ptrs Pall, float* 
   if (tid == 0) { P.cnt[C_NPTS] = nl + nc; Pall.dn[DN_PTS * gridDim.x + b] = nl + nc; Pall.dn[DN_ROOM * gridDim.x + b] = max(P.N - nl - nc, 0) + 1; if (reset) { Pall.dn[DN_PNP * gridDim.x + b] = 0; Pall.dn[DN_RIPE * gridDim.x + b] = 0; } }
 }
 
+// constant-velocity guess of every entry of the resident point set [landmarks | candidates] for this frame's tracking (vo_set_klt_predict):
+// g = uv + (uv - prev) in float32 per component, uv = the slab point (the tracker's p0), prev = history entry hist_len - 2 of the keypoint
+// row behind the entry (LM_K[i] / CAND[i - n_landmarks]); hist_len < 2 or a prev that is not finite: g = uv.  No clamping.  Slots beyond the
+// sequence's count read NaN.  Reads the lists, K_HISTLEN and K_HIST as the previous frame's promote (resurrection) and spawn left them: it runs
+// on the tracker's stream right before the tracker, which is behind both on every stream layout.
+__global__ void __launch_bounds__(256) k_pipe_predict(pipe_ptrs Pall, const float* __restrict__ pts, size_t slab_seq, float* __restrict__ guess,
+                                                      size_t guess_seq) {
+  const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  const pipe_ptrs P = pipe_select(Pall, b);
+  if (i >= P.N) return;
+  const int nl = P.cnt[C_NLM], npts = Pall.dn[DN_PTS * gridDim.y + b];       // (npts: the count the tracker itself goes by)
+  float2 g = make_float2(__builtin_nanf(""), __builtin_nanf(""));
+  if (i < npts) {
+    const float2 uv = reinterpret_cast<const float2*>(vo_seq(pts, slab_seq, b))[i];
+    g = uv;
+    const int row = (i < nl) ? P.lm_K[i] : P.cand[i - nl];
+    if (row >= 0 && row < P.R) {
+      const int len = P.k_len[row];
+      if (len >= 2) {
+        const float2 prev = pipe_hist_slot(P, len - 2)[row];
+        if (fabsf(prev.x) < __builtin_inff() && fabsf(prev.y) < __builtin_inff()) g = make_float2(uv.x + (uv.x - prev.x), uv.y + (uv.y - prev.y));
+      }
+    }
+  }
+  reinterpret_cast<float2*>(vo_seq(guess, guess_seq, b))[i] = g;
+}
+
 // ================================================================================================
 // host
 // ================================================================================================
@@ -1514,8 +1541,17 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
       r = vo_build_pyramid(c, tq, c->d_seq + (size_t)frame_idx * fr, fr * c->seq_n, nullptr);
     }
     w->fb_active = vo_fb_on(c);                      // vo_set_fb_check: track with the forward-backward check
-    if (r == VO_OK) r = w->fb_active ? vo_klt_track_resident_fb(c, tq, w->N, &prm.klt, w->d_dn + DN_PTS * B)
-                                     : vo_klt_track_resident_counts(c, tq, w->N, &prm.klt, w->d_dn + DN_PTS * B);
+    if (r == VO_OK && vo_predict_on(c)) {            // vo_set_klt_predict: the predictor right before the seeded tracker, on its stream
+      r = vo_guess_reserve(c);
+      if (r == VO_OK && w->N > 0) {
+        hipLaunchKernelGGL(k_pipe_predict, dim3(vo_div_up(w->N, 256), B), dim3(256), 0, tq, P, vo_slab<const float>(c, vo_off_p(c)), c->slab_seq,
+                           c->d_guess, vo_guess_seq(c));
+        if (hipGetLastError() != hipSuccess) r = vo_fail(c, VO_E_HIP, "pipe_step: k_pipe_predict launch");
+      }
+      if (r == VO_OK) r = vo_klt_track_resident_seeded(c, tq, w->N, &prm.klt, w->d_dn + DN_PTS * B, w->fb_active);
+    }
+    else if (r == VO_OK) r = w->fb_active ? vo_klt_track_resident_fb(c, tq, w->N, &prm.klt, w->d_dn + DN_PTS * B)
+                                          : vo_klt_track_resident_counts(c, tq, w->N, &prm.klt, w->d_dn + DN_PTS * B);
     if (track_side) {                                  // joined on every path
       const hipError_t e1 = hipEventRecord(w->ev_track, c->stream2);
       const hipError_t e2 = hipStreamWaitEvent(c->stream, w->ev_track, 0);

@@ -202,6 +202,25 @@ __global__ void __launch_bounds__(256) k_trk_obs(trk_ptrs P, int t_now, int wind
   reinterpret_cast<double2*>(obs)[((size_t)b * window + s) * P.cap + i] = v;
 }
 
+// ---- constant-velocity guess of every live track for the tracking to frame t (vo_set_klt_predict): g = uv + (uv - prev) in float32 per
+//      component, uv = the resident point (the tracker's p0), prev = the ring entry of frame t - 2; a track born at t - 1 has none, and
+//      without a finite prev g = uv.  No clamping.  guess [B][guess_seq bytes]; slots i >= the sequence's count read NaN ----
+__global__ void __launch_bounds__(256) k_trk_predict(trk_ptrs P, const float* __restrict__ pts, size_t slab_seq, int t, int n_hi,
+                                                     float* __restrict__ guess, size_t guess_seq) {
+  const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_hi) return;
+  float2 g = make_float2(__builtin_nanf(""), __builtin_nanf(""));
+  if (i < P.n[b]) {
+    const float2 uv = reinterpret_cast<const float2*>(vo_seq(pts, slab_seq, b))[i];
+    g = uv;
+    if (t - 2 >= P.tf[(size_t)b * P.cap + i]) {
+      const float2 prev = trk_hist_row(P, b, t - 2)[i];
+      if (fabsf(prev.x) < __builtin_inff() && fabsf(prev.y) < __builtin_inff()) g = make_float2(uv.x + (uv.x - prev.x), uv.y + (uv.y - prev.y));
+    }
+  }
+  reinterpret_cast<float2*>(vo_seq(guess, guess_seq, b))[i] = g;
+}
+
 // ================================================================================================
 // host
 // ================================================================================================
@@ -233,7 +252,17 @@ extern "C" int32_t vo_tracks_track(vo_ctx* c, int32_t t, const vo_klt_params* pr
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   vo_trk_ws* tw = c->trk;
   const bool fb = vo_fb_on(c);           // vo_set_fb_check: the forward-backward check joins the keep rule
-  if (tw->n_hi > 0) {
+  if (vo_predict_on(c)) {                // vo_set_klt_predict: the predictor right before the seeded tracker, on the same stream
+    VO_CHECK(c, tw->n_hi <= c->n_resident, VO_E_INVALID, "n exceeds the resident point set");
+    { const int32_t rg = vo_guess_reserve(c); if (rg != VO_OK) return rg; }
+    if (tw->n_hi > 0) {
+      hipLaunchKernelGGL(k_trk_predict, dim3(vo_div_up(tw->n_hi, 256), c->batch), dim3(256), 0, c->stream, trk_make(tw),
+                         vo_slab<const float>(c, vo_off_p(c)), c->slab_seq, t, tw->n_hi, c->d_guess, vo_guess_seq(c));
+      VO_HIP(c, hipGetLastError());
+    }
+    const int32_t r = vo_klt_track_resident_seeded(c, c->stream, tw->n_hi, prm, c->d_pt_counts, fb);
+    if (r != VO_OK) return r;
+  } else if (tw->n_hi > 0) {
     const int32_t r = fb ? vo_klt_track_resident_fb(c, c->stream, tw->n_hi, prm, c->d_pt_counts) : vo_klt_track_resident(c, tw->n_hi, prm);
     if (r != VO_OK) return r;
   }

@@ -137,6 +137,11 @@ SIGNATURES = {
     "vo_set_fb_check": (C.c_int32, [_ctx, C.c_float]),
     "vo_get_fb_check": (C.c_int32, [_ctx, _f32p]),
     "vo_fb_read": (C.c_int32, [_ctx, _u8p, _f32p, C.c_int32]),
+    "vo_klt_track_init": (C.c_int32, [_ctx, _f32p, _f32p, C.c_int32, C.POINTER(KltParams), _f32p, _u8p, _f32p, _i32p]),
+    "vo_klt_track_fb_init": (C.c_int32, [_ctx, _f32p, _f32p, C.c_int32, C.POINTER(KltParams), _f32p, _u8p, _f32p, _f32p, _f32p, _i32p]),
+    "vo_set_klt_predict": (C.c_int32, [_ctx, C.c_int32]),
+    "vo_get_klt_predict": (C.c_int32, [_ctx, _i32p]),
+    "vo_klt_guess_read": (C.c_int32, [_ctx, _f32p, C.c_int32]),
     "vo_st_default_params": (C.c_int32, [C.POINTER(StParams)]),
     "vo_shi_tomasi": (C.c_int32, [_ctx, _f32p, C.c_int32, C.c_int32, _u8p, C.POINTER(StParams), _f32p, _i32p]),
     "vo_shi_tomasi_resident": (C.c_int32, [_ctx, C.c_int32, C.c_int32, C.POINTER(StParams)]),

@@ -14,6 +14,9 @@ import numpy as np
 from . import _lib
 from ._lib import BaParams, BaStats, EssParams, EssStats, KltParams, SiftKp, PnpParams, PnpStats, StParams, Tuning, VoError, as_c, ptr
 
+# vo_set_klt_predict modes (include/vo_mi355x.h)
+KLT_PREDICT_MODES = {"off": 0, "constant_velocity": 1}
+
 
 class VoContext:
     # vo_tuning fields applied to every NEW context (a test module forces one kernel family for all the contexts its tests make this way; the
@@ -159,8 +162,19 @@ class VoContext:
             raise ValueError("points must have shape [batch, n, 2]")
         return np.ascontiguousarray(p), p.shape[1]
 
-    def klt_track(self, p0, params=None, return_iters=False):
-        """prev -> cur tracking.  p0 (n,2) float32 -> p1 (n,2) f32, status (n,) u8, err (n,) f32  [leading batch dim if batch > 1]"""
+    def _guess(self, init, n):
+        """init of klt_track / klt_track_fb -> (the guess array or None, its pointer or NULL)"""
+        if init is None:
+            return None, None
+        g, ng = self._npts(init)
+        if ng != n:
+            raise ValueError("init must have the shape of p0")
+        return g, ptr(g, C.c_float)
+
+    def klt_track(self, p0, params=None, return_iters=False, init=None):
+        """prev -> cur tracking.  p0 (n,2) float32 -> p1 (n,2) f32, status (n,) u8, err (n,) f32  [leading batch dim if batch > 1]
+        init (the shape of p0, or None): a start position per point for the top pyramid level, OpenCV's OPTFLOW_USE_INITIAL_FLOW
+        (vo_klt_track_init); a guess with a non-finite component starts from p0, init = p0 gives the bits of init = None."""
         p0, n = self._npts(p0)
         B = self.batch
         prm = params if params is not None else self.klt_params()
@@ -168,16 +182,22 @@ class VoContext:
         st = np.zeros((B, n), np.uint8)
         err = np.zeros((B, n), np.float32)
         it = np.full((B, n, prm.max_level + 1), -1, np.int32)
-        self._ck(self._L.vo_klt_track(self._h, ptr(p0, C.c_float), n, C.byref(prm), ptr(p1, C.c_float),
-                                      ptr(st, C.c_uint8), ptr(err, C.c_float), ptr(it, C.c_int32)))
+        g, gp = self._guess(init, n)
+        if g is None:
+            self._ck(self._L.vo_klt_track(self._h, ptr(p0, C.c_float), n, C.byref(prm), ptr(p1, C.c_float),
+                                          ptr(st, C.c_uint8), ptr(err, C.c_float), ptr(it, C.c_int32)))
+        else:
+            self._ck(self._L.vo_klt_track_init(self._h, ptr(p0, C.c_float), gp, n, C.byref(prm), ptr(p1, C.c_float),
+                                               ptr(st, C.c_uint8), ptr(err, C.c_float), ptr(it, C.c_int32)))
         if return_iters:
             return self._out(p1), self._out(st), self._out(err), self._out(it)
         return self._out(p1), self._out(st), self._out(err)
 
-    def klt_track_fb(self, p0, params=None, return_iters=False):
+    def klt_track_fb(self, p0, params=None, return_iters=False, init=None):
         """klt_track with the forward-backward check in the same launch (vo_klt_track_fb): p1, status, err exactly as klt_track, plus
         p0r (n,2) f32 = the backward track of p1 (current -> previous frame) and fb_err (n,) f32 = max(|p0 - p0r|) over x, y.  The ok flags
-        (fb_err < the context's threshold) come from fb_read(n)."""
+        (fb_err < the context's threshold) come from fb_read(n).  init: as in klt_track, for the forward pass (vo_klt_track_fb_init); the
+        backward pass starts at p1 as always."""
         p0, n = self._npts(p0)
         B = self.batch
         prm = params if params is not None else self.klt_params()
@@ -187,8 +207,13 @@ class VoContext:
         p0r = np.zeros((B, n, 2), np.float32)
         fb_err = np.zeros((B, n), np.float32)
         it = np.full((B, n, prm.max_level + 1), -1, np.int32)
-        self._ck(self._L.vo_klt_track_fb(self._h, ptr(p0, C.c_float), n, C.byref(prm), ptr(p1, C.c_float), ptr(st, C.c_uint8),
-                                         ptr(err, C.c_float), ptr(p0r, C.c_float), ptr(fb_err, C.c_float), ptr(it, C.c_int32)))
+        g, gp = self._guess(init, n)
+        if g is None:
+            self._ck(self._L.vo_klt_track_fb(self._h, ptr(p0, C.c_float), n, C.byref(prm), ptr(p1, C.c_float), ptr(st, C.c_uint8),
+                                             ptr(err, C.c_float), ptr(p0r, C.c_float), ptr(fb_err, C.c_float), ptr(it, C.c_int32)))
+        else:
+            self._ck(self._L.vo_klt_track_fb_init(self._h, ptr(p0, C.c_float), gp, n, C.byref(prm), ptr(p1, C.c_float), ptr(st, C.c_uint8),
+                                                  ptr(err, C.c_float), ptr(p0r, C.c_float), ptr(fb_err, C.c_float), ptr(it, C.c_int32)))
         out = (self._out(p1), self._out(st), self._out(err), self._out(p0r), self._out(fb_err))
         return out + (self._out(it),) if return_iters else out
 
@@ -209,6 +234,24 @@ class VoContext:
         fb_err = np.zeros((B, n), np.float32)
         self._ck(self._L.vo_fb_read(self._h, ptr(ok, C.c_uint8), ptr(fb_err, C.c_float), n))
         return self._out(ok.astype(bool)), self._out(fb_err)
+
+    def set_klt_predict(self, mode="off"):
+        """motion-predicted start of the tracker (vo_set_klt_predict): "constant_velocity" (or 1) makes tracks_track and the closed loop's
+        TRACK stage start every point at uv + (uv - prev) from the track's own history (uv without one); "off" (or 0, the default): at uv."""
+        self._ck(self._L.vo_set_klt_predict(self._h, int(KLT_PREDICT_MODES.get(mode, mode))))
+
+    def get_klt_predict(self):
+        """the mode as its name ("off" / "constant_velocity")"""
+        v = C.c_int32(-1)
+        self._ck(self._L.vo_get_klt_predict(self._h, C.byref(v)))
+        return {code: name for name, code in KLT_PREDICT_MODES.items()}[v.value]
+
+    def klt_guess_read(self, n):
+        """(n,2) f32: the start positions the last track's predictor wrote, in the tracker's point order; dead slots NaN
+        [leading batch dim if batch > 1]"""
+        g = np.zeros((self.batch, n, 2), np.float32)
+        self._ck(self._L.vo_klt_guess_read(self._h, ptr(g, C.c_float), n))
+        return self._out(g)
 
     def points_upload(self, p):
         p, n = self._npts(p)

@@ -26,7 +26,8 @@ class DMatch:
 
 
 class Extractor:
-    def __init__(self, cfg=None, min_kp_dist=10, ctx=None, device=0, max_pts=8192, lazy=None, lazy_backend=None, bidir="reference"):
+    def __init__(self, cfg=None, min_kp_dist=10, ctx=None, device=0, max_pts=8192, lazy=None, lazy_backend=None, bidir="reference",
+                 predict="off"):
         """lazy (default: on unless VO_LAZY=0): once a frame has come through the reference's call order (pipeline.py:98-156) the state moves
         into device tables and the lists this class hands out are views of them (vo_mi355x/lazy.py); lazy_backend: test hook
         (ctx, K, params, width, height) -> backend, default the GPU one.  max_pts: keypoints per call AND the capacity of those tables (<= 8192).
@@ -35,10 +36,17 @@ class Extractor:
         LK(cur, prev, p1) as in the OpenCV sample the reference copies (notebooks/tracking.py:39-42), both passes in one vo_klt_track_fb
         launch; a keypoint whose round trip misses its start by max_bidir_error or more (max over x, y; float32) is dropped / goes to the dead
         lists like one outside the image.  max_bidir_error = inf is the plain path in both modes.  A lazy session serves only the infinite
-        threshold: a call with a finite one takes the plain path (the session ends there), as it always has."""
+        threshold: a call with a finite one takes the plain path (the session ends there), as it always has.
+        predict: where extend_tracks / extend_landmarks start the tracker.  "off" (default): at k.uv, the reference's flags = 0 call
+        (extractor.py:44,65).  "constant_velocity": at g = uv + (uv - k.uv_history[-2]) in float32 (g = uv for a history of fewer than two
+        entries), OpenCV's OPTFLOW_USE_INITIAL_FLOW through VoContext.klt_track(init=g); the second pass of either bidir mode is not seeded.
+        A lazy session serves only "off": with a prediction every call takes the plain path."""
         if bidir not in ("reference", "backward"):
             raise ValueError("bidir must be 'reference' or 'backward'")
+        if predict not in ("off", "constant_velocity"):
+            raise ValueError("predict must be 'off' or 'constant_velocity'")
         self._bidir = bidir
+        self._predict = predict
         from . import lazy as _lz
         self._cfg = cfg
         self._lazy_on = _lz.enabled() if lazy is None else bool(lazy)
@@ -90,19 +98,32 @@ class Extractor:
         return self._ctx.klt_params(win=self._lk_params["winSize"][0], max_level=self._lk_params["maxLevel"],
                                     max_count=self._lk_params["criteria"][1], epsilon=self._lk_params["criteria"][2])
 
-    def _klt(self, p0):
-        return self._ctx.klt_track(p0, self._klt_prm())
+    def _klt(self, p0, init=None):
+        if init is None:
+            return self._ctx.klt_track(p0, self._klt_prm())
+        return self._ctx.klt_track(p0, self._klt_prm(), init=init)
 
-    def _track(self, im_curr, p0, max_bidir_error):
+    def _guess(self, kps, p0):
+        """predict="constant_velocity": the start positions (n, 2) float32 of a keypoint list whose positions are p0; else None"""
+        if self._predict == "off":
+            return None
+        g = p0.copy()
+        for i, k in enumerate(kps):
+            if len(k.uv_history) >= 2:
+                prev = np.asarray(k.uv_history[-2], np.float64).reshape(2).astype(np.float32)
+                g[i] = p0[i] + (p0[i] - prev)
+        return g
+
+    def _track(self, im_curr, p0, max_bidir_error, init=None):
         """p1 and the 'bidirectional' flag.  bidir="reference": the reference's second pass tracks FORWARD again from
         p1 (extractor.py:45,66); with an infinite threshold its result cannot change `good` (NaN aside), so it
         is skipped then.  bidir="backward" with a finite threshold: the forward-backward check (vo_klt_track_fb)."""
         self._ensure_pair(self._im_prev, im_curr)
         if self._bidir == "backward" and max_bidir_error != np.inf:
             c = self._ctx
-            p1, _st, _err, _p0r, fb_err = c.klt_track_fb(p0, self._klt_prm())
+            p1, _st, _err, _p0r, fb_err = c.klt_track_fb(p0, self._klt_prm(), **({} if init is None else dict(init=init)))
             return p1, fb_err < np.float32(max_bidir_error)
-        p1, _st, _err = self._klt(p0)
+        p1, _st, _err = self._klt(p0, init)
         if np.isinf(max_bidir_error):
             good = ~np.isnan(p1).any(axis=1)
         else:
@@ -161,7 +182,7 @@ class Extractor:
         new_tracks = []
         if len(kp):
             p0 = self._uv_block(kp)
-            p1, good = self._track(im_curr, p0, max_bidir_error)
+            p1, good = self._track(im_curr, p0, max_bidir_error, self._guess(kp, p0))
             keep, uv, hist = self._survivors(im_curr, p1, good)
             for i in np.nonzero(keep)[0]:
                 k = kp[i]
@@ -183,7 +204,7 @@ class Extractor:
         if not len(landmarks_kp):
             return landmarks_new, kp_new, landmarks_dead, kp_dead
         p0 = self._uv_block(landmarks_kp)
-        p1, good = self._track(im_curr, p0, max_bidir_error)
+        p1, good = self._track(im_curr, p0, max_bidir_error, self._guess(landmarks_kp, p0))
         keep, uv, hist = self._survivors(im_curr, p1, good)
         # the reference converts p1 with .tolist() here (python floats): uv / history entries are float64 in this method
         uv, hist = uv.astype(np.float64), hist.astype(np.float64)

@@ -782,6 +782,8 @@ def seed_after_adjust(adjuster, state, dead_l, dead_k, K, t_now):
     seen = ext._seen
     if not np.isinf(seen.get("max_bidir_error", 0.0)):
         return None
+    if getattr(ext, "_predict", "off") != "off":      # (a session tracks from uv; Extractor(predict=...) stays on the plain path)
+        return None
     prm = dict(ba_window=adjuster._window_size, ba_ftol=adjuster._ftol, ba_xtol=adjuster._xtol, ba_max_iters=adjuster._max_iters,
                min_track_length=seen.get("min_track_length", 3), min_bearing_angle=seen.get("min_bearing_angle", 0.5),
                max_reproj_err=seen.get("pose_max_err", 2.0), mask_radius=seen.get("mask_radius", int(ext._shitomasi_params["minDistance"])),

@@ -50,11 +50,13 @@ class ResidentPipeline:
     resurrect=False leaves dead landmarks dead (not the reference; see include/vo_mi355x.h).
     fb_max_error: threshold of the forward-backward KLT check (the context's vo_set_fb_check).  Finite: the TRACK stage tracks every keypoint
     back to the previous frame as well, and a landmark or candidate whose round trip misses its start by fb_max_error or more (max over x, y)
-    dies like one that left the image; ctx.fb_read(n) returns the flags after a fetch.  np.inf (the default): off, the reference's behaviour."""
+    dies like one that left the image; ctx.fb_read(n) returns the flags after a fetch.  np.inf (the default): off, the reference's behaviour.
+    klt_predict: "constant_velocity" starts the TRACK stage's tracker at uv + (uv - prev) from every keypoint's own history (the context's
+    vo_set_klt_predict; ctx.klt_guess_read(n) returns the start positions after a fetch).  "off" (the default): at uv, the reference's call."""
 
     def __init__(self, ctx, K, ba_window=4, min_track_length=3, mask_radius=7, max_new=1000, max_reproj_err=2.0, min_bearing_angle=0.5,
                  ba_max_iters=50, ba_budget=None, ba_ftol=1e-3, ba_xtol=1e-3, pnp_blind_batches=4, pnp_seed=0, min_kp_dist=7, resurrect=True,
-                 fb_max_error=np.inf, ba_loss='huber', ba_f_scale=1.0):
+                 fb_max_error=np.inf, ba_loss='huber', ba_f_scale=1.0, klt_predict="off"):
         self.ctx, self._L = ctx, ctx._L
         B = ctx.batch
         K = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (B, 3, 3)))
@@ -73,6 +75,8 @@ class ResidentPipeline:
         ctx._ck(self._L.vo_pipe_create(ctx._h, K.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p)))
         if not (fb_max_error == np.inf and ctx.get_fb_check() == np.inf):     # (off on a context that never set it: no call at all)
             ctx.set_fb_check(fb_max_error)
+        if not (klt_predict in ("off", 0) and ctx.get_klt_predict() == "off"):
+            ctx.set_klt_predict(klt_predict)
         self.N, self.R, self.B = ctx.max_pts, 4 * ctx.max_pts, B
         self.ba_window = ba_window
         self._inflight = 0
