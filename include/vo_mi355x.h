@@ -297,6 +297,43 @@ int32_t vo_shi_tomasi_fetch(vo_ctx* ctx, float* out_pts, int32_t* n_out);     /*
  * More than 16384 candidates are consumed in rank-ordered chunks, like OpenCV's scan; VO_E_CAPACITY only beyond 262144. */
 int32_t vo_shi_tomasi_read(vo_ctx* ctx, float* eig_out, uint8_t* mask_out, int32_t* n_candidates);
 
+/* ---- sub-pixel corner refinement --------------------------------------------------------------
+ * The reference keeps the integer corners of cv2.goodFeaturesToTrack (extractor.py:111).  This is the call OpenCV's own pipelines put right
+ * behind it, cv2.cornerSubPix (imgproc/cornersubpix.cpp with getRectSubPix 8u -> 32f): per corner, iterate
+ *   S    = (2 win_y + 3) x (2 win_x + 3) bilinear samples (f32) of level 0 around the corner, pixel coordinates clamped to the image
+ *   sums = over the window, weighted by a separable exp(-t^2) mask (zero inside the zero zone): gxx, gxy, gyy, gxx*px + gxy*py,
+ *          gxy*px + gyy*py of the central differences of S, in float64, in a fixed order (tests/subpix_model.py states it)
+ *   step = corner + (2 x 2 solve), rounded to f32; stop when the system is singular (|det| <= DBL_EPSILON^2), the corner leaves
+ *          [0, w) x [0, h), max_count steps were taken, or a step is no longer than epsilon
+ * and a result further than win from the input on either axis goes back to the input.  A result just outside the image is possible (the step
+ * that left it is kept when within win), as in OpenCV; the tracker's and the keep rule's range tests meet it in the next frame.  A corner that
+ * is not finite or lies outside [0, w) x [0, h) comes back unchanged (OpenCV asserts there; NaN rows pad a batch).
+ * Parameters: win_x, win_y half sizes in 1..7; zero_x, zero_y half sizes of the zero zone, -1 = none; max_count clamped to 1..100;
+ * epsilon clamped at 0.  Defaults: (5, 5), (-1, -1), 40, 0.001.
+ * Kernel k_corner_subpix: one wave per corner; parity with OpenCV itself is not pinned, the numpy model is the definition (bit for bit).
+ *   vo_corner_subpix   synchronous.  which = 0 the previous / 1 the current frame of the frame store; corners, out [batch][n][2] f32;
+ *                      iters [batch][n] i32 (steps counted) and flags [batch][n] u8 may be NULL.  flags: 0 ran to a stopping test,
+ *                      1 singular, 2 left the image, 3 reverted to the input, 4 input not usable.
+ *                      VO_E_INVALID, nothing enqueued: win outside 1..7, an image smaller than 2 * win + 5 on either axis, a NaN epsilon,
+ *                      n > max_pts.  VO_E_STATE: the named frame has not been pushed.
+ *   vo_set_subpix      per context; NULL = off (the default); the same parameter checks.  Takes effect at the next enqueue.  On,
+ *                      vo_tracks_detect and the DETECT stage of vo_pipe_step / vo_pipe_step_host enqueue the kernel on the detection's stream
+ *                      between the Shi-Tomasi selection and the spawn: the corner rows are refined in place against the current frame, and the
+ *                      new tracks / candidates (uv, uv_first, history entry 0) are born at the refined positions.  The min-distance rule is not
+ *                      run again (OpenCV does not either).  Results do not depend on the stream layout.
+ *                      These never refine: vo_shi_tomasi; vo_shi_tomasi_resident / vo_shi_tomasi_fetch when not behind a vo_tracks_detect
+ *                      (after one, vo_shi_tomasi_fetch returns the refined rows); the fused vo_frame_step_*.
+ *   vo_subpix_read     synchronous, no step in flight (else VO_E_STATE): the integer corners raw [batch][n][2] f32, iters, flags (any may be
+ *                      NULL) of the last vo_tracks_detect / DETECT stage, if it refined (else VO_E_STATE; a vo_corner_subpix call in between
+ *                      also ends it).  Slots beyond a sequence's corner count read raw = NaN, iters 0, flags 4. */
+typedef struct { int32_t win_x, win_y, zero_x, zero_y, max_count, _pad; double epsilon; } vo_subpix_params;  /* 32 bytes */
+int32_t vo_subpix_default_params(vo_subpix_params* p);
+int32_t vo_corner_subpix(vo_ctx* ctx, int32_t which, const float* corners, int32_t n, const vo_subpix_params* prm, float* out, int32_t* iters,
+                         uint8_t* flags);
+int32_t vo_set_subpix(vo_ctx* ctx, const vo_subpix_params* prm);
+int32_t vo_get_subpix(vo_ctx* ctx, int32_t* on, vo_subpix_params* prm);
+int32_t vo_subpix_read(vo_ctx* ctx, float* raw, int32_t* iters, uint8_t* flags, int32_t n);
+
 /* ---- DLT triangulation ----------------------------------------------------------------------
  * Replaces cv2.triangulatePoints(P0, P1, uv0, uv1) at extractor.py:270 and the reprojection
  * statistics TriangulatorNL.refine filters on (src/extractor/triangulate.py:87-111,139).

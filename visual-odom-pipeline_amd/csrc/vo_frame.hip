@@ -357,6 +357,7 @@ extern "C" int32_t vo_ctx_destroy(vo_ctx* c) {
   vo_ba_destroy(c);
   vo_fb_destroy(c);
   vo_guess_destroy(c);
+  vo_subpix_destroy(c);
   for (int f = 0; f < 2; f++)
     for (int l = 0; l < VO_MAX_LEVELS; l++) {
       if (c->fr[f].img[l]) (void)hipFree(c->fr[f].img[l]);

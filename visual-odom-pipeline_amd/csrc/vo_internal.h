@@ -109,6 +109,12 @@ struct vo_ctx {
   int klt_predict = VO_KLT_PREDICT_OFF;
   float* d_guess = nullptr;
   int guess_n = -1;                  // points of the last track if a predictor wrote its start positions, else -1
+  // sub-pixel corner refinement (vo_subpix.hip): the setting of vo_set_subpix, and the kernel's rows per sequence -- the integer corners, the
+  // synchronous form's in / out rows, iters, flags -- in an allocation of their own, made when a refinement is first asked for
+  bool subpix_on = false;
+  vo_subpix_params subpix_prm = {};
+  uint8_t* d_subpix = nullptr;
+  int subpix_n = -1;                 // corner slots the last resident detection refined, else -1
   // DLT inputs
   float* d_uv0 = nullptr; float* d_uv1 = nullptr;    // [batch][max_pts][2]
   vo_dlt_cam* d_dlt_cam = nullptr;   // [batch]
@@ -255,6 +261,11 @@ inline size_t vo_guess_seq(const vo_ctx* c) { return sizeof(float) * 2 * (size_t
 int32_t vo_guess_reserve(vo_ctx* c);
 int32_t vo_klt_track_resident_seeded(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts, bool fb);
 void vo_guess_destroy(vo_ctx* c);
+// sub-pixel refinement (vo_subpix.hip).  vo_subpix_refine_detected: called by the detections that spawn tracks (vo_tracks_detect, the closed
+// loop's DETECT stage) right behind the Shi-Tomasi enqueue on q: with vo_set_subpix on, k_corner_subpix refines the corner rows of st_out in
+// place against the current frame; off, it only notes that the last detection did not refine
+int32_t vo_subpix_refine_detected(vo_ctx* c, hipStream_t q, int max_corners);
+void vo_subpix_destroy(vo_ctx* c);
 int32_t vo_shi_tomasi_resident_counts(vo_ctx* c, hipStream_t q, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm, const int32_t* d_counts,
                                       const int32_t* d_limit);
 

@@ -31,6 +31,11 @@ class KltParams(C.Structure):
                 ("epsilon", C.c_double), ("min_eig_threshold", C.c_float), ("_pad", C.c_int32)]
 
 
+class SubpixParams(C.Structure):
+    _fields_ = [("win_x", C.c_int32), ("win_y", C.c_int32), ("zero_x", C.c_int32), ("zero_y", C.c_int32), ("max_count", C.c_int32),
+                ("_pad", C.c_int32), ("epsilon", C.c_double)]
+
+
 class StParams(C.Structure):
     _fields_ = [("max_corners", C.c_int32), ("block_size", C.c_int32), ("quality_level", C.c_double),
                 ("min_distance", C.c_double), ("use_harris", C.c_int32), ("_pad", C.c_int32), ("harris_k", C.c_double)]
@@ -142,6 +147,11 @@ SIGNATURES = {
     "vo_set_klt_predict": (C.c_int32, [_ctx, C.c_int32]),
     "vo_get_klt_predict": (C.c_int32, [_ctx, _i32p]),
     "vo_klt_guess_read": (C.c_int32, [_ctx, _f32p, C.c_int32]),
+    "vo_subpix_default_params": (C.c_int32, [C.POINTER(SubpixParams)]),
+    "vo_corner_subpix": (C.c_int32, [_ctx, C.c_int32, _f32p, C.c_int32, C.POINTER(SubpixParams), _f32p, _i32p, _u8p]),
+    "vo_set_subpix": (C.c_int32, [_ctx, C.POINTER(SubpixParams)]),
+    "vo_get_subpix": (C.c_int32, [_ctx, _i32p, C.POINTER(SubpixParams)]),
+    "vo_subpix_read": (C.c_int32, [_ctx, _f32p, _i32p, _u8p, C.c_int32]),
     "vo_st_default_params": (C.c_int32, [C.POINTER(StParams)]),
     "vo_shi_tomasi": (C.c_int32, [_ctx, _f32p, C.c_int32, C.c_int32, _u8p, C.POINTER(StParams), _f32p, _i32p]),
     "vo_shi_tomasi_resident": (C.c_int32, [_ctx, C.c_int32, C.c_int32, C.POINTER(StParams)]),

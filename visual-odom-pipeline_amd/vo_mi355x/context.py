@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BaParams, BaStats, EssParams, EssStats, KltParams, SiftKp, PnpParams, PnpStats, StParams, Tuning, VoError, as_c, ptr
+from ._lib import BaParams, BaStats, EssParams, EssStats, KltParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
 
 # vo_set_klt_predict modes (include/vo_mi355x.h)
 KLT_PREDICT_MODES = {"off": 0, "constant_velocity": 1}
@@ -33,6 +33,7 @@ class VoContext:
         self.width, self.height, self.max_pts = width, height, max_pts
         self.max_level, self.win, self.device, self.batch = max_level, win, device, batch
         self._st_max_corners = 1000
+        self._subpix_slots = 1000       # corner slots of the last detection that may have refined (subpix_read)
         self._klt_levels = max_level + 1
         self.comm_ranks, self.comm_rank = 1, 0
         if self.default_tuning:
@@ -252,6 +253,64 @@ class VoContext:
         g = np.zeros((self.batch, n, 2), np.float32)
         self._ck(self._L.vo_klt_guess_read(self._h, ptr(g, C.c_float), n))
         return self._out(g)
+
+    # -- sub-pixel corner refinement ---------------------------------------------------------------
+    def subpix_params(self, win=(5, 5), zero_zone=(-1, -1), max_count=40, epsilon=0.001):
+        """cv2.cornerSubPix's arguments: win / zero_zone are (x, y) half sizes (win 1..7, zero_zone -1 = none), criteria = (max_count, epsilon)"""
+        p = SubpixParams()
+        self._L.vo_subpix_default_params(C.byref(p))
+        p.win_x, p.win_y = int(win[0]), int(win[1])
+        p.zero_x, p.zero_y = int(zero_zone[0]), int(zero_zone[1])
+        p.max_count, p.epsilon = int(max_count), float(epsilon)
+        return p
+
+    def corner_subpix(self, corners, which="cur", params=None, return_info=False):
+        """cv2.cornerSubPix on a frame of the frame store (vo_corner_subpix): corners (n,2) f32 -> refined (n,2) f32, with return_info also
+        iters (n,) i32 and flags (n,) u8 (0 stopped, 1 singular, 2 left the image, 3 reverted, 4 input not usable)  [leading batch dim if
+        batch > 1].  which: "cur" (1) or "prev" (0).  Rows that are not finite or outside the image come back unchanged."""
+        p, n = self._npts(corners)
+        B = self.batch
+        prm = params if params is not None else self.subpix_params()
+        w = {"prev": 0, "cur": 1}.get(which, which)
+        out = p.copy()
+        it = np.zeros((B, n), np.int32)
+        fl = np.zeros((B, n), np.uint8)
+        self._ck(self._L.vo_corner_subpix(self._h, int(w), ptr(p, C.c_float), n, C.byref(prm), ptr(out, C.c_float), ptr(it, C.c_int32),
+                                          ptr(fl, C.c_uint8)))
+        if return_info:
+            return self._out(out), self._out(it), self._out(fl)
+        return self._out(out)
+
+    def set_subpix(self, params=None):
+        """refine the corners of tracks_detect and of the closed loop's DETECT stage before they become tracks (vo_set_subpix): a
+        subpix_params() struct, a dict of its keywords, or None = off (the default)"""
+        if isinstance(params, dict):
+            params = self.subpix_params(**params)
+        self._ck(self._L.vo_set_subpix(self._h, None if params is None else C.byref(params)))
+
+    def get_subpix(self):
+        """None when off, else the SubpixParams in effect"""
+        on, p = C.c_int32(0), SubpixParams()
+        self._ck(self._L.vo_get_subpix(self._h, C.byref(on), C.byref(p)))
+        return p if on.value else None
+
+    def subpix_read(self, n=None):
+        """what the last refined detection started from (vo_subpix_read): dict of raw (m,2) f32 = the integer corners, iters (m,) i32,
+        flags (m,) u8 per sequence [list of B dicts if batch > 1]; the refined positions are in the tracks.  n: corner slots to read
+        (default: all the detection could fill); slots the detection did not fill hold NaN and are cut off."""
+        B = self.batch
+        if n is None:
+            n = self._subpix_slots
+        raw = np.zeros((B, n, 2), np.float32)
+        it = np.zeros((B, n), np.int32)
+        fl = np.zeros((B, n), np.uint8)
+        self._ck(self._L.vo_subpix_read(self._h, ptr(raw, C.c_float), ptr(it, C.c_int32), ptr(fl, C.c_uint8), n))
+        out = []
+        for b in range(B):
+            dead = np.isnan(raw[b]).any(axis=1)
+            m = int(np.argmax(dead)) if dead.any() else n
+            out.append(dict(raw=raw[b, :m].copy(), iters=it[b, :m].copy(), flags=fl[b, :m].copy()))
+        return out[0] if B == 1 else out
 
     def points_upload(self, p):
         p, n = self._npts(p)
@@ -713,6 +772,7 @@ class VoContext:
     def tracks_detect(self, t, mask_radius=7, params=None, max_new=1000):
         """Shi-Tomasi re-detection around the live tracks; corners become tracks born at t (async)."""
         prm = params if params is not None else self.st_params()
+        self._subpix_slots = prm.max_corners if 0 < prm.max_corners < 4096 else 4096
         self._ck(self._L.vo_tracks_detect(self._h, int(t), int(mask_radius), C.byref(prm), int(max_new)))
 
     def tracks_read(self):

@@ -27,7 +27,7 @@ class DMatch:
 
 class Extractor:
     def __init__(self, cfg=None, min_kp_dist=10, ctx=None, device=0, max_pts=8192, lazy=None, lazy_backend=None, bidir="reference",
-                 predict="off"):
+                 predict="off", subpix=None):
         """lazy (default: on unless VO_LAZY=0): once a frame has come through the reference's call order (pipeline.py:98-156) the state moves
         into device tables and the lists this class hands out are views of them (vo_mi355x/lazy.py); lazy_backend: test hook
         (ctx, K, params, width, height) -> backend, default the GPU one.  max_pts: keypoints per call AND the capacity of those tables (<= 8192).
@@ -40,7 +40,17 @@ class Extractor:
         predict: where extend_tracks / extend_landmarks start the tracker.  "off" (default): at k.uv, the reference's flags = 0 call
         (extractor.py:44,65).  "constant_velocity": at g = uv + (uv - k.uv_history[-2]) in float32 (g = uv for a history of fewer than two
         entries), OpenCV's OPTFLOW_USE_INITIAL_FLOW through VoContext.klt_track(init=g); the second pass of either bidir mode is not seeded.
-        A lazy session serves only "off": with a prediction every call takes the plain path."""
+        A lazy session serves only "off": with a prediction every call takes the plain path.
+        subpix: None (default): extract(detector='shi-tomasi') hands out the detector's integer corners, as the reference does
+        (extractor.py:111).  dict(win=(5, 5), zero_zone=(-1, -1), criteria=(3, 40, 0.001)) -- cv2.cornerSubPix's arguments, any key may be
+        left out: the corners are refined against the image they were detected on (VoContext.corner_subpix), and the new keypoints' uv,
+        uv_first and uv_history[0] are the refined positions.  A lazy session serves only None: with refinement every call takes the
+        plain path."""
+        if subpix is not None:
+            unknown = set(subpix) - {"win", "zero_zone", "criteria"}
+            if unknown:
+                raise ValueError("subpix: unknown keys %r" % sorted(unknown))
+        self._subpix = None if subpix is None else dict(subpix)
         if bidir not in ("reference", "backward"):
             raise ValueError("bidir must be 'reference' or 'backward'")
         if predict not in ("off", "constant_velocity"):
@@ -251,6 +261,10 @@ class Extractor:
         kp = c.shi_tomasi(cur if len(cur) else None, mask_radius=mask_radius, params=prm)
         if kp.shape[0] == 0:
             return []
+        if self._subpix is not None:         # cv2.cornerSubPix(img, kp, win, zero_zone, criteria) on the image just detected on
+            crit = self._subpix.get("criteria", (3, 40, 0.001))
+            kp = c.corner_subpix(kp, "cur", c.subpix_params(win=self._subpix.get("win", (5, 5)), zero_zone=self._subpix.get("zero_zone", (-1, -1)),
+                                                            max_count=crit[1], epsilon=crit[2]))
         # like the reference (extractor.py:127-131) uv_first, uv and the first history entry of a new keypoint are three
         # VIEWS of the same row of the detector output (kp[i, :].reshape((2, 1)) is a view); des a view of the zero column
         kp3 = kp.reshape(-1, 2, 1)

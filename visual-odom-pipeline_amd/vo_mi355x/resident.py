@@ -52,11 +52,14 @@ class ResidentPipeline:
     back to the previous frame as well, and a landmark or candidate whose round trip misses its start by fb_max_error or more (max over x, y)
     dies like one that left the image; ctx.fb_read(n) returns the flags after a fetch.  np.inf (the default): off, the reference's behaviour.
     klt_predict: "constant_velocity" starts the TRACK stage's tracker at uv + (uv - prev) from every keypoint's own history (the context's
-    vo_set_klt_predict; ctx.klt_guess_read(n) returns the start positions after a fetch).  "off" (the default): at uv, the reference's call."""
+    vo_set_klt_predict; ctx.klt_guess_read(n) returns the start positions after a fetch).  "off" (the default): at uv, the reference's call.
+    subpix: ctx.subpix_params(...) or a dict of its keywords makes the DETECT stage refine its corners (cv2.cornerSubPix, the context's
+    vo_set_subpix) before they become candidates; ctx.subpix_read() returns the integer corners, iterations and flags after a fetch.  None
+    (the default): integer corners, the reference's behaviour."""
 
     def __init__(self, ctx, K, ba_window=4, min_track_length=3, mask_radius=7, max_new=1000, max_reproj_err=2.0, min_bearing_angle=0.5,
                  ba_max_iters=50, ba_budget=None, ba_ftol=1e-3, ba_xtol=1e-3, pnp_blind_batches=4, pnp_seed=0, min_kp_dist=7, resurrect=True,
-                 fb_max_error=np.inf, ba_loss='huber', ba_f_scale=1.0, klt_predict="off"):
+                 fb_max_error=np.inf, ba_loss='huber', ba_f_scale=1.0, klt_predict="off", subpix=None):
         self.ctx, self._L = ctx, ctx._L
         B = ctx.batch
         K = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (B, 3, 3)))
@@ -77,6 +80,9 @@ class ResidentPipeline:
             ctx.set_fb_check(fb_max_error)
         if not (klt_predict in ("off", 0) and ctx.get_klt_predict() == "off"):
             ctx.set_klt_predict(klt_predict)
+        if not (subpix is None and ctx.get_subpix() is None):
+            ctx.set_subpix(subpix)
+        ctx._subpix_slots = p.st.max_corners if 0 < p.st.max_corners < 4096 else 4096
         self.N, self.R, self.B = ctx.max_pts, 4 * ctx.max_pts, B
         self.ba_window = ba_window
         self._inflight = 0
