@@ -201,6 +201,34 @@ int32_t vo_frame_push(vo_ctx* ctx, const uint8_t* img, int32_t stride);
  * level 0, so a raw frame can be pushed as read from disk.  d = 0: off (default; the drop-in classes receive frames the
  * reference's loader has already filtered); d < 0: diameter from sigma_space as OpenCV does; diameter <= 7. */
 int32_t vo_set_prefilter(vo_ctx* ctx, int32_t d, double sigma_color, double sigma_space);
+/* Lens undistortion of every frame entering the frame store: cv2.undistort(src, K, dist, None, newK) of OpenCV 4.4, i.e.
+ * cv2.initUndistortRectifyMap (imgproc/undistort.cpp, no rectification, fixed-point map) followed by cv2.remap(INTER_LINEAR,
+ * BORDER_CONSTANT 0) (imgproc/imgwarp.cpp).  The reference only ever loads rectified sets; this lets a raw-camera frame be pushed as it is.
+ * Off by default.  On, every ingest path -- vo_frame_push, vo_frame_push_resident, vo_frame_step_resident / _host, vo_pipe_step /
+ * _step_host -- runs kernel k_undistort in front of the level-0 kernel, so it precedes the bilateral pre-filter (vo_set_prefilter).
+ * Definition (tests/undistort_model.py, bit for bit): per output pixel (j, i), in float64 without fused multiply-add,
+ *   x = (j - cx') / fx', y = (i - cy') / fy', r2 = x x + y y, kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2)
+ *   u = fx (x kr + p1 2xy + p2 (r2 + 2 x x)) + cx, v = fy (y kr + p1 (r2 + 2 y y) + p2 2xy) + cy
+ * quantised to 1/32 pixel (rint, half to even): tap origin (sx, sy) = q >> 5, fractions q & 31; the four bilinear taps with the integer
+ * weights (32 - fx5)(32 - fy5) 32, ... (sum 32768), a tap outside the image reads 0, dst = (sum + 16384) >> 15.  A map value that is not
+ * finite, or a tap origin outside [-2, w] x [-2, h], gives 0.  OpenCV walks each map row with running sums over an inverted newK, so a live
+ * cv2 can quantise a value within rounding noise of a tie differently: parity is with the model, as for use_harris.
+ * K, newK: (fx, fy, cx, cy); newK == NULL: K.  dist: (k1, k2, p1, p2, k3, k4, k5, k6), the first n_dist of them, the rest 0.
+ *   vo_set_undistort       builds the map on the host, waits for the context's streams and replaces the table.  VO_E_INVALID with nothing
+ *                          changed: n_dist not one of 0, 4, 5, 8; dist == NULL with n_dist > 0; a value that is not finite; fx, fy, fx' or
+ *                          fy' <= 0.  (VO_E_CAPACITY: an image side above 32766.)  Takes effect at the next enqueue; a captured frame step
+ *                          is never replayed with another table.
+ *   vo_clear_undistort     off again.
+ *   vo_get_undistort       *on, and K [4], dist [8], newK [4] of the setting (zeros when off; any of the three may be NULL).
+ *   vo_undistort           synchronous: `batch` images in (rows of `stride` bytes) and out (tight) with the current setting; the frame store
+ *                          and its frame count are untouched.  VO_E_STATE: no setting is active.
+ *   vo_undistort_map_read  the table the kernel reads: sxy [h][w][2] i16 (sx, sy), frac [h][w] u16 = fy5 * 32 + fx5, outside [h][w] u8
+ *                          (any may be NULL).  VO_E_STATE: no setting is active. */
+int32_t vo_set_undistort(vo_ctx* ctx, const double K[4], const double* dist, int32_t n_dist, const double* newK);
+int32_t vo_clear_undistort(vo_ctx* ctx);
+int32_t vo_get_undistort(vo_ctx* ctx, int32_t* on, double K[4], double dist[8], double newK[4]);
+int32_t vo_undistort(vo_ctx* ctx, const uint8_t* img, int32_t stride, uint8_t* out);
+int32_t vo_undistort_map_read(vo_ctx* ctx, int16_t* sxy, uint16_t* frac, uint8_t* outside);
 /* frames preloaded into HBM (bench: inputs resident before the timed region); frames: [batch][n_frames][h][w] */
 int32_t vo_seq_upload(vo_ctx* ctx, const uint8_t* frames, int32_t n_frames);
 int32_t vo_frame_push_resident(vo_ctx* ctx, int32_t frame_index);           /* async */

@@ -358,6 +358,7 @@ extern "C" int32_t vo_ctx_destroy(vo_ctx* c) {
   vo_fb_destroy(c);
   vo_guess_destroy(c);
   vo_subpix_destroy(c);
+  vo_undistort_destroy(c);
   for (int f = 0; f < 2; f++)
     for (int l = 0; l < VO_MAX_LEVELS; l++) {
       if (c->fr[f].img[l]) (void)hipFree(c->fr[f].img[l]);
@@ -512,6 +513,11 @@ int32_t vo_build_pyramid(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, siz
   vo_frame& F = c->fr[c->cur];
   const int B = c->batch;
   const int remap = (!c->tune.xcd_remap_off && B % 8 == 0) ? 1 : 0;       // every sequence's frame chain on one XCD (vo_xcd_assign)
+  if (c->und_on) {
+    // vo_set_undistort: cv2.undistort first, into the tight staging image; level 0 (plain or bilateral) then reads that as its raw frame
+    vo_undistort_enqueue(c, q, d_raw_img, raw_seq_stride, d_frame_idx, remap);
+    d_raw_img = c->d_und; raw_seq_stride = (size_t)c->width * c->height; d_frame_idx = nullptr;
+  }
   {
     const vo_level& L = c->lv[0];
     dim3 grid(vo_div_up(((L.w + 2 * VO_PAD + 15) / 16) * L.ph, 256), 1, B);   // 16 columns per thread, flat (row, group) index

@@ -115,6 +115,13 @@ struct vo_ctx {
   vo_subpix_params subpix_prm = {};
   uint8_t* d_subpix = nullptr;
   int subpix_n = -1;                 // corner slots the last resident detection refined, else -1
+  // lens undistortion (vo_undistort.hip): the setting of vo_set_undistort, its fixed-point map [h][w] of 8-byte entries (shared by the batch)
+  // and the tight [batch][h][w] staging image the level-0 kernels read instead of the raw frame -- allocated when first switched on
+  bool und_on = false;
+  double und_K[4] = {0, 0, 0, 0}, und_dist[8] = {0, 0, 0, 0, 0, 0, 0, 0}, und_newK[4] = {0, 0, 0, 0};
+  uint64_t* d_und_tab = nullptr;
+  uint8_t* d_und = nullptr;
+  unsigned und_gen = 0;              // bumped by every vo_set_undistort / vo_clear_undistort: part of a captured step's key
   // DLT inputs
   float* d_uv0 = nullptr; float* d_uv1 = nullptr;    // [batch][max_pts][2]
   vo_dlt_cam* d_dlt_cam = nullptr;   // [batch]
@@ -266,6 +273,10 @@ void vo_guess_destroy(vo_ctx* c);
 // place against the current frame; off, it only notes that the last detection did not refine
 int32_t vo_subpix_refine_detected(vo_ctx* c, hipStream_t q, int max_corners);
 void vo_subpix_destroy(vo_ctx* c);
+// lens undistortion (vo_undistort.hip).  vo_undistort_enqueue: called by vo_build_pyramid with vo_set_undistort on: k_undistort takes the raw
+// frames (k_pad_level0's triple) to c->d_und on q, and the level-0 kernel then reads that staging image
+void vo_undistort_enqueue(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx, int remap);
+void vo_undistort_destroy(vo_ctx* c);
 int32_t vo_shi_tomasi_resident_counts(vo_ctx* c, hipStream_t q, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm, const int32_t* d_counts,
                                       const int32_t* d_limit);
 

@@ -114,6 +114,55 @@ class VoContext:
         finally:
             self.set_prefilter(0)
 
+    @staticmethod
+    def _k4(K, name):
+        """a 3 x 3 camera matrix or (fx, fy, cx, cy) -> float64 [4]"""
+        K = np.asarray(K, np.float64)
+        if K.shape == (3, 3):
+            return np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
+        if K.shape != (4,):
+            raise ValueError("%s: a 3 x 3 matrix or (fx, fy, cx, cy), got shape %r" % (name, K.shape))
+        return np.ascontiguousarray(K)
+
+    def set_undistort(self, K, dist, new_K=None):
+        """cv2.undistort(img, K, dist, None, new_K) on every frame entering the frame store, in front of the bilateral pre-filter
+        (vo_set_undistort).  K, new_K: 3 x 3 or (fx, fy, cx, cy), new_K = None: K; dist: (k1, k2, p1, p2[, k3[, k4, k5, k6]]) or empty."""
+        K4 = self._k4(K, "K")
+        N4 = None if new_K is None else self._k4(new_K, "new_K")
+        d = np.ascontiguousarray(np.asarray([] if dist is None else dist, np.float64).reshape(-1))
+        self._ck(self._L.vo_set_undistort(self._h, ptr(K4, C.c_double), ptr(d, C.c_double) if d.size else None, int(d.size),
+                                          None if N4 is None else ptr(N4, C.c_double)))
+
+    def clear_undistort(self):
+        self._ck(self._L.vo_clear_undistort(self._h))
+
+    def get_undistort(self):
+        """-> None when off, else dict(K=(fx, fy, cx, cy), dist=[8], new_K=(fx', fy', cx', cy')) as float64 arrays"""
+        on = C.c_int32()
+        K, d, N = np.zeros(4), np.zeros(8), np.zeros(4)
+        self._ck(self._L.vo_get_undistort(self._h, C.byref(on), ptr(K, C.c_double), ptr(d, C.c_double), ptr(N, C.c_double)))
+        return dict(K=K, dist=d, new_K=N) if on.value else None
+
+    def undistort(self, img):
+        """cv2.undistort of `img` ([h, w] uint8, [batch, h, w] on a batched context) with the setting of set_undistort (vo_undistort);
+        the frame store is not touched"""
+        img = np.asarray(img)
+        if img.dtype != np.uint8:
+            raise ValueError("undistort: expected uint8")
+        img = self._in(img, np.uint8, (self.height, self.width))
+        out = np.empty_like(img)
+        self._ck(self._L.vo_undistort(self._h, ptr(img, C.c_uint8), self.width, ptr(out, C.c_uint8)))
+        return self._out(out)
+
+    def undistort_map_read(self):
+        """the fixed-point map of the setting (vo_undistort_map_read): dict of sxy (h, w, 2) i16 = the top-left tap (sx, sy),
+        frac (h, w) u16 = fy5 * 32 + fx5, outside (h, w) u8"""
+        sxy = np.empty((self.height, self.width, 2), np.int16)
+        frac = np.empty((self.height, self.width), np.uint16)
+        out = np.empty((self.height, self.width), np.uint8)
+        self._ck(self._L.vo_undistort_map_read(self._h, ptr(sxy, C.c_int16), ptr(frac, C.c_uint16), ptr(out, C.c_uint8)))
+        return dict(sxy=sxy, frac=frac, outside=out)
+
     def push_frame(self, img):
         img = np.asarray(img)
         if img.dtype != np.uint8:

@@ -27,7 +27,7 @@ class DMatch:
 
 class Extractor:
     def __init__(self, cfg=None, min_kp_dist=10, ctx=None, device=0, max_pts=8192, lazy=None, lazy_backend=None, bidir="reference",
-                 predict="off", subpix=None):
+                 predict="off", subpix=None, undistort=None):
         """lazy (default: on unless VO_LAZY=0): once a frame has come through the reference's call order (pipeline.py:98-156) the state moves
         into device tables and the lists this class hands out are views of them (vo_mi355x/lazy.py); lazy_backend: test hook
         (ctx, K, params, width, height) -> backend, default the GPU one.  max_pts: keypoints per call AND the capacity of those tables (<= 8192).
@@ -45,7 +45,15 @@ class Extractor:
         (extractor.py:111).  dict(win=(5, 5), zero_zone=(-1, -1), criteria=(3, 40, 0.001)) -- cv2.cornerSubPix's arguments, any key may be
         left out: the corners are refined against the image they were detected on (VoContext.corner_subpix), and the new keypoints' uv,
         uv_first and uv_history[0] are the refined positions.  A lazy session serves only None: with refinement every call takes the
-        plain path."""
+        plain path.
+        undistort: None (default): images are tracked as given.  dict(K=, dist=[, new_K=]) -- cv2.undistort's arguments: the setting goes to
+        this extractor's context (VoContext.set_undistort), so _im_prev and im_curr enter the frame store undistorted and extend_tracks /
+        extend_landmarks / extract work in the undistorted camera.  A lazy session serves only None."""
+        if undistort is not None:
+            unknown = set(undistort) - {"K", "dist", "new_K"}
+            if unknown or "K" not in undistort:
+                raise ValueError("undistort: a dict with K, dist and optionally new_K, got keys %r" % sorted(undistort))
+        self._undistort = None if undistort is None else dict(undistort)
         if subpix is not None:
             unknown = set(subpix) - {"win", "zero_zone", "criteria"}
             if unknown:
@@ -73,6 +81,8 @@ class Extractor:
         self._im_prev = None            # set by the caller, exactly like the reference (pipeline.py:36,103)
         self._dev_prev = None           # host copies of what the device frame store currently holds
         self._dev_cur = None
+        if ctx is not None:
+            self._apply_undistort(ctx)
 
     # -- device frame store ---------------------------------------------------------------------
     def _context(self, img):
@@ -81,7 +91,14 @@ class Extractor:
             h, w = img.shape
             self._ctx = VoContext(w, h, max_pts=self._max_pts, device=self._device,
                                   max_level=self._lk_params["maxLevel"], win=self._lk_params["winSize"][0])
+            self._apply_undistort(self._ctx)
         return self._ctx
+
+    def _apply_undistort(self, ctx):
+        """the setting goes to the context the frames are pushed to; None makes no call at all (a caller's context keeps what it has)"""
+        u = self._undistort
+        if u is not None:
+            ctx.set_undistort(u["K"], u.get("dist"), u.get("new_K"))
 
     def _push(self, img):
         img = np.ascontiguousarray(img, dtype=np.uint8)

@@ -6,6 +6,10 @@ whether ground-truth poses exist -- read by one generic routine.  Frames are dec
 that relates to cv2.imread(IMREAD_GRAYSCALE)); the pre-filter cv2.bilateralFilter(d=5, sigmaColor=1.5, sigmaSpace=1.5) that
 the reference applies to every frame (:16-20, :86) runs on the GPU (`VoContext.bilateral`, the kernel fused into the
 frame store's level-0 pass; bit-identical to the oracle's restatement, tests/test_gpu_prefilter.py).
+
+A raw-camera set: optional `distortion` ((k1, k2, p1, p2[, k3[, k4, k5, k6]])) and `new_K` (3 x 3 or (fx, fy, cx, cy)) entries in the
+dataset's cfg row make getImage return bilateral(cv2.undistort(raw, K, distortion, None, new_K)) -- one push through the loader's private
+context with both settings on -- and getCamera return new_K when one is given.  Without the entries nothing changes.
 """
 from collections import namedtuple
 from pathlib import Path
@@ -83,6 +87,8 @@ class Loader:
         self._ctx, self._device = ctx, device
         self.image_paths = sorted(str(p) for p in (base / lay.frames[0]).rglob(lay.frames[1]))
         self._camera = lay.camera(base)
+        self._distortion = cfg[name].get("distortion") if hasattr(cfg[name], "get") else None
+        self._new_K = cfg[name].get("new_K") if self._distortion is not None else None
         if lay.poses is not None:
             top = np.loadtxt(str(base / lay.poses)).reshape(-1, 3, 4)
             self._poses = np.concatenate([top, np.broadcast_to([[[0.0, 0.0, 0.0, 1.0]]], (len(top), 1, 4))], axis=1)
@@ -110,7 +116,14 @@ class Loader:
 
     def getImage(self, id):
         raw = imread_gray(self._at(self.image_paths, id))
-        return self._prefilter_context(raw.shape).bilateral(raw, PREFILTER["d"], PREFILTER["sigmaColor"], PREFILTER["sigmaSpace"])
+        c = self._prefilter_context(raw.shape)
+        if self._distortion is None:
+            return c.bilateral(raw, PREFILTER["d"], PREFILTER["sigmaColor"], PREFILTER["sigmaSpace"])
+        c.set_undistort(self._camera, self._distortion, self._new_K)       # undistortion runs in front of the filter, in the same push
+        try:
+            return c.bilateral(raw, PREFILTER["d"], PREFILTER["sigmaColor"], PREFILTER["sigmaSpace"])
+        finally:
+            c.clear_undistort()
 
     def getRawImage(self, id, out=None):
         """the frame as decoded, WITHOUT the pre-filter -- for a context that applies it while the frame enters the frame store
@@ -131,7 +144,10 @@ class Loader:
         return self.getImage(id), self.getPose(id)
 
     def getCamera(self):
-        return self._camera
+        if self._new_K is None:
+            return self._camera
+        n = np.asarray(self._new_K, np.float64)
+        return n if n.shape == (3, 3) else np.array([[n[0], 0.0, n[2]], [0.0, n[1], n[3]], [0.0, 0.0, 1.0]])
 
     def getInit(self):
         return tuple(self._cfg[self._name]["init"])

@@ -55,15 +55,25 @@ class ResidentPipeline:
     vo_set_klt_predict; ctx.klt_guess_read(n) returns the start positions after a fetch).  "off" (the default): at uv, the reference's call.
     subpix: ctx.subpix_params(...) or a dict of its keywords makes the DETECT stage refine its corners (cv2.cornerSubPix, the context's
     vo_set_subpix) before they become candidates; ctx.subpix_read() returns the integer corners, iterations and flags after a fetch.  None
-    (the default): integer corners, the reference's behaviour."""
+    (the default): integer corners, the reference's behaviour.
+    undistort: dict(K=, dist=[, new_K=]) makes every frame the loop takes in -- step on an uploaded sequence, step_host, the caller's own
+    push_frame -- pass through cv2.undistort first (the context's vo_set_undistort).  The geometry then works in the undistorted camera: the
+    pipeline's own K must equal new_K (K when new_K is absent), anything else raises ValueError.  None (the default): frames are used as given."""
 
     def __init__(self, ctx, K, ba_window=4, min_track_length=3, mask_radius=7, max_new=1000, max_reproj_err=2.0, min_bearing_angle=0.5,
                  ba_max_iters=50, ba_budget=None, ba_ftol=1e-3, ba_xtol=1e-3, pnp_blind_batches=4, pnp_seed=0, min_kp_dist=7, resurrect=True,
-                 fb_max_error=np.inf, ba_loss='huber', ba_f_scale=1.0, klt_predict="off", subpix=None):
+                 fb_max_error=np.inf, ba_loss='huber', ba_f_scale=1.0, klt_predict="off", subpix=None, undistort=None):
         self.ctx, self._L = ctx, ctx._L
         B = ctx.batch
         K = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (B, 3, 3)))
         self.K = K
+        if undistort is not None:
+            unknown = set(undistort) - {"K", "dist", "new_K"}
+            if unknown or "K" not in undistort:
+                raise ValueError("undistort: a dict with K, dist and optionally new_K, got keys %r" % sorted(undistort))
+            cam = ctx._k4(undistort["K"] if undistort.get("new_K") is None else undistort["new_K"], "undistort camera")
+            if not all(np.array_equal(cam, [k[0, 0], k[1, 1], k[0, 2], k[1, 2]]) for k in K):
+                raise ValueError("undistort: the pipeline's K must be the camera the frames are undistorted to (new_K, or K without one)")
         p = PipeParams()
         ctx._ck(self._L.vo_pipe_default_params(C.byref(p)))
         p.ba_window, p.min_track_length, p.mask_radius, p.max_new = ba_window, min_track_length, mask_radius, max_new
@@ -82,6 +92,10 @@ class ResidentPipeline:
             ctx.set_klt_predict(klt_predict)
         if not (subpix is None and ctx.get_subpix() is None):
             ctx.set_subpix(subpix)
+        if undistort is not None:
+            ctx.set_undistort(undistort["K"], undistort.get("dist"), undistort.get("new_K"))
+        elif ctx.get_undistort() is not None:
+            ctx.clear_undistort()
         ctx._subpix_slots = p.st.max_corners if 0 < p.st.max_corners < 4096 else 4096
         self.N, self.R, self.B = ctx.max_pts, 4 * ctx.max_pts, B
         self.ba_window = ba_window
