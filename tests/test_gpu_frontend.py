@@ -273,8 +273,7 @@ def test_dlt_vs_oracle_and_ground_truth(golden_dir):
     # TRI-1: the reference's own filter statistics (golden G2, generated by importing the reference)
     ok = np.abs(g["depth1"]) > 1e-3
     assert np.allclose(depth1[ok], g["depth1"][ok], rtol=1e-3, atol=1e-3)
-    assert np.abs(reproj - g["f0_all"]).max() <= 1e-3 * max(1.0, g["f0_all"].max()) or \
-        np.percentile(np.abs(reproj - g["f0_all"]), 99) <= 1e-3
+    assert np.abs(reproj - g["f0_all"]).max() <= 1e-3 * max(1.0, g["f0_all"].max())
     keep = np.nonzero((depth1 > 0) & (reproj < float(g["max_err"])))[0]
     border = np.abs(g["f0_all"] - float(g["max_err"])) < 1e-3
     sym = set(keep.tolist()) ^ set(g["keep"].tolist())

@@ -11,7 +11,7 @@
 // 1/sqrt(x) and 1/x from the hardware estimates + two Newton steps (relative error ~1e-16): the IEEE-exact sqrt / divide
 // expansions are ~30 dependent f64 instructions each and a Jacobi rotation needs three of each; the kernel is one long
 // dependent chain per point (500 waves on 1024 SIMDs), so their latency IS the run time.  Parity here is by tolerance
-// (1e-4 relative on X), not bit-exact.
+// (1e-4 relative on X; against a float64 SVD: residual within 2 * 2^-24 s1 of s4, tests/test_gpu_dlt.py), not bit-exact.
 __device__ __forceinline__ double dlt_rsqrt(double x) {
   double y = __builtin_amdgcn_rsq(x);
   double e = fma(-x * y, y, 1.0);
@@ -67,7 +67,10 @@ __global__ void __launch_bounds__(64) k_dlt(const vo_dlt_cam* __restrict__ cams,
           changed = true;
           const double zeta = (be - al) * (0.5 * dlt_rcp(ga));
           const double z2 = 1.0 + zeta * zeta;
-          const double t = (zeta >= 0 ? 1.0 : -1.0) * dlt_rcp(fabs(zeta) + z2 * dlt_rsqrt(z2));
+          double t = (zeta >= 0 ? 1.0 : -1.0) * dlt_rcp(fabs(zeta) + z2 * dlt_rsqrt(z2));
+          // a rank-deficient A (a camera that did not move) shrinks its null columns sweep by sweep until ga is denormal or zeta^2
+          // overflows; the Newton steps turn the estimates' inf / 0 there into NaN where the IEEE divide and sqrt give t = 0
+          if (!(fabs(t) <= 2.0)) t = 0.0;
           const double c = dlt_rsqrt(1.0 + t * t), s = c * t;
 #pragma unroll
           for (int k = 0; k < 4; k++) {
