@@ -11,7 +11,7 @@ import re
 import numpy as np
 import pytest
 
-from test_klt_fb_build import _resources
+from build_helpers import kernel_resources
 
 import ba_loss_model as lm
 
@@ -54,8 +54,8 @@ ROBUST = {   # soft_l1 (2), cauchy (3), arctan (4).  The updates came out better
 
 
 @pytest.fixture(scope="module")
-def ba_resources(tmp_path_factory):
-    return _resources("vo_ba.hip", tmp_path_factory.mktemp("ba"))
+def ba_resources():
+    return kernel_resources("vo_ba.hip")
 
 
 def _fig(r):

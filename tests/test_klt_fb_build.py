@@ -5,78 +5,25 @@ klt_lk_point (csrc/vo_klt_lk.h).  k_klt_track_fb must run without scratch at >= 
 k_klt_track<4|5|6> where they were: 79 / 81 VGPRs, 88 SGPRs, no scratch, occupancy 6 / 5, and -- stronger than the register pin -- the
 same count of every vector, buffer, LDS and global instruction as the build of the commit before the body was shared
 (tests/golden/klt_parent_opcodes.json)."""
-import collections
 import json
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "visual-odom-pipeline_amd", "csrc")
+from build_helpers import ROOT, kernel_opcodes, kernel_resources
 
 
-def _hipcc():
-    for p in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc")):
-        if p and os.path.exists(p):
-            return p
-    pytest.skip("no hipcc")
-
-
-def _flags():
-    """CXXFLAGS of the Makefile, as the library is built"""
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    m = re.search(r"^CXXFLAGS \?=(.*?)(?<!\\)\n", mk, flags=re.M | re.S)
-    flags = m.group(1).replace("\\\n", " ").replace("$(ARCH)", "gfx950").split()
-    return [f for f in flags if f != "-fPIC"]
-
-
-def _opcodes(src, kernel, tmp_path):
-    """opcode -> count over the device assembly of the one kernel whose mangled name contains `kernel`"""
-    asm = tmp_path / "k.s"
-    out = subprocess.run([_hipcc()] + _flags() + ["--cuda-device-only", "-S", src, "-o", str(asm)], cwd=CSRC, capture_output=True, text=True,
-                         timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    lines = asm.read_text().split("\n")
-    (start,) = [i for i, l in enumerate(lines) if re.match(r"_Z\w*%s\w*:" % kernel, l)]
-    end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith(".Lfunc_end"))
-    h = collections.Counter()
-    for l in lines[start + 1:end]:
-        m = re.match(r"\s+([a-z][a-z0-9_]+)(\s|$)", l)
-        if m:
-            h[m.group(1)] += 1
-    return h
-
-
-def _resources(src, tmp_path):
-    out = subprocess.run([_hipcc()] + _flags() + ["--cuda-device-only", "-c", src, "-o", str(tmp_path / "k.o"),
-                                                  "-Rpass-analysis=kernel-resource-usage"],
-                         cwd=CSRC, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1); res[cur] = {}
-            continue
-        m = re.search(r"remark:\s+(TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur:
-            res[cur][m.group(1).split()[0]] = int(m.group(2))
-    return res
-
-
-def test_klt_fb_kernel_has_no_scratch_and_occupancy_5(tmp_path):
-    res = _resources("vo_klt_fb.hip", tmp_path)
+def test_klt_fb_kernel_has_no_scratch_and_occupancy_5():
+    res = kernel_resources("vo_klt_fb.hip")
     fb = {k: v for k, v in res.items() if "k_klt_track_fb" in k}
     assert len(fb) == 1, sorted(res)                       # ONE instantiation
     (r,) = fb.values()
     assert r["ScratchSize"] == 0 and r["Occupancy"] >= 5, r
 
 
-def test_klt_track_resources_unchanged(tmp_path):
-    res = _resources("vo_klt.hip", tmp_path)
+def test_klt_track_resources_unchanged():
+    res = kernel_resources("vo_klt.hip")
     want = {4: (81, 5), 5: (81, 5), 6: (79, 6)}
     for wv, (vgpr, occ) in want.items():
         (r,) = [v for k, v in res.items() if re.search(r"k_klt_trackILi%dE" % wv, k)]
@@ -85,11 +32,11 @@ def test_klt_track_resources_unchanged(tmp_path):
 
 @pytest.mark.parametrize("src,kernel,name", [("vo_klt.hip", "k_klt_trackILi6E", "k_klt_track<6>"),
                                              ("vo_klt_fb.hip", "k_klt_track_fbILi6E", "k_klt_track_fb<6>")])
-def test_klt_vector_and_memory_opcodes_equal_the_parents(src, kernel, name, tmp_path):
+def test_klt_vector_and_memory_opcodes_equal_the_parents(src, kernel, name):
     """every v_*, buffer_*, ds_* and global_* opcode as often as in the parent commit's build of the same kernel (a committed histogram,
     never the tree under test); scalar opcodes are reported, not asserted"""
     want = json.load(open(os.path.join(ROOT, "tests", "golden", "klt_parent_opcodes.json")))[name]
-    got = _opcodes(src, kernel, tmp_path)
+    got = kernel_opcodes(src, kernel)
     pinned = ("v_", "buffer_", "ds_", "global_")
     assert sum(1 for k in want if k.startswith(pinned)) > 50 and any(k.startswith("buffer_load") for k in want), "fixture"
     diff = {k: (want.get(k, 0), got.get(k, 0)) for k in sorted(set(want) | set(got)) if want.get(k, 0) != got.get(k, 0)}

@@ -135,7 +135,7 @@ struct vo_ctx {
   struct vo_pipe_ws* pipe = nullptr; // closed-loop Pipeline.step on the device (vo_pipeline.hip)
   const int32_t* d_pt_counts = nullptr;   // vo_tracks_* only (set by vo_tracks_seed, cleared by vo_trk_destroy): per-sequence number of live tracks the
                                           // PUBLIC resident entry points (vo_klt_track_resident, vo_shi_tomasi_resident) then use; null = uniform n.
-                                          // The closed-loop pipeline passes its own counters explicitly (vo_*_resident_counts) and never touches this.
+                                          // The closed-loop pipeline passes its own counters explicitly (the resident enqueues) and never touches this.
   vo_ba_ws* ba = nullptr;
   vo_prof prof;
   unsigned long long* d_dbg = nullptr;   // 4 x 8 phase stamps (vo_debug_cycles)
@@ -255,18 +255,19 @@ hipError_t vo_stream_create(hipStream_t* st, int reserve_cus);      // reserve_c
 int32_t vo_st_prepare(vo_ctx* c, const vo_st_params* prm);
 // the resident enqueues with the per-sequence counters named by the caller (device arrays [batch], null = uniform): d_counts = live
 // points of each sequence (KLT input / exclusion discs), d_limit = cap on the corners each sequence's re-detection needs
-int32_t vo_klt_track_resident_counts(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts);
-// the same tracking with the forward-backward check (k_klt_track_fb): the ok flags land in vo_fb_ok(c) [batch][fb_seq bytes]
-int32_t vo_klt_track_resident_fb(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts);
+// The tracker's form word: KLT_FORM_FB = with the forward-backward check (the ok flags land in vo_fb_ok(c) [batch][fb_seq bytes]),
+// KLT_FORM_SEEDED = started at the guesses a predictor kernel has just written to c->d_guess on q (vo_guess_reserve: those rows exist
+// afterwards).  The four values select k_klt_track, k_klt_track_fb, k_klt_seeded, k_klt_seeded_fb (vo_klt_enqueue, vo_klt.hip).
+enum : unsigned { KLT_FORM_FB = 1u, KLT_FORM_SEEDED = 2u };
+int32_t vo_klt_track_resident_enqueue(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts, unsigned form);
 inline bool vo_fb_on(const vo_ctx* c) { return !(c->fb_max_err == __builtin_inff()); }     // +inf = off
 inline const uint8_t* vo_fb_ok(const vo_ctx* c) { return c->d_fb + c->fb_off_ok; }
 void vo_fb_destroy(vo_ctx* c);
-// motion prediction (vo_klt_seed.hip).  vo_guess_reserve: the guess rows exist afterwards.  vo_klt_track_resident_seeded: the resident
-// tracking started at the guesses a predictor kernel has just written to c->d_guess on q (k_klt_seeded, or k_klt_seeded_fb with fb)
 inline bool vo_predict_on(const vo_ctx* c) { return c->klt_predict != VO_KLT_PREDICT_OFF; }
+// the form the context's settings ask for (vo_set_fb_check, vo_set_klt_predict): what vo_tracks_track and the closed loop's TRACK stage run
+inline unsigned vo_klt_form(const vo_ctx* c) { return (vo_fb_on(c) ? KLT_FORM_FB : 0u) | (vo_predict_on(c) ? KLT_FORM_SEEDED : 0u); }
 inline size_t vo_guess_seq(const vo_ctx* c) { return sizeof(float) * 2 * (size_t)c->max_pts; }      // bytes per sequence
 int32_t vo_guess_reserve(vo_ctx* c);
-int32_t vo_klt_track_resident_seeded(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts, bool fb);
 void vo_guess_destroy(vo_ctx* c);
 // sub-pixel refinement (vo_subpix.hip).  vo_subpix_refine_detected: called by the detections that spawn tracks (vo_tracks_detect, the closed
 // loop's DETECT stage) right behind the Shi-Tomasi enqueue on q: with vo_set_subpix on, k_corner_subpix refines the corner rows of st_out in

@@ -324,7 +324,7 @@ static float klt_min_eig_numerator(float thr, float c) {
   return from_ord(hi);
 }
 
-// the argument checks and the argument block of a tracker launch (also k_klt_track_fb's forward pass, vo_klt_fb.hip); nothing to fill for n = 0
+// the argument checks and the argument block of a tracker launch, whatever its form; nothing to fill for n = 0
 int32_t vo_klt_make_args(vo_ctx* c, int n, const vo_klt_params* prm, klt_args& A) {
   VO_CHECK(c, c->n_pushed >= 2, VO_E_STATE, "need two pushed frames");
   VO_CHECK(c, n >= 0 && n <= c->max_pts, VO_E_CAPACITY, "n exceeds max_pts");
@@ -357,68 +357,99 @@ int32_t vo_klt_make_args(vo_ctx* c, int n, const vo_klt_params* prm, klt_args& A
   return VO_OK;
 }
 
-static int32_t klt_launch(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* counts) {
-  c->fb_n = -1;                         // the last track ran without the forward-backward check (vo_fb_read)
-  c->guess_n = -1;                      // ... and without a predicted start (vo_klt_guess_read)
+// k_klt_track on L.q; the only form with a choice of instantiation (vo_tuning.klt_waves), the experiment's pair kernel and the diagnostic stamps
+static void klt_launch_plain(vo_ctx* c, const klt_launch_rows& L, const klt_args& A) {
+  const int waves = c->tune.klt_waves > 0 ? c->tune.klt_waves : 6;
+#define VO_KLT_LAUNCH(WV) hipLaunchKernelGGL(k_klt_track<WV>, dim3(L.n, c->batch), dim3(64), 0, L.q, A, L.p0, L.p1, L.status, L.err, c->d_iters, c->d_dbg, L.counts)
+#ifdef VO_EXPERIMENTS
+  // vo_tuning.klt_pair (builds with -DVO_EXPERIMENTS): two keypoints per wave (k_klt_track2, slower); read per launch so that a test can compare both
+  const int pair = c->tune.klt_pair;
+  if (pair) {
+    const int npair = (L.n + 1) / 2;
+#define VO_KLT_LAUNCH2(WV) hipLaunchKernelGGL(k_klt_track2<WV>, dim3(npair, c->batch), dim3(64), 0, L.q, A, L.p0, L.p1, L.status, L.err, c->d_iters, L.counts)
+    if (pair == 3) VO_KLT_LAUNCH2(3); else if (pair == 5) VO_KLT_LAUNCH2(5); else VO_KLT_LAUNCH2(4);
+#undef VO_KLT_LAUNCH2
+  } else
+#endif
+  if (waves <= 4) VO_KLT_LAUNCH(4); else if (waves == 5) VO_KLT_LAUNCH(5); else VO_KLT_LAUNCH(6);
+#undef VO_KLT_LAUNCH
+}
+
+// the one launch path of the four forms (vo_klt_lk.h)
+int32_t vo_klt_enqueue(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* d_counts, unsigned form) {
+  const bool fb = form & KLT_FORM_FB, seeded = form & KLT_FORM_SEEDED;
+  c->fb_n = -1;                         // until this launch is enqueued, the last track ran without the forward-backward check (vo_fb_read)
+  c->guess_n = -1;                      // ... and without a predicted start (vo_klt_guess_read; set by the resident seeded form)
   klt_args A;
-  { const int32_t r = vo_klt_make_args(c, n, prm, A); if (r != VO_OK || n == 0) return r; }
+  { const int32_t r = vo_klt_make_args(c, n, prm, A); if (r != VO_OK) return r; }
+  if (n == 0) { if (fb) c->fb_n = 0; return VO_OK; }
+  if (seeded) VO_CHECK(c, c->d_guess, VO_E_STATE, "no guesses");
+  klt_fb_args F;
+  if (fb) {
+    { const int32_t r = vo_fb_reserve(c); if (r != VO_OK) return r; }
+    vo_klt_fb_make_args(c, A, F);
+  }
+  const klt_launch_rows L = {q, n, vo_slab<const float>(c, off_in), vo_slab<float>(c, off_out), vo_slab<uint8_t>(c, c->off_status),
+                        vo_slab<float>(c, c->off_err), d_counts};
   {
     vo_prof_scope prof(c, q, VO_PROF_KLT);   // brackets exactly this launch (bench.py roofline figure)
-    const int waves = c->tune.klt_waves > 0 ? c->tune.klt_waves : 6;
-#define VO_KLT_LAUNCH(WV) hipLaunchKernelGGL(k_klt_track<WV>, dim3(n, c->batch), dim3(64), 0, q, A,                \
-                       vo_slab<const float>(c, off_in), vo_slab<float>(c, off_out), vo_slab<uint8_t>(c, c->off_status),     \
-                       vo_slab<float>(c, c->off_err), c->d_iters, c->d_dbg, counts)
-#ifdef VO_EXPERIMENTS
-    // vo_tuning.klt_pair (builds with -DVO_EXPERIMENTS): two keypoints per wave (k_klt_track2, slower); read per launch so that a test can compare both
-    const int pair = c->tune.klt_pair;
-    if (pair) {
-      const int npair = (n + 1) / 2;
-#define VO_KLT_LAUNCH2(WV) hipLaunchKernelGGL(k_klt_track2<WV>, dim3(npair, c->batch), dim3(64), 0, q, A,            \
-                       vo_slab<const float>(c, off_in), vo_slab<float>(c, off_out), vo_slab<uint8_t>(c, c->off_status),     \
-                       vo_slab<float>(c, c->off_err), c->d_iters, counts)
-      if (pair == 3) VO_KLT_LAUNCH2(3); else if (pair == 5) VO_KLT_LAUNCH2(5); else VO_KLT_LAUNCH2(4);
-#undef VO_KLT_LAUNCH2
-    } else
-#endif
-    if (waves <= 4) VO_KLT_LAUNCH(4); else if (waves == 5) VO_KLT_LAUNCH(5); else VO_KLT_LAUNCH(6);
-#undef VO_KLT_LAUNCH
+    if (seeded) vo_klt_launch_seeded(c, L, A, fb ? &F : nullptr);
+    else if (fb) vo_klt_launch_fb(c, L, A, F);
+    else klt_launch_plain(c, L, A);
   }
   VO_HIP(c, hipGetLastError());
+  if (fb) c->fb_n = n;
   return VO_OK;
 }
 
-// strided copies between [batch][n * elem] host arrays and the per-sequence slab rows
-static hipError_t slab_h2d(vo_ctx* c, size_t off, const void* h, size_t row_bytes) {
-  return hipMemcpy2DAsync(c->d_slab + off, c->slab_seq, h, row_bytes, row_bytes, c->batch, hipMemcpyHostToDevice, c->stream);
-}
-static hipError_t slab_d2h(vo_ctx* c, void* h, size_t off, size_t row_bytes) {
-  return hipMemcpy2DAsync(h, row_bytes, c->d_slab + off, c->slab_seq, row_bytes, c->batch, hipMemcpyDeviceToHost, c->stream);
-}
-
-extern "C" int32_t vo_klt_track(vo_ctx* c, const float* p0, int32_t n, const vo_klt_params* prm,
-                                float* p1, uint8_t* status, float* err, int32_t* iters) {
+// the synchronous forms' one body: p0 (and the guesses of a seeded form) up, one launch, the results down.  p0r / fb_err: of a form with the check
+static int32_t klt_track_sync(vo_ctx* c, unsigned form, const float* p0, const float* guess, int32_t n, const vo_klt_params* prm, float* p1,
+                              uint8_t* status, float* err, float* p0r, float* fb_err, int32_t* iters) {
   if (!c) return VO_E_INVALID;
+  const bool fb = form & KLT_FORM_FB, seeded = form & KLT_FORM_SEEDED;
   vo_klt_params def;
   if (!prm) { vo_klt_default_params(&def); prm = &def; }
   VO_CHECK(c, n >= 0 && n <= c->max_pts, VO_E_CAPACITY, "n exceeds max_pts");
   if (n == 0) return VO_OK;
-  VO_CHECK(c, p0 && p1 && status && err, VO_E_INVALID, "null buffer");
+  VO_CHECK(c, p0 && p1 && status && err && (!fb || (p0r && fb_err)), VO_E_INVALID, "null buffer");
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
+  if (seeded) { const int32_t rg = vo_guess_reserve(c); if (rg != VO_OK) return rg; }
   const size_t off_in = vo_off_p(c), off_out = vo_off_p_next(c);
-  VO_HIP(c, slab_h2d(c, off_in, p0, sizeof(float) * 2 * n));
-  int32_t r = klt_launch(c, c->stream, n, prm, off_in, off_out, nullptr);
-  if (r != VO_OK) return r;
-  VO_HIP(c, slab_d2h(c, p1, off_out, sizeof(float) * 2 * n));
-  VO_HIP(c, slab_d2h(c, status, c->off_status, n));
-  VO_HIP(c, slab_d2h(c, err, c->off_err, sizeof(float) * n));
-  if (iters) {
-    const size_t row = sizeof(int32_t) * (size_t)n * (prm->max_level + 1);
-    VO_HIP(c, hipMemcpy2DAsync(iters, row, c->d_iters, sizeof(int32_t) * (size_t)c->max_pts * VO_MAX_LEVELS, row, c->batch,
-                               hipMemcpyDeviceToHost, c->stream));
+  VO_HIP(c, rows_h2d(c, c->d_slab + off_in, c->slab_seq, p0, sizeof(float) * 2 * n));
+  if (seeded) VO_HIP(c, rows_h2d(c, c->d_guess, vo_guess_seq(c), guess, sizeof(float) * 2 * n));
+  { const int32_t r = vo_klt_enqueue(c, c->stream, n, prm, off_in, off_out, nullptr, form); if (r != VO_OK) return r; }
+  VO_HIP(c, rows_d2h(c, p1, c->d_slab + off_out, c->slab_seq, sizeof(float) * 2 * n));
+  VO_HIP(c, rows_d2h(c, status, c->d_slab + c->off_status, c->slab_seq, n));
+  VO_HIP(c, rows_d2h(c, err, c->d_slab + c->off_err, c->slab_seq, sizeof(float) * n));
+  if (fb) {
+    VO_HIP(c, rows_d2h(c, p0r, c->d_fb, c->fb_seq, sizeof(float) * 2 * n));
+    VO_HIP(c, rows_d2h(c, fb_err, c->d_fb + c->fb_off_err, c->fb_seq, sizeof(float) * n));
   }
+  if (iters) VO_HIP(c, iters_d2h(c, iters, n, prm->max_level + 1));
   VO_HIP(c, hipStreamSynchronize(c->stream));
   return VO_OK;
+}
+
+extern "C" int32_t vo_klt_track(vo_ctx* c, const float* p0, int32_t n, const vo_klt_params* prm,
+                                float* p1, uint8_t* status, float* err, int32_t* iters) {
+  return klt_track_sync(c, 0, p0, nullptr, n, prm, p1, status, err, nullptr, nullptr, iters);
+}
+
+extern "C" int32_t vo_klt_track_fb(vo_ctx* c, const float* p0, int32_t n, const vo_klt_params* prm, float* p1, uint8_t* status, float* err,
+                                   float* p0r, float* fb_err, int32_t* iters) {
+  return klt_track_sync(c, KLT_FORM_FB, p0, nullptr, n, prm, p1, status, err, p0r, fb_err, iters);
+}
+
+// a null guess: the unseeded form
+extern "C" int32_t vo_klt_track_init(vo_ctx* c, const float* p0, const float* guess, int32_t n, const vo_klt_params* prm,
+                                     float* p1, uint8_t* status, float* err, int32_t* iters) {
+  return klt_track_sync(c, guess ? KLT_FORM_SEEDED : 0u, p0, guess, n, prm, p1, status, err, nullptr, nullptr, iters);
+}
+
+extern "C" int32_t vo_klt_track_fb_init(vo_ctx* c, const float* p0, const float* guess, int32_t n, const vo_klt_params* prm, float* p1,
+                                        uint8_t* status, float* err, float* p0r, float* fb_err, int32_t* iters) {
+  return klt_track_sync(c, KLT_FORM_FB | (guess ? KLT_FORM_SEEDED : 0u), p0, guess, n, prm, p1, status, err, p0r, fb_err, iters);
 }
 
 extern "C" int32_t vo_points_upload(vo_ctx* c, const float* p, int32_t n) {
@@ -426,7 +457,7 @@ extern "C" int32_t vo_points_upload(vo_ctx* c, const float* p, int32_t n) {
   VO_CHECK(c, p && n >= 0 && n <= c->max_pts, VO_E_CAPACITY, "bad point set");
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  if (n > 0) VO_HIP(c, slab_h2d(c, vo_off_p(c), p, sizeof(float) * 2 * n));
+  if (n > 0) VO_HIP(c, rows_h2d(c, c->d_slab + vo_off_p(c), c->slab_seq, p, sizeof(float) * 2 * n));
   VO_HIP(c, hipStreamSynchronize(c->stream));
   c->n_resident = n;
   return VO_OK;
@@ -438,14 +469,10 @@ extern "C" int32_t vo_points_download(vo_ctx* c, float* p, uint8_t* status, floa
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   if (n > 0) {
-    if (p) VO_HIP(c, slab_d2h(c, p, vo_off_p(c), sizeof(float) * 2 * n));
-    if (status) VO_HIP(c, slab_d2h(c, status, c->off_status, n));
-    if (err) VO_HIP(c, slab_d2h(c, err, c->off_err, sizeof(float) * n));
-    if (iters && c->iters_stride > 0) {
-      const size_t row = sizeof(int32_t) * (size_t)n * c->iters_stride;
-      VO_HIP(c, hipMemcpy2DAsync(iters, row, c->d_iters, sizeof(int32_t) * (size_t)c->max_pts * VO_MAX_LEVELS, row, c->batch,
-                                 hipMemcpyDeviceToHost, c->stream));
-    }
+    if (p) VO_HIP(c, rows_d2h(c, p, c->d_slab + vo_off_p(c), c->slab_seq, sizeof(float) * 2 * n));
+    if (status) VO_HIP(c, rows_d2h(c, status, c->d_slab + c->off_status, c->slab_seq, n));
+    if (err) VO_HIP(c, rows_d2h(c, err, c->d_slab + c->off_err, c->slab_seq, sizeof(float) * n));
+    if (iters && c->iters_stride > 0) VO_HIP(c, iters_d2h(c, iters, n, c->iters_stride));
   }
   VO_HIP(c, hipStreamSynchronize(c->stream));
   return VO_OK;
@@ -457,15 +484,18 @@ extern "C" int32_t vo_klt_track_resident(vo_ctx* c, int32_t n, const vo_klt_para
   VO_CHECK(c, n >= 0 && n <= c->n_resident, VO_E_INVALID, "n exceeds the resident point set");
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  return vo_klt_track_resident_counts(c, c->stream, n, prm, c->d_pt_counts);      // (non-null only while a vo_tracks_* table is seeded)
+  return vo_klt_track_resident_enqueue(c, c->stream, n, prm, c->d_pt_counts, 0);      // (counts: non-null only while a vo_tracks_* table is seeded)
 }
 
-int32_t vo_klt_track_resident_counts(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts) {
+// the resident form of every track (vo_frame_step_*, vo_tracks_track, the closed loop's TRACK stage): the resident point set in, the other half
+// of the ping-pong out.  A seeded form runs behind a predictor kernel on q, whose guesses stay in c->d_guess (vo_klt_guess_read)
+int32_t vo_klt_track_resident_enqueue(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts, unsigned form) {
   vo_klt_params def;
   if (!prm) { vo_klt_default_params(&def); prm = &def; }
   VO_CHECK(c, n >= 0 && n <= c->n_resident, VO_E_INVALID, "n exceeds the resident point set");
-  int32_t r = klt_launch(c, q, n, prm, vo_off_p(c), vo_off_p_next(c), d_counts);
+  const int32_t r = vo_klt_enqueue(c, q, n, prm, vo_off_p(c), vo_off_p_next(c), d_counts, form);
   if (r != VO_OK) return r;
+  if (form & KLT_FORM_SEEDED) c->guess_n = n;
   c->p_parity ^= 1;   // tracked positions become the resident set
   return VO_OK;
 }

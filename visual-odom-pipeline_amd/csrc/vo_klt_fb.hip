@@ -93,66 +93,8 @@ void vo_klt_fb_make_args(const vo_ctx* c, const klt_args& A, klt_fb_args& F) {
   F.max_err = c->fb_max_err;
 }
 
-static int32_t fb_launch(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* counts) {
-  c->fb_n = -1; c->guess_n = -1;
-  klt_args A;
-  { const int32_t r = vo_klt_make_args(c, n, prm, A); if (r != VO_OK) return r; }
-  if (n == 0) { c->fb_n = 0; return VO_OK; }
-  { const int32_t r = vo_fb_reserve(c); if (r != VO_OK) return r; }
-  klt_fb_args F;
-  vo_klt_fb_make_args(c, A, F);
-  {
-    vo_prof_scope prof(c, q, VO_PROF_KLT);
-    hipLaunchKernelGGL(k_klt_track_fb<6>, dim3(n, c->batch), dim3(64), 0, q, A, F, vo_slab<const float>(c, off_in),
-                       vo_slab<float>(c, off_out), vo_slab<uint8_t>(c, c->off_status), vo_slab<float>(c, c->off_err), c->d_iters, counts, c->d_fb);
-  }
-  VO_HIP(c, hipGetLastError());
-  c->fb_n = n;
-  return VO_OK;
-}
-
-static hipError_t rows_d2h(vo_ctx* c, void* h, const uint8_t* d, size_t d_stride, size_t row_bytes) {
-  return hipMemcpy2DAsync(h, row_bytes, d, d_stride, row_bytes, c->batch, hipMemcpyDeviceToHost, c->stream);
-}
-
-extern "C" int32_t vo_klt_track_fb(vo_ctx* c, const float* p0, int32_t n, const vo_klt_params* prm, float* p1, uint8_t* status, float* err,
-                                   float* p0r, float* fb_err, int32_t* iters) {
-  if (!c) return VO_E_INVALID;
-  vo_klt_params def;
-  if (!prm) { vo_klt_default_params(&def); prm = &def; }
-  VO_CHECK(c, n >= 0 && n <= c->max_pts, VO_E_CAPACITY, "n exceeds max_pts");
-  if (n == 0) return VO_OK;
-  VO_CHECK(c, p0 && p1 && status && err && p0r && fb_err, VO_E_INVALID, "null buffer");
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  const size_t off_in = vo_off_p(c), off_out = vo_off_p_next(c);
-  VO_HIP(c, hipMemcpy2DAsync(c->d_slab + off_in, c->slab_seq, p0, sizeof(float) * 2 * n, sizeof(float) * 2 * n, c->batch,
-                             hipMemcpyHostToDevice, c->stream));
-  const int32_t r = fb_launch(c, c->stream, n, prm, off_in, off_out, nullptr);
-  if (r != VO_OK) return r;
-  VO_HIP(c, rows_d2h(c, p1, c->d_slab + off_out, c->slab_seq, sizeof(float) * 2 * n));
-  VO_HIP(c, rows_d2h(c, status, c->d_slab + c->off_status, c->slab_seq, n));
-  VO_HIP(c, rows_d2h(c, err, c->d_slab + c->off_err, c->slab_seq, sizeof(float) * n));
-  VO_HIP(c, rows_d2h(c, p0r, c->d_fb, c->fb_seq, sizeof(float) * 2 * n));
-  VO_HIP(c, rows_d2h(c, fb_err, c->d_fb + c->fb_off_err, c->fb_seq, sizeof(float) * n));
-  if (iters) {
-    const size_t row = sizeof(int32_t) * (size_t)n * (prm->max_level + 1);
-    VO_HIP(c, hipMemcpy2DAsync(iters, row, c->d_iters, sizeof(int32_t) * (size_t)c->max_pts * VO_MAX_LEVELS, row, c->batch,
-                               hipMemcpyDeviceToHost, c->stream));
-  }
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  return VO_OK;
-}
-
-// the resident form (vo_tracks_track, the closed loop's TRACK stage): vo_klt_track_resident_counts with the check
-int32_t vo_klt_track_resident_fb(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts) {
-  vo_klt_params def;
-  if (!prm) { vo_klt_default_params(&def); prm = &def; }
-  VO_CHECK(c, n >= 0 && n <= c->n_resident, VO_E_INVALID, "n exceeds the resident point set");
-  const int32_t r = fb_launch(c, q, n, prm, vo_off_p(c), vo_off_p_next(c), d_counts);
-  if (r != VO_OK) return r;
-  c->p_parity ^= 1;   // tracked positions become the resident set
-  return VO_OK;
+void vo_klt_launch_fb(vo_ctx* c, const klt_launch_rows& L, const klt_args& A, const klt_fb_args& F) {
+  hipLaunchKernelGGL(k_klt_track_fb<6>, dim3(L.n, c->batch), dim3(64), 0, L.q, A, F, L.p0, L.p1, L.status, L.err, c->d_iters, L.counts, c->d_fb);
 }
 
 extern "C" int32_t vo_set_fb_check(vo_ctx* c, float max_err) {

@@ -123,92 +123,12 @@ void vo_guess_destroy(vo_ctx* c) {
   c->d_guess = nullptr;
 }
 
-// the seeded launch on q with the guesses in c->d_guess; fb: with the forward-backward check (k_klt_seeded_fb)
-static int32_t seeded_launch(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* counts, bool fb) {
-  c->fb_n = -1; c->guess_n = -1;
-  klt_args A;
-  { const int32_t r = vo_klt_make_args(c, n, prm, A); if (r != VO_OK) return r; }
-  if (n == 0) { if (fb) c->fb_n = 0; return VO_OK; }
-  VO_CHECK(c, c->d_guess, VO_E_STATE, "no guesses");
-  if (fb) {
-    { const int32_t r = vo_fb_reserve(c); if (r != VO_OK) return r; }
-    klt_fb_args F;
-    vo_klt_fb_make_args(c, A, F);
-    vo_prof_scope prof(c, q, VO_PROF_KLT);
-    hipLaunchKernelGGL(k_klt_seeded_fb<5>, dim3(n, c->batch), dim3(64), 0, q, A, F, vo_slab<const float>(c, off_in), c->d_guess, vo_guess_seq(c),
-                       vo_slab<float>(c, off_out), vo_slab<uint8_t>(c, c->off_status), vo_slab<float>(c, c->off_err), c->d_iters, counts, c->d_fb);
-  } else {
-    vo_prof_scope prof(c, q, VO_PROF_KLT);
-    hipLaunchKernelGGL(k_klt_seeded<5>, dim3(n, c->batch), dim3(64), 0, q, A, vo_slab<const float>(c, off_in), c->d_guess, vo_guess_seq(c),
-                       vo_slab<float>(c, off_out), vo_slab<uint8_t>(c, c->off_status), vo_slab<float>(c, c->off_err), c->d_iters, counts);
-  }
-  VO_HIP(c, hipGetLastError());
-  if (fb) c->fb_n = n;
-  return VO_OK;
-}
-
-static hipError_t rows_h2d(vo_ctx* c, uint8_t* d, size_t d_stride, const void* h, size_t row_bytes) {
-  return hipMemcpy2DAsync(d, d_stride, h, row_bytes, row_bytes, c->batch, hipMemcpyHostToDevice, c->stream);
-}
-static hipError_t rows_d2h(vo_ctx* c, void* h, const uint8_t* d, size_t d_stride, size_t row_bytes) {
-  return hipMemcpy2DAsync(h, row_bytes, d, d_stride, row_bytes, c->batch, hipMemcpyDeviceToHost, c->stream);
-}
-
-// the synchronous forms' common body; p0r / fb_err non-null: with the check
-static int32_t track_init(vo_ctx* c, const float* p0, const float* guess, int32_t n, const vo_klt_params* prm, float* p1, uint8_t* status,
-                          float* err, float* p0r, float* fb_err, int32_t* iters, bool fb) {
-  vo_klt_params def;
-  if (!prm) { vo_klt_default_params(&def); prm = &def; }
-  VO_CHECK(c, n >= 0 && n <= c->max_pts, VO_E_CAPACITY, "n exceeds max_pts");
-  if (n == 0) return VO_OK;
-  VO_CHECK(c, p0 && p1 && status && err && (!fb || (p0r && fb_err)), VO_E_INVALID, "null buffer");
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  { const int32_t rg = vo_guess_reserve(c); if (rg != VO_OK) return rg; }
-  const size_t off_in = vo_off_p(c), off_out = vo_off_p_next(c);
-  VO_HIP(c, rows_h2d(c, c->d_slab + off_in, c->slab_seq, p0, sizeof(float) * 2 * n));
-  VO_HIP(c, rows_h2d(c, reinterpret_cast<uint8_t*>(c->d_guess), vo_guess_seq(c), guess, sizeof(float) * 2 * n));
-  const int32_t r = seeded_launch(c, c->stream, n, prm, off_in, off_out, nullptr, fb);
-  if (r != VO_OK) return r;
-  VO_HIP(c, rows_d2h(c, p1, c->d_slab + off_out, c->slab_seq, sizeof(float) * 2 * n));
-  VO_HIP(c, rows_d2h(c, status, c->d_slab + c->off_status, c->slab_seq, n));
-  VO_HIP(c, rows_d2h(c, err, c->d_slab + c->off_err, c->slab_seq, sizeof(float) * n));
-  if (fb) {
-    VO_HIP(c, rows_d2h(c, p0r, c->d_fb, c->fb_seq, sizeof(float) * 2 * n));
-    VO_HIP(c, rows_d2h(c, fb_err, c->d_fb + c->fb_off_err, c->fb_seq, sizeof(float) * n));
-  }
-  if (iters) {
-    const size_t row = sizeof(int32_t) * (size_t)n * (prm->max_level + 1);
-    VO_HIP(c, rows_d2h(c, iters, reinterpret_cast<const uint8_t*>(c->d_iters), sizeof(int32_t) * (size_t)c->max_pts * VO_MAX_LEVELS, row));
-  }
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  return VO_OK;
-}
-
-extern "C" int32_t vo_klt_track_init(vo_ctx* c, const float* p0, const float* guess, int32_t n, const vo_klt_params* prm,
-                                     float* p1, uint8_t* status, float* err, int32_t* iters) {
-  if (!c) return VO_E_INVALID;
-  if (!guess) return vo_klt_track(c, p0, n, prm, p1, status, err, iters);
-  return track_init(c, p0, guess, n, prm, p1, status, err, nullptr, nullptr, iters, false);
-}
-
-extern "C" int32_t vo_klt_track_fb_init(vo_ctx* c, const float* p0, const float* guess, int32_t n, const vo_klt_params* prm, float* p1,
-                                        uint8_t* status, float* err, float* p0r, float* fb_err, int32_t* iters) {
-  if (!c) return VO_E_INVALID;
-  if (!guess) return vo_klt_track_fb(c, p0, n, prm, p1, status, err, p0r, fb_err, iters);
-  return track_init(c, p0, guess, n, prm, p1, status, err, p0r, fb_err, iters, true);
-}
-
-// the resident form (vo_tracks_track, the closed loop's TRACK stage) behind a predictor kernel on q
-int32_t vo_klt_track_resident_seeded(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts, bool fb) {
-  vo_klt_params def;
-  if (!prm) { vo_klt_default_params(&def); prm = &def; }
-  VO_CHECK(c, n >= 0 && n <= c->n_resident, VO_E_INVALID, "n exceeds the resident point set");
-  const int32_t r = seeded_launch(c, q, n, prm, vo_off_p(c), vo_off_p_next(c), d_counts, fb);
-  if (r != VO_OK) return r;
-  c->guess_n = n;     // the predictor's guesses of this track stay in c->d_guess (vo_klt_guess_read)
-  c->p_parity ^= 1;   // tracked positions become the resident set
-  return VO_OK;
+// the guesses are the rows of c->d_guess
+void vo_klt_launch_seeded(vo_ctx* c, const klt_launch_rows& L, const klt_args& A, const klt_fb_args* F) {
+  if (F) hipLaunchKernelGGL(k_klt_seeded_fb<5>, dim3(L.n, c->batch), dim3(64), 0, L.q, A, *F, L.p0, c->d_guess, vo_guess_seq(c), L.p1, L.status, L.err,
+                            c->d_iters, L.counts, c->d_fb);
+  else hipLaunchKernelGGL(k_klt_seeded<5>, dim3(L.n, c->batch), dim3(64), 0, L.q, A, L.p0, c->d_guess, vo_guess_seq(c), L.p1, L.status, L.err,
+                          c->d_iters, L.counts);
 }
 
 extern "C" int32_t vo_set_klt_predict(vo_ctx* c, int32_t mode) {
@@ -238,7 +158,7 @@ extern "C" int32_t vo_klt_guess_read(vo_ctx* c, float* guess, int32_t n) {
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   if (n > 0) {
     VO_CHECK(c, guess, VO_E_INVALID, "null buffer");
-    VO_HIP(c, rows_d2h(c, guess, reinterpret_cast<const uint8_t*>(c->d_guess), vo_guess_seq(c), sizeof(float) * 2 * n));
+    VO_HIP(c, rows_d2h(c, guess, c->d_guess, vo_guess_seq(c), sizeof(float) * 2 * n));
   }
   VO_HIP(c, hipStreamSynchronize(c->stream));
   return VO_OK;

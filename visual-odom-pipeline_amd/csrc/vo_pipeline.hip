@@ -1540,18 +1540,17 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
       const size_t fr = (size_t)c->width * c->height;
       r = vo_build_pyramid(c, tq, c->d_seq + (size_t)frame_idx * fr, fr * c->seq_n, nullptr);
     }
-    w->fb_active = vo_fb_on(c);                      // vo_set_fb_check: track with the forward-backward check
-    if (r == VO_OK && vo_predict_on(c)) {            // vo_set_klt_predict: the predictor right before the seeded tracker, on its stream
+    const unsigned form = vo_klt_form(c);            // vo_set_fb_check: track with the forward-backward check; vo_set_klt_predict: seeded
+    w->fb_active = form & KLT_FORM_FB;
+    if (r == VO_OK && (form & KLT_FORM_SEEDED)) {    // the predictor right before the seeded tracker, on its stream
       r = vo_guess_reserve(c);
       if (r == VO_OK && w->N > 0) {
         hipLaunchKernelGGL(k_pipe_predict, dim3(vo_div_up(w->N, 256), B), dim3(256), 0, tq, P, vo_slab<const float>(c, vo_off_p(c)), c->slab_seq,
                            c->d_guess, vo_guess_seq(c));
         if (hipGetLastError() != hipSuccess) r = vo_fail(c, VO_E_HIP, "pipe_step: k_pipe_predict launch");
       }
-      if (r == VO_OK) r = vo_klt_track_resident_seeded(c, tq, w->N, &prm.klt, w->d_dn + DN_PTS * B, w->fb_active);
     }
-    else if (r == VO_OK) r = w->fb_active ? vo_klt_track_resident_fb(c, tq, w->N, &prm.klt, w->d_dn + DN_PTS * B)
-                                          : vo_klt_track_resident_counts(c, tq, w->N, &prm.klt, w->d_dn + DN_PTS * B);
+    if (r == VO_OK) r = vo_klt_track_resident_enqueue(c, tq, w->N, &prm.klt, w->d_dn + DN_PTS * B, form);
     if (track_side) {                                  // joined on every path
       const hipError_t e1 = hipEventRecord(w->ev_track, c->stream2);
       const hipError_t e2 = hipStreamWaitEvent(c->stream, w->ev_track, 0);

@@ -84,7 +84,8 @@ static int32_t step_enqueue(vo_ctx* c, const step_cfg& s, const int32_t* d_frame
   // overlaps the chain's narrow tail groups, which run on the compute units stream A's CU mask leaves free (vo_set_side_stream)
   if (c->side_stream == 2 && s.do_ba && !d_frame_idx && c->ba_wide_groups > 0 && c->ba_wide_recorded)
     VO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_ba_wide[half ^ 1], 0));
-  r = vo_klt_track_resident_counts(c, c->stream, s.n_pts, &s.klt, c->d_pt_counts);     // (counts: non-null only while a vo_tracks_* table is seeded)
+  // the plain form whatever vo_set_fb_check / vo_set_klt_predict say: the fused frame step never runs the check or a predictor (no vo_klt_form here)
+  r = vo_klt_track_resident_enqueue(c, c->stream, s.n_pts, &s.klt, c->d_pt_counts, 0);     // (counts: non-null only while a vo_tracks_* table is seeded)
   if (r != VO_OK) return r;
   if (trace_a && c->side_stream == 2) trace_push(g_tb, c->stream, 6000);
   uint8_t* const h_dst = c->h_slab + (size_t)half * c->slab_bytes;

@@ -251,8 +251,9 @@ extern "C" int32_t vo_tracks_track(vo_ctx* c, int32_t t, const vo_klt_params* pr
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   vo_trk_ws* tw = c->trk;
-  const bool fb = vo_fb_on(c);           // vo_set_fb_check: the forward-backward check joins the keep rule
-  if (vo_predict_on(c)) {                // vo_set_klt_predict: the predictor right before the seeded tracker, on the same stream
+  const unsigned form = vo_klt_form(c);   // vo_set_fb_check: the forward-backward check joins the keep rule; vo_set_klt_predict: seeded
+  const bool fb = form & KLT_FORM_FB;
+  if (form & KLT_FORM_SEEDED) {          // the predictor right before the seeded tracker, on the same stream
     VO_CHECK(c, tw->n_hi <= c->n_resident, VO_E_INVALID, "n exceeds the resident point set");
     { const int32_t rg = vo_guess_reserve(c); if (rg != VO_OK) return rg; }
     if (tw->n_hi > 0) {
@@ -260,10 +261,9 @@ extern "C" int32_t vo_tracks_track(vo_ctx* c, int32_t t, const vo_klt_params* pr
                          vo_slab<const float>(c, vo_off_p(c)), c->slab_seq, t, tw->n_hi, c->d_guess, vo_guess_seq(c));
       VO_HIP(c, hipGetLastError());
     }
-    const int32_t r = vo_klt_track_resident_seeded(c, c->stream, tw->n_hi, prm, c->d_pt_counts, fb);
-    if (r != VO_OK) return r;
-  } else if (tw->n_hi > 0) {
-    const int32_t r = fb ? vo_klt_track_resident_fb(c, c->stream, tw->n_hi, prm, c->d_pt_counts) : vo_klt_track_resident(c, tw->n_hi, prm);
+  }
+  if ((form & KLT_FORM_SEEDED) || tw->n_hi > 0) {      // (an empty table skips the tracker unless it predicts: then the enqueue notes n = 0)
+    const int32_t r = vo_klt_track_resident_enqueue(c, c->stream, tw->n_hi, prm, c->d_pt_counts, form);
     if (r != VO_OK) return r;
   }
   hipLaunchKernelGGL(k_trk_extend, dim3(c->batch), dim3(1024), 0, c->stream, trk_make(tw), vo_slab<float>(c, vo_off_p(c)),
