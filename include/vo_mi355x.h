@@ -229,6 +229,39 @@ int32_t vo_clear_undistort(vo_ctx* ctx);
 int32_t vo_get_undistort(vo_ctx* ctx, int32_t* on, double K[4], double dist[8], double newK[4]);
 int32_t vo_undistort(vo_ctx* ctx, const uint8_t* img, int32_t stride, uint8_t* out);
 int32_t vo_undistort_map_read(vo_ctx* ctx, int16_t* sxy, uint16_t* frac, uint8_t* outside);
+/* Contrast-limited adaptive histogram equalisation of every frame entering the frame store: cv2.createCLAHE(clipLimit, tileGridSize)
+ * .apply(img) of OpenCV 4.4 (imgproc/clahe.cpp, 8-bit path, histSize 256), the usual answer of a VO front end to exposure and shadow changes
+ * that break the tracker's brightness constancy.  Not in the reference (its loaders do not equalise).  Off by default.  On, every ingest path
+ * -- vo_frame_push, vo_frame_push_resident, vo_frame_step_resident / _host, vo_pipe_step / _step_host -- runs kernels k_clahe_lut and
+ * k_clahe_apply in front of the level-0 kernel.  Order of the chain: undistortion (vo_set_undistort) -> CLAHE -> bilateral pre-filter
+ * (vo_set_prefilter) or plain level 0 -> pyramid.
+ * Definition (tests/clahe_model.py, bit for bit; a restatement -- no OpenCV source or binary was at hand, parity is with the model, as for
+ * use_harris and vo_set_undistort):
+ *   extension  w % tiles_x == 0 and h % tiles_y == 0: none.  Otherwise BOTH sides grow, by tiles_x - w % tiles_x columns and tiles_y - h % tiles_y
+ *              rows (an axis that divides still grows by a whole tiles_*: 1241 x 376 at 8 x 8 becomes 1248 x 384), BORDER_REFLECT_101.
+ *              tw = ext_w / tiles_x, th = ext_h / tiles_y, area = tw th.
+ *   clip       clip_limit > 0: max((int)(clip_limit * area / 256), 1) (double, truncated); clip_limit == 0: no clipping.
+ *   per tile   hist[256] over the tile of the extended image; clipped = sum of the excess above clip, bins cut; clipped / 256 added to every
+ *              bin; residual = clipped % 256 != 0: step = max(256 / residual, 1), bins 0, step, 2 step .. (residual of them) get one more;
+ *              lut[i] = clamp(rint((float)prefix_sum[i] * ((float)255 / (float)area)), 0, 255), rint = half to even.
+ *   per pixel  (x, y) of the original image, value v, float32, no fused multiply-add: txf = (float)x * (1.0f / tw) - 0.5f, tx1 = floor(txf),
+ *              xa = txf - tx1, xa1 = 1.0f - xa, then tx2 = min(tx1 + 1, tiles_x - 1), tx1 = max(tx1, 0); the same in y;
+ *              dst = clamp(rint((lut[ty1][tx1][v] xa1 + lut[ty1][tx2][v] xa) ya1 + (lut[ty2][tx1][v] xa1 + lut[ty2][tx2][v] xa) ya), 0, 255).
+ *   vo_set_clahe       (cv2.createCLAHE) waits for the context's streams, then replaces the setting.  VO_E_INVALID with nothing changed:
+ *                      clip_limit negative or not finite; tiles_x or tiles_y outside 1 .. 16; an extension that is not smaller than the image
+ *                      side on its axis (reflect-101 needs that).  Takes effect at the next enqueue; a captured frame step is never replayed
+ *                      with another setting.
+ *   vo_clear_clahe     off again.
+ *   vo_get_clahe       *on and the setting (zeros when off; any of the three may be NULL).
+ *   vo_clahe           (CLAHE::apply) synchronous: `batch` images in (rows of `stride` bytes) and out (tight) with the current setting; CLAHE
+ *                      alone, NOT the undistortion in front of it; the frame store and its frame count are untouched.  VO_E_STATE: off.
+ *   vo_clahe_lut_read  the tables the last launch (a frame entering the store, or vo_clahe) wrote: lut [batch][tiles_y][tiles_x][256] u8
+ *                      (zeros before the first launch of a setting).  VO_E_STATE: off. */
+int32_t vo_set_clahe(vo_ctx* ctx, double clip_limit, int32_t tiles_x, int32_t tiles_y);
+int32_t vo_clear_clahe(vo_ctx* ctx);
+int32_t vo_get_clahe(vo_ctx* ctx, int32_t* on, double* clip_limit, int32_t* tiles_x, int32_t* tiles_y);
+int32_t vo_clahe(vo_ctx* ctx, const uint8_t* img, int32_t stride, uint8_t* out);
+int32_t vo_clahe_lut_read(vo_ctx* ctx, uint8_t* lut);
 /* frames preloaded into HBM (bench: inputs resident before the timed region); frames: [batch][n_frames][h][w] */
 int32_t vo_seq_upload(vo_ctx* ctx, const uint8_t* frames, int32_t n_frames);
 int32_t vo_frame_push_resident(vo_ctx* ctx, int32_t frame_index);           /* async */
@@ -732,8 +765,10 @@ int32_t vo_step_layout(vo_ctx* ctx, int32_t* layout, int32_t* gate_groups, int32
 /* ---- in-stream timing (hipEvent pairs recorded on the ctx stream around a region's launches) -----
  * Used by bench.py for the roofline figure: region VO_PROF_KLT brackets exactly the k_klt_track launch.
  * vo_profile_read synchronises the stream and returns the summed elapsed time and the number of
- * recorded regions since vo_profile_enable(ctx, mask); mask = OR of (1 << region), 0 = off. */
-enum { VO_PROF_FRAME = 0, VO_PROF_KLT = 1, VO_PROF_ST = 2, VO_PROF_DLT = 3, VO_PROF_BA = 4, VO_PROF_COUNT = 5 };
+ * recorded regions since vo_profile_enable(ctx, mask); mask = OR of (1 << region), 0 = off.
+ * VO_PROF_CLAHE_LUT / VO_PROF_CLAHE_APPLY bracket the k_clahe_lut / k_clahe_apply launch of a pyramid build (inside its VO_PROF_FRAME bracket). */
+enum { VO_PROF_FRAME = 0, VO_PROF_KLT = 1, VO_PROF_ST = 2, VO_PROF_DLT = 3, VO_PROF_BA = 4, VO_PROF_CLAHE_LUT = 5, VO_PROF_CLAHE_APPLY = 6,
+       VO_PROF_COUNT = 7 };
 int32_t vo_profile_enable(vo_ctx* ctx, int32_t region_mask);
 int32_t vo_profile_read(vo_ctx* ctx, int32_t region, double* total_ms, int32_t* count);
 /* diagnostic: shader-clock stamps (s_memtime deltas, cycles) of the phases of the last launch of a

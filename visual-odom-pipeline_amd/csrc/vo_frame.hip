@@ -359,6 +359,7 @@ extern "C" int32_t vo_ctx_destroy(vo_ctx* c) {
   vo_guess_destroy(c);
   vo_subpix_destroy(c);
   vo_undistort_destroy(c);
+  vo_clahe_destroy(c);
   for (int f = 0; f < 2; f++)
     for (int l = 0; l < VO_MAX_LEVELS; l++) {
       if (c->fr[f].img[l]) (void)hipFree(c->fr[f].img[l]);
@@ -517,6 +518,11 @@ int32_t vo_build_pyramid(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, siz
     // vo_set_undistort: cv2.undistort first, into the tight staging image; level 0 (plain or bilateral) then reads that as its raw frame
     vo_undistort_enqueue(c, q, d_raw_img, raw_seq_stride, d_frame_idx, remap);
     d_raw_img = c->d_und; raw_seq_stride = (size_t)c->width * c->height; d_frame_idx = nullptr;
+  }
+  if (c->cl_on) {
+    // vo_set_clahe: cv2.createCLAHE(..).apply next (on the undistorted frame when that is on), into a staging image of its own
+    vo_clahe_enqueue(c, q, d_raw_img, raw_seq_stride, d_frame_idx, remap);
+    d_raw_img = c->d_clahe; raw_seq_stride = (size_t)c->width * c->height; d_frame_idx = nullptr;
   }
   {
     const vo_level& L = c->lv[0];

@@ -122,6 +122,14 @@ struct vo_ctx {
   uint64_t* d_und_tab = nullptr;
   uint8_t* d_und = nullptr;
   unsigned und_gen = 0;              // bumped by every vo_set_undistort / vo_clear_undistort: part of a captured step's key
+  // CLAHE (vo_clahe.hip): the setting of vo_set_clahe, the tables [batch][tiles_y][tiles_x][256] u8 the last launch wrote (room for 16 x 16
+  // tiles) and the tight [batch][h][w] staging image the level-0 kernels read instead of the raw frame -- allocated when first switched on
+  bool cl_on = false;
+  double cl_clip = 0.0;
+  int cl_tx = 0, cl_ty = 0;
+  uint8_t* d_clahe_lut = nullptr;
+  uint8_t* d_clahe = nullptr;
+  unsigned cl_gen = 0;               // bumped by every vo_set_clahe / vo_clear_clahe: part of a captured step's key
   // DLT inputs
   float* d_uv0 = nullptr; float* d_uv1 = nullptr;    // [batch][max_pts][2]
   vo_dlt_cam* d_dlt_cam = nullptr;   // [batch]
@@ -278,6 +286,10 @@ void vo_subpix_destroy(vo_ctx* c);
 // frames (k_pad_level0's triple) to c->d_und on q, and the level-0 kernel then reads that staging image
 void vo_undistort_enqueue(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx, int remap);
 void vo_undistort_destroy(vo_ctx* c);
+// CLAHE (vo_clahe.hip).  vo_clahe_enqueue: called by vo_build_pyramid with vo_set_clahe on, behind the undistortion hook: k_clahe_lut and
+// k_clahe_apply take the frames (k_pad_level0's triple) to c->d_clahe on q, and the level-0 kernel then reads that staging image
+void vo_clahe_enqueue(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx, int remap);
+void vo_clahe_destroy(vo_ctx* c);
 int32_t vo_shi_tomasi_resident_counts(vo_ctx* c, hipStream_t q, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm, const int32_t* d_counts,
                                       const int32_t* d_limit);
 

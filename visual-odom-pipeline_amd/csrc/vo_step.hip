@@ -180,7 +180,7 @@ static uint64_t step_signature(vo_ctx* c, const step_cfg& s) {
   auto mix = [&](const void* p, size_t n) { const unsigned char* b = static_cast<const unsigned char*>(p); for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; } };
   auto mix_i = [&](long long v) { mix(&v, sizeof(v)); };
   mix(&s, sizeof(s));                       // the caller zero-fills the struct, so padding bytes are defined
-  mix_i(c->p_parity); mix_i(c->dlt_n); mix_i(c->dlt_stats); mix_i(c->bil_maxk); mix_i(c->und_on ? 1 : 0); mix_i(c->und_gen); mix_i(c->ba_sharded); mix_i(c->side_stream);
+  mix_i(c->p_parity); mix_i(c->dlt_n); mix_i(c->dlt_stats); mix_i(c->bil_maxk); mix_i(c->und_on ? 1 : 0); mix_i(c->und_gen); mix_i(c->cl_on ? 1 : 0); mix_i(c->cl_gen); mix_i(c->ba_sharded); mix_i(c->side_stream);
   mix_i((long long)(uintptr_t)c->d_seq); mix_i(c->seq_n);
   mix_i((long long)(uintptr_t)c->d_uv0); mix_i((long long)(uintptr_t)c->d_dlt_cam);
   mix_i((long long)(uintptr_t)c->st); mix_i((long long)(uintptr_t)c->ba); mix_i((long long)(uintptr_t)c->d_pt_counts);

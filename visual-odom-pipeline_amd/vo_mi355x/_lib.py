@@ -134,6 +134,11 @@ SIGNATURES = {
     "vo_get_undistort": (C.c_int32, [_ctx, _i32p, _f64p, _f64p, _f64p]),
     "vo_undistort": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p]),
     "vo_undistort_map_read": (C.c_int32, [_ctx, _i16p, C.POINTER(C.c_uint16), _u8p]),
+    "vo_set_clahe": (C.c_int32, [_ctx, C.c_double, C.c_int32, C.c_int32]),
+    "vo_clear_clahe": (C.c_int32, [_ctx]),
+    "vo_get_clahe": (C.c_int32, [_ctx, _i32p, _f64p, _i32p, _i32p]),
+    "vo_clahe": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p]),
+    "vo_clahe_lut_read": (C.c_int32, [_ctx, _u8p]),
     "vo_seq_upload": (C.c_int32, [_ctx, _u8p, C.c_int32]),
     "vo_frame_push_resident": (C.c_int32, [_ctx, C.c_int32]),
     "vo_pyramid_level_size": (C.c_int32, [_ctx, C.c_int32, _i32p, _i32p]),

@@ -163,6 +163,63 @@ class VoContext:
         self._ck(self._L.vo_undistort_map_read(self._h, ptr(sxy, C.c_int16), ptr(frac, C.c_uint16), ptr(out, C.c_uint8)))
         return dict(sxy=sxy, frac=frac, outside=out)
 
+    @staticmethod
+    def _clahe_args(clahe):
+        """(clip_limit, (tiles_x, tiles_y)) -- cv2.createCLAHE's arguments -- or a dict with clip_limit / tiles -> (float, int, int)"""
+        if isinstance(clahe, dict):
+            unknown = set(clahe) - {"clip_limit", "tiles"}
+            if unknown:
+                raise ValueError("clahe: a dict with clip_limit and tiles, got keys %r" % sorted(clahe))
+            clahe = (clahe.get("clip_limit", 40.0), clahe.get("tiles", (8, 8)))
+        try:
+            clip, (tx, ty) = clahe
+            clip, tx, ty = float(clip), int(tx), int(ty)
+        except (TypeError, ValueError):
+            raise ValueError("clahe: (clip_limit, (tiles_x, tiles_y)), got %r" % (clahe,))
+        return clip, tx, ty
+
+    def set_clahe(self, clip_limit=40.0, tiles=(8, 8)):
+        """cv2.createCLAHE(clip_limit, tiles).apply(img) on every frame entering the frame store, behind the undistortion and in front of the
+        bilateral pre-filter (vo_set_clahe).  tiles = (tiles_x, tiles_y), 1 .. 16 each; clip_limit = 0: no clipping."""
+        clip, tx, ty = self._clahe_args((clip_limit, tiles))
+        self._ck(self._L.vo_set_clahe(self._h, clip, tx, ty))
+
+    def clear_clahe(self):
+        self._ck(self._L.vo_clear_clahe(self._h))
+
+    def get_clahe(self):
+        """-> None when off, else (clip_limit, (tiles_x, tiles_y))"""
+        on, tx, ty, clip = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+        self._ck(self._L.vo_get_clahe(self._h, C.byref(on), C.byref(clip), C.byref(tx), C.byref(ty)))
+        return (clip.value, (tx.value, ty.value)) if on.value else None
+
+    def clahe(self, img):
+        """CLAHE of `img` ([h, w] uint8, [batch, h, w] on a batched context) with the setting of set_clahe (vo_clahe): CLAHE alone, not the
+        undistortion in front of it; the frame store is not touched.  A view whose rows are `stride` >= w bytes apart (buf[..., :w] of a
+        C-contiguous buffer) is read in place."""
+        img = np.asarray(img)
+        if img.dtype != np.uint8:
+            raise ValueError("clahe: expected uint8")
+        h, w = self.height, self.width
+        stride = img.strides[-2] if img.ndim >= 2 else 0
+        rows_in_place = (img.shape == (self.batch, h, w) and img.strides == (h * stride, stride, 1)) or \
+                        (self.batch == 1 and img.shape == (h, w) and img.strides == (stride, 1))
+        if not (rows_in_place and stride >= w):
+            img, stride = self._in(img, np.uint8, (h, w)), w
+        out = np.empty((self.batch, h, w), np.uint8)
+        self._ck(self._L.vo_clahe(self._h, ptr(img, C.c_uint8), stride, ptr(out, C.c_uint8)))
+        return self._out(out)
+
+    def clahe_lut_read(self):
+        """the tables the last launch wrote (vo_clahe_lut_read): uint8 [tiles_y, tiles_x, 256] ([batch, ...] on a batched context)"""
+        g = self.get_clahe()
+        if g is None:
+            self._ck(self._L.vo_clahe_lut_read(self._h, None))               # the library's own refusal
+        tx, ty = g[1]
+        lut = np.empty((self.batch, ty, tx, 256), np.uint8)
+        self._ck(self._L.vo_clahe_lut_read(self._h, ptr(lut, C.c_uint8)))
+        return self._out(lut)
+
     def push_frame(self, img):
         img = np.asarray(img)
         if img.dtype != np.uint8:
@@ -599,7 +656,7 @@ class VoContext:
         return out
 
     # -- in-stream timing -----------------------------------------------------------------------
-    PROF_FRAME, PROF_KLT, PROF_ST, PROF_DLT, PROF_BA = range(5)
+    PROF_FRAME, PROF_KLT, PROF_ST, PROF_DLT, PROF_BA, PROF_CLAHE_LUT, PROF_CLAHE_APPLY = range(7)
 
     def profile_enable(self, regions=(0, 1, 2, 3, 4)):
         """regions: iterable of PROF_* ids to time with hipEvent pairs on the ctx stream; () switches timing off"""

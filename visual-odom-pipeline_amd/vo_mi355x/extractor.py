@@ -27,7 +27,7 @@ class DMatch:
 
 class Extractor:
     def __init__(self, cfg=None, min_kp_dist=10, ctx=None, device=0, max_pts=8192, lazy=None, lazy_backend=None, bidir="reference",
-                 predict="off", subpix=None, undistort=None):
+                 predict="off", subpix=None, undistort=None, clahe=None):
         """lazy (default: on unless VO_LAZY=0): once a frame has come through the reference's call order (pipeline.py:98-156) the state moves
         into device tables and the lists this class hands out are views of them (vo_mi355x/lazy.py); lazy_backend: test hook
         (ctx, K, params, width, height) -> backend, default the GPU one.  max_pts: keypoints per call AND the capacity of those tables (<= 8192).
@@ -48,7 +48,14 @@ class Extractor:
         plain path.
         undistort: None (default): images are tracked as given.  dict(K=, dist=[, new_K=]) -- cv2.undistort's arguments: the setting goes to
         this extractor's context (VoContext.set_undistort), so _im_prev and im_curr enter the frame store undistorted and extend_tracks /
-        extend_landmarks / extract work in the undistorted camera.  A lazy session serves only None."""
+        extend_landmarks / extract work in the undistorted camera.  A lazy session serves only None.
+        clahe: None (default): images are tracked as given.  (clip_limit, (tiles_x, tiles_y)) -- cv2.createCLAHE's arguments: the setting goes
+        to this extractor's context (VoContext.set_clahe), so _im_prev and im_curr enter the frame store equalised (behind the undistortion).
+        A lazy session serves only None."""
+        if clahe is not None:
+            from .context import VoContext
+            clahe = VoContext._clahe_args(clahe)
+        self._clahe = clahe
         if undistort is not None:
             unknown = set(undistort) - {"K", "dist", "new_K"}
             if unknown or "K" not in undistort:
@@ -95,10 +102,13 @@ class Extractor:
         return self._ctx
 
     def _apply_undistort(self, ctx):
-        """the setting goes to the context the frames are pushed to; None makes no call at all (a caller's context keeps what it has)"""
+        """the settings (undistort=, clahe=) go to the context the frames are pushed to; None makes no call at all (a caller's context keeps
+        what it has)"""
         u = self._undistort
         if u is not None:
             ctx.set_undistort(u["K"], u.get("dist"), u.get("new_K"))
+        if self._clahe is not None:
+            ctx.set_clahe(self._clahe[0], self._clahe[1:])
 
     def _push(self, img):
         img = np.ascontiguousarray(img, dtype=np.uint8)

@@ -786,6 +786,8 @@ def seed_after_adjust(adjuster, state, dead_l, dead_k, K, t_now):
         return None
     if getattr(ext, "_undistort", None) is not None:  # (a session's frames enter its own store as given; Extractor(undistort=...) stays plain)
         return None
+    if getattr(ext, "_clahe", None) is not None:      # (likewise Extractor(clahe=...))
+        return None
     if getattr(ext, "_predict", "off") != "off":      # (a session tracks from uv; Extractor(predict=...) stays on the plain path)
         return None
     prm = dict(ba_window=adjuster._window_size, ba_ftol=adjuster._ftol, ba_xtol=adjuster._xtol, ba_max_iters=adjuster._max_iters,

@@ -10,6 +10,10 @@ frame store's level-0 pass; bit-identical to the oracle's restatement, tests/tes
 A raw-camera set: optional `distortion` ((k1, k2, p1, p2[, k3[, k4, k5, k6]])) and `new_K` (3 x 3 or (fx, fy, cx, cy)) entries in the
 dataset's cfg row make getImage return bilateral(cv2.undistort(raw, K, distortion, None, new_K)) -- one push through the loader's private
 context with both settings on -- and getCamera return new_K when one is given.  Without the entries nothing changes.
+
+An optional `clahe` entry ((clip_limit, (tiles_x, tiles_y)), cv2.createCLAHE's arguments) equalises the frame in the same push, behind the
+undistortion and in front of the filter: getImage returns bilateral(clahe(undistort(raw))).  Like the two entries above it needs a dataset on
+disk to run and has no test of its own; the chain it switches on is the one tests/test_gpu_clahe.py checks on pushed frames.
 """
 from collections import namedtuple
 from pathlib import Path
@@ -89,6 +93,7 @@ class Loader:
         self._camera = lay.camera(base)
         self._distortion = cfg[name].get("distortion") if hasattr(cfg[name], "get") else None
         self._new_K = cfg[name].get("new_K") if self._distortion is not None else None
+        self._clahe = cfg[name].get("clahe") if hasattr(cfg[name], "get") else None
         if lay.poses is not None:
             top = np.loadtxt(str(base / lay.poses)).reshape(-1, 3, 4)
             self._poses = np.concatenate([top, np.broadcast_to([[[0.0, 0.0, 0.0, 1.0]]], (len(top), 1, 4))], axis=1)
@@ -117,13 +122,19 @@ class Loader:
     def getImage(self, id):
         raw = imread_gray(self._at(self.image_paths, id))
         c = self._prefilter_context(raw.shape)
-        if self._distortion is None:
+        if self._distortion is None and self._clahe is None:
             return c.bilateral(raw, PREFILTER["d"], PREFILTER["sigmaColor"], PREFILTER["sigmaSpace"])
-        c.set_undistort(self._camera, self._distortion, self._new_K)       # undistortion runs in front of the filter, in the same push
+        # undistortion, then CLAHE, run in front of the filter, in the same push
         try:
+            if self._distortion is not None:
+                c.set_undistort(self._camera, self._distortion, self._new_K)
+            if self._clahe is not None:
+                cl = c._clahe_args(self._clahe)
+                c.set_clahe(cl[0], cl[1:])
             return c.bilateral(raw, PREFILTER["d"], PREFILTER["sigmaColor"], PREFILTER["sigmaSpace"])
         finally:
             c.clear_undistort()
+            c.clear_clahe()
 
     def getRawImage(self, id, out=None):
         """the frame as decoded, WITHOUT the pre-filter -- for a context that applies it while the frame enters the frame store

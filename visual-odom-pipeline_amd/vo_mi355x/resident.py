@@ -58,11 +58,13 @@ class ResidentPipeline:
     (the default): integer corners, the reference's behaviour.
     undistort: dict(K=, dist=[, new_K=]) makes every frame the loop takes in -- step on an uploaded sequence, step_host, the caller's own
     push_frame -- pass through cv2.undistort first (the context's vo_set_undistort).  The geometry then works in the undistorted camera: the
-    pipeline's own K must equal new_K (K when new_K is absent), anything else raises ValueError.  None (the default): frames are used as given."""
+    pipeline's own K must equal new_K (K when new_K is absent), anything else raises ValueError.  None (the default): frames are used as given.
+    clahe: (clip_limit, (tiles_x, tiles_y)) -- cv2.createCLAHE's arguments -- makes every such frame pass through CLAHE (the context's
+    vo_set_clahe), behind the undistortion and in front of the bilateral pre-filter.  None (the default) switches a context's setting off."""
 
     def __init__(self, ctx, K, ba_window=4, min_track_length=3, mask_radius=7, max_new=1000, max_reproj_err=2.0, min_bearing_angle=0.5,
                  ba_max_iters=50, ba_budget=None, ba_ftol=1e-3, ba_xtol=1e-3, pnp_blind_batches=4, pnp_seed=0, min_kp_dist=7, resurrect=True,
-                 fb_max_error=np.inf, ba_loss='huber', ba_f_scale=1.0, klt_predict="off", subpix=None, undistort=None):
+                 fb_max_error=np.inf, ba_loss='huber', ba_f_scale=1.0, klt_predict="off", subpix=None, undistort=None, clahe=None):
         self.ctx, self._L = ctx, ctx._L
         B = ctx.batch
         K = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (B, 3, 3)))
@@ -96,6 +98,11 @@ class ResidentPipeline:
             ctx.set_undistort(undistort["K"], undistort.get("dist"), undistort.get("new_K"))
         elif ctx.get_undistort() is not None:
             ctx.clear_undistort()
+        if clahe is not None:
+            cl = ctx._clahe_args(clahe)
+            ctx.set_clahe(cl[0], cl[1:])
+        elif ctx.get_clahe() is not None:
+            ctx.clear_clahe()
         ctx._subpix_slots = p.st.max_corners if 0 < p.st.max_corners < 4096 else 4096
         self.N, self.R, self.B = ctx.max_pts, 4 * ctx.max_pts, B
         self.ba_window = ba_window
