@@ -199,7 +199,8 @@ int32_t vo_frame_push(vo_ctx* ctx, const uint8_t* img, int32_t stride);
 /* Loader pre-filter (SURVEY.md 8f "next" row 2): cv2.bilateralFilter(img, d=5, sigmaColor=1.5, sigmaSpace=1.5) that
  * Loader.getImage applies to every frame (src/loader/loader.py:16-20,86), fused into the kernel that writes pyramid
  * level 0, so a raw frame can be pushed as read from disk.  d = 0: off (default; the drop-in classes receive frames the
- * reference's loader has already filtered); d < 0: diameter from sigma_space as OpenCV does; diameter <= 7. */
+ * reference's loader has already filtered); d < 0: diameter from sigma_space as OpenCV does; diameter <= 7.  A captured frame step
+ * (vo_set_graph_mode) follows the setting: every accepted call gives the next step a new capture key. */
 int32_t vo_set_prefilter(vo_ctx* ctx, int32_t d, double sigma_color, double sigma_space);
 /* Lens undistortion of every frame entering the frame store: cv2.undistort(src, K, dist, None, newK) of OpenCV 4.4, i.e.
  * cv2.initUndistortRectifyMap (imgproc/undistort.cpp, no rectification, fixed-point map) followed by cv2.remap(INTER_LINEAR,

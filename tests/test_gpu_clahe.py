@@ -5,14 +5,13 @@ multiply-add behind them.  1. the tables and the synchronous call on the smalles
 paths (push_frame, push_frame_resident, the tracker and the detector), alone and with undistortion and the bilateral pre-filter around it;
 3. the fused frame steps with and without graph replay, the setting switched between steps; 4. the closed loop on every stream layout;
 5. the drop-in Extractor; 6. errors."""
-import copy
-
 import numpy as np
 import pytest
 
 import clahe_model as cm
-import pipe_helpers as ph
+import ingest_helpers as ih
 import undistort_model as um
+from ingest_helpers import H, W, code as _code, same_store as _same_store
 
 pytestmark = pytest.mark.gpu
 
@@ -76,12 +75,6 @@ def test_synchronous_call_leaves_the_frame_store_alone_and_skips_the_undistortio
 
 
 # ---- 2. the ingest paths --------------------------------------------------------------------------------------------------------------
-def _same_store(a, b, seq=0, which=1, levels=3):
-    for l in range(levels):
-        xa, xb = a.pyramid_read(which, l, seq=seq), b.pyramid_read(which, l, seq=seq)
-        assert np.array_equal(xa[0], xb[0]) and np.array_equal(xa[1], xb[1]), (seq, which, l)
-
-
 @pytest.mark.parametrize("w,h,tiles", [SHAPES[1], SHAPES[2], SHAPES[5]], ids=[IDS[1], IDS[2], IDS[5]])
 def test_pushed_frames_enter_the_store_equalised(w, h, tiles):
     from vo_mi355x import VoContext
@@ -180,29 +173,12 @@ def test_fused_steps_see_equalised_frames_and_every_change_of_the_setting(host, 
     order = [1, 2, 3, 2, 1, 2, 3, 2, 1]
     pts = syn.grid_points(n, w, h, seed=4)
     fed = [frames[f] if s is None else cm.clahe(frames[f], s[0], s[1]) for f, s in zip(order, plan)]
-    with VoContext(w, h, max_pts=512) as a, VoContext(w, h, max_pts=512) as b:
-        for c in (a, b):
-            c.set_graph_mode(graph)
-            c.points_upload(pts)
-        a.upload_sequence(frames)
-        a.push_frame_resident(0); b.push_frame(frames[0])
-        cur = None
-        for k, (f, s) in enumerate(zip(order, plan)):
-            if s != cur:
-                a.clear_clahe() if s is None else a.set_clahe(*s)
-                cur = s
-            if host:
-                a.frame_step_host(frames[f].copy(), n, do_dlt=False, do_ba=False)
-            else:
-                a.frame_step_resident(f, n, do_dlt=False, do_ba=False)
-            b.frame_step_host(fed[k], n, do_dlt=False, do_ba=False)
-            ga, gb = a.frame_fetch(), b.frame_fetch()
-            for key in ("points2d", "status", "err", "corners"):
-                assert np.array_equal(ga[key], gb[key]), (k, f, s, key)
-            _same_store(a, b)
+    with ih.fused_pair(w, h, frames, pts, graph, graph, frames[0]) as (a, b):
+        def after(k, f, s):
             assert np.array_equal(a.pyramid_read(1, 0)[0], fed[k]), k
             if s is not None:
                 assert np.array_equal(a.clahe_lut_read(), cm.luts(frames[f], s[0], s[1])), k
+        ih.fused_plan(a, b, frames, order, plan, fed, n, host, lambda s: a.clear_clahe() if s is None else a.set_clahe(*s), after)
 
 
 def test_fused_steps_with_undistortion_and_the_bilateral_filter_around_it():
@@ -229,62 +205,24 @@ def test_fused_steps_with_undistortion_and_the_bilateral_filter_around_it():
 
 
 # ---- 4. the closed loop ---------------------------------------------------------------------------------------------------------------
-W, H, T1 = 256, 160, 3
 LOOP_CLAHE = (3.0, (5, 3))                                                 # 256 % 5 and 160 % 3 both leave a remainder
 
 
 @pytest.fixture(scope="module")
 def loop_scene():
-    from vo_mi355x import VoContext
-    sc = ph.scene(T1 + 8, w=W, h=H, f=260.0, seed=2024, pose_fn=lambda t: ph.sway_pose(t, period=24.0))
-    with VoContext(W, H, max_pts=1024) as boot:
-        state, t1 = ph.gt_bootstrap(boot, sc, 0, T1)
-    assert t1 == T1
-    eq = np.stack([cm.clahe(f, *LOOP_CLAHE) for f in sc["frames"]])
-    assert (eq != sc["frames"]).mean() > 0.2
-    return sc, state, eq
+    return ih.loop_scene(lambda f, sc: cm.clahe(f, *LOOP_CLAHE))
 
 
 @pytest.mark.parametrize("side,inflight", [(True, 1), (False, 1), (True, 4)], ids=["side", "one_stream", "side_inflight"])
 @pytest.mark.parametrize("host", [False, True], ids=["step", "step_host"])
 def test_closed_loop_equals_a_loop_fed_the_models_frames(loop_scene, host, side, inflight):
-    from vo_mi355x import VoContext
-    from vo_mi355x.resident import INFLIGHT, ResidentPipeline
-    assert inflight <= INFLIGHT
     sc, state, eq = loop_scene
-    n = 4
-
-    def run(frames, **kw):
-        with VoContext(W, H, max_pts=1024) as c:
-            c.set_side_stream(side)
-            rp = ResidentPipeline(c, sc["K"], ba_max_iters=12, pnp_blind_batches=8, **kw)
-            assert (c.get_clahe() is not None) == bool(kw)
-            rp.seed(copy.deepcopy(state), [], [], 1)
-            c.upload_sequence(frames)
-            c.push_frame_resident(T1)
-            recs, pending = [], 0
-            for s in range(n):
-                if host:
-                    rp.step_host(frames[T1 + 1 + s].copy())
-                else:
-                    rp.step(T1 + 1 + s)
-                pending += 1
-                if pending == inflight or s == n - 1:
-                    while pending:
-                        recs.append(rp.fetch()); pending -= 1
-            return recs, rp.read_tables(), [c.pyramid_read(1, l) for l in range(3)]
-
-    ra, Ta, pa = run(sc["frames"], clahe=LOOP_CLAHE)
-    rb, Tb, pb = run(eq)
+    run_a = ih.run_loop(sc, state, sc["frames"], host, side, inflight, "get_clahe", clahe=LOOP_CLAHE)
+    run_b = ih.run_loop(sc, state, eq, host, side, inflight, "get_clahe")
+    ra = run_a[0]
     print("closed loop with CLAHE: status %s, tracked %s" % ([r["status"] for r in ra], [r["n_tracked"] for r in ra]))
     assert sum(r["n_tracked"] for r in ra) > 0                             # the comparison below is not of two empty loops
-    for s, (x, y) in enumerate(zip(ra, rb)):
-        for k, v in x.items():
-            assert (np.array_equal(y[k], v, equal_nan=True) if isinstance(v, np.ndarray) else y[k] == v), (s, k)
-    for name in Ta:
-        assert np.array_equal(Ta[name], Tb[name], equal_nan=Ta[name].dtype.kind == "f"), name
-    for x, y in zip(pa, pb):
-        assert np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1])
+    ih.same_loop(run_a, run_b)
 
 
 def test_pipeline_argument_sets_and_clears_the_contexts_setting(loop_scene):
@@ -327,13 +265,6 @@ def test_dropin_extractor_tracks_on_equalised_images():
 
 
 # ---- 6. argument and state errors -----------------------------------------------------------------------------------------------------
-def _code(fn):
-    from vo_mi355x import VoError
-    with pytest.raises(VoError) as ei:
-        fn()
-    return ei.value.code
-
-
 def test_every_refusal_leaves_the_setting_and_the_next_frame_as_they_were():
     from vo_mi355x import VoContext
     w, h = 16, 9

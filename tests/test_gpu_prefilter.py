@@ -1,7 +1,10 @@
 """GPU: the loader's bilateral pre-filter fused into the level-0 kernel is bit-identical to the
-oracle's cv2.bilateralFilter restatement, for pushed and resident frames, and the rest of the path sees the filtered image."""
+oracle's cv2.bilateralFilter restatement, for pushed and resident frames, and the rest of the path sees the filtered image; a fused frame
+step, captured or not, follows every change of the setting."""
 import numpy as np
 import pytest
+
+import ingest_helpers as ih
 
 pytestmark = pytest.mark.gpu
 
@@ -60,3 +63,28 @@ def test_prefilter_feeds_pyramid_klt_and_resident_batch():
                 assert np.array_equal(img_l, lv[l]) and np.array_equal(der_l, o.scharr(lv[l]))
             q1, qs, qe = o.klt(f0, f1, pts)
             assert np.array_equal(p1[b], q1) and np.array_equal(st[b], qs) and np.array_equal(err[b], qe)
+
+
+@pytest.mark.parametrize("graph", [False, True], ids=["launches", "graph"])
+def test_fused_steps_see_every_change_of_the_prefilter(graph):
+    """a context that steps over an uploaded sequence, with graph replay or without, against one fed the same raw frames through
+    frame_step_host (plain launches always), both given the same setting before each step.  A captured step holds the tap list and its
+    spatial weights by value: A and B have the same 13 taps and other weights, so a captured A step replayed under B shows A's image.  C
+    changes the colour table alone, which the kernel reads from device memory: a control.  Every setting sees both store parities, A twice
+    (capture, then replay).  The oracle's shares of differing level-0 pixels on these frames: A / B 0.099 .. 0.101, A / C 0.863 .. 0.865."""
+    import vo_oracle as o
+    from vo_mi355x import synthetic as syn
+    w, h, n = 320, 240, 300
+    A, B, C = (5, 1.5, 1.5), (5, 1.5, 4.0), (5, 30.0, 1.5)
+    plan = [A, A, A, A, B, B, C, C, None, A]
+    order = [1, 2, 3, 2, 1, 2, 3, 2, 1, 2]
+    frames, _ = syn.make_sequence(4, w=w, h=h, seed=21, margin=64)
+    pts = syn.grid_points(n, w, h, seed=4)
+    for f in (1, 2, 3):
+        fa = o.bilateral(frames[f], *A)
+        assert (fa != o.bilateral(frames[f], *B)).mean() > 0.05 and (fa != o.bilateral(frames[f], *C)).mean() > 0.4
+    with ih.fused_pair(w, h, frames, pts, graph, False, frames[0]) as (a, b):
+        def apply(s):
+            for c in (a, b):
+                c.set_prefilter(0) if s is None else c.set_prefilter(*s)
+        ih.fused_plan(a, b, frames, order, plan, [frames[f] for f in order], n, False, apply)

@@ -3,13 +3,12 @@
 Every comparison with the model is exact: one float64 map on the host, integers behind it.  1. the table; 2. the synchronous call; 3. the
 ingest paths (push_frame, push_frame_resident, with the bilateral pre-filter, the tracker); 4. the fused frame steps with and without graph
 replay, coefficients switched between steps; 5. the closed loop on every stream layout; 6. the drop-in Extractor; 7. errors."""
-import copy
-
 import numpy as np
 import pytest
 
-import pipe_helpers as ph
+import ingest_helpers as ih
 import undistort_model as um
+from ingest_helpers import H, W, code as _code
 
 pytestmark = pytest.mark.gpu
 
@@ -163,89 +162,32 @@ def test_fused_steps_see_undistorted_frames_and_every_change_of_the_setting(host
     order = [1, 2, 3, 2, 1, 2, 3, 2, 1]
     pts = syn.grid_points(n, w, h, seed=4)
     fed = [frames[f] if s is None else um.undistort(frames[f], cam, s[0], s[1]) for f, s in zip(order, plan)]
-    with VoContext(w, h, max_pts=512) as a, VoContext(w, h, max_pts=512) as b:
-        for c in (a, b):
-            c.set_graph_mode(graph)
-            c.points_upload(pts)
-        a.upload_sequence(frames)
-        a.push_frame_resident(0); b.push_frame(frames[0])
-        cur = None
-        for k, (f, s) in enumerate(zip(order, plan)):
-            if s != cur:
-                a.clear_undistort() if s is None else a.set_undistort(cam, s[0], s[1])
-                cur = s
-            if host:
-                a.frame_step_host(frames[f].copy(), n, do_dlt=False, do_ba=False)
-            else:
-                a.frame_step_resident(f, n, do_dlt=False, do_ba=False)
-            b.frame_step_host(fed[k], n, do_dlt=False, do_ba=False)
-            ga, gb = a.frame_fetch(), b.frame_fetch()
-            want = (gb["points2d"], gb["status"], gb["err"], gb["corners"])
-            for x, y in zip((ga["points2d"], ga["status"], ga["err"], ga["corners"]), want):
-                assert np.array_equal(x, y), (k, f, s)
-            for l in range(3):
-                xa, xb = a.pyramid_read(1, l), b.pyramid_read(1, l)
-                assert np.array_equal(xa[0], xb[0]) and np.array_equal(xa[1], xb[1]), (k, l)
+    with ih.fused_pair(w, h, frames, pts, graph, graph, frames[0]) as (a, b):
+        def after(k, f, s):
             assert np.array_equal(a.pyramid_read(1, 0)[0], fed[k]), k
+        ih.fused_plan(a, b, frames, order, plan, fed, n, host, lambda s: a.clear_undistort() if s is None else a.set_undistort(cam, s[0], s[1]),
+                      after)
 
 
 # ---- 5. the closed loop -------------------------------------------------------------------------------------------------------------------
-W, H, T1 = 256, 160, 3
 LOOP_DIST = (-0.02, 0.004, 0.0003, -0.0002)          # about a pixel at the corners: the rendered scene's geometry survives it
 
 
 @pytest.fixture(scope="module")
 def loop_scene():
-    from vo_mi355x import VoContext
-    sc = ph.scene(T1 + 8, w=W, h=H, f=260.0, seed=2024, pose_fn=lambda t: ph.sway_pose(t, period=24.0))
-    with VoContext(W, H, max_pts=1024) as boot:
-        state, t1 = ph.gt_bootstrap(boot, sc, 0, T1)
-    assert t1 == T1
-    und = np.stack([um.undistort(f, sc["K"], LOOP_DIST) for f in sc["frames"]])
-    assert (und != sc["frames"]).mean() > 0.2
-    return sc, state, und
+    return ih.loop_scene(lambda f, sc: um.undistort(f, sc["K"], LOOP_DIST))
 
 
 @pytest.mark.parametrize("side,inflight", [(True, 1), (False, 1), (True, 4)], ids=["side", "one_stream", "side_inflight"])
 @pytest.mark.parametrize("host", [False, True], ids=["step", "step_host"])
 def test_closed_loop_equals_a_loop_fed_the_models_frames(loop_scene, host, side, inflight):
-    from vo_mi355x import VoContext
-    from vo_mi355x.resident import INFLIGHT, ResidentPipeline
-    assert inflight <= INFLIGHT
     sc, state, und = loop_scene
-    n = 4
-
-    def run(frames, **kw):
-        with VoContext(W, H, max_pts=1024) as c:
-            c.set_side_stream(side)
-            rp = ResidentPipeline(c, sc["K"], ba_max_iters=12, pnp_blind_batches=8, **kw)
-            assert (c.get_undistort() is not None) == bool(kw)
-            rp.seed(copy.deepcopy(state), [], [], 1)
-            c.upload_sequence(frames)
-            c.push_frame_resident(T1)
-            recs, pending = [], 0
-            for s in range(n):
-                if host:
-                    rp.step_host(frames[T1 + 1 + s].copy())
-                else:
-                    rp.step(T1 + 1 + s)
-                pending += 1
-                if pending == inflight or s == n - 1:
-                    while pending:
-                        recs.append(rp.fetch()); pending -= 1
-            return recs, rp.read_tables(), [c.pyramid_read(1, l) for l in range(3)]
-
-    ra, Ta, pa = run(sc["frames"], undistort=dict(K=sc["K"], dist=LOOP_DIST))
-    rb, Tb, pb = run(und)
+    run_a = ih.run_loop(sc, state, sc["frames"], host, side, inflight, "get_undistort", undistort=dict(K=sc["K"], dist=LOOP_DIST))
+    run_b = ih.run_loop(sc, state, und, host, side, inflight, "get_undistort")
+    ra = run_a[0]
     assert sum(r["n_tracked"] for r in ra) > 100
     print("closed loop with undistortion: status %s, tracked %s" % ([r["status"] for r in ra], [r["n_tracked"] for r in ra]))
-    for s, (x, y) in enumerate(zip(ra, rb)):
-        for k, v in x.items():
-            assert (np.array_equal(y[k], v, equal_nan=True) if isinstance(v, np.ndarray) else y[k] == v), (s, k)
-    for name in Ta:
-        assert np.array_equal(Ta[name], Tb[name], equal_nan=Ta[name].dtype.kind == "f"), name
-    for x, y in zip(pa, pb):
-        assert np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1])
+    ih.same_loop(run_a, run_b)
 
 
 def test_pipeline_camera_must_be_the_undistorted_camera(loop_scene):
@@ -294,13 +236,6 @@ def test_dropin_extractor_tracks_on_undistorted_images():
 
 
 # ---- 7. argument and state errors -------------------------------------------------------------------------------------------------------------
-def _code(fn):
-    from vo_mi355x import VoError
-    with pytest.raises(VoError) as ei:
-        fn()
-    return ei.value.code
-
-
 def _raw_set(c, K4, dist, n_dist, new_K):
     import ctypes as C
     arr = lambda v: None if v is None else (C.c_double * len(v))(*v)

@@ -187,13 +187,7 @@ static bool cl_geometry(int w, int h, double clip_limit, int tiles_x, int tiles_
   return true;
 }
 
-void vo_clahe_destroy(vo_ctx* c) {
-  if (c->d_clahe) (void)hipFree(c->d_clahe);
-  if (c->d_clahe_lut) (void)hipFree(c->d_clahe_lut);
-  c->d_clahe = nullptr; c->d_clahe_lut = nullptr; c->cl_on = false;
-}
-
-// vo_build_pyramid's hook (cl_on): the raw (or undistorted) frames -> c->d_clahe on q
+// the stage's enqueue (vo_build_pyramid's chain, vo_ingest_run): the raw (or undistorted) frames -> c->d_clahe on q
 void vo_clahe_enqueue(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx, int remap) {
   const int w = c->width, h = c->height;
   cl_geom g;
@@ -210,14 +204,6 @@ void vo_clahe_enqueue(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t
   }
 }
 
-// every stream of the context that may still run a pyramid build with the present setting
-static int32_t cl_sync_all(vo_ctx* c) {
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->stream2) VO_HIP(c, hipStreamSynchronize(c->stream2));
-  if (c->stream3) VO_HIP(c, hipStreamSynchronize(c->stream3));
-  return VO_OK;
-}
-
 extern "C" int32_t vo_set_clahe(vo_ctx* c, double clip_limit, int32_t tiles_x, int32_t tiles_y) {
   if (!c) return VO_E_INVALID;
   VO_CHECK(c, isfinite(clip_limit) && clip_limit >= 0.0, VO_E_INVALID, "clip_limit must be finite and >= 0");
@@ -226,23 +212,23 @@ extern "C" int32_t vo_set_clahe(vo_ctx* c, double clip_limit, int32_t tiles_x, i
   VO_CHECK(c, cl_geometry(c->width, c->height, clip_limit, tiles_x, tiles_y, g), VO_E_INVALID,
            "the reflect-101 extension to whole tiles is not smaller than the image");
   VO_HIP(c, hipSetDevice(c->device));
-  const size_t px = (size_t)c->width * c->height;
   const size_t lut_bytes = (size_t)c->batch * CL_MAX_TILES * CL_MAX_TILES * 256;      // room for every accepted grid
-  if (!c->d_clahe) VO_HIP(c, hipMalloc((void**)&c->d_clahe, px * (size_t)c->batch));
+  int32_t r = vo_ingest_reserve(c, &c->d_clahe);
+  if (r != VO_OK) return r;
   if (!c->d_clahe_lut) VO_HIP(c, hipMalloc((void**)&c->d_clahe_lut, lut_bytes));
-  { const int32_t rs = cl_sync_all(c); if (rs != VO_OK) return rs; }     // no build in flight runs with the setting that is replaced
+  r = vo_sync_streams(c);                                                // no build in flight runs with the setting that is replaced
+  if (r != VO_OK) return r;
   VO_HIP(c, hipMemsetAsync(c->d_clahe_lut, 0, lut_bytes, c->stream));    // vo_clahe_lut_read before the first launch of a setting: zeros
-  VO_HIP(c, hipStreamSynchronize(c->stream));
+  r = vo_ingest_commit(c, &c->cl_on);
+  if (r != VO_OK) return r;
   c->cl_clip = clip_limit; c->cl_tx = tiles_x; c->cl_ty = tiles_y;
-  c->cl_on = true;
-  c->cl_gen++;
   return VO_OK;
 }
 
 extern "C" int32_t vo_clear_clahe(vo_ctx* c) {
   if (!c) return VO_E_INVALID;
   c->cl_on = false;                  // enqueued builds have their launches; the buffers stay for the next vo_set_clahe
-  c->cl_gen++;
+  c->ingest_gen++;
   return VO_OK;
 }
 
@@ -255,21 +241,10 @@ extern "C" int32_t vo_get_clahe(vo_ctx* c, int32_t* on, double* clip_limit, int3
   return VO_OK;
 }
 
-// img, out: `batch` images, [batch][height] rows of `stride` (in) / width (out) bytes.  CLAHE alone: not the undistortion in front of it
+// CLAHE alone: not the undistortion in front of it
 extern "C" int32_t vo_clahe(vo_ctx* c, const uint8_t* img, int32_t stride, uint8_t* out) {
   if (!c) return VO_E_INVALID;
-  VO_CHECK(c, img != nullptr && out != nullptr && stride >= c->width, VO_E_INVALID, "bad image / stride");
-  VO_CHECK(c, c->cl_on, VO_E_STATE, "no CLAHE set (vo_set_clahe)");
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  // c->d_raw is vo_frame_push's staging: everything that reads it was enqueued on the ctx stream before this copy
-  const size_t rows = (size_t)c->height * c->batch, px = (size_t)c->width * c->height;
-  VO_HIP(c, hipMemcpy2DAsync(c->d_raw, c->width, img, stride, c->width, rows, hipMemcpyHostToDevice, c->stream));
-  vo_clahe_enqueue(c, c->stream, c->d_raw, px, nullptr, 0);
-  VO_HIP(c, hipGetLastError());
-  VO_HIP(c, hipMemcpyAsync(out, c->d_clahe, px * (size_t)c->batch, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  return VO_OK;
+  return vo_ingest_run(c, {c->cl_on, vo_clahe_enqueue, c->d_clahe}, "no CLAHE set (vo_set_clahe)", img, stride, out);
 }
 
 // lut: [batch][tiles_y][tiles_x][256] of the current setting, as the last launch wrote it

@@ -358,8 +358,8 @@ extern "C" int32_t vo_ctx_destroy(vo_ctx* c) {
   vo_fb_destroy(c);
   vo_guess_destroy(c);
   vo_subpix_destroy(c);
-  vo_undistort_destroy(c);
-  vo_clahe_destroy(c);
+  vo_ingest_free(&c->und_on, &c->d_und, (void**)&c->d_und_tab);
+  vo_ingest_free(&c->cl_on, &c->d_clahe, (void**)&c->d_clahe_lut);
   for (int f = 0; f < 2; f++)
     for (int l = 0; l < VO_MAX_LEVELS; l++) {
       if (c->fr[f].img[l]) (void)hipFree(c->fr[f].img[l]);
@@ -498,9 +498,7 @@ extern "C" int32_t vo_ctx_create_batched(int32_t device, int32_t width, int32_t 
 extern "C" int32_t vo_sync(vo_ctx* c) {
   if (!c) return VO_E_INVALID;
   VO_HIP(c, hipSetDevice(c->device));
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->stream2) VO_HIP(c, hipStreamSynchronize(c->stream2));     // branches of a frame step that has not been fetched
-  if (c->stream3) VO_HIP(c, hipStreamSynchronize(c->stream3));
+  { const int32_t rs = vo_sync_streams(c); if (rs != VO_OK) return rs; }   // stream2 / stream3: branches of a frame step that has not been fetched
   if (c->stream_h2d) VO_HIP(c, hipStreamSynchronize(c->stream_h2d));
   return VO_OK;
 }
@@ -508,22 +506,54 @@ extern "C" int32_t vo_sync(vo_ctx* c) {
 // ------------------------------------------------------------------------------------------------
 // frames
 // ------------------------------------------------------------------------------------------------
+// ---- what the ingest stages' entry points share (vo_internal.h) ----
+int32_t vo_ingest_reserve(vo_ctx* c, uint8_t** staging) {
+  if (!*staging) VO_HIP(c, hipMalloc((void**)staging, (size_t)c->width * c->height * c->batch));
+  return VO_OK;
+}
+
+int32_t vo_ingest_commit(vo_ctx* c, bool* on) {
+  VO_HIP(c, hipStreamSynchronize(c->stream));
+  *on = true;
+  c->ingest_gen++;
+  return VO_OK;
+}
+
+void vo_ingest_free(bool* on, uint8_t** staging, void** table) {
+  if (*staging) (void)hipFree(*staging);
+  if (*table) (void)hipFree(*table);
+  *staging = nullptr; *table = nullptr; *on = false;
+}
+
+int32_t vo_ingest_run(vo_ctx* c, const vo_ingest_stage& s, const char* off_msg, const uint8_t* img, int32_t stride, uint8_t* out) {
+  VO_CHECK(c, img != nullptr && out != nullptr && stride >= c->width, VO_E_INVALID, "bad image / stride");
+  VO_CHECK(c, s.on, VO_E_STATE, off_msg);
+  VO_HIP(c, hipSetDevice(c->device));
+  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
+  // c->d_raw is vo_frame_push's staging: everything that reads it was enqueued on the ctx stream before this copy
+  const size_t rows = (size_t)c->height * c->batch, px = (size_t)c->width * c->height;
+  VO_HIP(c, hipMemcpy2DAsync(c->d_raw, c->width, img, stride, c->width, rows, hipMemcpyHostToDevice, c->stream));
+  s.enqueue(c, c->stream, c->d_raw, px, nullptr, 0);
+  VO_HIP(c, hipGetLastError());
+  VO_HIP(c, hipMemcpyAsync(out, s.staging, px * (size_t)c->batch, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP(c, hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
 int32_t vo_build_pyramid(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx) {
   vo_prof_scope prof(c, q, VO_PROF_FRAME);
   c->cur ^= 1;
   vo_frame& F = c->fr[c->cur];
   const int B = c->batch;
   const int remap = (!c->tune.xcd_remap_off && B % 8 == 0) ? 1 : 0;       // every sequence's frame chain on one XCD (vo_xcd_assign)
-  if (c->und_on) {
-    // vo_set_undistort: cv2.undistort first, into the tight staging image; level 0 (plain or bilateral) then reads that as its raw frame
-    vo_undistort_enqueue(c, q, d_raw_img, raw_seq_stride, d_frame_idx, remap);
-    d_raw_img = c->d_und; raw_seq_stride = (size_t)c->width * c->height; d_frame_idx = nullptr;
-  }
-  if (c->cl_on) {
-    // vo_set_clahe: cv2.createCLAHE(..).apply next (on the undistorted frame when that is on), into a staging image of its own
-    vo_clahe_enqueue(c, q, d_raw_img, raw_seq_stride, d_frame_idx, remap);
-    d_raw_img = c->d_clahe; raw_seq_stride = (size_t)c->width * c->height; d_frame_idx = nullptr;
-  }
+  // the ingest chain, in this order: cv2.undistort, then cv2.createCLAHE(..).apply, each into a tight staging image of its own (with both on,
+  // CLAHE reads d_und and writes d_clahe); level 0 (plain or bilateral) then reads the last stage's image as its raw frame
+  const vo_ingest_stage chain[2] = {{c->und_on, vo_undistort_enqueue, c->d_und}, {c->cl_on, vo_clahe_enqueue, c->d_clahe}};
+  for (const vo_ingest_stage& s : chain)
+    if (s.on) {
+      s.enqueue(c, q, d_raw_img, raw_seq_stride, d_frame_idx, remap);
+      d_raw_img = s.staging; raw_seq_stride = (size_t)c->width * c->height; d_frame_idx = nullptr;
+    }
   {
     const vo_level& L = c->lv[0];
     dim3 grid(vo_div_up(((L.w + 2 * VO_PAD + 15) / 16) * L.ph, 256), 1, B);   // 16 columns per thread, flat (row, group) index
@@ -585,9 +615,7 @@ extern "C" int32_t vo_seq_upload(vo_ctx* c, const uint8_t* frames, int32_t n_fra
   if (!c) return VO_E_INVALID;
   VO_CHECK(c, frames != nullptr && n_frames > 0, VO_E_INVALID, "bad sequence");
   VO_HIP(c, hipSetDevice(c->device));
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->stream2) VO_HIP(c, hipStreamSynchronize(c->stream2));
-  if (c->stream3) VO_HIP(c, hipStreamSynchronize(c->stream3));
+  { const int32_t rs = vo_sync_streams(c); if (rs != VO_OK) return rs; }
   if (c->d_seq) { VO_HIP(c, hipFree(c->d_seq)); c->d_seq = nullptr; c->seq_n = 0; }
   const size_t bytes = (size_t)c->width * c->height * n_frames * c->batch;
   VO_HIP(c, hipMalloc((void**)&c->d_seq, bytes));
@@ -640,7 +668,7 @@ extern "C" int32_t vo_pyramid_read_seq(vo_ctx* c, int32_t seq, int32_t which, in
 // the weight tables are built exactly like OpenCV 4.4 bilateralFilter_8u does (double exp rounded to float).
 extern "C" int32_t vo_set_prefilter(vo_ctx* c, int32_t d, double sigma_color, double sigma_space) {
   if (!c) return VO_E_INVALID;
-  if (d == 0) { c->bil_maxk = 0; return VO_OK; }
+  if (d == 0) { c->bil_maxk = 0; c->ingest_gen++; return VO_OK; }
   if (sigma_color <= 0) sigma_color = 1;
   if (sigma_space <= 0) sigma_space = 1;
   int radius = d < 0 ? (int)lrint(sigma_space * 1.5) : d / 2;
@@ -663,5 +691,6 @@ extern "C" int32_t vo_set_prefilter(vo_ctx* c, int32_t d, double sigma_color, do
   VO_HIP(c, hipMemcpyAsync(c->d_bil_cw, cw, sizeof(cw), hipMemcpyHostToDevice, c->stream));
   VO_HIP(c, hipStreamSynchronize(c->stream));
   c->bil_maxk = maxk;
+  c->ingest_gen++;                   // a captured step bakes the tap list and its weights in by value: a new key
   return VO_OK;
 }

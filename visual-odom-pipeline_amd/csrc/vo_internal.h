@@ -121,7 +121,6 @@ struct vo_ctx {
   double und_K[4] = {0, 0, 0, 0}, und_dist[8] = {0, 0, 0, 0, 0, 0, 0, 0}, und_newK[4] = {0, 0, 0, 0};
   uint64_t* d_und_tab = nullptr;
   uint8_t* d_und = nullptr;
-  unsigned und_gen = 0;              // bumped by every vo_set_undistort / vo_clear_undistort: part of a captured step's key
   // CLAHE (vo_clahe.hip): the setting of vo_set_clahe, the tables [batch][tiles_y][tiles_x][256] u8 the last launch wrote (room for 16 x 16
   // tiles) and the tight [batch][h][w] staging image the level-0 kernels read instead of the raw frame -- allocated when first switched on
   bool cl_on = false;
@@ -129,7 +128,9 @@ struct vo_ctx {
   int cl_tx = 0, cl_ty = 0;
   uint8_t* d_clahe_lut = nullptr;
   uint8_t* d_clahe = nullptr;
-  unsigned cl_gen = 0;               // bumped by every vo_set_clahe / vo_clear_clahe: part of a captured step's key
+  // bumped by every accepted change of an ingest setting (vo_set_prefilter, vo_set / vo_clear_undistort, vo_set / vo_clear_clahe): all that a
+  // captured step's key holds of the ingest chain
+  unsigned ingest_gen = 0;
   // DLT inputs
   float* d_uv0 = nullptr; float* d_uv1 = nullptr;    // [batch][max_pts][2]
   vo_dlt_cam* d_dlt_cam = nullptr;   // [batch]
@@ -233,6 +234,14 @@ struct vo_prof_scope {
 
 static inline int vo_div_up(int a, int b) { return (a + b - 1) / b; }
 
+// waits for every stream a frame step enqueues on: the ctx stream, then the side streams where they exist
+inline int32_t vo_sync_streams(vo_ctx* c) {
+  VO_HIP(c, hipStreamSynchronize(c->stream));
+  if (c->stream2) VO_HIP(c, hipStreamSynchronize(c->stream2));
+  if (c->stream3) VO_HIP(c, hipStreamSynchronize(c->stream3));
+  return VO_OK;
+}
+
 // cross-unit internals used by the fused frame step (vo_step.hip).  Every function that enqueues takes the stream q its launches, copies, event
 // records and profile brackets go to, and never waits for the side streams: that (vo_quiesce_side) is the extern "C" entry points' business
 int32_t vo_build_pyramid(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx);
@@ -282,14 +291,21 @@ void vo_guess_destroy(vo_ctx* c);
 // place against the current frame; off, it only notes that the last detection did not refine
 int32_t vo_subpix_refine_detected(vo_ctx* c, hipStream_t q, int max_corners);
 void vo_subpix_destroy(vo_ctx* c);
-// lens undistortion (vo_undistort.hip).  vo_undistort_enqueue: called by vo_build_pyramid with vo_set_undistort on: k_undistort takes the raw
-// frames (k_pad_level0's triple) to c->d_und on q, and the level-0 kernel then reads that staging image
+// The ingest chain (vo_frame.hip): the optional stages vo_build_pyramid runs in front of level 0, in this order: lens undistortion
+// (vo_undistort.hip), then CLAHE (vo_clahe.hip).  A stage's enqueue takes the frames (k_pad_level0's triple) to its own tight [batch][h][w]
+// staging image on q; the next stage, and at last the level-0 kernel, read that image as their raw frame.
+typedef void (*vo_ingest_enqueue_fn)(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx, int remap);
+struct vo_ingest_stage { bool on; vo_ingest_enqueue_fn enqueue; uint8_t* staging; };
 void vo_undistort_enqueue(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx, int remap);
-void vo_undistort_destroy(vo_ctx* c);
-// CLAHE (vo_clahe.hip).  vo_clahe_enqueue: called by vo_build_pyramid with vo_set_clahe on, behind the undistortion hook: k_clahe_lut and
-// k_clahe_apply take the frames (k_pad_level0's triple) to c->d_clahe on q, and the level-0 kernel then reads that staging image
 void vo_clahe_enqueue(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx, int remap);
-void vo_clahe_destroy(vo_ctx* c);
+// what the stages' entry points share.  A setting change: vo_ingest_reserve (the staging image, if absent), vo_sync_streams (no build in flight
+// runs with the setting that is replaced), the caller's upload or reset on the ctx stream, vo_ingest_commit (waits for it, switches the stage
+// on, bumps ingest_gen), then the caller's fields.  vo_ingest_run: a stage alone on `batch` host images, [batch][height] rows of `stride` (in) /
+// width (out) bytes; VO_E_STATE with `off_msg` when the stage is off.  vo_ingest_free: a stage's two device buffers (vo_ctx_destroy)
+int32_t vo_ingest_reserve(vo_ctx* c, uint8_t** staging);
+int32_t vo_ingest_commit(vo_ctx* c, bool* on);
+int32_t vo_ingest_run(vo_ctx* c, const vo_ingest_stage& s, const char* off_msg, const uint8_t* img, int32_t stride, uint8_t* out);
+void vo_ingest_free(bool* on, uint8_t** staging, void** table);
 int32_t vo_shi_tomasi_resident_counts(vo_ctx* c, hipStream_t q, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm, const int32_t* d_counts,
                                       const int32_t* d_limit);
 

@@ -1295,9 +1295,7 @@ extern "C" int32_t vo_shi_tomasi_read(vo_ctx* c, float* eig_out, uint8_t* mask_o
   VO_CHECK(c, c->st->eig_valid || (!eig_out && !mask_out), VO_E_STATE,
            "the last launch was a resident one: it keeps neither the eigenvalue map nor the mask (vo_tuning.st_keep_eig makes it)");
   VO_HIP(c, hipSetDevice(c->device));
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->stream2) VO_HIP(c, hipStreamSynchronize(c->stream2));
-  if (c->stream3) VO_HIP(c, hipStreamSynchronize(c->stream3));
+  { const int32_t rs = vo_sync_streams(c); if (rs != VO_OK) return rs; }
   const size_t np = (size_t)c->width * c->height * c->batch;
   if (eig_out) VO_HIP(c, hipMemcpy(eig_out, c->st->d_eig, np * sizeof(float), hipMemcpyDeviceToHost));
   if (mask_out) VO_HIP(c, hipMemcpy(mask_out, c->st->d_mask, np, hipMemcpyDeviceToHost));

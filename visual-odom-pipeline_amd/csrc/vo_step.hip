@@ -180,7 +180,7 @@ static uint64_t step_signature(vo_ctx* c, const step_cfg& s) {
   auto mix = [&](const void* p, size_t n) { const unsigned char* b = static_cast<const unsigned char*>(p); for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; } };
   auto mix_i = [&](long long v) { mix(&v, sizeof(v)); };
   mix(&s, sizeof(s));                       // the caller zero-fills the struct, so padding bytes are defined
-  mix_i(c->p_parity); mix_i(c->dlt_n); mix_i(c->dlt_stats); mix_i(c->bil_maxk); mix_i(c->und_on ? 1 : 0); mix_i(c->und_gen); mix_i(c->cl_on ? 1 : 0); mix_i(c->cl_gen); mix_i(c->ba_sharded); mix_i(c->side_stream);
+  mix_i(c->p_parity); mix_i(c->dlt_n); mix_i(c->dlt_stats); mix_i(c->ingest_gen); mix_i(c->ba_sharded); mix_i(c->side_stream);
   mix_i((long long)(uintptr_t)c->d_seq); mix_i(c->seq_n);
   mix_i((long long)(uintptr_t)c->d_uv0); mix_i((long long)(uintptr_t)c->d_dlt_cam);
   mix_i((long long)(uintptr_t)c->st); mix_i((long long)(uintptr_t)c->ba); mix_i((long long)(uintptr_t)c->d_pt_counts);
@@ -444,9 +444,7 @@ extern "C" int32_t vo_frame_fetch(vo_ctx* c, int32_t n_pts, float* p, uint8_t* s
   } else {
     VO_CHECK(c, c->steps_enq > 0, VO_E_STATE, "no step to fetch");
     half = (int)((c->steps_enq - 1) & 1);
-    VO_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->stream2) VO_HIP(c, hipStreamSynchronize(c->stream2));
-    if (c->stream3) VO_HIP(c, hipStreamSynchronize(c->stream3));
+    { const int32_t rs = vo_sync_streams(c); if (rs != VO_OK) return rs; }
   }
   const size_t off_p = c->step_off_p[half];
   const int mc = vo_st_last_max_corners(c) > 0 ? vo_st_last_max_corners(c) : 4096;

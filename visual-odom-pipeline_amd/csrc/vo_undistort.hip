@@ -94,25 +94,11 @@ static void und_build_table(int w, int h, const double* K, const double* d, cons
     }
 }
 
-void vo_undistort_destroy(vo_ctx* c) {
-  if (c->d_und) (void)hipFree(c->d_und);
-  if (c->d_und_tab) (void)hipFree(c->d_und_tab);
-  c->d_und = nullptr; c->d_und_tab = nullptr; c->und_on = false;
-}
-
-// vo_build_pyramid's hook (und_on): the raw frames -> c->d_und on q
+// the stage's enqueue (vo_build_pyramid's chain, vo_ingest_run): the raw frames -> c->d_und on q
 void vo_undistort_enqueue(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx, int remap) {
   const int w = c->width, h = c->height;
   hipLaunchKernelGGL(k_undistort, dim3(vo_div_up(vo_div_up(w, 4) * h, 256), 1, c->batch), dim3(256), 0, q, d_raw_img, raw_seq_stride, d_frame_idx,
                      w, h, reinterpret_cast<const uint2*>(c->d_und_tab), c->d_und, remap);
-}
-
-// every stream of the context that may still run a pyramid build with the present table
-static int32_t und_sync_all(vo_ctx* c) {
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->stream2) VO_HIP(c, hipStreamSynchronize(c->stream2));
-  if (c->stream3) VO_HIP(c, hipStreamSynchronize(c->stream3));
-  return VO_OK;
 }
 
 extern "C" int32_t vo_set_undistort(vo_ctx* c, const double* K, const double* dist, int32_t n_dist, const double* newK) {
@@ -132,21 +118,21 @@ extern "C" int32_t vo_set_undistort(vo_ctx* c, const double* K, const double* di
   und_build_table(c->width, c->height, K, d, nK, tab);
   const size_t px = (size_t)c->width * c->height;
   if (!c->d_und_tab) VO_HIP(c, hipMalloc((void**)&c->d_und_tab, px * sizeof(uint64_t)));
-  if (!c->d_und) VO_HIP(c, hipMalloc((void**)&c->d_und, px * (size_t)c->batch));
-  { const int32_t rs = und_sync_all(c); if (rs != VO_OK) return rs; }   // no build in flight reads the table that is replaced
+  int32_t r = vo_ingest_reserve(c, &c->d_und);
+  if (r == VO_OK) r = vo_sync_streams(c);                               // no build in flight reads the table that is replaced
+  if (r != VO_OK) return r;
   VO_HIP(c, hipMemcpyAsync(c->d_und_tab, tab.data(), px * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-  VO_HIP(c, hipStreamSynchronize(c->stream));
+  r = vo_ingest_commit(c, &c->und_on);
+  if (r != VO_OK) return r;
   for (int k = 0; k < 4; k++) { c->und_K[k] = K[k]; c->und_newK[k] = nK[k]; }
   for (int k = 0; k < 8; k++) c->und_dist[k] = d[k];
-  c->und_on = true;
-  c->und_gen++;
   return VO_OK;
 }
 
 extern "C" int32_t vo_clear_undistort(vo_ctx* c) {
   if (!c) return VO_E_INVALID;
   c->und_on = false;                 // enqueued builds have their launches; the buffers stay for the next vo_set_undistort
-  c->und_gen++;
+  c->ingest_gen++;
   return VO_OK;
 }
 
@@ -158,21 +144,9 @@ extern "C" int32_t vo_get_undistort(vo_ctx* c, int32_t* on, double* K, double* d
   return VO_OK;
 }
 
-// img, out: `batch` images, [batch][height] rows of `stride` (in) / width (out) bytes
 extern "C" int32_t vo_undistort(vo_ctx* c, const uint8_t* img, int32_t stride, uint8_t* out) {
   if (!c) return VO_E_INVALID;
-  VO_CHECK(c, img != nullptr && out != nullptr && stride >= c->width, VO_E_INVALID, "bad image / stride");
-  VO_CHECK(c, c->und_on, VO_E_STATE, "no undistortion set (vo_set_undistort)");
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  // c->d_raw is vo_frame_push's staging: everything that reads it was enqueued on the ctx stream before this copy
-  const size_t rows = (size_t)c->height * c->batch, px = (size_t)c->width * c->height;
-  VO_HIP(c, hipMemcpy2DAsync(c->d_raw, c->width, img, stride, c->width, rows, hipMemcpyHostToDevice, c->stream));
-  vo_undistort_enqueue(c, c->stream, c->d_raw, px, nullptr, 0);
-  VO_HIP(c, hipGetLastError());
-  VO_HIP(c, hipMemcpyAsync(out, c->d_und, px * (size_t)c->batch, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  return VO_OK;
+  return vo_ingest_run(c, {c->und_on, vo_undistort_enqueue, c->d_und}, "no undistortion set (vo_set_undistort)", img, stride, out);
 }
 
 extern "C" int32_t vo_undistort_map_read(vo_ctx* c, int16_t* sxy, uint16_t* frac, uint8_t* outside) {

@@ -143,16 +143,25 @@ class VoContext:
         self._ck(self._L.vo_get_undistort(self._h, C.byref(on), ptr(K, C.c_double), ptr(d, C.c_double), ptr(N, C.c_double)))
         return dict(K=K, dist=d, new_K=N) if on.value else None
 
-    def undistort(self, img):
-        """cv2.undistort of `img` ([h, w] uint8, [batch, h, w] on a batched context) with the setting of set_undistort (vo_undistort);
-        the frame store is not touched"""
+    def _ingest_call(self, name, fn, img):
+        """the body of undistort() / clahe(): `img` ([h, w] uint8, [batch, h, w] on a batched context) through the stage `fn` alone into a
+        fresh array.  A view whose rows are `stride` >= w bytes apart (buf[..., :w] of a C-contiguous buffer) is read in place."""
         img = np.asarray(img)
         if img.dtype != np.uint8:
-            raise ValueError("undistort: expected uint8")
-        img = self._in(img, np.uint8, (self.height, self.width))
-        out = np.empty_like(img)
-        self._ck(self._L.vo_undistort(self._h, ptr(img, C.c_uint8), self.width, ptr(out, C.c_uint8)))
+            raise ValueError("%s: expected uint8" % name)
+        h, w = self.height, self.width
+        stride = img.strides[-2] if img.ndim >= 2 else 0
+        rows_in_place = (img.shape == (self.batch, h, w) and img.strides == (h * stride, stride, 1)) or \
+                        (self.batch == 1 and img.shape == (h, w) and img.strides == (stride, 1))
+        if not (rows_in_place and stride >= w):
+            img, stride = self._in(img, np.uint8, (h, w)), w
+        out = np.empty((self.batch, h, w), np.uint8)
+        self._ck(fn(self._h, ptr(img, C.c_uint8), stride, ptr(out, C.c_uint8)))
         return self._out(out)
+
+    def undistort(self, img):
+        """cv2.undistort of `img` with the setting of set_undistort (vo_undistort, see _ingest_call); the frame store is not touched"""
+        return self._ingest_call("undistort", self._L.vo_undistort, img)
 
     def undistort_map_read(self):
         """the fixed-point map of the setting (vo_undistort_map_read): dict of sxy (h, w, 2) i16 = the top-left tap (sx, sy),
@@ -162,6 +171,14 @@ class VoContext:
         out = np.empty((self.height, self.width), np.uint8)
         self._ck(self._L.vo_undistort_map_read(self._h, ptr(sxy, C.c_int16), ptr(frac, C.c_uint16), ptr(out, C.c_uint8)))
         return dict(sxy=sxy, frac=frac, outside=out)
+
+    @staticmethod
+    def _undistort_args(undistort):
+        """dict(K=, dist=[, new_K=]) -- cv2.undistort's arguments -> (K, dist, new_K)"""
+        unknown = set(undistort) - {"K", "dist", "new_K"}
+        if unknown or "K" not in undistort:
+            raise ValueError("undistort: a dict with K, dist and optionally new_K, got keys %r" % sorted(undistort))
+        return undistort["K"], undistort.get("dist"), undistort.get("new_K")
 
     @staticmethod
     def _clahe_args(clahe):
@@ -187,6 +204,20 @@ class VoContext:
     def clear_clahe(self):
         self._ck(self._L.vo_clear_clahe(self._h))
 
+    def apply_ingest(self, undistort, clahe, clear_missing):
+        """undistort = dict(K=, dist=[, new_K=]), clahe = (clip_limit, (tiles_x, tiles_y)) or a dict, both validated before either is set.
+        None: with clear_missing a setting the context has is switched off, without it no call at all (the context keeps what it has)."""
+        u = None if undistort is None else self._undistort_args(undistort)
+        cl = None if clahe is None else self._clahe_args(clahe)
+        if u is not None:
+            self.set_undistort(*u)
+        elif clear_missing and self.get_undistort() is not None:
+            self.clear_undistort()
+        if cl is not None:
+            self.set_clahe(cl[0], cl[1:])
+        elif clear_missing and self.get_clahe() is not None:
+            self.clear_clahe()
+
     def get_clahe(self):
         """-> None when off, else (clip_limit, (tiles_x, tiles_y))"""
         on, tx, ty, clip = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
@@ -194,21 +225,9 @@ class VoContext:
         return (clip.value, (tx.value, ty.value)) if on.value else None
 
     def clahe(self, img):
-        """CLAHE of `img` ([h, w] uint8, [batch, h, w] on a batched context) with the setting of set_clahe (vo_clahe): CLAHE alone, not the
-        undistortion in front of it; the frame store is not touched.  A view whose rows are `stride` >= w bytes apart (buf[..., :w] of a
-        C-contiguous buffer) is read in place."""
-        img = np.asarray(img)
-        if img.dtype != np.uint8:
-            raise ValueError("clahe: expected uint8")
-        h, w = self.height, self.width
-        stride = img.strides[-2] if img.ndim >= 2 else 0
-        rows_in_place = (img.shape == (self.batch, h, w) and img.strides == (h * stride, stride, 1)) or \
-                        (self.batch == 1 and img.shape == (h, w) and img.strides == (stride, 1))
-        if not (rows_in_place and stride >= w):
-            img, stride = self._in(img, np.uint8, (h, w)), w
-        out = np.empty((self.batch, h, w), np.uint8)
-        self._ck(self._L.vo_clahe(self._h, ptr(img, C.c_uint8), stride, ptr(out, C.c_uint8)))
-        return self._out(out)
+        """CLAHE of `img` with the setting of set_clahe (vo_clahe, see _ingest_call): CLAHE alone, not the undistortion in front of it; the
+        frame store is not touched"""
+        return self._ingest_call("clahe", self._L.vo_clahe, img)
 
     def clahe_lut_read(self):
         """the tables the last launch wrote (vo_clahe_lut_read): uint8 [tiles_y, tiles_x, 256] ([batch, ...] on a batched context)"""

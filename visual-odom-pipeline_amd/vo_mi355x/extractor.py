@@ -11,6 +11,7 @@ from copy import deepcopy
 
 import numpy as np
 
+from .context import VoContext
 from .state import Keypoint, Landmark
 
 
@@ -53,13 +54,11 @@ class Extractor:
         to this extractor's context (VoContext.set_clahe), so _im_prev and im_curr enter the frame store equalised (behind the undistortion).
         A lazy session serves only None."""
         if clahe is not None:
-            from .context import VoContext
-            clahe = VoContext._clahe_args(clahe)
+            clip, tx, ty = VoContext._clahe_args(clahe)
+            clahe = (clip, (tx, ty))
         self._clahe = clahe
         if undistort is not None:
-            unknown = set(undistort) - {"K", "dist", "new_K"}
-            if unknown or "K" not in undistort:
-                raise ValueError("undistort: a dict with K, dist and optionally new_K, got keys %r" % sorted(undistort))
+            VoContext._undistort_args(undistort)
         self._undistort = None if undistort is None else dict(undistort)
         if subpix is not None:
             unknown = set(subpix) - {"win", "zero_zone", "criteria"}
@@ -89,26 +88,22 @@ class Extractor:
         self._dev_prev = None           # host copies of what the device frame store currently holds
         self._dev_cur = None
         if ctx is not None:
-            self._apply_undistort(ctx)
+            self._apply_ingest(ctx)
 
     # -- device frame store ---------------------------------------------------------------------
     def _context(self, img):
         if self._ctx is None:
-            from .context import VoContext
             h, w = img.shape
             self._ctx = VoContext(w, h, max_pts=self._max_pts, device=self._device,
                                   max_level=self._lk_params["maxLevel"], win=self._lk_params["winSize"][0])
-            self._apply_undistort(self._ctx)
+            self._apply_ingest(self._ctx)
         return self._ctx
 
-    def _apply_undistort(self, ctx):
+    def _apply_ingest(self, ctx):
         """the settings (undistort=, clahe=) go to the context the frames are pushed to; None makes no call at all (a caller's context keeps
-        what it has)"""
-        u = self._undistort
-        if u is not None:
-            ctx.set_undistort(u["K"], u.get("dist"), u.get("new_K"))
-        if self._clahe is not None:
-            ctx.set_clahe(self._clahe[0], self._clahe[1:])
+        what it has, and a stand-in context needs no such method)"""
+        if self._undistort is not None or self._clahe is not None:
+            ctx.apply_ingest(self._undistort, self._clahe, clear_missing=False)
 
     def _push(self, img):
         img = np.ascontiguousarray(img, dtype=np.uint8)

@@ -126,11 +126,8 @@ class Loader:
             return c.bilateral(raw, PREFILTER["d"], PREFILTER["sigmaColor"], PREFILTER["sigmaSpace"])
         # undistortion, then CLAHE, run in front of the filter, in the same push
         try:
-            if self._distortion is not None:
-                c.set_undistort(self._camera, self._distortion, self._new_K)
-            if self._clahe is not None:
-                cl = c._clahe_args(self._clahe)
-                c.set_clahe(cl[0], cl[1:])
+            und = None if self._distortion is None else dict(K=self._camera, dist=self._distortion, new_K=self._new_K)
+            c.apply_ingest(und, self._clahe, clear_missing=False)
             return c.bilateral(raw, PREFILTER["d"], PREFILTER["sigmaColor"], PREFILTER["sigmaSpace"])
         finally:
             c.clear_undistort()

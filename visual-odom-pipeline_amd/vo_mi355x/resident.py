@@ -70,10 +70,8 @@ class ResidentPipeline:
         K = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (B, 3, 3)))
         self.K = K
         if undistort is not None:
-            unknown = set(undistort) - {"K", "dist", "new_K"}
-            if unknown or "K" not in undistort:
-                raise ValueError("undistort: a dict with K, dist and optionally new_K, got keys %r" % sorted(undistort))
-            cam = ctx._k4(undistort["K"] if undistort.get("new_K") is None else undistort["new_K"], "undistort camera")
+            uK, _, uN = ctx._undistort_args(undistort)
+            cam = ctx._k4(uK if uN is None else uN, "undistort camera")
             if not all(np.array_equal(cam, [k[0, 0], k[1, 1], k[0, 2], k[1, 2]]) for k in K):
                 raise ValueError("undistort: the pipeline's K must be the camera the frames are undistorted to (new_K, or K without one)")
         p = PipeParams()
@@ -94,15 +92,7 @@ class ResidentPipeline:
             ctx.set_klt_predict(klt_predict)
         if not (subpix is None and ctx.get_subpix() is None):
             ctx.set_subpix(subpix)
-        if undistort is not None:
-            ctx.set_undistort(undistort["K"], undistort.get("dist"), undistort.get("new_K"))
-        elif ctx.get_undistort() is not None:
-            ctx.clear_undistort()
-        if clahe is not None:
-            cl = ctx._clahe_args(clahe)
-            ctx.set_clahe(cl[0], cl[1:])
-        elif ctx.get_clahe() is not None:
-            ctx.clear_clahe()
+        ctx.apply_ingest(undistort, clahe, clear_missing=True)
         ctx._subpix_slots = p.st.max_corners if 0 < p.st.max_corners < 4096 else 4096
         self.N, self.R, self.B = ctx.max_pts, 4 * ctx.max_pts, B
         self.ba_window = ba_window
