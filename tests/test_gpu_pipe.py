@@ -491,6 +491,87 @@ def test_tables_beyond_4096_slots_at_1080p_window20():
     assert biggest > 4096, biggest          # reached with nothing cut
 
 
+def _small_loop(n):
+    """the smallest closed loop of this file: one 256 x 160 sequence, t1 = 3, n steps -> (scene, bootstrap state, t1)"""
+    w, h, t1 = 256, 160, 3
+    sc = ph.scene(t1 + n + 1, w=w, h=h, f=260.0, seed=2024, pose_fn=lambda t: ph.sway_pose(t, period=24.0))
+    return sc, ph.gt_bootstrap(_ctx(w, h), sc, 0, t1)[0], t1
+
+
+def _same_run(a, b):
+    (ra, Ta), (rb, Tb) = a, b
+    assert len(ra) == len(rb)
+    for s, (x, y) in enumerate(zip(ra, rb)):
+        assert x["status"] == 0, (s, x)
+        for k in x:
+            assert np.array_equal(np.asarray(x[k]), np.asarray(y[k])), (s, k, x[k], y[k])
+    for name in Ta:
+        assert np.array_equal(Ta[name], Tb[name], equal_nan=Ta[name].dtype.kind == "f"), name
+
+
+def test_side_stream_starts_behind_another_entry_point_between_steps():
+    """Between two closed-loop steps the side stream is ordered against the ctx stream by the steps' own events only; after any other entry
+    point (here vo_frame_push_resident of the frame the store already holds, asynchronous on the ctx stream) the next step's pyramid and tracker
+    start behind it (pipe_step's main_dirty fork).  Records and tables = the same calls on ONE stream, bit for bit.  Every step is fetched before
+    the next push, so without the fork the tracker would have to overtake a push that is already queued: a missing fork shows as a mismatch in
+    some runs, not in every one."""
+    from vo_mi355x.resident import ResidentPipeline
+    n = 4
+    sc, state, t1 = _small_loop(n)
+    runs = []
+    for side in (True, False):
+        c = _ctx(256, 160)
+        c.set_side_stream(side)
+        c.upload_sequence(sc["frames"])
+        rp = ResidentPipeline(c, sc["K"], ba_max_iters=12)
+        rp.seed(copy.deepcopy(state), [], [], 1)
+        c.push_frame_resident(t1)
+        recs = []
+        for s in range(n):
+            if s >= 1:
+                c.push_frame_resident(t1 + s)            # the current frame again: the ctx stream is dirty, the frame store's two halves = that frame
+            rp.step(t1 + 1 + s); recs.append(rp.fetch())
+        runs.append((recs, rp.read_tables()))
+        c.close()
+    assert all(r["n_tracked"] > 0 for r in runs[0][0])
+    _same_run(*runs)
+
+
+def test_refused_host_step_arguments_leave_no_trace():
+    """vo_pipe_step_host refuses a null image pointer and a row stride below the width with VO_E_INVALID before anything reaches the GPU: no step
+    is in flight afterwards (vo_pipe_fetch: VO_E_STATE), and every step that follows gives the record -- and the loop the tables -- of a context
+    that never saw the refused calls"""
+    import ctypes as C
+    from vo_mi355x import VoError
+    from vo_mi355x.resident import ResidentPipeline
+    n = 3
+    sc, state, t1 = _small_loop(n)
+    w = 256
+
+    def run(refusing):
+        c = _ctx(256, 160)
+        rp = ResidentPipeline(c, sc["K"], ba_max_iters=12)
+        rp.seed(copy.deepcopy(state), [], [], 1)
+        c.push_frame(sc["frames"][t1])
+        recs = []
+        for s in range(n):
+            im = np.ascontiguousarray(sc["frames"][t1 + 1 + s])
+            if refusing:
+                for ptr, stride in ((None, w), (im.ctypes.data, w - 1)):
+                    with pytest.raises(VoError) as e:
+                        rp.step_host(((C.c_void_p * 1)(ptr), stride, [im]))
+                    assert e.value.code == -1, str(e.value)
+                    with pytest.raises(VoError) as e:
+                        rp.fetch()                       # nothing in flight
+                    assert e.value.code == -4, str(e.value)
+            rp.step_host([im]); recs.append(rp.fetch())
+        out = recs, rp.read_tables()
+        c.close()
+        return out
+
+    _same_run(run(True), run(False))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("source", ["pinned", "pageable"])
 def test_closed_loop_with_host_frames_equals_resident_frames(source):

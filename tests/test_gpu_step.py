@@ -363,6 +363,52 @@ def test_host_frame_step_equals_resident_step(batch, layout, source):
         assert [(x["cost"], x["iters"], x["status"]) for x in gs] == [(x["cost"], x["iters"], x["status"]) for x in rs], k
 
 
+def test_refused_host_frame_step_arguments_leave_no_trace():
+    """vo_frame_step_host refuses a null image pointer (here the second sequence's) and a row stride below the width with VO_E_INVALID before
+    anything reaches the GPU: the refused call takes neither of the two in-flight slots, and the steps that follow -- two in flight, then one --
+    give the results of a context that never saw the refused calls"""
+    import ctypes as C
+    from vo_mi355x import VoContext, VoError, synthetic as syn
+    w, h, n = 128, 96, 40
+    seqs = [syn.make_sequence(4, w=w, h=h, seed=3 + b, margin=32)[0] for b in range(2)]
+    pts = np.stack([syn.grid_points(n, w, h, seed=b, margin=12) for b in range(2)])
+    kw = dict(do_dlt=False, do_ba=False, do_st=False)
+
+    def run(refusing):
+        def refuse(c, f):
+            ims = [seqs[0][f], seqs[1][f]]
+            for p1, stride in ((None, w), (ims[1].ctypes.data, w - 1)):
+                with pytest.raises(VoError) as e:
+                    c.frame_step_host(((C.c_void_p * 2)(ims[0].ctypes.data, p1), stride, ims), n, **kw)
+                assert e.value.code == -1, str(e.value)
+        with VoContext(w, h, max_pts=64, batch=2) as c:
+            c.points_upload(pts)
+            c.push_frame(np.stack([seqs[0][0], seqs[1][0]]))
+            out = []
+            if refusing:
+                refuse(c, 1)
+            c.frame_step_host([seqs[0][1], seqs[1][1]], n, **kw)
+            if refusing:
+                refuse(c, 2)                              # one step in flight
+            c.frame_step_host([seqs[0][2], seqs[1][2]], n, **kw)      # accepted: the refused calls took no slot
+            with pytest.raises(VoError) as e:
+                c.frame_step_host([seqs[0][3], seqs[1][3]], n, **kw)  # ... and two are in flight, no fewer
+            assert e.value.code == -4, str(e.value)
+            out += [c.frame_fetch(), c.frame_fetch()]
+            if refusing:
+                refuse(c, 3)                              # nothing in flight
+            c.frame_step_host([seqs[0][3], seqs[1][3]], n, **kw)
+            out.append(c.frame_fetch())
+        return out
+
+    got, ref = run(True), run(False)
+    assert len(got) == len(ref) == 3
+    for k, (g, r) in enumerate(zip(got, ref)):
+        assert r["status"][0].any() and r["status"][1].any(), k      # points were tracked in both sequences
+        for key in ("points2d", "status", "err"):
+            assert np.array_equal(g[key], r[key], equal_nan=True), (k, key)
+
+
 def test_host_alloc_is_a_plain_numpy_array_and_frees_itself():
     import gc
     from vo_mi355x import VoContext

@@ -242,9 +242,36 @@ inline int32_t vo_sync_streams(vo_ctx* c) {
   return VO_OK;
 }
 
+// Stream fork and join of the two step orchestrators (step_enqueue, vo_step.hip; pipe_step, vo_pipeline.hip); after a call that failed nothing
+// further is issued.  fork: `ev` recorded on `from`; `to` waits for it, and `to2` (null = there is none: the library forks to streams it made)
+inline hipError_t vo_stream_fork(hipEvent_t ev, hipStream_t from, hipStream_t to, hipStream_t to2 = nullptr) {
+  hipError_t e = hipEventRecord(ev, from);
+  if (e == hipSuccess) e = hipStreamWaitEvent(to, ev, 0);
+  if (e == hipSuccess && to2) e = hipStreamWaitEvent(to2, ev, 0);
+  return e;
+}
+// join: `ev` recorded on `side`, `main` waits for it.  Every exit behind a fork joins: work queued on the side stream stays ordered before what the
+// caller enqueues (or frees) next on the main stream, also when a later enqueue fails -- a caller on a failing path joins, then returns its own code
+inline hipError_t vo_stream_join(hipEvent_t ev, hipStream_t side, hipStream_t main) {
+  const hipError_t e = hipEventRecord(ev, side);
+  return e == hipSuccess ? hipStreamWaitEvent(main, ev, 0) : e;
+}
+
 // cross-unit internals used by the fused frame step (vo_step.hip).  Every function that enqueues takes the stream q its launches, copies, event
 // records and profile brackets go to, and never waits for the side streams: that (vo_quiesce_side) is the extern "C" entry points' business
 int32_t vo_build_pyramid(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx);
+// Where a step's frame comes from: sequence 0's image, the bytes to the next sequence's, the frame index on the device (a captured step: `raw` is then the
+// sequence store) or null, the d_host_raw half of an upload (-1: resident).  vo_frame_src_pyramid on q: waits for ev_h2d[half], builds the pyramid, records ev_raw_free[half]
+struct vo_frame_src { const uint8_t* raw; size_t seq_stride; const int32_t* d_frame_idx; int host_half; };
+inline vo_frame_src vo_frame_src_host(const vo_ctx* c, int half) { return {c->d_host_raw[half], (size_t)c->width * c->height, nullptr, half}; }
+inline vo_frame_src vo_frame_src_resident(const vo_ctx* c, int frame_idx, const int32_t* d_frame_idx) {
+  return {c->d_seq + (d_frame_idx ? 0 : (size_t)frame_idx * c->width * c->height), (size_t)c->width * c->height * c->seq_n, d_frame_idx, -1};
+}
+int32_t vo_frame_src_pyramid(vo_ctx* c, hipStream_t q, const vo_frame_src& s);
+// what the two *_step_host entries share.  vo_host_frames_admit: `frames`, `stride` and every frames[b], VO_E_INVALID under the entry's name `who`;
+// vo_host_frames_abandon: (error path) the step does not count, so its pointer-table row goes to the next one: let the gather finish reading it
+int32_t vo_host_frames_admit(vo_ctx* c, const char* who, const uint8_t* const* frames, int32_t stride);
+inline void vo_host_frames_abandon(vo_ctx* c) { (void)hipStreamSynchronize(c->stream_h2d); }
 // a step's `batch` images from the host into d_host_raw[slot] on the copy stream (vo_step.hip); ev_h2d[slot] is recorded behind it
 // tab_slot: the row of h_ptr_tab this step's pointers go to (vo_host_tab_slot_frame / vo_host_tab_slot_pipe)
 int32_t vo_host_frames_upload(vo_ctx* c, const uint8_t* const* frames, int32_t stride, int slot, int tab_slot);

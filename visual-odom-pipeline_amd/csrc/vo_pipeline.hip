@@ -101,21 +101,6 @@ __device__ __forceinline__ pipe_ptrs pipe_select(pipe_ptrs P, int b) {
 __device__ __forceinline__ int ld_i32(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_i32(int32_t* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// block-wide exclusive scan of a 0/1 flag over the 1024 threads in thread order; s_w: 16 ints of LDS
-__device__ __forceinline__ int pipe_scan(int flag, int* s_w, int& total) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned long long bal = __ballot(flag);
-  const int within = __popcll(bal & ((1ull << lane) - 1ull));
-  __syncthreads();                       // s_w may still be read from the previous call
-  if (lane == 0) s_w[wave] = __popcll(bal);
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 16; w++) { const int v = s_w[w]; if (w < wave) off += v; tot += v; }
-  total = tot;
-  return off + within;
-}
-
 // A thread owns the CH CONSECUTIVE list entries j = tid * CH + c, so list order is thread order and ONE block-wide scan of the
 // per-thread counts ranks the flagged entries: rank[c] = position of entry (tid, c) among the flagged ones; returns their number.
 template <int CH>
@@ -140,6 +125,7 @@ __device__ __forceinline__ int pipe_rank(const bool* flag, int* rank, int* s_w) 
 }
 
 // block-wide exclusive scan of one count per thread, in thread order; returns the offset of this thread, total = sum over the workgroup
+// (pipe_rank's tail once more: with pipe_rank calling this function the compiler commutes one add in every list kernel)
 __device__ __forceinline__ int pipe_scan_count(int cnt, int* s_w, int& total) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int x = cnt;
@@ -157,12 +143,28 @@ __device__ __forceinline__ int pipe_scan_count(int cnt, int* s_w, int& total) {
 
 __device__ __forceinline__ float2* pipe_hist_slot(const pipe_ptrs& P, int idx) { return P.k_hist + (size_t)(idx & (PIPE_HIST - 1)) * P.R; }
 
-__device__ __forceinline__ void pipe_copy_K(const pipe_ptrs& P, int dst, int src) {
-  P.k_tf[dst] = P.k_tf[src]; P.k_tt[dst] = P.k_tt[src]; P.k_len[dst] = P.k_len[src];
-  P.k_uv[dst] = P.k_uv[src]; P.k_first[dst] = P.k_first[src];
-#pragma unroll 8
-  for (int h = 0; h < PIPE_HIST; h++) P.k_hist[(size_t)h * P.R + dst] = P.k_hist[(size_t)h * P.R + src];
+// a survivor updates its keypoint row IN PLACE: position, t_total + 1, one more history entry (uv by reference: by value k_pipe_extend<1> gets other registers)
+__device__ __forceinline__ void pipe_survivor_update(const pipe_ptrs& P, int k, const float2& uv, int tt, int len) {
+  P.k_uv[k] = uv; P.k_tt[k] = tt + 1; pipe_hist_slot(P, len)[k] = uv; P.k_len[k] = len + 1;
 }
+
+// the keypoint-row copies src[i] -> dst[i], i < n, as one cooperative pass of the workgroup: 37 values per row (32 history slots, t_first,
+// t_total, history length, uv, uv_first), 40 work items per row
+__device__ __forceinline__ void pipe_copy_rows(const pipe_ptrs& P, const int32_t* s_src, const int32_t* s_dst, int n) {
+  for (int e = threadIdx.x; e < n * 40; e += PIPE_TPB) {
+    const int i = e / 40, f = e - i * 40;
+    const int src = s_src[i], dst = s_dst[i];
+    if (f < PIPE_HIST) P.k_hist[(size_t)f * P.R + dst] = P.k_hist[(size_t)f * P.R + src];
+    else if (f == 32) P.k_tf[dst] = P.k_tf[src];
+    else if (f == 33) P.k_tt[dst] = P.k_tt[src];
+    else if (f == 34) P.k_len[dst] = P.k_len[src];
+    else if (f == 35) P.k_uv[dst] = P.k_uv[src];
+    else if (f == 36) P.k_first[dst] = P.k_first[src];
+  }
+}
+
+// entry i of the window a kernel loads of a free list (nf rows, handed out from `head` on): the row, -1 behind the list's end
+__device__ __forceinline__ int pipe_free_at(const int32_t* list, int head, int nf, int i) { return (head + i < nf) ? list[head + i] : -1; }
 
 // (free rows are handed out from the front of the ascending free lists: head counters C_HEADK / C_HEADL, rebuilt by k_pipe_spawn)
 __device__ __forceinline__ bool pipe_inside(float2 q, int W, int H) {
@@ -208,8 +210,8 @@ __device__ inline void pipe_log_so3(const double* R, double* r) {
 // first form made ~24 of them (row fields fetched where they were needed, free rows fetched when their rank was known, the leader election
 // and the t_latest increments as global atomics, every row copy a chain of 32 load-store pairs in one thread: 31 us for one sequence,
 // 75 in a batch of 32).  Now: (1) counters, (2) the lists and the tracked points, (3) EVERY row field any phase will need plus a window
-// of both free lists into LDS, then all bookkeeping on registers and LDS words (one word per landmark row: survivor count, then the
-// election), (4) the row copies as one cooperative pass of the whole workgroup over a work list.
+// of both free lists into LDS (pipe_free_at), then all bookkeeping on registers and LDS words (one word per landmark row: survivor count, then the
+// election; survivors' rows: pipe_survivor_update), (4) the row copies as one cooperative pass of the whole workgroup over a work list (pipe_copy_rows).
 // Dynamic LDS: int32 [R] per-landmark-row word | [N] free K rows | [N] free L rows | [N] copy sources  (28 bytes per slot of the table)
 template <int CH>
 // which: bit 0 the candidates (extend_tracks), bit 1 the landmarks (extend_landmarks) -- both in the closed loop; the object boundary
@@ -295,8 +297,8 @@ __global__ void __launch_bounds__(PIPE_TPB) k_pipe_extend(pipe_ptrs Pall, const 
     }
   }
   for (int i = tid; i < P.N; i += PIPE_TPB) {        // no phase takes more than N rows of either kind
-    s_fk[i] = (headK + i < nfK) ? P.freeK[headK + i] : -1;
-    s_fl[i] = (headL + i < nfL) ? P.freeL[headL + i] : -1;
+    s_fk[i] = pipe_free_at(P.freeK, headK, nfK, i);
+    s_fl[i] = pipe_free_at(P.freeL, headL, nfL, i);
   }
   __syncthreads();
 
@@ -308,7 +310,7 @@ __global__ void __launch_bounds__(PIPE_TPB) k_pipe_extend(pipe_ptrs Pall, const 
     for (int c = 0; c < CH; c++)
       if (kp[c]) {
         const int k = kc[c];
-        P.k_uv[k] = pc[c]; P.k_tt[k] = ttk[c] + 1; pipe_hist_slot(P, ln[c])[k] = pc[c]; P.k_len[k] = ln[c] + 1;
+        pipe_survivor_update(P, k, pc[c], ttk[c], ln[c]);
         P.cand[rank[c]] = k;
       }
     if (tid == 0) { P.cnt[C_NCAND] = n_out; P.cnt[C_NKLT] = nl + nc; }
@@ -345,7 +347,7 @@ __global__ void __launch_bounds__(PIPE_TPB) k_pipe_extend(pipe_ptrs Pall, const 
   for (int c = 0; c < CH; c++)
     if (keep[c]) {
       const int k = K[c];
-      P.k_uv[k] = q[c]; P.k_tt[k] = tt[c] + 1; pipe_hist_slot(P, len[c])[k] = q[c]; P.k_len[k] = len[c] + 1;
+      pipe_survivor_update(P, k, q[c], tt[c], len[c]);
       atomicAdd(&s_row[L[c]], 1);                    // LDS (global scratch above 4 096 slots)
     }
   __syncthreads();
@@ -412,17 +414,8 @@ __global__ void __launch_bounds__(PIPE_TPB) k_pipe_extend(pipe_ptrs Pall, const 
     if (tid == 0) P.cnt[C_NDEAD] = nd0 + n_ok;
   }
   __syncthreads();                                   // the in-place row updates and the work list are complete
-  // ---- trip 4: the row copies src = s_src[i] -> dst = s_fk[i], 37 values each, spread over the workgroup ----
-  for (int e = tid; e < n_copy * 40; e += PIPE_TPB) {
-    const int i = e / 40, f = e - i * 40;
-    const int src = s_src[i], dst = s_fk[i];
-    if (f < PIPE_HIST) P.k_hist[(size_t)f * P.R + dst] = P.k_hist[(size_t)f * P.R + src];
-    else if (f == 32) P.k_tf[dst] = P.k_tf[src];
-    else if (f == 33) P.k_tt[dst] = P.k_tt[src];
-    else if (f == 34) P.k_len[dst] = P.k_len[src];
-    else if (f == 35) P.k_uv[dst] = P.k_uv[src];
-    else if (f == 36) P.k_first[dst] = P.k_first[src];
-  }
+  // ---- trip 4: the row copies src = s_src[i] -> dst = s_fk[i], 37 values each, spread over the workgroup (pipe_copy_rows) ----
+  pipe_copy_rows(P, s_src, s_fk, n_copy);
   // ---- ordered compaction of the landmark list; the survivors are the 3D-2D correspondences of the pose stage (extractor.py:176-177) ----
   {
     int rank[CH];
@@ -448,8 +441,8 @@ __global__ void __launch_bounds__(PIPE_TPB) k_pipe_extend(pipe_ptrs Pall, const 
 // ================================================================================================
 // k_pipe_prune: PnP result -> trajectory, non-inliers to the dead lists; ripe candidates -> DLT inputs
 // ================================================================================================
-// (same construction as k_pipe_extend: lists, then every row field and the free-list heads in one trip, the keypoint-row copies as one
-//  cooperative pass.)  Dynamic LDS: int32 [N] free K rows | [N] free L rows | [N] copy sources
+// (same construction as k_pipe_extend: lists, then every row field and the free-list heads (pipe_free_at) in one trip, the keypoint-row copies as
+//  one cooperative pass (pipe_copy_rows).)  Dynamic LDS: int32 [N] free K rows | [N] free L rows | [N] copy sources
 template <int CH>
 __global__ void __launch_bounds__(PIPE_TPB) k_pipe_prune(pipe_ptrs Pall, int do_pose, int do_tri, const uint8_t* __restrict__ mask, const double* __restrict__ pnp_out,
                                                          int pnp_cap, int min_len, float* __restrict__ uv0, float* __restrict__ uv1, size_t uv_seq,
@@ -502,8 +495,8 @@ __global__ void __launch_bounds__(PIPE_TPB) k_pipe_prune(pipe_ptrs Pall, int do_
   }
   if (do_pose)
     for (int i = tid; i < P.N; i += PIPE_TPB) {
-      s_fk[i] = (headK + i < nfK) ? P.freeK[headK + i] : -1;
-      s_fl[i] = (headL + i < nfL) ? P.freeL[headL + i] : -1;
+      s_fk[i] = pipe_free_at(P.freeK, headK, nfK, i);
+      s_fl[i] = pipe_free_at(P.freeL, headL, nfL, i);
     }
   __syncthreads();
   int n_copy = 0;
@@ -537,17 +530,8 @@ __global__ void __launch_bounds__(PIPE_TPB) k_pipe_prune(pipe_ptrs Pall, int do_
       double* Hd = P.H + 12 * (size_t)(t & (PIPE_HIST - 1));
       for (int r = 0; r < 3; r++) { for (int k = 0; k < 3; k++) Hd[4 * r + k] = R[3 * r + k]; Hd[4 * r + 3] = pnp_out[3 + r]; }
     }
-    // the keypoint-row copies src = s_src[i] -> dst = s_fk[i]
-    for (int e = tid; e < n_copy * 40; e += PIPE_TPB) {
-      const int i = e / 40, f = e - i * 40;
-      const int src = s_src[i], dst = s_fk[i];
-      if (f < PIPE_HIST) P.k_hist[(size_t)f * P.R + dst] = P.k_hist[(size_t)f * P.R + src];
-      else if (f == 32) P.k_tf[dst] = P.k_tf[src];
-      else if (f == 33) P.k_tt[dst] = P.k_tt[src];
-      else if (f == 34) P.k_len[dst] = P.k_len[src];
-      else if (f == 35) P.k_uv[dst] = P.k_uv[src];
-      else if (f == 36) P.k_first[dst] = P.k_first[src];
-    }
+    // the keypoint-row copies src = s_src[i] -> dst = s_fk[i] (pipe_copy_rows)
+    pipe_copy_rows(P, s_src, s_fk, n_copy);
   }
   __syncthreads();                                     // the new pose is in the ring
   if (do_tri) {
@@ -706,8 +690,8 @@ __global__ void __launch_bounds__(256) k_pipe_problem(pipe_ptrs Pall, int do_adj
 // ================================================================================================
 // k_pipe_promote: triangulation filters + gate + promotion; then the selection half of BundleAdjuster.adjust
 // ================================================================================================
-// (Constructed like k_pipe_extend: trip 1 counters; trip 2 every list and per-candidate input, the free-row window and the whole trajectory
-//  ring into LDS; trip 3 the row fields of the dead entries, of the EXISTING state entries -- thread j owns final entry j, and entries are
+// (Constructed like k_pipe_extend: trip 1 counters; trip 2 every list and per-candidate input, the free-row window (pipe_free_at) and the whole
+//  trajectory ring into LDS; trip 3 the row fields of the dead entries, of the EXISTING state entries -- thread j owns final entry j, and entries are
 //  only appended -- and of the candidates; trips 4 / 5 the rows of appended entries and the history entries of the observation table.
 //  The landmark list is kept in LDS while it grows, "this landmark row is in the state's list" is a byte per row in LDS.)
 // Dynamic LDS: int32 [N] landmark rows of the list | [N] keypoint rows of the list | [N] free L rows | bytes [R] row-in-list marks
@@ -774,7 +758,7 @@ __global__ void __launch_bounds__(PIPE_TPB) k_pipe_promote(pipe_ptrs Pall, int d
     }
     if (j < nc) cK[c] = P.cand[j];
   }
-  for (int i = tid; i < P.N; i += PIPE_TPB) s_fl[i] = (headL0 + i < nfL) ? P.freeL[headL0 + i] : -1;
+  for (int i = tid; i < P.N; i += PIPE_TPB) s_fl[i] = pipe_free_at(P.freeL, headL0, nfL, i);
   for (int i = tid; i < PIPE_HIST * 12; i += PIPE_TPB) s_H[i] = P.H[i];
   // ---- trip 3: row fields ----
   int dtl[CH], dlen[CH], elen[CE], etl[CE];
@@ -1425,10 +1409,12 @@ extern "C" int32_t vo_pipe_set_ba_budget(vo_ctx* c, int32_t budget) {
 }
 
 static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main_dirty);
+static int32_t pipe_step_entry(vo_ctx* c, int32_t frame_idx, int32_t stages);
+
+// k_pipe_extend's `which`: bit 0 the candidates' half, bit 1 the landmarks'; a step that names neither runs both
+static inline int pipe_halves(int32_t st) { return (st & (VO_PIPE_TRACK_CANDIDATES | VO_PIPE_TRACK_LANDMARKS)) ? (((st & VO_PIPE_TRACK_CANDIDATES) ? 1 : 0) | ((st & VO_PIPE_TRACK_LANDMARKS) ? 2 : 0)) : 3; }
 
 #define PIPE_FRAME_FROM_HOST (-2)      // internal frame index: the step's images are in c->d_host_raw[c->pipe_host_slot] behind ev_h2d
-
-static int32_t pipe_step_entry(vo_ctx* c, int32_t frame_idx, int32_t stages);
 
 extern "C" int32_t vo_pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages) {
   if (!c) return VO_E_INVALID;
@@ -1442,7 +1428,7 @@ static int32_t pipe_step_admit(vo_ctx* c, int32_t frame_idx, int32_t stages) {
   VO_CHECK(c, c->pipe->enq - c->pipe->fetched < VO_PIPE_INFLIGHT, VO_E_STATE, "vo_pipe_fetch the oldest step first");
   if (c->stream_reserve > 0 || c->ba_wide_groups > 0)
     VO_CHECK(c, c->pipe->enq == c->pipe->fetched && c->steps_enq == c->steps_fetched, VO_E_STATE, "steps in flight on the gated stream layout");
-  const int halves = (stages & (VO_PIPE_TRACK_CANDIDATES | VO_PIPE_TRACK_LANDMARKS)) ? (((stages & VO_PIPE_TRACK_CANDIDATES) ? 1 : 0) | ((stages & VO_PIPE_TRACK_LANDMARKS) ? 2 : 0)) : 3;
+  const int halves = pipe_halves(stages);
   // the landmarks' half on its own reads the positions a TRACK | TRACK_CANDIDATES call left in the point buffer: without that call before it
   // k_pipe_extend would take stale positions for tracked ones
   if (!(stages & VO_PIPE_TRACK) && (stages & VO_PIPE_TRACK_LANDMARKS))
@@ -1462,9 +1448,8 @@ static int32_t pipe_step_admit(vo_ctx* c, int32_t frame_idx, int32_t stages) {
 extern "C" int32_t vo_pipe_step_host(vo_ctx* c, const uint8_t* const* frames, int32_t stride, int32_t stages) {
   if (!c) return VO_E_INVALID;
   VO_CHECK(c, c->pipe, VO_E_STATE, "vo_pipe_create first");
-  VO_CHECK(c, frames != nullptr && stride >= c->width, VO_E_INVALID, "bad frame pointers / stride");
+  { const int32_t rf = vo_host_frames_admit(c, __func__, frames, stride); if (rf != VO_OK) return rf; }
   VO_CHECK(c, (stages & VO_PIPE_TRACK) != 0, VO_E_INVALID, "a step that takes a frame tracks it (VO_PIPE_TRACK)");
-  for (int b = 0; b < c->batch; b++) VO_CHECK(c, frames[b] != nullptr, VO_E_INVALID, "null frame pointer");
   { const int32_t ra = pipe_step_admit(c, PIPE_FRAME_FROM_HOST, stages); if (ra != VO_OK) return ra; }
   VO_HIP(c, hipSetDevice(c->device));
   // d_host_raw: the two halves in turn (ev_raw_free orders each); the pointers: this step's own row of the table, free since the step
@@ -1473,8 +1458,7 @@ extern "C" int32_t vo_pipe_step_host(vo_ctx* c, const uint8_t* const* frames, in
   { const int32_t ru = vo_host_frames_upload(c, frames, stride, half, vo_host_tab_slot_pipe(c->pipe->enq)); if (ru != VO_OK) return ru; }
   c->pipe_host_slot = half;
   const int32_t r = pipe_step_entry(c, PIPE_FRAME_FROM_HOST, stages);
-  // (error path) the step does not count, so its pointer-table row goes to the next one: let the gather finish reading it first
-  if (r != VO_OK) (void)hipStreamSynchronize(c->stream_h2d);
+  if (r != VO_OK) vo_host_frames_abandon(c);
   return r;
 }
 
@@ -1515,7 +1499,7 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
   // flight.  The main stream waits for the side stream twice per step (before extend, before the record leaves), so after every call
   // it is downstream of all side work.  A frame the caller pushed itself (frame_idx < 0) is tracked on the main stream as before.
   const bool side = c->side_stream != 0 && c->stream2 != nullptr;
-  const int halves = (stages & (VO_PIPE_TRACK_CANDIDATES | VO_PIPE_TRACK_LANDMARKS)) ? (((stages & VO_PIPE_TRACK_CANDIDATES) ? 1 : 0) | ((stages & VO_PIPE_TRACK_LANDMARKS) ? 2 : 0)) : 3;
+  const int halves = pipe_halves(stages);
   // (the stage combinations, the frame store and the resident sequence were checked by pipe_step_admit)
   if (stages & (VO_PIPE_TRACK | VO_PIPE_TRACK_LANDMARKS)) w->lm_half_pending = (stages & VO_PIPE_TRACK) && halves == 1;
   if (stages & VO_PIPE_TRACK) {
@@ -1525,21 +1509,12 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
     if (track_side && main_dirty) {
       // between two pipe steps the side stream needs no order against the main stream beyond the events below (that is the overlap); after
       // anything else (vo_frame_push_resident, a table write, another stage call: all asynchronous on the ctx stream) it starts behind it
-      VO_HIP(c, hipEventRecord(c->ev_fork, c->stream));
-      VO_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+      VO_HIP(c, vo_stream_fork(c->ev_fork, c->stream, c->stream2));
     }
     // (the pyramid on a stream of its own, ahead of the side stream's re-detection: measured, slower -- every cross-stream event costs more
     //  than the five launches it would overlap; one context of 96 sequences 37.5 k against 39.0 k frames/s, one sequence 2 320 against 2 715)
     hipStream_t const tq = track_side ? c->stream2 : c->stream;      // the stream of the pyramid and the tracker
-    if (from_host) {
-      const int slot = c->pipe_host_slot;
-      VO_HIP(c, hipStreamWaitEvent(tq, c->ev_h2d[slot], 0));
-      r = vo_build_pyramid(c, tq, c->d_host_raw[slot], (size_t)c->width * c->height, nullptr);
-      if (r == VO_OK && hipEventRecord(c->ev_raw_free[slot], tq) == hipSuccess) c->raw_free_recorded[slot] = true;
-    } else if (frame_idx >= 0) {
-      const size_t fr = (size_t)c->width * c->height;
-      r = vo_build_pyramid(c, tq, c->d_seq + (size_t)frame_idx * fr, fr * c->seq_n, nullptr);
-    }
+    if (has_frame) r = vo_frame_src_pyramid(c, tq, from_host ? vo_frame_src_host(c, c->pipe_host_slot) : vo_frame_src_resident(c, frame_idx, nullptr));
     const unsigned form = vo_klt_form(c);            // vo_set_fb_check: track with the forward-backward check; vo_set_klt_predict: seeded
     w->fb_active = form & KLT_FORM_FB;
     if (r == VO_OK && (form & KLT_FORM_SEEDED)) {    // the predictor right before the seeded tracker, on its stream
@@ -1551,12 +1526,9 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
       }
     }
     if (r == VO_OK) r = vo_klt_track_resident_enqueue(c, tq, w->N, &prm.klt, w->d_dn + DN_PTS * B, form);
-    if (track_side) {                                  // joined on every path
-      const hipError_t e1 = hipEventRecord(w->ev_track, c->stream2);
-      const hipError_t e2 = hipStreamWaitEvent(c->stream, w->ev_track, 0);
-      if (r == VO_OK) { VO_HIP(c, e1); VO_HIP(c, e2); }
-    }
+    const hipError_t ej = track_side ? vo_stream_join(w->ev_track, c->stream2, c->stream) : hipSuccess;      // joined on every path
     if (r != VO_OK) return r;
+    VO_HIP(c, ej);
   }
   // the keep rule / bookkeeping on the tracked point set: with TRACK, or alone (VO_PIPE_TRACK_LANDMARKS after a TRACK | VO_PIPE_TRACK_CANDIDATES call)
   if ((stages & VO_PIPE_TRACK) || (stages & (VO_PIPE_TRACK_CANDIDATES | VO_PIPE_TRACK_LANDMARKS))) {
@@ -1597,17 +1569,15 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
   ba_live.d_live = (const int32_t*)w->tab[VO_PIPE_COUNTS] + C_NLM; ba_live.live_stride = PIPE_NCNT;
   if (side) {
     // re-detection + spawn on the side stream behind promote / dense; adjustment + write-back on the main stream
-    VO_HIP(c, hipEventRecord(c->ev_fork, c->stream));
-    VO_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+    VO_HIP(c, vo_stream_fork(c->ev_fork, c->stream, c->stream2));
     r = (stages & VO_PIPE_DETECT) ? vo_shi_tomasi_resident_counts(c, c->stream2, w->N, prm.mask_radius, &prm.st, w->d_dn + DN_PTS * B, w->d_dn + DN_ROOM * B) : VO_OK;
     if (r == VO_OK && (stages & VO_PIPE_DETECT)) r = vo_subpix_refine_detected(c, c->stream2, prm.st.max_corners);     // vo_set_subpix: before the spawn
     if (r == VO_OK) pipe_launch_spawn(c, c->stream2, (stages & VO_PIPE_DETECT) ? 1 : 0, (stages & VO_PIPE_KEEP_FREE_LISTS) ? 0 : 1);
     if (r == VO_OK && (stages & VO_PIPE_ADJUST)) r = vo_ba_enqueue_budget(c, c->stream, &prm.ba, 0, prm.ba_budget, ba_live);
     if (r == VO_OK) PIPE_DISPATCH_LDS(k_pipe_writeback, 0, c->stream, P, (stages & VO_PIPE_ADJUST) ? 1 : 0, bv.pub, bv.pub_bytes, bv.x0, bv.x_stride, bv.W, w->d_rec);
-    const hipError_t e1 = hipEventRecord(c->ev_join, c->stream2);
-    const hipError_t e2 = hipStreamWaitEvent(c->stream, c->ev_join, 0);     // joined on every path: nothing is left running on the side stream
+    const hipError_t ej = vo_stream_join(c->ev_join, c->stream2, c->stream);     // joined on every path: nothing is left running on the side stream
     if (r != VO_OK) return r;
-    VO_HIP(c, e1); VO_HIP(c, e2);
+    VO_HIP(c, ej);
   } else {
     if (stages & VO_PIPE_ADJUST) {
       r = vo_ba_enqueue_budget(c, c->stream, &prm.ba, 0, prm.ba_budget, ba_live);

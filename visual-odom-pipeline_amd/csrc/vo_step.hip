@@ -60,23 +60,27 @@ struct step_cfg {
   vo_ba_params ba;
 };
 
+static bool step_trace_on() { static const bool on = getenv("VO_STEP_TRACE") != nullptr; return on; }
+
+int32_t vo_frame_src_pyramid(vo_ctx* c, hipStream_t q, const vo_frame_src& s) {
+  const int h = s.host_half;
+  if (h >= 0) VO_HIP(c, hipStreamWaitEvent(q, c->ev_h2d[h], 0));
+  const int32_t r = vo_build_pyramid(c, q, s.raw, s.seq_stride, s.d_frame_idx);
+  if (r != VO_OK || h < 0) return r;
+  VO_HIP(c, hipEventRecord(c->ev_raw_free[h], q));
+  c->raw_free_recorded[h] = true;
+  return VO_OK;
+}
+
 // enqueue everything of one frame (also used under stream capture: then all of it on the ctx stream); *recorded: ev_step[half] has been recorded
 // frame_idx < 0: the frames of this step arrive from the host in c->d_host_raw[half] (vo_frame_step_host: the upload runs on the copy stream,
 // ev_h2d[half] says when it is there)
-static bool step_trace_on() { static const bool on = getenv("VO_STEP_TRACE") != nullptr; return on; }
-
 static int32_t step_enqueue(vo_ctx* c, const step_cfg& s, const int32_t* d_frame_idx, int frame_idx, int half, bool* recorded) {
   int32_t r;
   *recorded = false;
   const bool trace_a = step_trace_on();
   if (trace_a && c->side_stream == 2) trace_push(g_ta, c->stream, 4000);
-  const size_t fr = (size_t)c->width * c->height;
-  if (frame_idx < 0) {
-    VO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_h2d[half], 0));
-    r = vo_build_pyramid(c, c->stream, c->d_host_raw[half], fr, nullptr);
-    if (r == VO_OK) { VO_HIP(c, hipEventRecord(c->ev_raw_free[half], c->stream)); c->raw_free_recorded[half] = true; }
-  } else if (d_frame_idx) r = vo_build_pyramid(c, c->stream, c->d_seq, fr * c->seq_n, d_frame_idx);
-  else r = vo_build_pyramid(c, c->stream, c->d_seq + (size_t)frame_idx * fr, fr * c->seq_n, nullptr);
+  r = vo_frame_src_pyramid(c, c->stream, frame_idx < 0 ? vo_frame_src_host(c, half) : vo_frame_src_resident(c, frame_idx, d_frame_idx));
   if (r != VO_OK) return r;
   if (trace_a && c->side_stream == 2) trace_push(g_tb, c->stream, 6000);
   // pipelined layout: the tracker's launch takes every free wave slot for its whole duration, the previous frame's LM chain would stand still
@@ -100,9 +104,7 @@ static int32_t step_enqueue(vo_ctx* c, const step_cfg& s, const int32_t* d_frame
     // the fork comes BEFORE A's result copy: device-to-host copies of all streams pass through the copy engine in submission
     // order, and the copies of the previous step (submitted earlier, waiting for ITS bundle adjustment) would hold this one -- and
     // with it the start of this step's bundle adjustment -- until that BA has finished (measured: 185 us of a 250 us frame)
-    VO_HIP(c, hipEventRecord(c->ev_fork, c->stream));
-    VO_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-    VO_HIP(c, hipStreamWaitEvent(c->stream3, c->ev_fork, 0));
+    VO_HIP(c, vo_stream_fork(c->ev_fork, c->stream, c->stream2, c->stream3));
     if (c->batch == 1) VO_HIP(c, hipMemcpyAsync(h_dst, c->d_slab, part1, hipMemcpyDeviceToHost, c->stream));
     else VO_HIP(c, hipMemcpy2DAsync(h_dst, c->slab_seq, c->d_slab, c->slab_seq, part1, c->batch, hipMemcpyDeviceToHost, c->stream));
     VO_HIP(c, hipEventRecord(c->ev_copy1[half], c->stream));
@@ -142,18 +144,10 @@ static int32_t step_enqueue(vo_ctx* c, const step_cfg& s, const int32_t* d_frame
   const bool fork = s.do_st && (s.do_dlt || s.do_ba) && !d_frame_idx && c->side_stream;
   const bool dlt_side = fork && s.do_dlt && s.do_ba;
   bool forked = false;
-  // every exit after the fork joins the side stream again: work queued there must stay ordered before whatever the caller
-  // enqueues (or frees) next on c->stream, also when a later enqueue fails
-  auto join = [&]() -> hipError_t {
-    if (!forked) return hipSuccess;
-    forked = false;
-    hipError_t e = hipEventRecord(c->ev_join, c->stream2);
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->ev_join, 0);
-    return e;
-  };
+  // every exit after the fork joins the side stream again (vo_stream_join)
+  auto join = [&]() { const bool f = forked; forked = false; return f ? vo_stream_join(c->ev_join, c->stream2, c->stream) : hipSuccess; };
   if (fork) {
-    VO_HIP(c, hipEventRecord(c->ev_fork, c->stream));
-    VO_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+    VO_HIP(c, vo_stream_fork(c->ev_fork, c->stream, c->stream2));
     forked = true;
     r = vo_shi_tomasi_resident_counts(c, c->stream2, s.n_pts, s.mask_radius, &s.st, c->d_pt_counts, nullptr);
     // the triangulation does not feed this frame's bundle adjustment (the BA problem is resident): beside a BA it goes to
@@ -228,8 +222,6 @@ __global__ __launch_bounds__(256) void k_gather_frames(const uint8_t* const* __r
   }
 }
 
-// the upload of a host-frame step on the copy stream into d_host_raw[half].  Page-locked images: the gather kernel; pageable ones: a copy per
-// image (runs of images that follow each other in host memory -- a [batch][h][w] array -- go as ONE copy), which the runtime stages
 // first use: the copy stream, the pointer table, both halves and their events -- made into locals and handed to the context only when every one
 // of them exists (a failure part way leaves no null resource behind for the next call to take as made)
 static int32_t host_frames_setup(vo_ctx* c) {
@@ -325,9 +317,14 @@ extern "C" int32_t vo_frame_step_host(vo_ctx* c, const uint8_t* const* frames, i
                                       int32_t do_st, int32_t mask_radius, const vo_klt_params* klt,
                                       const vo_st_params* st, const vo_ba_params* ba) {
   if (!c) return VO_E_INVALID;
-  VO_CHECK(c, frames != nullptr && stride >= c->width, VO_E_INVALID, "bad frame pointers / stride");
-  for (int b = 0; b < c->batch; b++) VO_CHECK(c, frames[b] != nullptr, VO_E_INVALID, "null frame pointer");
+  { const int32_t ra = vo_host_frames_admit(c, __func__, frames, stride); if (ra != VO_OK) return ra; }
   return frame_step(c, -1, frames, stride, n_pts, do_dlt, do_ba, do_st, mask_radius, klt, st, ba);
+}
+
+int32_t vo_host_frames_admit(vo_ctx* c, const char* who, const uint8_t* const* frames, int32_t stride) {
+  if (!frames || stride < c->width) return vo_fail(c, VO_E_INVALID, std::string(who) + ": bad frame pointers / stride");
+  for (int b = 0; b < c->batch; b++) if (!frames[b]) return vo_fail(c, VO_E_INVALID, std::string(who) + ": null frame pointer");
+  return VO_OK;
 }
 
 extern "C" int32_t vo_host_alloc(uint64_t bytes, void** out) {
@@ -340,6 +337,10 @@ extern "C" int32_t vo_host_free(void* p) {
   if (!p) return VO_OK;
   return hipHostFree(p) == hipSuccess ? VO_OK : VO_E_HIP;
 }
+
+// the host-side state the enqueue functions advance (frame / point parities, Shi-Tomasi launch flags): put back when a capture launched nothing
+struct step_host_state { int cur, n_pushed, p_parity, st_flags; };
+static void step_state_restore(vo_ctx* c, const step_host_state& s) { c->cur = s.cur; c->n_pushed = s.n_pushed; c->p_parity = s.p_parity; vo_st_flags_restore(c, s.st_flags); }
 
 static int32_t frame_step(vo_ctx* c, int32_t frame_idx, const uint8_t* const* host_frames, int32_t stride, int32_t n_pts, int32_t do_dlt, int32_t do_ba,
                           int32_t do_st, int32_t mask_radius, const vo_klt_params* klt, const vo_st_params* st, const vo_ba_params* ba) {
@@ -373,11 +374,7 @@ static int32_t frame_step(vo_ctx* c, int32_t frame_idx, const uint8_t* const* ho
   if (!graph_ok) {
     bool recorded = false;
     const int32_t r = step_enqueue(c, s, nullptr, frame_idx, half, &recorded);
-    if (r != VO_OK) {
-      // (error path) the step does not count, so its pointer-table row goes to the next one: let the gather finish reading it first
-      if (host_frames) (void)hipStreamSynchronize(c->stream_h2d);
-      return r;
-    }
+    if (r != VO_OK) { if (host_frames) vo_host_frames_abandon(c); return r; }
     if (!recorded) VO_HIP(c, hipEventRecord(c->ev_step[half], c->stream));
     c->steps_enq++;
     return VO_OK;
@@ -394,21 +391,20 @@ static int32_t frame_step(vo_ctx* c, int32_t frame_idx, const uint8_t* const* ho
       c->step_graphs.clear();
     }
     hipGraph_t g = nullptr;
-    const int cur0 = c->cur, pushed0 = c->n_pushed, parity0 = c->p_parity, st0 = vo_st_flags_save(c);
+    const step_host_state before = {c->cur, c->n_pushed, c->p_parity, vo_st_flags_save(c)};
     VO_HIP(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     bool recorded = false;
     const int32_t r = step_enqueue(c, s, c->d_frame_idx, frame_idx, half, &recorded);
     const hipError_t e = hipStreamEndCapture(c->stream, &g);
     if (r != VO_OK || e != hipSuccess) {
-      // nothing was launched: undo what the enqueue functions did to the host-side frame / point parities and launch flags
-      c->cur = cur0; c->n_pushed = pushed0; c->p_parity = parity0; vo_st_flags_restore(c, st0);
+      step_state_restore(c, before);
       if (g) (void)hipGraphDestroy(g);
       if (r != VO_OK) return r;
     }
     VO_HIP(c, e);
     const hipError_t ei = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
-    if (ei != hipSuccess) { c->cur = cur0; c->n_pushed = pushed0; c->p_parity = parity0; vo_st_flags_restore(c, st0); }
+    if (ei != hipSuccess) step_state_restore(c, before);
     VO_HIP(c, ei);
     c->step_graphs.emplace_back(sig, exec);
   } else {
@@ -508,23 +504,28 @@ static int32_t step_layout_apply(vo_ctx* c) {
   return vo_main_stream_reserve(c, reserve);
 }
 
+// first use of the pipelined layout: stream C and its steps' four event pairs.  On demand (streams share the hardware queues: a third, idle stream per context
+// re-deals which share one -- three batched contexts lost 10 % to it), all or nothing like host_frames_setup (vo_ctx_destroy releases exactly these)
+static int32_t pipelined_setup(vo_ctx* c) {
+  hipEvent_t (*const pairs[4])[2] = {&c->ev_ba_wide, &c->ev_ba, &c->ev_pub, &c->ev_copy1};
+  hipStream_t st = nullptr; hipEvent_t ev[8] = {};
+  VO_HIP(c, hipSetDevice(c->device));
+  hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);     // (a highest-priority stream for the BA chain: no difference)
+  for (int i = 0; i < 8 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+  if (e != hipSuccess) {
+    for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+    if (st) (void)hipStreamDestroy(st);
+    VO_HIP(c, e);
+  }
+  for (int i = 0; i < 8; i++) (*pairs[i / 2])[i % 2] = ev[i];
+  c->stream3 = st;                            // last: the key of the first-use test
+  return VO_OK;
+}
+
 extern "C" int32_t vo_set_side_stream(vo_ctx* c, int32_t on) {
   if (!c) return VO_E_INVALID;
   VO_CHECK(c, c->steps_enq == c->steps_fetched && !vo_pipe_busy(c), VO_E_STATE, "fetch the steps in flight before switching the stream layout");
-  if (on == 2 && !c->stream3) {
-    // created on demand: streams share the hardware queues, and a third (idle) stream per context re-deals which of them share one --
-    // three batched contexts lost 10 % of their throughput to it
-    VO_HIP(c, hipSetDevice(c->device));
-    VO_HIP(c, hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));     // (a highest-priority stream for the BA chain: no difference)
-    VO_HIP(c, hipEventCreateWithFlags(&c->ev_ba_wide[0], hipEventDisableTiming));
-    VO_HIP(c, hipEventCreateWithFlags(&c->ev_ba_wide[1], hipEventDisableTiming));
-    VO_HIP(c, hipEventCreateWithFlags(&c->ev_ba[0], hipEventDisableTiming));
-    VO_HIP(c, hipEventCreateWithFlags(&c->ev_ba[1], hipEventDisableTiming));
-    VO_HIP(c, hipEventCreateWithFlags(&c->ev_pub[0], hipEventDisableTiming));
-    VO_HIP(c, hipEventCreateWithFlags(&c->ev_pub[1], hipEventDisableTiming));
-    VO_HIP(c, hipEventCreateWithFlags(&c->ev_copy1[0], hipEventDisableTiming));
-    VO_HIP(c, hipEventCreateWithFlags(&c->ev_copy1[1], hipEventDisableTiming));
-  }
+  if (on == 2 && !c->stream3) { const int32_t rs = pipelined_setup(c); if (rs != VO_OK) return rs; }
   c->side_stream = (on == 2) ? 2 : (on ? 1 : 0);      // 2: pipelined (BA of frame t beside the front end of frame t + 1)
   return step_layout_apply(c);
 }
