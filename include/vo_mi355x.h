@@ -507,6 +507,24 @@ int32_t vo_pnp_fetch(vo_ctx* ctx, double* rvec, double* tvec, uint8_t* inlier_ma
  * with 5 model points; the best model is returned as found (OpenCV does not re-fit); then the four (R, t)
  * candidates of E and OpenCV's cheirality vote by DLT triangulation of the inliers.  Sample draws differ from
  * OpenCV's: statistical parity; the algorithm is defined by oracle/essential_oracle.py.
+ * Every root of the 10th-degree determinant is refined by up to 12 Gauss-Newton steps on the ten cubic constraints (in the
+ * unit 4-vector of null-space coordinates), since the determinant alone loses up to half the digits of a root.  Measured
+ * against an independent float64 model (tests/essential_model.py) on general, forward, sideways, rotating, planar,
+ * fronto-parallel and wide-angle five-point sets (32 sets, 164 real roots): every root that comes back is within
+ * 0.4 x 2^-52 / sigma of an exact root (sigma = smallest singular value of the full system's Jacobian): |E - E_k| <= 1.1e-13
+ * on general, forward, sideways, rotating and wide-angle sets (sigma 7e-5 .. 7e-2), <= 5.6e-13 on planar and 1.9e-13 on
+ * fronto-parallel ones (sigma 2e-5 .. 2e-3); without the refinement 25 of 164 roots were off by more than 1e6 of those
+ * units, up to 0.34 in E.  Completeness holds for the search, not for a single sample: every one of the 164 roots is
+ * reached through the 256 samples of a round (they draw the same points in many orders), but one solve can miss a
+ * root -- on 2 of the 32 sets (both fronto-parallel) it returned 5 of 6: two roots 2e-3 apart in the hidden variable
+ * leave the determinant 1e-2 off, both refinements run into the same root, and the same E is then listed twice.
+ * Tie rule of the cheirality vote: ties at a non-zero count keep OpenCV's order of preference (R1 = U W V^T before
+ * R2 = U W^T V^T, +t before -t, in the labelling of this library's Jacobi SVD).  When all four counts are 0 the choice
+ * is a property of E alone: the rotation with the larger trace (the smaller angle), then the t with E = +[t]x R.
+ * distance_thresh = 50 (OpenCV's) counts a point only if its depth is under 50 BASELINES in both views, so with a
+ * baseline under 2 % of the scene depth every point lies beyond it, all four candidates score 0, n_good = 0 and only
+ * the tie rule picks the pose (t is then no more than a sign convention): a bootstrap frame pair must have a baseline
+ * over 2 % of the depth of its points.
  * K [batch][9]; pts1, pts2 [batch][n][2] f32 pixels (NaN rows are never inliers); E [batch][9] (unit Frobenius norm,
  * may be NULL), R [batch][9], t [batch][3] (|t| = 1, x2 ~ R x1 + t); inlier_mask [batch][n] u8 (may be NULL). */
 int32_t vo_essential_default_params(vo_ess_params* p);

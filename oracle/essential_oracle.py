@@ -12,12 +12,14 @@ vectors of it exist here.  Restated from the published algorithm and the call's 
   * minimal solver: Nister, "An efficient solution to the five-point relative pose problem" (PAMI 2004): 4-dimensional
     null space of the 5 epipolar constraints, the 10 cubic constraints det E = 0 and 2 E E^T E - tr(E E^T) E = 0 as a
     10 x 20 matrix, Gauss-Jordan elimination, the 3 x 3 polynomial matrix B(z) and its 10th-degree determinant, one
-    essential matrix per real root (<= 10 per sample);
+    essential matrix per real root (<= 10 per sample); the determinant loses up to half the digits of a root, so each is
+    refined by Gauss-Newton on the ten cubics in the unit 4-vector of null-space coordinates (refine_root);
   * consensus: squared Sampson distance <= threshold^2; the iteration bound follows RANSACUpdateNumIters with 5 model
     points, default bound 1000; the best model is returned as it is (OpenCV does not re-fit either);
   * recoverPose: E = U diag(1,1,0) V^T, the four (R, t) candidates, DLT triangulation of every inlier against
     [I | 0], a point is "good" when its depth is in (0, distance_thresh = 50) in both cameras, most good points win
-    (OpenCV's order of preference on ties).
+    (OpenCV's order of preference on ties; when all four counts are 0 the rotation with the larger trace and the t with
+    E = +[t]x R, a choice that does not depend on how the SVD labels its vectors).
 This file DEFINES what csrc/vo_essential.hip implements (hypothesis h = 5 indices from splitmix64(seed, h, draw),
 roots in ascending order, batches of 256 hypotheses, ties to the smallest (h, root)) so that the two can be compared
 hypothesis by hypothesis.  Real roots are isolated between the critical points of the polynomial (recursively through
@@ -219,6 +221,114 @@ def real_roots(p):
     return roots
 
 
+NEWTON_STEPS = 12
+
+
+def cubics(E):
+    """the ten constraints at a 3 x 3 E given as 9 numbers: 2 E E^T E - tr(E E^T) E (9) and det E"""
+    G = [0.0] * 9                                        # E E^T
+    for i in range(3):
+        for j in range(3):
+            G[3 * i + j] = (E[3 * i] * E[3 * j] + E[3 * i + 1] * E[3 * j + 1]) + E[3 * i + 2] * E[3 * j + 2]
+    tr = (G[0] + G[4]) + G[8]
+    c = [0.0] * 10
+    for i in range(3):
+        for j in range(3):
+            c[3 * i + j] = 2.0 * ((G[3 * i] * E[j] + G[3 * i + 1] * E[3 + j]) + G[3 * i + 2] * E[6 + j]) - tr * E[3 * i + j]
+    c[9] = (E[0] * (E[4] * E[8] - E[5] * E[7]) - E[1] * (E[3] * E[8] - E[5] * E[6])) + E[2] * (E[3] * E[7] - E[4] * E[6])
+    return c
+
+
+def cubics_dir(E, D):
+    """directional derivative of cubics() at E along D"""
+    G, H = [0.0] * 9, [0.0] * 9                           # E E^T and D E^T + E D^T
+    for i in range(3):
+        for j in range(3):
+            G[3 * i + j] = (E[3 * i] * E[3 * j] + E[3 * i + 1] * E[3 * j + 1]) + E[3 * i + 2] * E[3 * j + 2]
+            H[3 * i + j] = ((D[3 * i] * E[3 * j] + D[3 * i + 1] * E[3 * j + 1]) + D[3 * i + 2] * E[3 * j + 2]) + \
+                ((E[3 * i] * D[3 * j] + E[3 * i + 1] * D[3 * j + 1]) + E[3 * i + 2] * D[3 * j + 2])
+    tr, dtr = (G[0] + G[4]) + G[8], (H[0] + H[4]) + H[8]
+    c = [0.0] * 10
+    for i in range(3):
+        for j in range(3):
+            c[3 * i + j] = 2.0 * (((H[3 * i] * E[j] + H[3 * i + 1] * E[3 + j]) + H[3 * i + 2] * E[6 + j]) +
+                                  ((G[3 * i] * D[j] + G[3 * i + 1] * D[3 + j]) + G[3 * i + 2] * D[6 + j])) - (dtr * E[3 * i + j] + tr * D[3 * i + j])
+    c[9] = ((D[0] * (E[4] * E[8] - E[5] * E[7]) - D[1] * (E[3] * E[8] - E[5] * E[6])) + D[2] * (E[3] * E[7] - E[4] * E[6])) + \
+        ((E[0] * ((D[4] * E[8] + E[4] * D[8]) - (D[5] * E[7] + E[5] * D[7])) - E[1] * ((D[3] * E[8] + E[3] * D[8]) - (D[5] * E[6] + E[5] * D[6]))) +
+         E[2] * ((D[3] * E[7] + E[3] * D[7]) - (D[4] * E[6] + E[4] * D[6])))
+    return c
+
+
+def refine_root(basis, x, y, z):
+    """up to NEWTON_STEPS Gauss-Newton steps on the ten cubics in the unit 4-vector w, E = w0 B0 + w1 B1 + w2 B2 + w3 B3 (the epipolar
+    equations hold by construction; homogeneous, so a root with a small last coordinate is as well scaled as any other): the normal equations
+    of the 10 x 4 Jacobian with the row w for |w| = 1, solved by Cholesky.  The iterate with the smallest sum of squares is returned, so a
+    step that does not help changes nothing.  The 10th-degree determinant loses up to half the digits of a root; this restores them.
+    -> w (4)"""
+    nn = math.sqrt(((x * x + y * y) + z * z) + 1.0)
+    w = [x / nn, y / nn, z / nn, 1.0 / nn]
+    best, last = None, False
+    for it in range(NEWTON_STEPS + 1):
+        E = [((w[0] * basis[0][k] + w[1] * basis[1][k]) + w[2] * basis[2][k]) + w[3] * basis[3][k] for k in range(9)]
+        c = cubics(E)
+        f = 0.0
+        for k in range(10):
+            f += c[k] * c[k]
+        if not math.isfinite(f):
+            break
+        if best is None or f < best[0]:
+            best = (f, list(w))
+        if last or it == NEWTON_STEPS:
+            break
+        J = [cubics_dir(E, basis[v]) for v in range(4)]
+        r = 0.5 * ((((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]) + w[3] * w[3]) - 1.0)
+        H = [[0.0] * 4 for _ in range(4)]
+        g = [0.0] * 4
+        for a in range(4):
+            for k in range(10):
+                g[a] += J[a][k] * c[k]
+            g[a] += w[a] * r
+            for b in range(a + 1):
+                h = 0.0
+                for k in range(10):
+                    h += J[a][k] * J[b][k]
+                H[a][b] = h + w[a] * w[b]
+        ok = True                                            # Cholesky H = L L^T in place (lower triangle), then two triangular solves
+        for a in range(4):
+            for b in range(a + 1):
+                v = H[a][b]
+                for k in range(b):
+                    v -= H[a][k] * H[b][k]
+                if a == b:
+                    if not v > 0:
+                        ok = False
+                        break
+                    H[a][a] = math.sqrt(v)
+                else:
+                    H[a][b] = v / H[b][b]
+            if not ok:
+                break
+        if not ok:
+            break
+        for a in range(4):
+            v = g[a]
+            for k in range(a):
+                v -= H[a][k] * g[k]
+            g[a] = v / H[a][a]
+        for a in range(3, -1, -1):
+            v = g[a]
+            for k in range(a + 1, 4):
+                v -= H[k][a] * g[k]
+            g[a] = v / H[a][a]
+        step = 0.0
+        for a in range(4):
+            w[a] = w[a] - g[a]
+            step = max(step, abs(g[a]))
+        if step <= 1e-15:
+            last = True                                      # converged: one more evaluation, no more steps
+    return best[1] if best is not None else w
+
+
 def five_point(q1, q2):
     """q1, q2: 5 x 2 normalised image points.  -> list of 3 x 3 essential matrices (Frobenius norm 1), ascending z."""
     basis = null_space_5x9(q1, q2)
@@ -254,8 +364,8 @@ def five_point(q1, q2):
                 best, nv = nn, c
         if not best > 0 or abs(nv[2]) <= 1e-10 * math.sqrt(best):
             continue
-        x, y = nv[0] / nv[2], nv[1] / nv[2]
-        E = [x * basis[0][k] + y * basis[1][k] + z * basis[2][k] + basis[3][k] for k in range(9)]
+        w = refine_root(basis, nv[0] / nv[2], nv[1] / nv[2], z)
+        E = [((w[0] * basis[0][k] + w[1] * basis[1][k]) + w[2] * basis[2][k]) + w[3] * basis[3][k] for k in range(9)]
         nn = math.sqrt(sum(v * v for v in E))
         if not nn > 0 or not math.isfinite(nn):
             continue
@@ -322,6 +432,13 @@ def recover_pose(E, q1, q2, dist=50.0):
         k = 2
     else:
         k = 3
+    if g1 == 0 and g2 == 0 and g3 == 0 and g4 == 0:
+        # no candidate has a good point: which of R1 / R2 is which depends on the SVD's labelling, so the choice is made a property of E:
+        # the rotation with the larger trace (the smaller angle), then the t with E = +[t]x R
+        r = 1 if np.trace(R2) > np.trace(R1) else 0
+        R = cands[r][0]
+        tx = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+        k = r + (2 if np.sum((tx @ R) * np.asarray(E)) < 0 else 0)
     return cands[k][0], cands[k][1], good[k], good
 
 

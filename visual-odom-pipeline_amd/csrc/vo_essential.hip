@@ -9,7 +9,8 @@
 // 5 model points, OpenCV's four-candidate cheirality vote) and is compared with it hypothesis by hypothesis.
 //
 // GPU mapping (as for the 3D-2D pose, vo_pnp.hip): a LANE per hypothesis for the minimal solve -- null space, 10 x 20
-// constraint matrix, Gauss-Jordan, 10th-degree polynomial, real roots by bisection between critical points; all of it in
+// constraint matrix, Gauss-Jordan, 10th-degree polynomial, real roots by bisection between critical points, Gauss-Newton
+// refinement of every root on the ten cubics; all of it in
 // per-lane scratch arrays, it runs 256 x once per call -- then a WAVE per (hypothesis, root) for the consensus count,
 // one workgroup per sequence for the running best / iteration bound, and one for the cheirality vote.
 // The arithmetic follows the oracle operation by operation (this library is built with -ffp-contract=off).
@@ -243,6 +244,99 @@ __device__ inline int e5_real_roots(const double* p, int len, double* roots) {
   return nr;
 }
 
+#define E5_NEWTON_STEPS 12
+
+// the ten constraints at E: 2 E E^T E - tr(E E^T) E (9) and det E (oracle: cubics)
+__device__ inline void e5_cubics(const double* E, double* c) {
+  double G[9];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) G[3 * i + j] = (E[3 * i] * E[3 * j] + E[3 * i + 1] * E[3 * j + 1]) + E[3 * i + 2] * E[3 * j + 2];
+  const double tr = (G[0] + G[4]) + G[8];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++)
+      c[3 * i + j] = 2.0 * ((G[3 * i] * E[j] + G[3 * i + 1] * E[3 + j]) + G[3 * i + 2] * E[6 + j]) - tr * E[3 * i + j];
+  c[9] = (E[0] * (E[4] * E[8] - E[5] * E[7]) - E[1] * (E[3] * E[8] - E[5] * E[6])) + E[2] * (E[3] * E[7] - E[4] * E[6]);
+}
+
+// directional derivative of e5_cubics at E along D (oracle: cubics_dir)
+__device__ inline void e5_cubics_dir(const double* E, const double* D, double* c) {
+  double G[9], H[9];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      G[3 * i + j] = (E[3 * i] * E[3 * j] + E[3 * i + 1] * E[3 * j + 1]) + E[3 * i + 2] * E[3 * j + 2];
+      H[3 * i + j] = ((D[3 * i] * E[3 * j] + D[3 * i + 1] * E[3 * j + 1]) + D[3 * i + 2] * E[3 * j + 2]) +
+                     ((E[3 * i] * D[3 * j] + E[3 * i + 1] * D[3 * j + 1]) + E[3 * i + 2] * D[3 * j + 2]);
+    }
+  const double tr = (G[0] + G[4]) + G[8], dtr = (H[0] + H[4]) + H[8];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++)
+      c[3 * i + j] = 2.0 * (((H[3 * i] * E[j] + H[3 * i + 1] * E[3 + j]) + H[3 * i + 2] * E[6 + j]) +
+                            ((G[3 * i] * D[j] + G[3 * i + 1] * D[3 + j]) + G[3 * i + 2] * D[6 + j])) - (dtr * E[3 * i + j] + tr * D[3 * i + j]);
+  c[9] = ((D[0] * (E[4] * E[8] - E[5] * E[7]) - D[1] * (E[3] * E[8] - E[5] * E[6])) + D[2] * (E[3] * E[7] - E[4] * E[6])) +
+         ((E[0] * ((D[4] * E[8] + E[4] * D[8]) - (D[5] * E[7] + E[5] * D[7])) - E[1] * ((D[3] * E[8] + E[3] * D[8]) - (D[5] * E[6] + E[5] * D[6]))) +
+          E[2] * ((D[3] * E[7] + E[3] * D[7]) - (D[4] * E[6] + E[4] * D[6])));
+}
+
+// up to E5_NEWTON_STEPS Gauss-Newton steps on the ten cubics in the unit 4-vector w, E = w0 B0 + w1 B1 + w2 B2 + w3 B3 (homogeneous, so a
+// root with a small last coordinate is as well scaled as any other): normal equations of the 10 x 4 Jacobian with the row w for |w| = 1,
+// Cholesky; the iterate with the smallest sum of squares is kept (oracle: refine_root).  The 10th-degree determinant loses up to half the
+// digits of a root; this restores them.
+__device__ inline void e5_refine(const double basis[4][9], double x, double y, double z, double* wout) {
+  const double nn = sqrt(((x * x + y * y) + z * z) + 1.0);
+  double w[4] = {x / nn, y / nn, z / nn, 1.0 / nn};
+  double bf = 0.0;
+  bool have = false, last = false;
+  for (int k = 0; k < 4; k++) wout[k] = w[k];
+  for (int it = 0; it <= E5_NEWTON_STEPS; it++) {
+    double E[9], c[10], f = 0.0;
+    for (int k = 0; k < 9; k++) E[k] = ((w[0] * basis[0][k] + w[1] * basis[1][k]) + w[2] * basis[2][k]) + w[3] * basis[3][k];
+    e5_cubics(E, c);
+    for (int k = 0; k < 10; k++) f += c[k] * c[k];
+    if (!(f < __builtin_inf())) break;                                  // inf or NaN
+    if (!have || f < bf) { have = true; bf = f; for (int k = 0; k < 4; k++) wout[k] = w[k]; }
+    if (last || it == E5_NEWTON_STEPS) break;
+    double J[4][10], H[4][4], g[4];
+    for (int v = 0; v < 4; v++) e5_cubics_dir(E, basis[v], J[v]);
+    const double r = 0.5 * ((((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]) + w[3] * w[3]) - 1.0);
+    for (int a = 0; a < 4; a++) {
+      g[a] = 0.0;
+      for (int k = 0; k < 10; k++) g[a] += J[a][k] * c[k];
+      g[a] += w[a] * r;
+      for (int b = 0; b <= a; b++) {
+        double h = 0.0;
+        for (int k = 0; k < 10; k++) h += J[a][k] * J[b][k];
+        H[a][b] = h + w[a] * w[b];
+      }
+    }
+    bool ok = true;                                                     // Cholesky H = L L^T in place (lower triangle)
+    for (int a = 0; a < 4 && ok; a++)
+      for (int b = 0; b <= a; b++) {
+        double v = H[a][b];
+        for (int k = 0; k < b; k++) v -= H[a][k] * H[b][k];
+        if (a == b) {
+          if (!(v > 0)) { ok = false; break; }
+          H[a][a] = sqrt(v);
+        } else {
+          H[a][b] = v / H[b][b];
+        }
+      }
+    if (!ok) break;
+    for (int a = 0; a < 4; a++) {
+      double v = g[a];
+      for (int k = 0; k < a; k++) v -= H[a][k] * g[k];
+      g[a] = v / H[a][a];
+    }
+    for (int a = 3; a >= 0; a--) {
+      double v = g[a];
+      for (int k = a + 1; k < 4; k++) v -= H[k][a] * g[k];
+      g[a] = v / H[a][a];
+    }
+    double step = 0.0;
+    for (int a = 0; a < 4; a++) { w[a] = w[a] - g[a]; step = fmax(step, fabs(g[a])); }
+    if (step <= 1e-15) last = true;                                     // converged: one more evaluation, no more steps
+  }
+}
+
 // Nister five-point: -> number of essential matrices (unit Frobenius norm, ascending z) written to Eout
 __device__ inline int e5_five_point(const double q1[5][2], const double q2[5][2], double Eout[E5_MAXSOL][9]) {
   double basis[4][9];
@@ -287,9 +381,10 @@ __device__ inline int e5_five_point(const double q1[5][2], const double q2[5][2]
       if (nn > best) { best = nn; nv[0] = c0; nv[1] = c1; nv[2] = c2; }
     }
     if (!(best > 0) || fabs(nv[2]) <= 1e-10 * sqrt(best)) continue;
-    const double x = nv[0] / nv[2], y = nv[1] / nv[2];
+    double w[4];
+    e5_refine(basis, nv[0] / nv[2], nv[1] / nv[2], z, w);
     double E[9], nn = 0.0;
-    for (int k = 0; k < 9; k++) { E[k] = x * basis[0][k] + y * basis[1][k] + z * basis[2][k] + basis[3][k]; nn += E[k] * E[k]; }
+    for (int k = 0; k < 9; k++) { E[k] = ((w[0] * basis[0][k] + w[1] * basis[1][k]) + w[2] * basis[2][k]) + w[3] * basis[3][k]; nn += E[k] * E[k]; }
     nn = sqrt(nn);
     if (!(nn > 0) || !(nn < __builtin_inf())) continue;
     for (int k = 0; k < 9; k++) Eout[ns][k] = E[k] / nn;
@@ -459,7 +554,8 @@ __device__ inline void e5_triangulate(const double* R, const double* t, double x
 }
 
 // E = U diag(s, s, 0) V^T by one-sided Jacobi on the columns; u2 = u0 x u1, v2 = v0 x v1 (det U = det V = +1)
-// -> R1 = U W V^T, R2 = U W^T V^T, t = u2 (OpenCV decomposeEssentialMat up to the sign conventions of its SVD)
+// -> R1 = U W V^T, R2 = U W^T V^T, t = u2 (OpenCV decomposeEssentialMat up to the labelling of its SVD: which rotation is R1 and the sign of
+// t follow the order and signs of u0, u1; k_e5_finish makes the one case where that would show, a four-way tie, independent of it)
 __device__ inline void e5_decompose(const double* E, double* R1, double* R2, double* t) {
   double U[3][3], V[3][3];
   for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { U[i][j] = E[3 * i + j]; V[i][j] = (i == j) ? 1.0 : 0.0; }
@@ -558,6 +654,19 @@ __global__ void __launch_bounds__(256) k_e5_finish(const double* __restrict__ q,
     else if (g[1] >= g[0] && g[1] >= g[2] && g[1] >= g[3]) k = 1;
     else if (g[2] >= g[0] && g[2] >= g[1] && g[2] >= g[3]) k = 2;
     else k = 3;
+    if (g[0] == 0 && g[1] == 0 && g[2] == 0 && g[3] == 0) {
+      // no candidate has a good point (no baseline to speak of): which of R1 / R2 is which depends on the SVD's labelling, so the choice
+      // is made a property of E: the rotation with the larger trace (the smaller angle), then the t with E = +[t]x R
+      const int r = ((s_R[1][0] + s_R[1][4]) + s_R[1][8] > (s_R[0][0] + s_R[0][4]) + s_R[0][8]) ? 1 : 0;
+      const double* R = s_R[r];
+      double dot = 0.0;
+      for (int j = 0; j < 3; j++) {
+        dot += (s_t[1] * R[6 + j] - s_t[2] * R[3 + j]) * cs.E[j];
+        dot += (s_t[2] * R[j] - s_t[0] * R[6 + j]) * cs.E[3 + j];
+        dot += (s_t[0] * R[3 + j] - s_t[1] * R[j]) * cs.E[6 + j];
+      }
+      k = r + ((dot < 0) ? 2 : 0);
+    }
     for (int i = 0; i < 9; i++) { out[i] = cs.E[i]; out[9 + i] = s_R[k & 1][i]; }
     for (int i = 0; i < 3; i++) out[18 + i] = ((k & 2) ? -1.0 : 1.0) * s_t[i];
     out[21] = (double)g[4]; out[22] = (double)g[k];
