@@ -538,7 +538,14 @@ int32_t vo_essential_ransac(vo_ctx* ctx, const double* K, const float* pts1, con
  * frames of Pipeline._get_init_state, src/pipeline/pipeline.py:48-49): doubled base image, Gaussian / DoG scale space
  * (3 layers per octave, sigma 1.6), 26-neighbour extrema, quadratic refinement with contrast (0.04) and edge (10)
  * tests, orientation histogram peaks, removeDuplicatedSorted + retainBest(nfeatures), 4 x 4 x 8 descriptors scaled to
- * 0..255.  The float32 operation order is defined by oracle/sift_oracle.py (parity with OpenCV itself is unpinned).
+ * 0..255.  The float32 operation order is defined by oracle/sift_oracle.py; the algorithm is pinned to an independent
+ * float64 model and to scale-space truths (tests/sift_model.py, tests/test_gpu_sift_model.py).  Conventions, as in
+ * OpenCV 4.4: a feature at pixel centre (cx, cy) is reported at (cx + 0.25, cy + 0.25) -- createInitialImage doubles
+ * the image with INTER_LINEAR, whose sample d sits at (d + 0.5) / 2 - 0.5 of the source, and the halved keypoints keep
+ * that quarter pixel (later OpenCV: enable_precise_upscale); angle = direction of the intensity gradient in degrees,
+ * from +x towards +y with y pointing down, atan2(gy_down, gx) mod 360.  Unpinned without OpenCV itself: the float
+ * summation order inside its SIMD filters, and compute() rebuilding the pyramid from the keypoints' lowest octave
+ * when no first-octave keypoint survives (here the descriptors always come from the detection pyramid).
  * img [batch][height][stride] u8 (the context's image size); mask the same layout or NULL (0 = drop the keypoint);
  * kps [batch][max_out]; desc [batch][max_out][128] f32; n_out [batch].  VO_E_CAPACITY if max_out is too small. */
 int32_t vo_sift_detect_compute(vo_ctx* ctx, const uint8_t* img, int32_t stride, const uint8_t* mask, int32_t nfeatures,

@@ -4,20 +4,33 @@ Reference call site: Extractor.extract(img, t, detector='custom', describe=True)
 /root/reference/src/extractor/extractor.py:26-28 (cv2.SIFT_create(nfeatures=1000)), :114-122 (detect, compute);
 used once per sequence by Pipeline._get_init_state, pipeline.py:48-49 (SURVEY.md 8f "next" row 4).
 
-PARITY STATUS: *** unpinned ***.  The arithmetic lives in OpenCV 4.4.0 (modules/features2d/src/sift.dispatch.cpp,
-sift.simd.hpp, imgproc smooth / resize), which is absent here, and the reference holds no vectors for it.  This file
-restates that implementation from its published structure (Lowe 2004 + OpenCV's constants and control flow):
+PARITY STATUS: the ALGORITHM is pinned, OpenCV's own rounding is not.  OpenCV 4.4.0 (modules/features2d/src/sift.dispatch.cpp,
+sift.simd.hpp, imgproc smooth / resize) is absent here and the reference holds no vectors for it; this file restates it from its published
+structure (Lowe 2004 + OpenCV's constants and control flow):
   createInitialImage (float image, 2x INTER_LINEAR upsample, blur to sigma 1.6), buildGaussianPyramid (nOctaveLayers + 3
   images per octave, incremental separable Gaussian blurs with kernel size cvRound(8 sigma + 1) | 1, REFLECT_101, next
   octave by INTER_NEAREST decimation), DoG, 26-neighbour extrema above floor(0.5 * 0.04 / 3 * 255), adjustLocalExtrema
   (<= 5 quadratic-fit steps, contrast and edge tests), calcOrientationHist (36 bins, fastAtan2 polynomial, [1 4 6 4 1] / 16
   smoothing, peaks >= 0.8 max with parabolic interpolation), KeyPointsFilter::removeDuplicatedSorted + retainBest(1000),
   first-octave rescale, calcSIFTDescriptor (4 x 4 x 8 trilinear histogram, 0.2 clamp, x 512, saturate to uchar).
-Deviations that cannot be resolved without OpenCV itself (rounding level only): float summation order inside the separable
-filter (here: centre tap, then symmetric pairs outward), the Gaussian kernel from double exp instead of softdouble,
-exp / cos / sin / pow evaluated in float64 and rounded to float32 (OpenCV: its own float32 SIMD approximations), the
-3 x 3 solve by Cramer's rule in float32.  fastAtan2 is OpenCV's own polynomial.  The final keypoint ORDER (unspecified in
-OpenCV after nth_element) is the removeDuplicatedSorted order.
+What pins it: tests/sift_model.py, a float64 model of the same published structure that shares only data with this file (constants, fastAtan2
+coefficients, KeyPoint_LessThan) and reaches every result by another route, with a margin on every discrete decision; this file (CPU,
+tests/test_sift_model.py) and the kernel (tests/test_gpu_sift_model.py) pass through the same verdict functions, and both answer to scale-space
+truths: Gaussian blobs (origin, size, octave), blobs on ramps (angle), transposed / negated / translated images (axes, descriptor cell layout).
+Pinned conventions:
+  * origin: a feature at pixel centre (cx, cy) is reported at (cx + 0.25, cy + 0.25).  That is OpenCV 4.4's own: createInitialImage doubles with
+    INTER_LINEAR (sample d of the doubled image sits at (d + 0.5) / 2 - 0.5) and the halved keypoints keep the quarter pixel; later versions grew
+    enable_precise_upscale for it.  Behaviour to keep (drop-in for 4.4), not to fix.
+  * angle: the direction of the intensity gradient in degrees from +x towards +y with y pointing DOWN, atan2(gy_down, gx) mod 360.
+  * fastAtan2 is 0.0095 degrees short at 45 degrees, so it jumps by 0.019 degrees where |dx| = |dy|; 45 degrees is a histogram bin boundary, so
+    on corners of axis-aligned blocks (|dx| = |dy| by symmetry) rounding decides the bin of whole rows of samples and the angle moves by ~0.5
+    degrees.  Inherent to OpenCV's histogram; the model carries it as a per-keypoint angle slack.
+Still unpinned without OpenCV itself (rounding level only): float summation order inside its SIMD separable filter (here: centre tap, then
+symmetric pairs outward), the Gaussian kernel from double exp instead of softdouble, exp / cos / sin / pow evaluated in float64 and rounded to
+float32 (OpenCV: its own float32 SIMD approximations), the 3 x 3 solve by Cramer's rule in float32; and compute() rebuilding the pyramid from
+the keypoints' lowest octave when no first-octave keypoint survives (here the descriptors always come from the detection pyramid; with a first
+octave of -1 present, as on every textured image, the two are the same).  The final keypoint ORDER (unspecified in OpenCV after nth_element) is
+the removeDuplicatedSorted order.
 This file DEFINES what csrc/vo_sift.hip implements; every float32 operation is written so that the GPU can follow it
 operation by operation (no fused multiply-add, sequential histogram accumulation in sample order).
 """
