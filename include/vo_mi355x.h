@@ -67,7 +67,16 @@ typedef struct {
                                 the response map is unchanged.
                                 A frame whose largest masked response is not positive yields no corners here (OpenCV would rank negative
                                 responses). */
-  int32_t _pad;
+  int32_t fast_threshold;    /* 0: the response above (the default; what every caller that leaves the field alone gets, bit for bit).
+                                1..254: the response is the FAST-9/16 corner score at threshold t = fast_threshold, what
+                                cv2.FastFeatureDetector_create(t, True, TYPE_9_16) reports as a keypoint's `response`: with d_k the 16 differences
+                                ring pixel - centre on the radius-3 circle, m = max over the 16 arcs of 9 consecutive k of
+                                max(min d, min -d); a pixel at least 3 from every border with m > t scores m - 1 (the largest threshold at
+                                which it still passes the segment test), every other pixel 0.  block_size (still validated), use_harris and
+                                harris_k play no part; the mask, the quality threshold, the 3 x 3 >= test, the rank order (value, then pixel
+                                index, both descending -- scores are small integers, ties are the rule) and the min-distance pass are unchanged.
+                                Parity is with tests/fast_model.py, compared with a live cv2 where one is importable.
+                                Outside 0..254, or > 0 together with use_harris: VO_E_INVALID, nothing enqueued. */
   double  harris_k;          /* 0.04 (OpenCV default) */
 } vo_st_params;
 
@@ -345,7 +354,15 @@ int32_t vo_klt_guess_read(vo_ctx* ctx, float* guess, int32_t n);
  * at extractor.py:103-112 on the CURRENT frame.  cur_pts (n_cur x 2 f32, may be NULL) are the
  * tracked keypoints; discs of `mask_radius` at int32-truncated coordinates are excluded
  * (cv2.circle fill semantics).  `mask` (h x w u8, may be NULL) is an optional explicit mask that
- * is AND-ed with the discs.  out_pts: max_corners x 2 f32 (integer-valued x, y); *n_out set. */
+ * is AND-ed with the discs.  out_pts: max_corners x 2 f32 (integer-valued x, y); *n_out set.
+ * The detector is a choice of RESPONSE MAP (vo_st_params): the minimum eigenvalue (default), the Harris response (use_harris), or the
+ * FAST-9/16 corner score of cv2.FastFeatureDetector (fast_threshold = 1..254; k_fast_score, csrc/vo_fast.hip -- the detector ORB builds
+ * on; no orientation, no descriptor).  What follows the map is the same for all three on every path that takes a vo_st_params
+ * (vo_shi_tomasi*, vo_tracks_detect, vo_frame_step_*, vo_pipe_params.st): quality threshold against the masked maximum, 3 x 3 >= test,
+ * mask, rank order (value, then pixel index, both descending), min-distance grid, max_corners.  With the FAST response the map that
+ * vo_shi_tomasi_read returns is the score map (0 where no corner, also within 3 pixels of a border), and the resident forms keep it and
+ * the mask.  A fast_threshold outside 0..254, or one > 0 together with use_harris, is VO_E_INVALID on each of those paths (vo_pipe_create
+ * for the closed loop) with nothing enqueued.  Contexts are at least 7 x 7 pixels: the smallest frame that holds a whole FAST ring. */
 int32_t vo_st_default_params(vo_st_params* p);
 int32_t vo_shi_tomasi(vo_ctx* ctx, const float* cur_pts, int32_t n_cur, int32_t mask_radius,
                       const uint8_t* mask, const vo_st_params* prm, float* out_pts, int32_t* n_out);

@@ -413,7 +413,7 @@ extern "C" int32_t vo_ctx_create_batched(int32_t device, int32_t width, int32_t 
                                          int32_t max_level, int32_t win, int32_t batch, vo_ctx** out) {
   if (!out) return VO_E_INVALID;
   *out = nullptr;
-  if (width < 8 || height < 8 || max_pts < 1 || max_level < 0 || max_level >= VO_MAX_LEVELS ||
+  if (width < 7 || height < 7 || max_pts < 1 || max_level < 0 || max_level >= VO_MAX_LEVELS ||
       win < 3 || win > VO_MAX_WIN || (win & 1) == 0 || batch < 1 || batch > 1024) {
     g_create_err = "vo_ctx_create: invalid argument";
     return VO_E_INVALID;

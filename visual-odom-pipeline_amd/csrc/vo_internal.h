@@ -297,6 +297,14 @@ bool vo_blocking_sync();             // environment VO_BLOCKING_SYNC=1: events a
 int32_t vo_main_stream_reserve(vo_ctx* c, int reserve);               // the ctx stream re-created with / without a CU mask (vo_set_side_stream(c, 2) of a batch)
 hipError_t vo_stream_create(hipStream_t* st, int reserve_cus);      // reserve_cus > 0: the queue never uses the last `reserve_cus` bits of the CU mask
 int32_t vo_st_prepare(vo_ctx* c, const vo_st_params* prm);
+// vo_st_params.fast_threshold and what it excludes: VO_OK or VO_E_INVALID (nothing enqueued); the orchestrators ask before their first enqueue
+int32_t vo_st_check_params(vo_ctx* c, const vo_st_params* prm);
+// a captured step that re-detects is replayed: the host-side notes its st_launch made at capture time (mask state, kept map, corner capacity), made again
+void vo_st_note_replay(vo_ctx* c, const vo_st_params* prm);
+// FAST-9/16 response (vo_fast.hip) of the current frame's level 0 for st_launch: R [batch][h][w] into d_R (every pixel), the masked maxima of its
+// vo_fast_n_blockmax(w, h) workgroups per sequence into d_blockmax
+int vo_fast_n_blockmax(int W, int H);
+void vo_fast_enqueue(vo_ctx* c, hipStream_t q, int t, const uint8_t* d_mask, float* d_R, float* d_blockmax);
 // the resident enqueues with the per-sequence counters named by the caller (device arrays [batch], null = uniform): d_counts = live
 // points of each sequence (KLT input / exclusion discs), d_limit = cap on the corners each sequence's re-detection needs
 // The tracker's form word: KLT_FORM_FB = with the forward-backward check (the ok flags land in vo_fb_ok(c) [batch][fb_seq bytes]),

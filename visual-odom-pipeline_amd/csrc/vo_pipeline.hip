@@ -1194,6 +1194,7 @@ static int32_t pipe_create(vo_ctx* c, const double* K, const vo_pipe_params* prm
   VO_CHECK(c, prm->ba.max_iters >= 0 && prm->ba.max_iters <= 1000 && prm->ba_budget >= 0 && prm->ba_budget <= prm->ba.max_iters, VO_E_INVALID,
            "ba_budget must be 0..ba.max_iters");
   { const int32_t rc = vo_ba_check_params(c, &prm->ba); if (rc != VO_OK) return rc; }
+  { const int32_t rc = vo_st_check_params(c, &prm->st); if (rc != VO_OK) return rc; }
   VO_HIP(c, hipSetDevice(c->device));
   VO_HIP(c, hipStreamSynchronize(c->stream));
   vo_pipe_destroy(c);

@@ -1110,15 +1110,43 @@ int32_t vo_st_prepare(vo_ctx* c, const vo_st_params* prm) {
   if (r != VO_OK) return r;
   vo_st_ws* s = c->st;
   const bool fused = !c->tune.st_two_kernels && prm && prm->block_size == 31 && c->height > 31 && c->width > 31;
-  if (!fused && !s->d_h) VO_HIP(c, hipMalloc((void**)&s->d_h, (size_t)c->width * c->height * 3 * sizeof(int32_t) * c->batch));
+  if (!fused && !(prm && prm->fast_threshold > 0) && !s->d_h) VO_HIP(c, hipMalloc((void**)&s->d_h, (size_t)c->width * c->height * 3 * sizeof(int32_t) * c->batch));
   return VO_OK;
 }
 
 extern "C" int32_t vo_st_default_params(vo_st_params* p) {
   if (!p) return VO_E_INVALID;
   p->max_corners = 1000; p->block_size = 31; p->quality_level = 0.03; p->min_distance = 7.0;
-  p->use_harris = 0; p->_pad = 0; p->harris_k = 0.04;
+  p->use_harris = 0; p->fast_threshold = 0; p->harris_k = 0.04;
   return VO_OK;
+}
+
+int32_t vo_st_check_params(vo_ctx* c, const vo_st_params* prm) {
+  VO_CHECK(c, prm->fast_threshold >= 0 && prm->fast_threshold <= 254, VO_E_INVALID, "fast_threshold must be 0 (off) or 1..254");
+  VO_CHECK(c, !(prm->fast_threshold > 0 && prm->use_harris), VO_E_INVALID, "fast_threshold and use_harris exclude each other");
+  return VO_OK;
+}
+
+// which response a launch with these parameters forms: the FAST score (vo_fast.hip), k_st_eig_fused, or the two-kernel form
+static bool st_is_fast(const vo_st_params* prm) { return prm->fast_threshold > 0; }
+static bool st_is_fused(const vo_ctx* c, const vo_st_params* prm) {
+  return !st_is_fast(prm) && !c->tune.st_two_kernels && prm->block_size / 2 == 15 && c->height > 31 && c->width > 31 && !prm->use_harris;    // (single border reflection per row inside the kernel; the Harris
+                                                                                     //  response -- an option the reference never enables -- takes the two-kernel form)
+}
+// the host-side notes of a launch: is the mask handed back clean, was the response map stored
+static void st_note_flags(vo_ctx* c, const vo_st_params* prm, bool keep, bool user_mask) {
+  vo_st_ws* s = c->st;
+  if (st_is_fused(c, prm)) {
+    const bool nms_fused = !c->tune.st_separate_nms;
+    s->mask_clean = !keep && !user_mask && nms_fused; s->eig_valid = keep || !nms_fused;
+  } else {
+    s->mask_clean = false; s->eig_valid = true;
+  }
+}
+void vo_st_note_replay(vo_ctx* c, const vo_st_params* prm) {
+  if (!c->st) return;
+  st_note_flags(c, prm, c->tune.st_keep_eig != 0, false);      // (what vo_shi_tomasi_resident_counts hands st_launch)
+  c->st->last_max_corners = prm->max_corners;
 }
 
 // pts: sequence-0 pointer of the exclusion-disc centres, pts_seq: byte stride between sequences
@@ -1131,6 +1159,7 @@ static int32_t st_launch(vo_ctx* c, hipStream_t q, const float* d_pts, size_t pt
            "block_size must be odd, <= 31");
   VO_CHECK(c, mask_radius >= 0 && mask_radius <= ST_MAX_RADIUS, VO_E_INVALID, "mask_radius must be 0..31");
   VO_CHECK(c, prm->max_corners <= ST_OUT_CAP, VO_E_CAPACITY, "max_corners exceeds 4096");
+  { const int32_t rc = vo_st_check_params(c, prm); if (rc != VO_OK) return rc; }
   vo_st_ws* s = c->st;
   vo_prof_scope prof(c, q, VO_PROF_ST);
   const int W = c->width, H = c->height, r = prm->block_size / 2, B = c->batch;
@@ -1138,10 +1167,9 @@ static int32_t st_launch(vo_ctx* c, hipStream_t q, const float* d_pts, size_t pt
   const double scale_d = 1.0 / ((double)(1 << 2) * prm->block_size * 255.0);
   const float sf = (float)scale_d;
   const float s2 = sf * sf;
-  const bool fused = !c->tune.st_two_kernels && r == 15 && H > 31 && W > 31 && !prm->use_harris;    // (single border reflection per row inside the kernel; the Harris
-                                                                                     //  response -- an option the reference never enables -- takes the two-kernel form)
+  const bool fast = st_is_fast(prm), fused = st_is_fused(c, prm);
   int n_blockmax;
-  if (fused) {
+  if (fused || fast) {
     if (keep || d_user_mask || !s->mask_clean)
       hipLaunchKernelGGL(k_st_mask_init, dim3(vo_div_up((int)(((size_t)W * H + 15) / 16), 256), B), dim3(256), 0, q, s->d_mask, d_user_mask,
                          (size_t)W * H, s->d_scalars, c->slab_seq);
@@ -1157,7 +1185,13 @@ static int32_t st_launch(vo_ctx* c, hipStream_t q, const float* d_pts, size_t pt
     hipLaunchKernelGGL(k_st_discs, dim3(vo_div_up(total, 256), B), dim3(256), 0, q, d_pts, pts_seq, n_cur, mask_radius,
                        rows, s->d_mask, W, H, counts);
   }
-  if (fused) {
+  if (fast) {
+    // the FAST score as the response map: block_size, use_harris and harris_k play no part; the NMS and the selection are the two-kernel form's
+    n_blockmax = vo_fast_n_blockmax(W, H);
+    vo_fast_enqueue(c, q, prm->fast_threshold, s->d_mask, s->d_eig, s->d_blockmax);
+    hipLaunchKernelGGL(k_st_nms, dim3(vo_div_up(W - 2, 256), vo_div_up(H - 2, ST_NMS_ROWS), B), dim3(256), 0, q, s->d_eig,
+                       s->d_mask, W, H, prm->quality_level, s->d_blockmax, n_blockmax, s->d_cand, s->d_scalars, c->slab_seq, s->d_nraw);
+  } else if (fused) {
     // rows per band: few bands keep the 30-row start-up small; with few sequences in flight more, shorter bands fill the GPU
     const int gx = vo_div_up(W, 256 - 32);
     // (5 workgroups fit a CU: 95 registers, 28.7 KB of LDS.)  Bands of at least 12 rows; among the band counts the one with the least
@@ -1189,15 +1223,14 @@ static int32_t st_launch(vo_ctx* c, hipStream_t q, const float* d_pts, size_t pt
     if (!nms_fused)
       hipLaunchKernelGGL(k_st_nms, dim3(vo_div_up(W - 2, 256), vo_div_up(H - 2, ST_NMS_ROWS), B), dim3(256), 0, q, s->d_eig,
                          s->d_mask, W, H, prm->quality_level, s->d_blockmax, n_blockmax, s->d_cand, s->d_scalars, c->slab_seq, s->d_nraw);
-    s->mask_clean = restore; s->eig_valid = keep || !nms_fused;
   } else {
     n_blockmax = vo_div_up(W, 256) * vo_div_up(H, ST_ROWS);
     hipLaunchKernelGGL(k_st_vsum_eig, dim3(vo_div_up(W, 256), vo_div_up(H, ST_ROWS), B), dim3(256), 0, q, s->d_h,
                        s->d_mask, W, H, r, s2, s->d_eig, s->d_blockmax, prm->use_harris ? 1 : 0, prm->harris_k);
     hipLaunchKernelGGL(k_st_nms, dim3(vo_div_up(W - 2, 256), vo_div_up(H - 2, ST_NMS_ROWS), B), dim3(256), 0, q, s->d_eig,
                        s->d_mask, W, H, prm->quality_level, s->d_blockmax, n_blockmax, s->d_cand, s->d_scalars, c->slab_seq, s->d_nraw);
-    s->mask_clean = false; s->eig_valid = true;
   }
+  st_note_flags(c, prm, keep, d_user_mask != nullptr);
   const int use_dist = prm->min_distance >= 1.0 ? 1 : 0;
   // grid cell: >= min_distance (3x3 neighbourhood then covers the exclusion radius), coarse enough to fit LDS
   int cell = use_dist ? (int)ceil(prm->min_distance) : 1;
@@ -1245,6 +1278,7 @@ extern "C" int32_t vo_shi_tomasi(vo_ctx* c, const float* cur_pts, int32_t n_cur,
   if (!prm) { vo_st_default_params(&def); prm = &def; }
   VO_CHECK(c, out_pts && n_out, VO_E_INVALID, "null output");
   VO_CHECK(c, n_cur >= 0 && n_cur <= c->max_pts && (n_cur == 0 || cur_pts), VO_E_CAPACITY, "bad cur_pts");
+  { const int32_t rc = vo_st_check_params(c, prm); if (rc != VO_OK) return rc; }                          // (before the uploads: a refused call enqueues nothing)
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   int32_t r = st_init(c, c->stream);
@@ -1274,6 +1308,7 @@ int32_t vo_shi_tomasi_resident_counts(vo_ctx* c, hipStream_t q, int32_t n_cur, i
   vo_st_params def;
   if (!prm) { vo_st_default_params(&def); prm = &def; }
   VO_CHECK(c, n_cur >= 0 && n_cur <= c->n_resident, VO_E_INVALID, "n_cur exceeds the resident point set");
+  { const int32_t rc = vo_st_check_params(c, prm); if (rc != VO_OK) return rc; }
   int32_t r = st_init(c, q);
   if (r != VO_OK) return r;
   const bool dev_limit = !c->tune.st_host_limit;                                                           // (vo_tuning: A/B, read per call -- tests compare both)

@@ -360,6 +360,7 @@ static int32_t frame_step(vo_ctx* c, int32_t frame_idx, const uint8_t* const* ho
   if (s.do_dlt) VO_CHECK(c, c->dlt_n > 0, VO_E_STATE, "vo_dlt_upload first");
   if (s.do_ba) VO_CHECK(c, vo_ba_ready(c), VO_E_STATE, "vo_ba_upload first");
   if (s.do_ba) { const int32_t rc = vo_ba_check_params(c, &s.ba); if (rc != VO_OK) return rc; }
+  if (s.do_st) { const int32_t rc = vo_st_check_params(c, &s.st); if (rc != VO_OK) return rc; }
   if (s.do_st) { int32_t r = vo_st_prepare(c, &s.st); if (r != VO_OK) return r; }    // allocations happen outside any capture
 
   // up to two steps may be in flight: step t + 1 is enqueued while the host still reads step t's (pinned) results.
@@ -411,6 +412,7 @@ static int32_t frame_step(vo_ctx* c, int32_t frame_idx, const uint8_t* const* ho
     // replay: redo the host-side state changes the enqueue functions would have made
     c->cur ^= 1; c->n_pushed++;
     c->p_parity ^= 1;
+    if (s.do_st) vo_st_note_replay(c, &s.st);
   }
   c->frame_ring = (c->frame_ring + 1) & 63;
   c->h_frame_idx[c->frame_ring] = frame_idx;

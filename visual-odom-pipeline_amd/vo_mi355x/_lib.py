@@ -38,7 +38,7 @@ class SubpixParams(C.Structure):
 
 class StParams(C.Structure):
     _fields_ = [("max_corners", C.c_int32), ("block_size", C.c_int32), ("quality_level", C.c_double),
-                ("min_distance", C.c_double), ("use_harris", C.c_int32), ("_pad", C.c_int32), ("harris_k", C.c_double)]
+                ("min_distance", C.c_double), ("use_harris", C.c_int32), ("fast_threshold", C.c_int32), ("harris_k", C.c_double)]
 
 
 # vo_ba_params.loss: include/vo_mi355x.h VO_LOSS_*, under scipy.optimize.least_squares' names

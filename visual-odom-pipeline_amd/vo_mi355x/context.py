@@ -459,11 +459,14 @@ class VoContext:
         self._ck(self._L.vo_klt_track_resident(self._h, n, C.byref(prm)))
 
     # -- Shi-Tomasi -----------------------------------------------------------------------------
-    def st_params(self, max_corners=1000, quality_level=0.03, min_distance=7, block_size=31, use_harris=False, harris_k=0.04):
+    def st_params(self, max_corners=1000, quality_level=0.03, min_distance=7, block_size=31, use_harris=False, harris_k=0.04, fast_threshold=0):
+        """fast_threshold: 0 (default) = the Shi-Tomasi / Harris response; 1..254 = the FAST-9/16 corner score at that threshold
+        (cv2.FastFeatureDetector's `response`) is ranked instead, everything behind the response map unchanged"""
         p = StParams()
         self._L.vo_st_default_params(C.byref(p))
         p.max_corners, p.quality_level, p.min_distance, p.block_size = max_corners, quality_level, min_distance, block_size
         p.use_harris, p.harris_k = (1 if use_harris else 0), float(harris_k)
+        p.fast_threshold = int(fast_threshold)
         return p
 
     def _corners(self, out, n_out):

@@ -28,7 +28,7 @@ class DMatch:
 
 class Extractor:
     def __init__(self, cfg=None, min_kp_dist=10, ctx=None, device=0, max_pts=8192, lazy=None, lazy_backend=None, bidir="reference",
-                 predict="off", subpix=None, undistort=None, clahe=None):
+                 predict="off", subpix=None, undistort=None, clahe=None, fast_threshold=20):
         """lazy (default: on unless VO_LAZY=0): once a frame has come through the reference's call order (pipeline.py:98-156) the state moves
         into device tables and the lists this class hands out are views of them (vo_mi355x/lazy.py); lazy_backend: test hook
         (ctx, K, params, width, height) -> backend, default the GPU one.  max_pts: keypoints per call AND the capacity of those tables (<= 8192).
@@ -52,7 +52,10 @@ class Extractor:
         extend_landmarks / extract work in the undistorted camera.  A lazy session serves only None.
         clahe: None (default): images are tracked as given.  (clip_limit, (tiles_x, tiles_y)) -- cv2.createCLAHE's arguments: the setting goes
         to this extractor's context (VoContext.set_clahe), so _im_prev and im_curr enter the frame store equalised (behind the undistortion).
-        A lazy session serves only None."""
+        A lazy session serves only None.
+        fast_threshold: the threshold of extract(detector='fast') (self._fast_params, cv2.FastFeatureDetector_create's arguments): the FAST-9/16
+        score is ranked in place of the Shi-Tomasi response; maxCorners, qualityLevel and minDistance still come from _shitomasi_params.
+        A lazy session does not serve that detector: such a call takes the plain path."""
         if clahe is not None:
             clip, tx, ty = VoContext._clahe_args(clahe)
             clahe = (clip, (tx, ty))
@@ -82,6 +85,7 @@ class Extractor:
         # parameters hard-coded by the reference (extractor.py:16-24)
         self._lk_params = dict(winSize=(31, 31), maxLevel=3, criteria=(3, 30, 0.03))
         self._shitomasi_params = dict(maxCorners=1000, qualityLevel=0.03, minDistance=min_kp_dist, blockSize=31)
+        self._fast_params = dict(threshold=int(fast_threshold), nonmaxSuppression=True)
         self._ctx = ctx
         self._device, self._max_pts = device, max_pts
         self._im_prev = None            # set by the caller, exactly like the reference (pipeline.py:36,103)
@@ -259,13 +263,16 @@ class Extractor:
         if detector == 'custom':
             self._plain("extract_sift")
             return self._extract_sift(img, t, current_kp, describe)
-        if detector != 'shi-tomasi':
-            raise ValueError("detector must be 'shi-tomasi' or 'custom'")
+        if detector not in ('shi-tomasi', 'fast'):
+            raise ValueError("detector must be 'shi-tomasi', 'fast' or 'custom'")
         if describe:
-            raise NotImplementedError("describe=True needs detector='custom' (SIFT): a Shi-Tomasi corner has no SIFT scale")
+            raise NotImplementedError("describe=True needs detector='custom' (SIFT): a Shi-Tomasi or FAST corner has no SIFT scale")
+        fast = detector == 'fast'
+        if fast and not self._fast_params.get("nonmaxSuppression", True):
+            raise NotImplementedError("detector='fast' ranks 3 x 3 maxima of the score: nonmaxSuppression=False is not served")
         s = self._session()
         if s is not None:
-            r = s.extract(img, t, current_kp, mask_radius)
+            r = s.extract(img, t, current_kp, mask_radius, detector=detector) if fast else s.extract(img, t, current_kp, mask_radius)
             if r is not NotImplemented:
                 return r
         self._plain("extract", mask_radius=mask_radius)
@@ -277,6 +284,9 @@ class Extractor:
         prm = c.st_params(max_corners=sp["maxCorners"], quality_level=sp["qualityLevel"],
                           min_distance=sp["minDistance"], block_size=sp["blockSize"],
                           use_harris=bool(sp.get("useHarrisDetector", False)), harris_k=sp.get("k", 0.04))
+        if fast:                             # the FAST-9/16 score in place of the response; the selection keys above stay in force
+            prm = c.st_params(max_corners=sp["maxCorners"], quality_level=sp["qualityLevel"], min_distance=sp["minDistance"],
+                              block_size=sp["blockSize"], fast_threshold=self._fast_params["threshold"])
         # np.int32(kp.uv) truncation happens on the device; float32 carries every pixel coordinate exactly
         cur = (np.array([k.uv for k in current_kp], dtype=np.float64).reshape(-1, 2).astype(np.float32) if len(current_kp)
                else np.zeros((0, 2), np.float32))

@@ -725,7 +725,9 @@ class Session:
                      n_obs=rec["ba_observations"]) if rec["ba_observations"] > 0 else None
         return state, dead_l, dead_k, stats
 
-    def extract(self, img, t, current_kp, mask_radius):
+    def extract(self, img, t, current_kp, mask_radius, detector='shi-tomasi'):
+        if detector != 'shi-tomasi':        # (a session's DETECT stage runs the parameters it was created with; extract(detector='fast') stays plain)
+            return NotImplemented
         self._drop_hints()
         from .resident import DETECT
         if not (t == self.t and mask_radius == self.prm["mask_radius"] and self._same_image(img, self.cur_img) and current_kp == self.lm_K + self.cand

@@ -60,12 +60,17 @@ class ResidentPipeline:
     push_frame -- pass through cv2.undistort first (the context's vo_set_undistort).  The geometry then works in the undistorted camera: the
     pipeline's own K must equal new_K (K when new_K is absent), anything else raises ValueError.  None (the default): frames are used as given.
     clahe: (clip_limit, (tiles_x, tiles_y)) -- cv2.createCLAHE's arguments -- makes every such frame pass through CLAHE (the context's
-    vo_set_clahe), behind the undistortion and in front of the bilateral pre-filter.  None (the default) switches a context's setting off."""
+    vo_set_clahe), behind the undistortion and in front of the bilateral pre-filter.  None (the default) switches a context's setting off.
+    detector: 'shi-tomasi' (the default, the reference's) or 'fast': the DETECT stage ranks the FAST-9/16 corner score at fast_threshold
+    (vo_st_params.fast_threshold) instead of the Shi-Tomasi response; discs, quality threshold, min_kp_dist and max_new act as before."""
 
     def __init__(self, ctx, K, ba_window=4, min_track_length=3, mask_radius=7, max_new=1000, max_reproj_err=2.0, min_bearing_angle=0.5,
                  ba_max_iters=50, ba_budget=None, ba_ftol=1e-3, ba_xtol=1e-3, pnp_blind_batches=4, pnp_seed=0, min_kp_dist=7, resurrect=True,
-                 fb_max_error=np.inf, ba_loss='huber', ba_f_scale=1.0, klt_predict="off", subpix=None, undistort=None, clahe=None):
+                 fb_max_error=np.inf, ba_loss='huber', ba_f_scale=1.0, klt_predict="off", subpix=None, undistort=None, clahe=None,
+                 detector='shi-tomasi', fast_threshold=20):
         self.ctx, self._L = ctx, ctx._L
+        if detector not in ('shi-tomasi', 'fast'):
+            raise ValueError("detector must be 'shi-tomasi' or 'fast'")
         B = ctx.batch
         K = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (B, 3, 3)))
         self.K = K
@@ -84,6 +89,8 @@ class ResidentPipeline:
         p.resurrect = 1 if resurrect else 0
         p.pnp.reproj_err, p.pnp.seed = max_reproj_err, pnp_seed
         p.st.min_distance = float(min_kp_dist)
+        if detector == 'fast':
+            p.st.fast_threshold = int(fast_threshold)
         self.params = p
         ctx._ck(self._L.vo_pipe_create(ctx._h, K.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p)))
         if not (fb_max_error == np.inf and ctx.get_fb_check() == np.inf):     # (off on a context that never set it: no call at all)
