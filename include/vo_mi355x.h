@@ -357,7 +357,7 @@ int32_t vo_klt_guess_read(vo_ctx* ctx, float* guess, int32_t n);
  * is AND-ed with the discs.  out_pts: max_corners x 2 f32 (integer-valued x, y); *n_out set.
  * The detector is a choice of RESPONSE MAP (vo_st_params): the minimum eigenvalue (default), the Harris response (use_harris), or the
  * FAST-9/16 corner score of cv2.FastFeatureDetector (fast_threshold = 1..254; k_fast_score, csrc/vo_fast.hip -- the detector ORB builds
- * on; no orientation, no descriptor).  What follows the map is the same for all three on every path that takes a vo_st_params
+ * on; orientation and descriptor: vo_brief_* below).  What follows the map is the same for all three on every path that takes a vo_st_params
  * (vo_shi_tomasi*, vo_tracks_detect, vo_frame_step_*, vo_pipe_params.st): quality threshold against the masked maximum, 3 x 3 >= test,
  * mask, rank order (value, then pixel index, both descending), min-distance grid, max_corners.  With the FAST response the map that
  * vo_shi_tomasi_read returns is the score map (0 where no corner, also within 3 pixels of a border), and the resident forms keep it and
@@ -412,6 +412,56 @@ int32_t vo_corner_subpix(vo_ctx* ctx, int32_t which, const float* corners, int32
 int32_t vo_set_subpix(vo_ctx* ctx, const vo_subpix_params* prm);
 int32_t vo_get_subpix(vo_ctx* ctx, int32_t* on, vo_subpix_params* prm);
 int32_t vo_subpix_read(vo_ctx* ctx, float* raw, int32_t* iters, uint8_t* flags, int32_t n);
+
+/* ---- oriented BRIEF descriptor (the descriptor half of ORB) ------------------------------------
+ * The reference's Extractor names it: cv2.ORB_create() (src/extractor/extractor.py:30-31), extract(..., describe=True) for any detector
+ * (:119-122), and the commented "Alternative Method" of Pipeline.step (src/pipeline/pipeline.py:105-121), which matches landmarks to
+ * re-detected keypoints by descriptor.  The detector half is the FAST response above; this is orientation by intensity centroid and a steered
+ * 256-bit BRIEF at the detected corners.  Neither OpenCV nor its learned sampling table is part of this project: parity with cv2.ORB is not
+ * pinned, the numpy model tests/brief_model.py is the definition (bit for bit), and the sampling pattern is the caller's table -- a user who has
+ * OpenCV uploads ORB's own.  Per corner, at the integer pixel (x, y) = (rint(cx), rint(cy)) (half to even) of level 0 of the named frame
+ * (behind undistortion, CLAHE and the pre-filter where those are on):
+ *   margin   M = 24 (21 for the furthest rotated sample + 3 for the blur).  Described iff M <= x <= w-1-M and M <= y <= h-1-M; any other corner:
+ *            flags = 1, 32 zero bytes, angle 0.  A row that is not finite: flags = 2, the same zeros.  No border is ever extrapolated.
+ *   angle    ORB's IC_Angle on the raw (un-blurred) image: m10 = sum u I(x+u, y+v), m01 = sum v I(x+u, y+v) over |v| <= 15, |u| <= umax[|v|],
+ *            umax = {15,15,15,15,14,14,14,13,13,12,11,10,9,8,6,3}; exact in int32.  Both 0: c = 1, s = 0, angle = 0.  Otherwise in float64
+ *            r = sqrt(m10*m10 + m01*m01), c = (f32)(m10 / r), s = (f32)(m01 / r); angle = atan2(m01, m10) in degrees in [0, 360) as f32.
+ *            The angle is reported only and never enters the descriptor (ORB goes through fastAtan2 and cos / sin; this keeps the bits exact).
+ *   blur     separable 7-tap integer Gaussian (sigma ~ 2) g = {18,33,49,56,49,33,18}, sum 256: horizontal sums (they fit u16), the vertical
+ *            pass over those, S = (v + 32768) >> 16.  ORB's GaussianBlur(7 x 7, 2) in spirit, not bit for bit.
+ *   tests    the pattern: 256 rows (x1, y1, x2, y2) int8, every coordinate in [-15, 15], a row's two points differ.  Per point in float32
+ *            without contraction fx = x1*c - y1*s, fy = x1*s + y1*c (two rounded products, one rounded sum), ix = rint(fx), iy = rint(fy) half
+ *            to even.  Bit i = S(x+ix1, y+iy1) < S(x+ix2, y+iy2), in byte i / 8 at bit i % 8 (LSB first).
+ *   default  pattern: BRIEF's isotropic Gaussian sampling, N(0, 6^2) rounded, defined by tools/gen_brief_pattern.py (csrc/vo_brief_pattern.h).
+ * Not ORB: the 8-level pyramid and the Harris re-ranking (the corners are single-scale), the learned table, fastAtan2.
+ * Kernel k_brief_describe (csrc/vo_brief.hip): one wave per corner, the 49 x 49 tile and its blur in LDS.
+ *   vo_brief_default_pattern  out[1024]: the default table; needs no context.
+ *   vo_brief_params           n_bits must be 256; the rest is room to grow and must be 0.  vo_brief_default_params fills it.
+ *   vo_brief_compute          synchronous.  which = 0 the previous / 1 the current frame of the frame store; corners [batch][n][2] f32; prm NULL =
+ *                             the defaults; pattern NULL = the default table; desc [batch][n][32] u8; angle [batch][n] f32 and flags [batch][n] u8 may
+ *                             be NULL.  VO_E_INVALID, nothing enqueued: n > max_pts, n_bits != 256, a pattern coordinate outside +-15, a pattern row
+ *                             with equal points.  VO_E_STATE: the named frame has not been pushed.  A context smaller than 49 pixels on either axis
+ *                             is legal: every corner comes back with flags = 1.
+ *   vo_set_brief              per context; prm NULL = off (the default); pattern NULL = the default table; the same checks.  Takes effect at the next
+ *                             enqueue (a launch takes the table by value: steps in flight keep theirs).  On, vo_tracks_detect and the DETECT stage of
+ *                             vo_pipe_step / vo_pipe_step_host enqueue the kernel on the detection's stream behind the selection and BEFORE the
+ *                             sub-pixel refinement of vo_set_subpix, so it always sees the integer corners.  The descriptors live in a side buffer:
+ *                             no table, record or index list of the track table or the closed loop changes by a bit, on any stream layout.
+ *                             These never describe: vo_shi_tomasi*, outside a vo_tracks_detect; the fused vo_frame_step_* (so no captured graph
+ *                             holds the kernel).
+ *   vo_get_brief              *on = 0 / 1; prm (may be NULL) = the setting, the defaults when off.  vo_brief_pattern_read: the table in effect.
+ *   vo_brief_read             synchronous, no step in flight (else VO_E_STATE): desc [batch][n][32], angle, flags (any may be NULL) of the last
+ *                             vo_tracks_detect / DETECT stage in corner order, if it described (else VO_E_STATE; a vo_brief_compute call in between
+ *                             also ends it).  Slots beyond a sequence's corner count read zeros with flags = 2. */
+typedef struct { int32_t n_bits /* 256 */, _pad; int32_t reserved[6]; } vo_brief_params;  /* 32 bytes */
+int32_t vo_brief_default_pattern(int8_t* out);
+int32_t vo_brief_default_params(vo_brief_params* p);
+int32_t vo_brief_compute(vo_ctx* ctx, int32_t which, const float* corners, int32_t n, const vo_brief_params* prm, const int8_t* pattern,
+                         uint8_t* desc, float* angle, uint8_t* flags);
+int32_t vo_set_brief(vo_ctx* ctx, const vo_brief_params* prm, const int8_t* pattern);
+int32_t vo_get_brief(vo_ctx* ctx, int32_t* on, vo_brief_params* prm);
+int32_t vo_brief_pattern_read(vo_ctx* ctx, int8_t* out);
+int32_t vo_brief_read(vo_ctx* ctx, uint8_t* desc, float* angle, uint8_t* flags, int32_t n);
 
 /* ---- DLT triangulation ----------------------------------------------------------------------
  * Replaces cv2.triangulatePoints(P0, P1, uv0, uv1) at extractor.py:270 and the reprojection
@@ -575,6 +625,12 @@ int32_t vo_sift_detect_compute(vo_ctx* ctx, const uint8_t* img, int32_t stride, 
  * desc1 [batch][n1][dim], desc2 [batch][n2][dim] f32; idx [batch][n1][2] (-1 = no such neighbour), dist [batch][n1][2] f32. */
 int32_t vo_match_knn2(vo_ctx* ctx, const float* desc1, int32_t n1, const float* desc2, int32_t n2, int32_t dim,
                       int32_t* idx, float* dist);
+/* The reference's 'orb' branch, self._matcher.match(desc_1, desc_2) (src/extractor/extractor.py:144-145), over binary descriptors:
+ * cv2.BFMatcher(NORM_HAMMING).knnMatch(k = 2) -- for every query the two train rows of least bit distance, ordered by (distance, train
+ * index); column 0 is the 1-NN match.  desc1 [batch][n1][nbytes], desc2 [batch][n2][nbytes] u8; nbytes a multiple of 4 in 4..64, else
+ * VO_E_INVALID; idx [batch][n1][2] (-1 = no such neighbour), dist [batch][n1][2] i32 (INT32_MAX for an empty slot). */
+int32_t vo_match_hamming_knn2(vo_ctx* ctx, const uint8_t* desc1, int32_t n1, const uint8_t* desc2, int32_t n2, int32_t nbytes,
+                              int32_t* idx, int32_t* dist);
 
 /* ---- device-resident track table (SURVEY.md 8f "next" row 3) -----------------------------------
  * The bookkeeping Extractor.extend_tracks / extend_landmarks / extract do on Python lists of Keypoint objects

@@ -115,6 +115,14 @@ struct vo_ctx {
   vo_subpix_params subpix_prm = {};
   uint8_t* d_subpix = nullptr;
   int subpix_n = -1;                 // corner slots the last resident detection refined, else -1
+  // oriented BRIEF descriptor (vo_brief.hip): the setting of vo_set_brief with its sampling table (a launch takes it by value), and the kernel's
+  // rows per sequence -- descriptors, the synchronous form's corners, angles, flags -- in an allocation of their own: a side buffer, the
+  // pipeline's tables never hold a descriptor
+  bool brief_on = false;
+  vo_brief_params brief_prm = {};
+  int8_t brief_pat[1024] = {};
+  uint8_t* d_brief = nullptr;
+  int brief_n = -1;                  // corner slots the last resident detection described, else -1
   // lens undistortion (vo_undistort.hip): the setting of vo_set_undistort, its fixed-point map [h][w] of 8-byte entries (shared by the batch)
   // and the tight [batch][h][w] staging image the level-0 kernels read instead of the raw frame -- allocated when first switched on
   bool und_on = false;
@@ -326,6 +334,11 @@ void vo_guess_destroy(vo_ctx* c);
 // place against the current frame; off, it only notes that the last detection did not refine
 int32_t vo_subpix_refine_detected(vo_ctx* c, hipStream_t q, int max_corners);
 void vo_subpix_destroy(vo_ctx* c);
+// oriented BRIEF (vo_brief.hip).  vo_brief_describe_detected: called by the same detections right behind the Shi-Tomasi enqueue on q and BEFORE
+// vo_subpix_refine_detected, so it always sees the integer corners: with vo_set_brief on, k_brief_describe writes a descriptor, an angle and a
+// flag per corner row of st_out into the side buffer; off, it only notes that the last detection did not describe
+int32_t vo_brief_describe_detected(vo_ctx* c, hipStream_t q, int max_corners);
+void vo_brief_destroy(vo_ctx* c);
 // The ingest chain (vo_frame.hip): the optional stages vo_build_pyramid runs in front of level 0, in this order: lens undistortion
 // (vo_undistort.hip), then CLAHE (vo_clahe.hip).  A stage's enqueue takes the frames (k_pad_level0's triple) to its own tight [batch][h][w]
 // staging image on q; the next stage, and at last the level-0 kernel, read that image as their raw frame.

@@ -1572,6 +1572,7 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
     // re-detection + spawn on the side stream behind promote / dense; adjustment + write-back on the main stream
     VO_HIP(c, vo_stream_fork(c->ev_fork, c->stream, c->stream2));
     r = (stages & VO_PIPE_DETECT) ? vo_shi_tomasi_resident_counts(c, c->stream2, w->N, prm.mask_radius, &prm.st, w->d_dn + DN_PTS * B, w->d_dn + DN_ROOM * B) : VO_OK;
+    if (r == VO_OK && (stages & VO_PIPE_DETECT)) r = vo_brief_describe_detected(c, c->stream2, prm.st.max_corners);    // vo_set_brief: the integer corners
     if (r == VO_OK && (stages & VO_PIPE_DETECT)) r = vo_subpix_refine_detected(c, c->stream2, prm.st.max_corners);     // vo_set_subpix: before the spawn
     if (r == VO_OK) pipe_launch_spawn(c, c->stream2, (stages & VO_PIPE_DETECT) ? 1 : 0, (stages & VO_PIPE_KEEP_FREE_LISTS) ? 0 : 1);
     if (r == VO_OK && (stages & VO_PIPE_ADJUST)) r = vo_ba_enqueue_budget(c, c->stream, &prm.ba, 0, prm.ba_budget, ba_live);
@@ -1586,6 +1587,8 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
     }
     if (stages & VO_PIPE_DETECT) {
       r = vo_shi_tomasi_resident_counts(c, c->stream, w->N, prm.mask_radius, &prm.st, w->d_dn + DN_PTS * B, w->d_dn + DN_ROOM * B);
+      if (r != VO_OK) return r;
+      r = vo_brief_describe_detected(c, c->stream, prm.st.max_corners);    // vo_set_brief: the integer corners
       if (r != VO_OK) return r;
       r = vo_subpix_refine_detected(c, c->stream, prm.st.max_corners);     // vo_set_subpix: before the spawn
       if (r != VO_OK) return r;

@@ -283,6 +283,7 @@ extern "C" int32_t vo_tracks_detect(vo_ctx* c, int32_t t, int32_t mask_radius, c
   if (!st) { vo_st_default_params(&def); st = &def; }
   const int32_t r = vo_shi_tomasi_resident(c, tw->n_hi, mask_radius, st);
   if (r != VO_OK) return r;
+  { const int32_t rb = vo_brief_describe_detected(c, c->stream, st->max_corners); if (rb != VO_OK) return rb; }    // vo_set_brief: the integer corners
   { const int32_t rs = vo_subpix_refine_detected(c, c->stream, st->max_corners); if (rs != VO_OK) return rs; }     // vo_set_subpix: before the spawn
   if (max_new < 0) max_new = 0;
   hipLaunchKernelGGL(k_trk_spawn, dim3(c->batch), dim3(256), 0, c->stream, trk_make(tw), vo_slab<float>(c, vo_off_p(c)), c->slab_seq,

@@ -36,6 +36,11 @@ class SubpixParams(C.Structure):
                 ("_pad", C.c_int32), ("epsilon", C.c_double)]
 
 
+class BriefParams(C.Structure):
+    """vo_brief_params: n_bits = 256, the rest is room to grow (32 bytes)"""
+    _fields_ = [("n_bits", C.c_int32), ("_pad", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
 class StParams(C.Structure):
     _fields_ = [("max_corners", C.c_int32), ("block_size", C.c_int32), ("quality_level", C.c_double),
                 ("min_distance", C.c_double), ("use_harris", C.c_int32), ("fast_threshold", C.c_int32), ("harris_k", C.c_double)]
@@ -114,6 +119,7 @@ class PipeRecord(C.Structure):
 
 
 _u8p, _i16p, _i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int16), C.POINTER(C.c_int32)
+_i8p = C.POINTER(C.c_int8)
 _f32p, _f64p = C.POINTER(C.c_float), C.POINTER(C.c_double)
 _ctx = C.c_void_p
 
@@ -162,6 +168,13 @@ SIGNATURES = {
     "vo_set_subpix": (C.c_int32, [_ctx, C.POINTER(SubpixParams)]),
     "vo_get_subpix": (C.c_int32, [_ctx, _i32p, C.POINTER(SubpixParams)]),
     "vo_subpix_read": (C.c_int32, [_ctx, _f32p, _i32p, _u8p, C.c_int32]),
+    "vo_brief_default_pattern": (C.c_int32, [_i8p]),
+    "vo_brief_default_params": (C.c_int32, [C.POINTER(BriefParams)]),
+    "vo_brief_compute": (C.c_int32, [_ctx, C.c_int32, _f32p, C.c_int32, C.POINTER(BriefParams), _i8p, _u8p, _f32p, _u8p]),
+    "vo_set_brief": (C.c_int32, [_ctx, C.POINTER(BriefParams), _i8p]),
+    "vo_get_brief": (C.c_int32, [_ctx, _i32p, C.POINTER(BriefParams)]),
+    "vo_brief_pattern_read": (C.c_int32, [_ctx, _i8p]),
+    "vo_brief_read": (C.c_int32, [_ctx, _u8p, _f32p, _u8p, C.c_int32]),
     "vo_st_default_params": (C.c_int32, [C.POINTER(StParams)]),
     "vo_shi_tomasi": (C.c_int32, [_ctx, _f32p, C.c_int32, C.c_int32, _u8p, C.POINTER(StParams), _f32p, _i32p]),
     "vo_shi_tomasi_resident": (C.c_int32, [_ctx, C.c_int32, C.c_int32, C.POINTER(StParams)]),
@@ -209,6 +222,7 @@ SIGNATURES = {
                                         C.POINTER(EssStats)]),
     "vo_sift_detect_compute": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32, C.POINTER(SiftKp), _f32p, _i32p]),
     "vo_match_knn2": (C.c_int32, [_ctx, _f32p, C.c_int32, _f32p, C.c_int32, C.c_int32, _i32p, _f32p]),
+    "vo_match_hamming_knn2": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32, _i32p, _i32p]),
     "vo_pnp_upload": (C.c_int32, [_ctx, _f64p, _f32p, _f32p, C.c_int32]),
     "vo_pnp_solve_resident": (C.c_int32, [_ctx, C.POINTER(PnpParams), C.c_int32]),
     "vo_pnp_fetch": (C.c_int32, [_ctx, _f64p, _f64p, _u8p, C.POINTER(PnpStats)]),

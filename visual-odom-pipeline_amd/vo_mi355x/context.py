@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BaParams, BaStats, EssParams, EssStats, KltParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
+from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, KltParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
 
 # vo_set_klt_predict modes (include/vo_mi355x.h)
 KLT_PREDICT_MODES = {"off": 0, "constant_velocity": 1}
@@ -437,6 +437,90 @@ class VoContext:
             out.append(dict(raw=raw[b, :m].copy(), iters=it[b, :m].copy(), flags=fl[b, :m].copy()))
         return out[0] if B == 1 else out
 
+    # -- oriented BRIEF descriptor -------------------------------------------------------------------
+    @staticmethod
+    def brief_default_pattern():
+        """(256, 4) int8: rows (x1, y1, x2, y2) of the default sampling table (vo_brief_default_pattern; needs no context)"""
+        out = np.zeros((256, 4), np.int8)
+        rc = _lib.load().vo_brief_default_pattern(ptr(out, C.c_int8))
+        if rc != 0:
+            raise VoError(rc, "vo_brief_default_pattern")
+        return out
+
+    def brief_params(self, n_bits=256):
+        p = BriefParams()
+        self._L.vo_brief_default_params(C.byref(p))
+        p.n_bits = int(n_bits)
+        return p
+
+    @staticmethod
+    def _brief_pattern(pattern):
+        """None (the default table) or 256 rows (x1, y1, x2, y2) -> a contiguous int8 array or None; the library checks the values"""
+        if pattern is None:
+            return None
+        p = np.asarray(pattern)
+        if p.size != 1024:
+            raise ValueError("a BRIEF pattern has 256 rows (x1, y1, x2, y2)")
+        if (p != np.clip(p, -128, 127)).any() or (p != np.rint(p)).any():
+            raise ValueError("BRIEF pattern coordinates are int8")
+        return np.ascontiguousarray(p.reshape(256, 4), np.int8)
+
+    def brief_compute(self, corners, which="cur", params=None, pattern=None):
+        """oriented BRIEF at corners (n,2) f32 on a frame of the frame store (vo_brief_compute) -> desc (n,32) u8, angle (n,) f32 degrees,
+        flags (n,) u8 (0 described, 1 within 24 pixels of a border, 2 not finite)  [leading batch dim if batch > 1].  which: "cur" (1) or
+        "prev" (0); pattern: 256 rows (x1, y1, x2, y2) in [-15, 15], None = the default table."""
+        p, n = self._npts(corners)
+        B = self.batch
+        prm = params if params is not None else self.brief_params()
+        pat = self._brief_pattern(pattern)
+        w = {"prev": 0, "cur": 1}.get(which, which)
+        desc = np.zeros((B, n, 32), np.uint8)
+        ang = np.zeros((B, n), np.float32)
+        fl = np.zeros((B, n), np.uint8)
+        self._ck(self._L.vo_brief_compute(self._h, int(w), ptr(p, C.c_float), n, C.byref(prm), ptr(pat, C.c_int8), ptr(desc, C.c_uint8),
+                                          ptr(ang, C.c_float), ptr(fl, C.c_uint8)))
+        return self._out(desc), self._out(ang), self._out(fl)
+
+    def set_brief(self, params=None, pattern=None):
+        """describe the corners of tracks_detect and of the closed loop's DETECT stage (vo_set_brief): True or a brief_params() struct = on,
+        None / False = off (the default); pattern as in brief_compute.  The descriptors go to a side buffer (brief_read)."""
+        if params is None or params is False:
+            self._ck(self._L.vo_set_brief(self._h, None, None))
+            return
+        if params is True:
+            params = self.brief_params()
+        self._ck(self._L.vo_set_brief(self._h, C.byref(params), ptr(self._brief_pattern(pattern), C.c_int8)))
+
+    def get_brief(self):
+        """None when off, else the BriefParams in effect"""
+        on, p = C.c_int32(0), BriefParams()
+        self._ck(self._L.vo_get_brief(self._h, C.byref(on), C.byref(p)))
+        return p if on.value else None
+
+    def brief_pattern_read(self):
+        """(256, 4) int8: the sampling table in effect (the default one when off)"""
+        out = np.zeros((256, 4), np.int8)
+        self._ck(self._L.vo_brief_pattern_read(self._h, ptr(out, C.c_int8)))
+        return out
+
+    def brief_read(self, n=None):
+        """the descriptors of the last detection that described (vo_brief_read), in corner order: dict of desc (m,32) u8, angle (m,) f32,
+        flags (m,) u8 per sequence [list of B dicts if batch > 1].  n: corner slots to read (default: all the detection could fill); slots
+        the detection did not fill carry flags = 2 and are cut off."""
+        B = self.batch
+        if n is None:
+            n = self._subpix_slots
+        desc = np.zeros((B, n, 32), np.uint8)
+        ang = np.zeros((B, n), np.float32)
+        fl = np.zeros((B, n), np.uint8)
+        self._ck(self._L.vo_brief_read(self._h, ptr(desc, C.c_uint8), ptr(ang, C.c_float), ptr(fl, C.c_uint8), n))
+        out = []
+        for b in range(B):
+            dead = fl[b] == 2
+            m = int(np.argmax(dead)) if dead.any() else n
+            out.append(dict(desc=desc[b, :m].copy(), angle=ang[b, :m].copy(), flags=fl[b, :m].copy()))
+        return out[0] if B == 1 else out
+
     def points_upload(self, p):
         p, n = self._npts(p)
         self._ck(self._L.vo_points_upload(self._h, ptr(p, C.c_float), n))
@@ -832,6 +916,20 @@ class VoContext:
         idx = np.zeros((B, n1, 2), np.int32); dist = np.zeros((B, n1, 2), np.float32)
         self._ck(self._L.vo_match_knn2(self._h, ptr(d1, C.c_float), n1, ptr(d2, C.c_float), n2, dim, ptr(idx, C.c_int32),
                                        ptr(dist, C.c_float)))
+        return (idx[0], dist[0]) if B == 1 else (idx, dist)
+
+    def match_hamming_knn2(self, desc1, desc2):
+        """two nearest train descriptors under the bit distance of every query descriptor (vo_match_hamming_knn2;
+        cv2.BFMatcher(NORM_HAMMING).knnMatch(k=2)).  desc1 (n1,nbytes), desc2 (n2,nbytes) u8, nbytes a multiple of 4 in 4..64
+        [leading batch dim if batch > 1] -> idx (n1,2) int32 (-1 = none), dist (n1,2) int32 (INT32_MAX = none)"""
+        B = self.batch
+        nb = np.shape(desc1)[-1]
+        d1 = np.ascontiguousarray(desc1, np.uint8).reshape(B, -1, nb)
+        d2 = np.ascontiguousarray(desc2, np.uint8).reshape(B, -1, nb)
+        n1, n2 = d1.shape[1], d2.shape[1]
+        idx = np.zeros((B, n1, 2), np.int32); dist = np.zeros((B, n1, 2), np.int32)
+        self._ck(self._L.vo_match_hamming_knn2(self._h, ptr(d1, C.c_uint8), n1, ptr(d2, C.c_uint8), n2, nb, ptr(idx, C.c_int32),
+                                               ptr(dist, C.c_int32)))
         return (idx[0], dist[0]) if B == 1 else (idx, dist)
 
     # -- 2D-2D bootstrap pose ---------------------------------------------------------------------

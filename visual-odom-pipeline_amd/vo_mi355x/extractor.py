@@ -28,7 +28,7 @@ class DMatch:
 
 class Extractor:
     def __init__(self, cfg=None, min_kp_dist=10, ctx=None, device=0, max_pts=8192, lazy=None, lazy_backend=None, bidir="reference",
-                 predict="off", subpix=None, undistort=None, clahe=None, fast_threshold=20):
+                 predict="off", subpix=None, undistort=None, clahe=None, fast_threshold=20, descriptor=None, brief_pattern=None):
         """lazy (default: on unless VO_LAZY=0): once a frame has come through the reference's call order (pipeline.py:98-156) the state moves
         into device tables and the lists this class hands out are views of them (vo_mi355x/lazy.py); lazy_backend: test hook
         (ctx, K, params, width, height) -> backend, default the GPU one.  max_pts: keypoints per call AND the capacity of those tables (<= 8192).
@@ -55,7 +55,17 @@ class Extractor:
         A lazy session serves only None.
         fast_threshold: the threshold of extract(detector='fast') (self._fast_params, cv2.FastFeatureDetector_create's arguments): the FAST-9/16
         score is ranked in place of the Shi-Tomasi response; maxCorners, qualityLevel and minDistance still come from _shitomasi_params.
-        A lazy session does not serve that detector: such a call takes the plain path."""
+        A lazy session does not serve that detector: such a call takes the plain path.
+        descriptor: None (default): extract(detector='shi-tomasi' | 'fast', describe=True) raises NotImplementedError -- a corner has no SIFT
+        scale.  'brief': such a call describes the detector's integer corners with the oriented BRIEF descriptor (VoContext.brief_compute;
+        the reference's cv2.ORB_create() branch, extractor.py:30-31, 119-122) and returns Keypoints whose `des` is the (32, 1) uint8 column;
+        corners within 24 pixels of a border are dropped, as cv2.ORB.compute drops border keypoints.  brief_pattern: 256 rows
+        (x1, y1, x2, y2) in [-15, 15], None = the default table.  match / match_lists on uint8 descriptors take the reference's 'orb' branch
+        (1-NN under the Hamming distance, extractor.py:144-145).  A lazy session does not describe: such a call takes the plain path."""
+        if descriptor not in (None, 'brief'):
+            raise ValueError("descriptor must be None or 'brief'")
+        self._descriptor = descriptor
+        self._brief_pattern = None if brief_pattern is None else VoContext._brief_pattern(brief_pattern)
         if clahe is not None:
             clip, tx, ty = VoContext._clahe_args(clahe)
             clahe = (clip, (tx, ty))
@@ -265,14 +275,17 @@ class Extractor:
             return self._extract_sift(img, t, current_kp, describe)
         if detector not in ('shi-tomasi', 'fast'):
             raise ValueError("detector must be 'shi-tomasi', 'fast' or 'custom'")
-        if describe:
+        if describe and self._descriptor != 'brief':
             raise NotImplementedError("describe=True needs detector='custom' (SIFT): a Shi-Tomasi or FAST corner has no SIFT scale")
         fast = detector == 'fast'
         if fast and not self._fast_params.get("nonmaxSuppression", True):
             raise NotImplementedError("detector='fast' ranks 3 x 3 maxima of the score: nonmaxSuppression=False is not served")
         s = self._session()
         if s is not None:
-            r = s.extract(img, t, current_kp, mask_radius, detector=detector) if fast else s.extract(img, t, current_kp, mask_radius)
+            if describe:
+                r = s.extract(img, t, current_kp, mask_radius, detector=detector, describe=True)
+            else:
+                r = s.extract(img, t, current_kp, mask_radius, detector=detector) if fast else s.extract(img, t, current_kp, mask_radius)
             if r is not NotImplemented:
                 return r
         self._plain("extract", mask_radius=mask_radius)
@@ -293,6 +306,12 @@ class Extractor:
         kp = c.shi_tomasi(cur if len(cur) else None, mask_radius=mask_radius, params=prm)
         if kp.shape[0] == 0:
             return []
+        desc = None
+        if describe:                         # self._features.compute(img, cv_kp) on the integer corners; border keypoints leave the list
+            desc, _angle, flags = c.brief_compute(kp, "cur", pattern=self._brief_pattern)
+            kp, desc = np.ascontiguousarray(kp[flags == 0]), np.ascontiguousarray(desc[flags == 0]).reshape(-1, 32, 1)
+            if kp.shape[0] == 0:
+                return []
         if self._subpix is not None:         # cv2.cornerSubPix(img, kp, win, zero_zone, criteria) on the image just detected on
             crit = self._subpix.get("criteria", (3, 40, 0.001))
             kp = c.corner_subpix(kp, "cur", c.subpix_params(win=self._subpix.get("win", (5, 5)), zero_zone=self._subpix.get("zero_zone", (-1, -1)),
@@ -300,7 +319,8 @@ class Extractor:
         # like the reference (extractor.py:127-131) uv_first, uv and the first history entry of a new keypoint are three
         # VIEWS of the same row of the detector output (kp[i, :].reshape((2, 1)) is a view); des a view of the zero column
         kp3 = kp.reshape(-1, 2, 1)
-        desc = np.zeros((kp.shape[0], 1, 1))
+        if desc is None:
+            desc = np.zeros((kp.shape[0], 1, 1))
         return [Keypoint(t_first=t, t_total=1, uv_first=kp3[i], uv=kp3[i], des=desc[i], uv_history=[kp3[i]])
                 for i in range(len(kp))]
 
@@ -419,9 +439,17 @@ class Extractor:
 
     def match(self, desc_1, desc_2):
         """cv2.BFMatcher().knnMatch(desc_1, desc_2, k=2) + Lowe's ratio test (reference extractor.py:134-145): the
-        list of DMatch whose nearest neighbour is closer than _sift_ratio x the second nearest."""
+        list of DMatch whose nearest neighbour is closer than _sift_ratio x the second nearest.  uint8 descriptors (descriptor='brief'):
+        one DMatch per query, its nearest train row under the Hamming distance."""
         if self._ctx is None:
             raise RuntimeError("match needs the device context: track a frame first (or pass ctx=)")
+        if np.asarray(desc_1).dtype == np.uint8 and np.asarray(desc_2).dtype == np.uint8:
+            # binary descriptors: the reference's 'orb' branch, self._matcher.match(desc_1, desc_2) (extractor.py:144-145) -- the nearest train
+            # row of every query under the Hamming distance, no ratio test
+            if len(desc_1) == 0 or len(desc_2) == 0:
+                return []
+            idx, dist = self._ctx.match_hamming_knn2(desc_1, desc_2)
+            return [DMatch(q, idx[q, 0], dist[q, 0]) for q in range(len(desc_1))]
         desc_1 = np.ascontiguousarray(desc_1, np.float32); desc_2 = np.ascontiguousarray(desc_2, np.float32)
         if len(desc_2) < 2:
             raise ValueError("not enough values to unpack (expected 2, got %d)" % len(desc_2))   # the reference's `for m, n in matches`

@@ -725,8 +725,10 @@ class Session:
                      n_obs=rec["ba_observations"]) if rec["ba_observations"] > 0 else None
         return state, dead_l, dead_k, stats
 
-    def extract(self, img, t, current_kp, mask_radius, detector='shi-tomasi'):
+    def extract(self, img, t, current_kp, mask_radius, detector='shi-tomasi', describe=False):
         if detector != 'shi-tomasi':        # (a session's DETECT stage runs the parameters it was created with; extract(detector='fast') stays plain)
+            return NotImplemented
+        if describe:                        # (a session's keypoints carry no descriptor; Extractor(descriptor='brief') describes on the plain path)
             return NotImplemented
         self._drop_hints()
         from .resident import DETECT

@@ -61,14 +61,19 @@ class ResidentPipeline:
     pipeline's own K must equal new_K (K when new_K is absent), anything else raises ValueError.  None (the default): frames are used as given.
     clahe: (clip_limit, (tiles_x, tiles_y)) -- cv2.createCLAHE's arguments -- makes every such frame pass through CLAHE (the context's
     vo_set_clahe), behind the undistortion and in front of the bilateral pre-filter.  None (the default) switches a context's setting off.
+    descriptor: 'brief' makes the DETECT stage describe its integer corners with the oriented BRIEF descriptor (the context's vo_set_brief,
+    brief_pattern = 256 rows (x1, y1, x2, y2) or None for the default table); brief_read() returns descriptors, angles and flags of the last
+    detection after a fetch.  They live in a side buffer: tables, records and lists are what they are without it.  None (the default): off.
     detector: 'shi-tomasi' (the default, the reference's) or 'fast': the DETECT stage ranks the FAST-9/16 corner score at fast_threshold
     (vo_st_params.fast_threshold) instead of the Shi-Tomasi response; discs, quality threshold, min_kp_dist and max_new act as before."""
 
     def __init__(self, ctx, K, ba_window=4, min_track_length=3, mask_radius=7, max_new=1000, max_reproj_err=2.0, min_bearing_angle=0.5,
                  ba_max_iters=50, ba_budget=None, ba_ftol=1e-3, ba_xtol=1e-3, pnp_blind_batches=4, pnp_seed=0, min_kp_dist=7, resurrect=True,
                  fb_max_error=np.inf, ba_loss='huber', ba_f_scale=1.0, klt_predict="off", subpix=None, undistort=None, clahe=None,
-                 detector='shi-tomasi', fast_threshold=20):
+                 detector='shi-tomasi', fast_threshold=20, descriptor=None, brief_pattern=None):
         self.ctx, self._L = ctx, ctx._L
+        if descriptor not in (None, 'brief'):
+            raise ValueError("descriptor must be None or 'brief'")
         if detector not in ('shi-tomasi', 'fast'):
             raise ValueError("detector must be 'shi-tomasi' or 'fast'")
         B = ctx.batch
@@ -99,6 +104,8 @@ class ResidentPipeline:
             ctx.set_klt_predict(klt_predict)
         if not (subpix is None and ctx.get_subpix() is None):
             ctx.set_subpix(subpix)
+        if not (descriptor is None and ctx.get_brief() is None):
+            ctx.set_brief(descriptor == 'brief' or None, brief_pattern)
         ctx.apply_ingest(undistort, clahe, clear_missing=True)
         ctx._subpix_slots = p.st.max_corners if 0 < p.st.max_corners < 4096 else 4096
         self.N, self.R, self.B = ctx.max_pts, 4 * ctx.max_pts, B
@@ -106,6 +113,10 @@ class ResidentPipeline:
         self._inflight = 0
         self._host_refs = collections.deque()             # per step in flight, oldest first: the arrays step_host was given (None: a resident step)
         ctx._ba_shape = (ba_window, ctx.max_pts)          # VoContext.ba_probe reads the resident problem the ADJUST stage builds
+
+    def brief_read(self, n=None):
+        """descriptors, angles and flags of the last DETECT stage's corners (descriptor='brief'; VoContext.brief_read): after a fetch"""
+        return self.ctx.brief_read(n)
 
     # ---- tables ---------------------------------------------------------------------------------
     def read_table(self, name):
