@@ -165,6 +165,27 @@ typedef struct {
   int32_t pad;
 } vo_ess_stats;
 
+/* cv2.findHomography(p1, p2, cv2.RANSAC, ransacReprojThreshold=3.0, maxIters=2000, confidence=0.995): the model the reference's bootstrap
+ * names and never fits (src/pipeline/pipeline.py:66, "Estimate homography") */
+typedef struct {
+  double  threshold;         /* 3.0 px: consensus threshold on the forward transfer error |x2 - proj(H x1)| */
+  double  confidence;        /* 0.995 */
+  int32_t max_iters;         /* 2000 */
+  int32_t seed;              /* of the counter-based sample generator */
+  int32_t refine_iters;      /* 10: Levenberg-Marquardt steps after the DLT re-fit on the inliers; 0 returns the re-fit */
+  int32_t _pad;
+} vo_hom_params;
+
+typedef struct {
+  double  cost;              /* sum of squared forward transfer errors in pixels over the mask at the returned H */
+  int32_t n_inliers;         /* consensus set of H0 */
+  int32_t hypotheses;        /* four-point samples evaluated */
+  int32_t best;              /* index of the winning sample */
+  int32_t status;            /* 0, or VO_E_NUMERIC when no model with >= 4 inliers was found */
+  int32_t lm_iters;          /* refinement steps tried */
+  int32_t _pad;
+} vo_hom_stats;
+
 /* the fields of cv2.KeyPoint that cv2.SIFT fills (the reference reads pt through cv2.KeyPoint_convert and hands the
  * objects back to compute(), src/extractor/extractor.py:114-122) */
 typedef struct {
@@ -599,6 +620,26 @@ int32_t vo_essential_ransac(vo_ctx* ctx, const double* K, const float* pts1, con
                             const vo_ess_params* prm, double* E, double* R, double* t, uint8_t* inlier_mask,
                             vo_ess_stats* stats);
 
+/* ---- homography of the 2D-2D bootstrap and the two-view degeneracy check -------------------------
+ * cv2.findHomography(p1, p2, cv2.RANSAC, 3.0) of OpenCV 4.4, the step the reference's bootstrap names in a comment and leaves out
+ * (Pipeline._get_init_state, src/pipeline/pipeline.py:66 "Estimate homography", in front of the camera_pose call of :68): fitted next
+ * to the essential matrix it tells a frame pair without a baseline, or of a planar scene, from one whose five-point pose can be
+ * trusted (Extractor.bootstrap_check).  Rounds of 256 four-point samples: hypothesis h draws sample4(seed, h, n), the generator of
+ * the other two searches; a sample with three collinear points in either view, or one whose four triples do not keep or reverse
+ * their orientation together (OpenCV's checkSubset), has no model and still counts; a lane per sample solves the Hartley-normalised
+ * 8 x 8 system in float64; a wave per hypothesis counts |x2 - proj(H x1)|^2 <= threshold^2 in float64 (OpenCV: float32); most
+ * inliers win, ties to the smallest h, at least 4; the bound is RANSACUpdateNumIters with 4 model points.  The mask is the winner
+ * H0's and is not recomputed; with n > 4 the inliers are re-fitted by the normalised DLT and refined by at most refine_iters
+ * Levenberg-Marquardt steps on the forward transfer error (8 parameters in the normalised frame); n = 4 returns H = H0.  Sample
+ * draws differ from OpenCV's: statistical parity; the algorithm is defined by tests/homography_model.py.
+ * pts1, pts2 [batch][n][2] f32 pixels (NaN rows, and points whose projective w is 0 or not finite, are never inliers); H, H0
+ * [batch][9] row-major, unit Frobenius norm, h33 >= 0, x2 ~ H x1 (H0 may be NULL); inlier_mask [batch][n] u8 (may be NULL); stats
+ * [batch] (may be NULL).  A sequence without a model: status VO_E_NUMERIC, NaN H and H0, an empty mask; the call returns VO_OK.
+ * VO_E_INVALID with nothing enqueued: n < 4, threshold <= 0, confidence outside (0, 1), max_iters < 1, refine_iters outside 0..100. */
+int32_t vo_homography_default_params(vo_hom_params* p);
+int32_t vo_homography_ransac(vo_ctx* ctx, const float* pts1, const float* pts2, int32_t n, const vo_hom_params* prm,
+                             double* H, double* H0, uint8_t* inlier_mask, vo_hom_stats* stats);
+
 /* ---- SIFT features (SURVEY.md 8f "next" row 4, feature part) -----------------------------------
  * Replaces cv2.SIFT_create(nfeatures=1000).detect(img, mask) + .compute(img, kps) in
  * Extractor.extract(detector='custom', describe=True) (src/extractor/extractor.py:26-28, 114-122; the two bootstrap
@@ -865,9 +906,11 @@ int32_t vo_step_layout(vo_ctx* ctx, int32_t* layout, int32_t* gate_groups, int32
  * Used by bench.py for the roofline figure: region VO_PROF_KLT brackets exactly the k_klt_track launch.
  * vo_profile_read synchronises the stream and returns the summed elapsed time and the number of
  * recorded regions since vo_profile_enable(ctx, mask); mask = OR of (1 << region), 0 = off.
- * VO_PROF_CLAHE_LUT / VO_PROF_CLAHE_APPLY bracket the k_clahe_lut / k_clahe_apply launch of a pyramid build (inside its VO_PROF_FRAME bracket). */
+ * VO_PROF_CLAHE_LUT / VO_PROF_CLAHE_APPLY bracket the k_clahe_lut / k_clahe_apply launch of a pyramid build (inside its VO_PROF_FRAME bracket).
+ * VO_PROF_HOM_SOLVE / _SCORE / _SELECT / _FINISH bracket the k_h4_solve / k_h4_score / k_h4_select launch of every round of
+ * vo_homography_ransac and its k_h4_finish launch (tools/homography_timing.py). */
 enum { VO_PROF_FRAME = 0, VO_PROF_KLT = 1, VO_PROF_ST = 2, VO_PROF_DLT = 3, VO_PROF_BA = 4, VO_PROF_CLAHE_LUT = 5, VO_PROF_CLAHE_APPLY = 6,
-       VO_PROF_COUNT = 7 };
+       VO_PROF_HOM_SOLVE = 7, VO_PROF_HOM_SCORE = 8, VO_PROF_HOM_SELECT = 9, VO_PROF_HOM_FINISH = 10, VO_PROF_COUNT = 11 };
 int32_t vo_profile_enable(vo_ctx* ctx, int32_t region_mask);
 int32_t vo_profile_read(vo_ctx* ctx, int32_t region, double* total_ms, int32_t* count);
 /* diagnostic: shader-clock stamps (s_memtime deltas, cycles) of the phases of the last launch of a

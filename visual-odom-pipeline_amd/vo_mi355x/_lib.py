@@ -93,6 +93,16 @@ class EssStats(C.Structure):
                 ("status", C.c_int32), ("_pad", C.c_int32)]
 
 
+class HomParams(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("max_iters", C.c_int32), ("seed", C.c_int32),
+                ("refine_iters", C.c_int32), ("_pad", C.c_int32)]
+
+
+class HomStats(C.Structure):
+    _fields_ = [("cost", C.c_double), ("n_inliers", C.c_int32), ("hypotheses", C.c_int32), ("best", C.c_int32),
+                ("status", C.c_int32), ("lm_iters", C.c_int32), ("_pad", C.c_int32)]
+
+
 class SiftKp(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("size", C.c_float), ("angle", C.c_float), ("response", C.c_float),
                 ("octave", C.c_int32)]
@@ -220,6 +230,8 @@ SIGNATURES = {
     "vo_essential_default_params": (C.c_int32, [C.POINTER(EssParams)]),
     "vo_essential_ransac": (C.c_int32, [_ctx, _f64p, _f32p, _f32p, C.c_int32, C.POINTER(EssParams), _f64p, _f64p, _f64p, _u8p,
                                         C.POINTER(EssStats)]),
+    "vo_homography_default_params": (C.c_int32, [C.POINTER(HomParams)]),
+    "vo_homography_ransac": (C.c_int32, [_ctx, _f32p, _f32p, C.c_int32, C.POINTER(HomParams), _f64p, _f64p, _u8p, C.POINTER(HomStats)]),
     "vo_sift_detect_compute": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32, C.POINTER(SiftKp), _f32p, _i32p]),
     "vo_match_knn2": (C.c_int32, [_ctx, _f32p, C.c_int32, _f32p, C.c_int32, C.c_int32, _i32p, _f32p]),
     "vo_match_hamming_knn2": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32, _i32p, _i32p]),

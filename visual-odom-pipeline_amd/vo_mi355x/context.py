@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, KltParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
+from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, HomParams, HomStats, KltParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
 
 # vo_set_klt_predict modes (include/vo_mi355x.h)
 KLT_PREDICT_MODES = {"off": 0, "constant_velocity": 1}
@@ -763,6 +763,7 @@ class VoContext:
 
     # -- in-stream timing -----------------------------------------------------------------------
     PROF_FRAME, PROF_KLT, PROF_ST, PROF_DLT, PROF_BA, PROF_CLAHE_LUT, PROF_CLAHE_APPLY = range(7)
+    PROF_HOM_SOLVE, PROF_HOM_SCORE, PROF_HOM_SELECT, PROF_HOM_FINISH = range(7, 11)
 
     def profile_enable(self, regions=(0, 1, 2, 3, 4)):
         """regions: iterable of PROF_* ids to time with hipEvent pairs on the ctx stream; () switches timing off"""
@@ -955,6 +956,34 @@ class VoContext:
         if B == 1:
             return E[0], R[0], t[0], inl[0], stats[0]
         return E, R, t, inl, stats
+
+    def find_homography(self, pts1, pts2, threshold=3.0, confidence=0.995, max_iters=2000, seed=0, refine_iters=10):
+        """cv2.findHomography(pts1, pts2, cv2.RANSAC, threshold) (vo_homography_ransac).  pts1, pts2 (n,2) pixels, n >= 4 [leading batch dim
+        if batch > 1] -> H (3,3) with x2 ~ H x1, re-fitted on the inliers and refined, inlier indices (ascending, the consensus set of H0),
+        stats dict, H0 (3,3) the winning four-point sample's own model.  H and H0 are divided by h33 as cv2 returns them; where |h33| is under
+        1e-12 of the norm they stay at unit Frobenius norm.  Without a model: stats['status'] != 0, NaN matrices, no inliers."""
+        B = self.batch
+        p1 = np.ascontiguousarray(pts1, np.float32).reshape(B, -1, 2)
+        p2 = np.ascontiguousarray(pts2, np.float32).reshape(B, -1, 2)
+        n = p1.shape[1]
+        assert p2.shape[1] == n
+        prm = HomParams()
+        self._L.vo_homography_default_params(C.byref(prm))
+        prm.threshold, prm.confidence, prm.max_iters, prm.seed, prm.refine_iters = threshold, confidence, int(max_iters), int(seed), int(refine_iters)
+        H, H0 = np.zeros((B, 3, 3)), np.zeros((B, 3, 3))
+        mask = np.zeros((B, n), np.uint8)
+        st = (HomStats * B)()
+        self._ck(self._L.vo_homography_ransac(self._h, ptr(p1, C.c_float), ptr(p2, C.c_float), n, C.byref(prm), ptr(H, C.c_double),
+                                              ptr(H0, C.c_double), ptr(mask, C.c_uint8), st))
+        for M in (H, H0):
+            for b in range(B):
+                if abs(M[b, 2, 2]) >= 1e-12 * np.linalg.norm(M[b]):      # (False for NaN: left as it is)
+                    M[b] /= M[b, 2, 2]
+        stats = [dict(cost=s.cost, n_inliers=s.n_inliers, hypotheses=s.hypotheses, best=s.best, status=s.status, lm_iters=s.lm_iters) for s in st]
+        inl = [np.nonzero(mask[b])[0] for b in range(B)]
+        if B == 1:
+            return H[0], inl[0], stats[0], H0[0]
+        return H, inl, stats, H0
 
     def pnp_params(self, reproj_err=2.0, confidence=0.9999, max_iters=1000000, seed=0):
         prm = PnpParams()

@@ -511,3 +511,28 @@ class Extractor:
         H[:3, :3] = rodrigues_vec_to_mat(rvec)
         H[:3, 3] = t.reshape((3,))
         return inliers.reshape((-1,)).tolist(), H
+
+    def _uv_pairs(self, list_1, list_2):
+        return tuple(np.array([kp.uv.T for kp in lst]).astype(np.float32).reshape(-1, 2) for lst in (list_1, list_2))
+
+    def find_homography(self, list_1, list_2, **kw):
+        """cv2.findHomography(RANSAC) between the `uv` of two lists of keypoints (the lists camera_pose takes; the model the reference's
+        bootstrap names at pipeline.py:66 and never fits) -> (H 3x3 with x2 ~ H x1 and h33 = 1, inlier indices as a list, stats dict, H0);
+        keywords as VoContext.find_homography"""
+        if self._ctx is None:
+            raise RuntimeError("find_homography needs the device context: track a frame first (or pass ctx=)")
+        H, inliers, st, H0 = self._ctx.find_homography(*self._uv_pairs(list_1, list_2), **kw)
+        return H, inliers.reshape((-1,)).tolist(), st, H0
+
+    def bootstrap_check(self, K, list_1, list_2, threshold=1.0, max_h_ratio=0.8, seed=0):
+        """Is this frame pair fit for the 2D-2D bootstrap?  One essential_ransac and one find_homography call at the same pixel threshold;
+        -> dict e_inliers, h_inliers, h_ratio = h_inliers / max(e_inliers, 1), degenerate = h_ratio > max_h_ratio (COLMAP's
+        max_H_inlier_ratio rule): a homography that explains nearly every epipolar inlier means no baseline to speak of or a planar scene,
+        and the t of camera_pose(corr='2D-2D') is then not to be trusted.  camera_pose itself is unchanged."""
+        if self._ctx is None:
+            raise RuntimeError("bootstrap_check needs the device context: track a frame first (or pass ctx=)")
+        p1, p2 = self._uv_pairs(list_1, list_2)
+        e_st = self._ctx.essential_ransac(np.asarray(K, np.float64), p1, p2, threshold=threshold, prob=0.9999, seed=seed)[4]
+        h_st = self._ctx.find_homography(p1, p2, threshold=threshold, seed=seed)[2]
+        ratio = h_st["n_inliers"] / max(e_st["n_inliers"], 1)
+        return dict(e_inliers=e_st["n_inliers"], h_inliers=h_st["n_inliers"], h_ratio=ratio, degenerate=bool(ratio > max_h_ratio))
