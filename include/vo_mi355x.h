@@ -576,7 +576,23 @@ int32_t vo_ba_gather_points(vo_ctx* ctx, double* points_all);
  * OpenCV's sample sequence cannot be reproduced (own RNG, EPnP on 5 points): parity is statistical -- same consensus
  * set and minimiser whenever the inlier set is unambiguous; the algorithm itself is defined by oracle/pnp_oracle.py.
  * K [batch][9]; pts3d [batch][n][3], pts2d [batch][n][2] f32 (NaN rows are never inliers);
- * rvec, tvec [batch][3] f64 (x_cam = R(rvec) X + tvec); inlier_mask [batch][n] u8 (may be NULL); stats [batch]. */
+ * rvec, tvec [batch][3] f64 (x_cam = R(rvec) X + tvec); inlier_mask [batch][n] u8 (may be NULL); stats [batch].
+ * Held to an independent float64 model (tests/pnp_model.py; test_pnp_model.py on the CPU, test_gpu_pnp_model.py on the kernel):
+ *   P3P accuracy    every solution of Grunert's quartic is polished by Newton on the three distance equations in the depths (at most 16
+ *                   steps, skipped where the squared sides are already met to 1e-10 of the squared smallest altitude).  A returned pose
+ *                   reprojects the three points it was solved from within 2e-8 px (measured over 7 x 400 sets: general, wall, far, 5 cm
+ *                   triangles, near-equilateral, isosceles, near-collinear; bound 1e-6 px).  The quartic alone was off by up to 74 px on
+ *                   a wall and 7 px on tiny and symmetric triangles.  A double root that rounding split into a complex pair is kept, and where
+ *                   2 (cos gamma - v cos alpha) is under 1e-3 the depth ratio u is also taken from its quadratic (two solutions share v).
+ *   missed roots    a triangle of under a pixel (three points within 5 cm at 10-40 m) leaves the quartic's coefficients four or five
+ *                   digits: 23 of 400 such sets lose their roots (22 yield no pose at all).  One of 400 near-equilateral sets (1 mm off
+ *                   the symmetry) still loses one near-double root; next to a double root (one float32 near-collinear set, conditioning of the
+ *                   three reprojections 0.016 px per unit pose) Newton from either quartic root lands on the same neighbour.
+ *   consensus       no cheirality test: a point behind the camera that reprojects within reproj_err counts, as with
+ *                   cv2.projectPoints; NaN rows and points with p2 == 0 never count.  The division is v_rcp_f64 + two Newton steps:
+ *                   a point whose squared error is within 8 x 2^-52 x (e (|u| + |v|) + e^2) of reproj_err^2 may fall on either side.
+ *   rvec            within 1e-2 of pi the angle comes from atan2 (|w| / 2, c) and the axis from the symmetric part of R (a few 2^-52);
+ *                   th / (2 sin th) with th = acos(c) was off by 6e-6 rad at pi - 1e-5 and 2e-4 rad at pi - 2e-6. */
 int32_t vo_pnp_default_params(vo_pnp_params* p);
 int32_t vo_pnp_ransac(vo_ctx* ctx, const double* K, const float* pts3d, const float* pts2d, int32_t n,
                       const vo_pnp_params* prm, double* rvec, double* tvec, uint8_t* inlier_mask, vo_pnp_stats* stats);

@@ -60,8 +60,12 @@ def log_so3(R):
     w = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
     if th < 1e-10:
         return 0.5 * w
-    if math.pi - th < 1e-6:                      # near pi: from the symmetric part
-        A = (R + np.eye(3)) / 2
+    if math.pi - th < 1e-2:
+        # near pi, acos(c) and sin(acos(c)) keep only eps / (pi - th)^2 of their digits (1 + c is a difference): th / (2 sin th) w was off by
+        # 6e-6 rad at pi - 1e-5 and by 2e-4 at pi - 2e-6.  The angle comes from the accurate sine |w| / 2 instead, the axis from the
+        # symmetric part: (R + R^T) / 2 = c I + (1 - c) a a^T
+        th = math.atan2(0.5 * math.sqrt(np.dot(w, w)), c)
+        A = ((R + R.T) / 2 - c * np.eye(3)) / (1.0 - c)
         ax = np.sqrt(np.maximum(np.diag(A), 0))
         i = int(np.argmax(ax))
         v = A[:, i] / ax[i]
@@ -97,7 +101,7 @@ def quartic_real_roots(c4, c3, c2, c1, c0):
     p = b - 3.0 * a * a / 8.0
     q = c - a * b / 2.0 + a * a * a / 8.0
     r = d - a * c / 4.0 + a * a * b / 16.0 - 3.0 * a * a * a * a / 256.0
-    ys = []
+    ys, dbl = [], []                                     # dbl: roots of the depressed quartic that take no Newton step
     if abs(q) < 1e-14 * (1.0 + abs(p) ** 1.5):
         disc = p * p - 4.0 * r
         if disc >= 0:
@@ -113,19 +117,72 @@ def quartic_real_roots(c4, c3, c2, c1, c0):
                 # y^2 + sg s y + (p + z0) / 2 - sg q / (2 s) = 0
                 bb, cc = sg * s, (p + z0) / 2.0 - sg * q / (2.0 * s)
                 disc = bb * bb - 4.0 * cc
+                if disc < 0 and -disc <= QUARTIC_DISC_TOL * (1.0 + a * a / 16.0):
+                    # a double root that rounding split into a complex pair: kept, as a double root, without the Newton steps below
+                    # (f' vanishes there and a step would throw it far away)
+                    dbl += [len(ys), len(ys) + 1]
+                    ys += [-bb / 2.0, -bb / 2.0]
                 if disc >= 0:
                     sq = math.sqrt(disc)
                     ys += [(-bb + sq) / 2.0, (-bb - sq) / 2.0]
     out = []
-    for y in ys:
+    for i, y in enumerate(ys):
         x = y - a / 4.0
-        for _ in range(2):
+        for _ in range(0 if i in dbl else 2):
             f = (((c4 * x + c3) * x + c2) * x + c1) * x + c0
             fp = ((4.0 * c4 * x + 3.0 * c3) * x + 2.0 * c2) * x + c1
             if fp != 0.0:
                 x -= f / fp
         out.append(x)
     return out
+
+
+QUARTIC_DISC_TOL = 1e-10   # a quadratic factor's discriminant this little below zero counts as zero, in units of the squared root scale
+#                            1 + (a / 4)^2: p, q, r carry a few 1e-16 of the coefficients, the factor's constant term that over 2 sqrt(z0)
+P3P_ACCEPT = 1e-6          # a polished solution still off its squared sides by more than this x (smallest altitude)^2 is no solution (~1e-3 px)
+P3P_DEN_SMALL = 1e-3       # |2 (cg - v ca)| under this: u is taken from its quadratic as well (see p3p)
+P3P_POLISH_STEPS = 16
+P3P_POLISH_GATE = 1e-10   # a solution that meets the three squared side lengths to this x (smallest altitude)^2 is left as Grunert's algebra gave it
+
+
+def p3p_polish(s, a2, b2, c2, ca, cb, cg, h2):
+    """Newton on the three law-of-cosines equations in the depths (s1, s2, s3):
+        s2^2 + s3^2 - 2 s2 s3 ca = a2,   s1^2 + s3^2 - 2 s1 s3 cb = b2,   s1^2 + s2^2 - 2 s1 s2 cg = c2
+    with the closed-form inverse of the 3 x 3 Jacobian (its diagonal is zero).  At most P3P_POLISH_STEPS steps, ended by a step below the
+    rounding of the depths (two or three steps on a well-conditioned set; near a double root Newton is linear and uses them all) or by a
+    singular or non-finite Jacobian.  The polished depths are kept only if they are positive and their squared residual did not grow:
+    whatever happens, the solution is no worse than it was.  -> depths, ok; ok is False where the squared residual
+    is still over 3 (P3P_ACCEPT h2)^2: the candidate is no solution of the three equations and gives no pose.  (Newton is not monotone from the quartic's root: a test per step loses roots.)"""
+    def res(s1, s2, s3):
+        return (s2 * s2 + s3 * s3 - 2.0 * s2 * s3 * ca - a2, s1 * s1 + s3 * s3 - 2.0 * s1 * s3 * cb - b2, s1 * s1 + s2 * s2 - 2.0 * s1 * s2 * cg - c2)
+    s1, s2, s3 = s
+    f1, f2, f3 = res(s1, s2, s3)
+    # h2 = squared smallest altitude h of the world triangle.  A squared side off by f moves a vertex by about f / (2 h) -- the side's own
+    # error f / (2 d) times d / h, the lever of a thin triangle --, i.e. by f F / (2 h z) pixels = (f / h^2) x (h in pixels) / 2: with the
+    # gate and an altitude that spans the image (1300 px) that is under 1e-7 px.  Such a solution is left bit for bit as it was
+    tol = P3P_POLISH_GATE * h2
+    if abs(f1) <= tol and abs(f2) <= tol and abs(f3) <= tol:
+        return s, True
+    r0 = f1 * f1 + f2 * f2 + f3 * f3
+    for _ in range(P3P_POLISH_STEPS):
+        a, b = s2 - s3 * ca, s3 - s2 * ca               # half the Jacobian: [[0, a, b], [c, 0, d], [e, g, 0]]
+        c, d = s1 - s3 * cb, s3 - s1 * cb
+        e, g = s1 - s2 * cg, s2 - s1 * cg
+        det = a * d * e + b * c * g
+        if not (abs(det) > 0.0 and math.isfinite(det)):
+            break
+        idet = -0.5 / det
+        d1 = (-d * g * f1 + b * g * f2 + a * d * f3) * idet
+        d2 = (d * e * f1 - b * e * f2 + b * c * f3) * idet
+        d3 = (c * g * f1 + a * e * f2 - a * c * f3) * idet
+        s1, s2, s3 = s1 + d1, s2 + d2, s3 + d3
+        f1, f2, f3 = res(s1, s2, s3)
+        if abs(d1) + abs(d2) + abs(d3) <= 4.0e-16 * (abs(s1) + abs(s2) + abs(s3)):
+            break
+    r1 = f1 * f1 + f2 * f2 + f3 * f3
+    if not (s1 > 0 and s2 > 0 and s3 > 0 and r1 <= r0):  # (NaN lands here)
+        (s1, s2, s3), r1 = s, r0
+    return (s1, s2, s3), r1 <= 3.0 * (P3P_ACCEPT * h2) ** 2
 
 
 def p3p(f, P):
@@ -149,26 +206,44 @@ def p3p(f, P):
         return []
     e3 = e3 / n3
     e2 = np.cross(e3, e1)
+    h2 = n3 * n3 * c2 / max(a2, b2, c2)                 # n3 = altitude on the side P0 P1; the smallest altitude stands on the longest side
     for v in quartic_real_roots(A4, A3, A2, A1, A0):
         den = 2.0 * (cg - v * ca)
-        if v <= 0 or abs(den) < 1e-12:
+        if v <= 0:
             continue
-        u = ((qq - 1.0) * v * v - 2.0 * qq * cb * v + 1.0 + qq) / den
         w = 1.0 + v * v - 2.0 * v * cb
-        if u <= 0 or w <= 0:
-            continue
-        s1 = math.sqrt(b2 / w)
-        Q = [s1 * f[0], u * s1 * f[1], v * s1 * f[2]]
-        g1 = Q[1] - Q[0]; g1 = g1 / math.sqrt(np.dot(g1, g1))
-        g3 = np.cross(g1, Q[2] - Q[0]); m3 = math.sqrt(np.dot(g3, g3))
-        if m3 <= 0:
-            continue
-        g3 = g3 / m3
-        g2 = np.cross(g3, g1)
-        R = np.outer(g1, e1) + np.outer(g2, e2) + np.outer(g3, e3)
-        t = Q[0] - R @ P[0]
-        sols.append((R, t))
+        us = [((qq - 1.0) * v * v - 2.0 * qq * cb * v + 1.0 + qq) / den] if abs(den) >= 1e-12 else []
+        if abs(den) < P3P_DEN_SMALL and w > 0:
+            # two solutions that share v (a near-symmetric triangle: a double root of the quartic) differ in u alone; the rational form
+            # is then 0 / 0 and single-valued.  Both roots of  u^2 - 2 u cg + 1 = C w  are tried as well; the polish and the fourth
+            # point decide
+            sq = math.sqrt(max(cg * cg - 1.0 + C * w, 0.0))
+            us += [cg + sq, cg - sq]
+        for u in us:
+            sol = p3p_pose(u, v, w, f, P, e1, e2, e3, a2, b2, c2, ca, cb, cg, h2)
+            if sol is not None:
+                sols.append(sol)
     return sols
+
+
+def p3p_pose(u, v, w, f, P, e1, e2, e3, a2, b2, c2, ca, cb, cg, h2):
+    """pose of the depth ratios (u, v) = (s2, s3) / s1: depths, polish, triad -> (R, t) or None"""
+    if u <= 0 or w <= 0:
+        return None
+    s1 = math.sqrt(b2 / w)
+    (s1, s2, s3), ok = p3p_polish((s1, u * s1, v * s1), a2, b2, c2, ca, cb, cg, h2)
+    if not ok:
+        return None
+    Q = [s1 * f[0], s2 * f[1], s3 * f[2]]
+    g1 = Q[1] - Q[0]; g1 = g1 / math.sqrt(np.dot(g1, g1))
+    g3 = np.cross(g1, Q[2] - Q[0]); m3 = math.sqrt(np.dot(g3, g3))
+    if m3 <= 0:
+        return None
+    g3 = g3 / m3
+    g2 = np.cross(g3, g1)
+    R = np.outer(g1, e1) + np.outer(g2, e2) + np.outer(g3, e3)
+    t = Q[0] - R @ P[0]
+    return R, t
 
 
 def reproj_err2(K, R, t, X, uv):

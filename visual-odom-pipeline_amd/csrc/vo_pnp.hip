@@ -8,8 +8,10 @@
 // squared reprojection error <= reprojectionError^2, stop when an all-inlier sample has been drawn with probability
 // `confidence` (RANSACUpdateNumIters), returned pose = minimiser of the reprojection error over the consensus set.
 // The algorithm here is defined by oracle/pnp_oracle.py (hypothesis h = 4 indices from splitmix64(seed, h, draw);
-// Grunert P3P on three, the fourth disambiguates; batches of 256 hypotheses; ties to the smallest h) and is compared
-// with it hypothesis by hypothesis.
+// Grunert P3P on three, every solution polished by Newton on the three distance equations in the depths, the fourth
+// disambiguates; batches of 256 hypotheses; ties to the smallest h) and is compared with it hypothesis by hypothesis.
+// tests/pnp_model.py holds both to an independent float64 model; what the solver still misses is stated above vo_pnp_ransac
+// in include/vo_mi355x.h.
 //
 // GPU mapping: a LANE per hypothesis for the minimal solve, then FOUR WAVES per hypothesis for the consensus count (lanes
 // stride over the points).  32 (first batch of a search) or 256 hypotheses x batch sequences per launch; a one-workgroup-per-sequence kernel keeps the running best and the
@@ -88,6 +90,9 @@ __device__ inline double pnp_cubic_root(double A, double B, double C) {   // lar
   return t - A / 3.0;
 }
 
+// a quadratic factor's discriminant this little below zero counts as zero, in units of the squared root scale 1 + (a / 4)^2: p, q, r carry a
+// few 1e-16 of the coefficients, the factor's constant term that over 2 sqrt(z0)
+#define PNP_QUARTIC_DISC_TOL 1e-10
 __device__ inline int pnp_quartic(double c4, double c3, double c2, double c1, double c0, double x[4]) {
   if (fabs(c4) < 1e-300) return 0;
   const double a = c3 / c4, b = c2 / c4, c = c1 / c4, d = c0 / c4;
@@ -96,6 +101,7 @@ __device__ inline int pnp_quartic(double c4, double c3, double c2, double c1, do
   const double r = d - a * c / 4.0 + a * a * b / 16.0 - 3.0 * a * a * a * a / 256.0;
   double ys[4];
   int ny = 0;
+  unsigned dbl = 0;                                     // roots of the depressed quartic that take no Newton step
   if (fabs(q) < 1e-14 * (1.0 + pow(fabs(p), 1.5))) {
     const double disc = p * p - 4.0 * r;
     if (disc >= 0) {
@@ -112,6 +118,12 @@ __device__ inline int pnp_quartic(double c4, double c3, double c2, double c1, do
         const double sg = k ? -1.0 : 1.0;
         const double bb = sg * s, cc = (p + z0) / 2.0 - sg * q / (2.0 * s);
         const double disc = bb * bb - 4.0 * cc;
+        if (disc < 0 && -disc <= PNP_QUARTIC_DISC_TOL * (1.0 + a * a / 16.0)) {
+          // a double root that rounding split into a complex pair: kept, as a double root, without the Newton steps below
+          // (f' vanishes there and a step would throw it far away)
+          dbl |= 3u << ny;
+          ys[ny++] = -bb / 2.0; ys[ny++] = -bb / 2.0;
+        }
         if (disc >= 0) {
           const double sq = sqrt(disc);
           ys[ny++] = (-bb + sq) / 2.0; ys[ny++] = (-bb - sq) / 2.0;
@@ -121,7 +133,7 @@ __device__ inline int pnp_quartic(double c4, double c3, double c2, double c1, do
   }
   for (int i = 0; i < ny; i++) {
     double xv = ys[i] - a / 4.0;
-    for (int it = 0; it < 2; it++) {
+    for (int it = 0; it < (((dbl >> i) & 1u) ? 0 : 2); it++) {
       const double f = (((c4 * xv + c3) * xv + c2) * xv + c1) * xv + c0;
       const double fp = ((4.0 * c4 * xv + 3.0 * c3) * xv + 2.0 * c2) * xv + c1;
       if (fp != 0.0) xv -= f / fp;
@@ -190,7 +202,50 @@ __device__ __forceinline__ double pnp_err2(const double* K, const double* R, con
   return du * du + dv * dv;
 }
 
-// Grunert P3P on three correspondences, the fourth picks among the solutions.  -> true if a pose was found
+// Newton on the three law-of-cosines equations in the depths (oracle/pnp_oracle.py p3p_polish):
+//   s2^2 + s3^2 - 2 s2 s3 ca = a2,   s1^2 + s3^2 - 2 s1 s3 cb = b2,   s1^2 + s2^2 - 2 s1 s2 cg = c2
+// with the closed-form inverse of the 3 x 3 Jacobian (zero diagonal).  At most PNP_POLISH_STEPS steps, ended by a step below the rounding
+// of the depths (two or three steps on a well-conditioned set; near a double root Newton is linear and uses them all) or by a singular or
+// non-finite Jacobian.  The polished depths are kept only if they are positive and their squared residual did not grow: whatever happens,
+// the solution is no worse than it was.  -> false where the squared residual is still over 3 (PNP_P3P_ACCEPT h2)^2: the candidate is no
+// solution of the three equations and gives no pose.  Grunert's quartic alone leaves a backward error of up to pixels on near-double roots (walls, tiny
+// or symmetric triangles); see the comment above vo_pnp_ransac in include/vo_mi355x.h.
+// A solution that meets the three squared side lengths to PNP_POLISH_GATE x h2 (h: the smallest altitude of the world triangle) is left bit
+// for bit as it was: a squared side off by f moves a vertex by about f / (2 h) -- the side's own error times the lever d / h of a thin
+// triangle --, i.e. by (f / h^2) x (h in pixels) / 2: under 1e-7 px even for an altitude that spans the image.
+#define PNP_POLISH_STEPS 16
+#define PNP_DEN_SMALL 1e-3      // |2 (cg - v ca)| under this: u is taken from its quadratic as well (pnp_hypothesis)
+#define PNP_POLISH_GATE 1e-10
+#define PNP_P3P_ACCEPT 1e-6     // a polished solution still off its squared sides by more than this x h2 is no solution (~1e-3 px): no pose
+__device__ inline bool pnp_p3p_polish(double* s, double a2, double b2, double c2, double ca, double cb, double cg, double h2) {
+  double s1 = s[0], s2 = s[1], s3 = s[2];
+  double f1 = s2 * s2 + s3 * s3 - 2.0 * s2 * s3 * ca - a2, f2 = s1 * s1 + s3 * s3 - 2.0 * s1 * s3 * cb - b2, f3 = s1 * s1 + s2 * s2 - 2.0 * s1 * s2 * cg - c2;
+  const double tol = PNP_POLISH_GATE * h2;
+  if (fabs(f1) <= tol && fabs(f2) <= tol && fabs(f3) <= tol) return true;
+  const double r0 = f1 * f1 + f2 * f2 + f3 * f3;
+#pragma unroll 1
+  for (int it = 0; it < PNP_POLISH_STEPS; it++) {
+    const double a = s2 - s3 * ca, b = s3 - s2 * ca;          // half the Jacobian: [[0, a, b], [c, 0, d], [e, g, 0]]
+    const double c = s1 - s3 * cb, d = s3 - s1 * cb;
+    const double e = s1 - s2 * cg, g = s2 - s1 * cg;
+    const double det = a * d * e + b * c * g;
+    if (!(fabs(det) > 0.0 && isfinite(det))) break;
+    const double idet = -0.5 * pnp_rcp(det);          // (a Newton step forgives the last ulp; the IEEE divide is ~30 dependent instructions)
+    const double d1 = (-d * g * f1 + b * g * f2 + a * d * f3) * idet;
+    const double d2 = (d * e * f1 - b * e * f2 + b * c * f3) * idet;
+    const double d3 = (c * g * f1 + a * e * f2 - a * c * f3) * idet;
+    s1 += d1; s2 += d2; s3 += d3;
+    f1 = s2 * s2 + s3 * s3 - 2.0 * s2 * s3 * ca - a2; f2 = s1 * s1 + s3 * s3 - 2.0 * s1 * s3 * cb - b2; f3 = s1 * s1 + s2 * s2 - 2.0 * s1 * s2 * cg - c2;
+    if (fabs(d1) + fabs(d2) + fabs(d3) <= 4.0e-16 * (fabs(s1) + fabs(s2) + fabs(s3))) break;
+  }
+  double r1 = f1 * f1 + f2 * f2 + f3 * f3;
+  if (s1 > 0 && s2 > 0 && s3 > 0 && r1 <= r0) { s[0] = s1; s[1] = s2; s[2] = s3; }      // (false for NaN)
+  else r1 = r0;
+  const double acc = PNP_P3P_ACCEPT * h2;
+  return r1 <= 3.0 * (acc * acc);
+}
+
+// Grunert P3P on three correspondences, each solution polished on its depth equations, the fourth picks among them.  -> true if a pose was found
 __device__ inline bool pnp_hypothesis(const double* K, const double* Kinv, const double P[4][3], const double uv[4][2], double* Rb, double* tb) {
   double f[3][3];
   for (int i = 0; i < 3; i++) {
@@ -221,6 +276,7 @@ __device__ inline bool pnp_hypothesis(const double* K, const double* Kinv, const
   if (!(n3 > 0)) return false;
   e3[0] /= n3; e3[1] /= n3; e3[2] /= n3;
   v3_cross(e3, e1, e2);
+  const double h2 = n3 * n3 * c2 / fmax(a2, fmax(b2, c2));   // n3 = altitude on the side P0 P1; the smallest altitude stands on the longest side
   double roots[4];
   const int nr = pnp_quartic(A4, A3, A2, A1, A0, roots);
   bool found = false;
@@ -228,30 +284,41 @@ __device__ inline bool pnp_hypothesis(const double* K, const double* Kinv, const
   for (int k = 0; k < nr; k++) {
     const double v = roots[k];
     const double den = 2.0 * (cg - v * ca);
-    if (!(v > 0) || fabs(den) < 1e-12) continue;
-    const double u = ((qq - 1.0) * v * v - 2.0 * qq * cb * v + 1.0 + qq) / den;
+    if (!(v > 0)) continue;
     const double w = 1.0 + v * v - 2.0 * v * cb;
-    if (!(u > 0) || !(w > 0)) continue;
-    const double s1 = sqrt(b2 / w);
-    double Q[3][3];
-    for (int c = 0; c < 3; c++) { Q[0][c] = s1 * f[0][c]; Q[1][c] = u * s1 * f[1][c]; Q[2][c] = v * s1 * f[2][c]; }
-    double g1[3], g2[3], g3[3];
-    v3_sub(Q[1], Q[0], g1);
-    { const double nn = sqrt(v3_dot(g1, g1)); g1[0] /= nn; g1[1] /= nn; g1[2] /= nn; }
-    v3_sub(Q[2], Q[0], tmp); v3_cross(g1, tmp, g3);
-    const double m3 = sqrt(v3_dot(g3, g3));
-    if (!(m3 > 0)) continue;
-    g3[0] /= m3; g3[1] /= m3; g3[2] /= m3;
-    v3_cross(g3, g1, g2);
-    double R[9], t[3];
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++) R[3 * i + j] = g1[i] * e1[j] + g2[i] * e2[j] + g3[i] * e3[j];
-    for (int i = 0; i < 3; i++) t[i] = Q[0][i] - (R[3 * i] * P[0][0] + R[3 * i + 1] * P[0][1] + R[3 * i + 2] * P[0][2]);
-    const double e = pnp_err2(K, R, t, P[3], uv[3][0], uv[3][1]);
-    if (e < (found ? best_e : __builtin_inf())) {          // NaN never wins
-      found = true; best_e = e;
-      for (int i = 0; i < 9; i++) Rb[i] = R[i];
-      for (int i = 0; i < 3; i++) tb[i] = t[i];
+    const bool rational = !(fabs(den) < 1e-12);
+    const double u0 = ((qq - 1.0) * v * v - 2.0 * qq * cb * v + 1.0 + qq) / den;
+    // two solutions that share v (a near-symmetric triangle: a double root of the quartic) differ in u alone; the rational form is then
+    // 0 / 0 and single-valued.  Both roots of  u^2 - 2 u cg + 1 = C w  are tried as well; the polish and the fourth point decide
+    const bool both = fabs(den) < PNP_DEN_SMALL && w > 0;
+    const double usq = sqrt(fmax(cg * cg - 1.0 + C * w, 0.0));
+#pragma unroll 1
+    for (int cand = rational ? 0 : 1; cand < (both ? 3 : 1); cand++) {
+      const double u = cand == 0 ? u0 : (cand == 1 ? cg + usq : cg - usq);
+      if (!(u > 0) || !(w > 0)) continue;
+      const double s1 = sqrt(b2 / w);
+      double sd[3] = {s1, u * s1, v * s1};
+      if (!pnp_p3p_polish(sd, a2, b2, c2, ca, cb, cg, h2)) continue;
+      double Q[3][3];
+      for (int c = 0; c < 3; c++) { Q[0][c] = sd[0] * f[0][c]; Q[1][c] = sd[1] * f[1][c]; Q[2][c] = sd[2] * f[2][c]; }
+      double g1[3], g2[3], g3[3];
+      v3_sub(Q[1], Q[0], g1);
+      { const double nn = sqrt(v3_dot(g1, g1)); g1[0] /= nn; g1[1] /= nn; g1[2] /= nn; }
+      v3_sub(Q[2], Q[0], tmp); v3_cross(g1, tmp, g3);
+      const double m3 = sqrt(v3_dot(g3, g3));
+      if (!(m3 > 0)) continue;
+      g3[0] /= m3; g3[1] /= m3; g3[2] /= m3;
+      v3_cross(g3, g1, g2);
+      double R[9], t[3];
+      for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) R[3 * i + j] = g1[i] * e1[j] + g2[i] * e2[j] + g3[i] * e3[j];
+      for (int i = 0; i < 3; i++) t[i] = Q[0][i] - (R[3 * i] * P[0][0] + R[3 * i + 1] * P[0][1] + R[3 * i + 2] * P[0][2]);
+      const double e = pnp_err2(K, R, t, P[3], uv[3][0], uv[3][1]);
+      if (e < (found ? best_e : __builtin_inf())) {          // NaN never wins
+        found = true; best_e = e;
+        for (int i = 0; i < 9; i++) Rb[i] = R[i];
+        for (int i = 0; i < 3; i++) tb[i] = t[i];
+      }
     }
   }
   return found;
@@ -418,16 +485,22 @@ __device__ inline void pnp_log_so3(const double* R, double* r) {
   const double th = acos(c);
   const double w[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
   if (th < 1e-10) { r[0] = 0.5 * w[0]; r[1] = 0.5 * w[1]; r[2] = 0.5 * w[2]; return; }
-  if (3.141592653589793 - th < 1e-6) {
-    const double A[9] = {(R[0] + 1) / 2, R[1] / 2 + R[3] / 2, R[2] / 2 + R[6] / 2, R[3] / 2 + R[1] / 2, (R[4] + 1) / 2, R[5] / 2 + R[7] / 2,
-                         R[6] / 2 + R[2] / 2, R[7] / 2 + R[5] / 2, (R[8] + 1) / 2};
+  if (3.141592653589793 - th < 1e-2) {
+    // near pi, acos(c) and sin(acos(c)) keep only eps / (pi - th)^2 of their digits (1 + c is a difference): th / (2 sin th) w was off by
+    // 6e-6 rad at pi - 1e-5 and by 2e-4 at pi - 2e-6.  The angle comes from the accurate sine |w| / 2 instead, the axis from the symmetric
+    // part: (R + R^T) / 2 = c I + (1 - c) a a^T
+    const double tha = atan2(0.5 * sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), c);
+    const double ic = 1.0 / (1.0 - c);
+    const double A[9] = {((R[0] + R[0]) / 2 - c) * ic, ((R[1] + R[3]) / 2) * ic, ((R[2] + R[6]) / 2) * ic,
+                         ((R[3] + R[1]) / 2) * ic, ((R[4] + R[4]) / 2 - c) * ic, ((R[5] + R[7]) / 2) * ic,
+                         ((R[6] + R[2]) / 2) * ic, ((R[7] + R[5]) / 2) * ic, ((R[8] + R[8]) / 2 - c) * ic};
     const double ax[3] = {sqrt(fmax(A[0], 0.0)), sqrt(fmax(A[4], 0.0)), sqrt(fmax(A[8], 0.0))};
     int i = 0;
     if (ax[1] > ax[i]) i = 1;
     if (ax[2] > ax[i]) i = 2;
     double v[3] = {A[i] / ax[i], A[3 + i] / ax[i], A[6 + i] / ax[i]};
     if (w[0] * v[0] + w[1] * v[1] + w[2] * v[2] < 0) { v[0] = -v[0]; v[1] = -v[1]; v[2] = -v[2]; }
-    r[0] = th * v[0]; r[1] = th * v[1]; r[2] = th * v[2];
+    r[0] = tha * v[0]; r[1] = tha * v[1]; r[2] = tha * v[2];
     return;
   }
   const double k = th / (2.0 * sin(th));
