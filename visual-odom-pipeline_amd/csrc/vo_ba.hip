@@ -469,7 +469,10 @@ __device__ inline void ba_decide(const ba_state& in, const ba_info& info, const 
   const double F = info.cost_cur;
   if (in.iter == 0) out.cost0 = F;
   out.cost = F;
-  if (info.ginf < prm.gtol) { out.done = 1; out.status = 1; return; }
+  // a non-finite cost takes none of the convergence exits (the maxima behind ginf drop NaN: with every gradient entry NaN it arrives as 0);
+  // its steps are rejected until the damping overflows (status 4)
+  const bool fin = F - F == 0.0;
+  if (fin && info.ginf < prm.gtol) { out.done = 1; out.status = 1; return; }
   const double Ft = sums[0], predp = sums[1], step2 = sums[2], x2 = sums[3];
   const double pred = 0.5 * (predp + info.pred_pose);
   const double step = sqrt(step2 + info.step2_pose), xn = sqrt(x2 + info.x2_pose);
@@ -487,9 +490,9 @@ __device__ inline void ba_decide(const ba_state& in, const ba_info& info, const 
     if (lam < prm.lambda_min) lam = prm.lambda_min;
     out.lambda = lam; out.nu = 2.0;
     if ((F - Ft) < prm.ftol * Ft) { out.done = 1; out.status = 2; }
-    else if (step < prm.xtol * (prm.xtol + xn)) { out.done = 1; out.status = 3; }
+    else if (fin && step < prm.xtol * (prm.xtol + xn)) { out.done = 1; out.status = 3; }
   } else {
-    if (ok && step < prm.xtol * (prm.xtol + xn)) { out.done = 1; out.status = 3; }
+    if (ok && fin && step < prm.xtol * (prm.xtol + xn)) { out.done = 1; out.status = 3; }
     else {
       out.lambda = in.lambda * in.nu; out.nu = in.nu * 2.0;
       if (out.lambda > 1e12) { out.done = 1; out.status = 4; }
