@@ -846,7 +846,7 @@ int32_t vo_pipe_inliers_read(vo_ctx* ctx, uint8_t* mask, int32_t n);
  * last bits of a bundle adjustment (its partial sums are folded in another order: ~1e-12).  Set it with nothing in flight; the bundle-adjustment
  * fields marked (upload) shape the workspace and take effect at the next vo_ba_upload / vo_ba_upload_bank / vo_pipe_create. */
 typedef struct {
-  int32_t ba_kernels;          /* (upload) 1: lane-per-observation kernels (k_ba_build<>); 2: wave-private kernels (k_ba_build_w<>, windows <= 10) */
+  int32_t ba_kernels;          /* (upload) 0: the rule (windows of 9-10 slots, Huber / linear loss: the factored k_ba_build_f<>); 1: lane-per-observation kernels (k_ba_build<>); 2: wave-private kernels (k_ba_build_w<>, windows <= 10) */
   int32_t ba_lanes;            /* (upload) lanes per landmark: 8 = wave-private kernels at windows of 9-10 slots (rule: 5); 16 = lane-per-observation
                                   kernels at windows <= 8 (rule: 8) */
   int32_t ba_threads;          /* (upload) lane-per-observation kernels: workgroup size 256 / 512 / 1024 */
