@@ -454,7 +454,8 @@ int32_t vo_subpix_read(vo_ctx* ctx, float* raw, int32_t* iters, uint8_t* flags, 
  *            without contraction fx = x1*c - y1*s, fy = x1*s + y1*c (two rounded products, one rounded sum), ix = rint(fx), iy = rint(fy) half
  *            to even.  Bit i = S(x+ix1, y+iy1) < S(x+ix2, y+iy2), in byte i / 8 at bit i % 8 (LSB first).
  *   default  pattern: BRIEF's isotropic Gaussian sampling, N(0, 6^2) rounded, defined by tools/gen_brief_pattern.py (csrc/vo_brief_pattern.h).
- * Not ORB: the 8-level pyramid and the Harris re-ranking (the corners are single-scale), the learned table, fastAtan2.
+ * Not ORB by itself: the corners are single-scale.  The 8-level pyramid, the Harris re-ranking and the per-level quotas are vo_orb_detect_compute's
+ * (section "multi-scale ORB features"), which describes with this same code; the learned table and fastAtan2 are in neither.
  * Kernel k_brief_describe (csrc/vo_brief.hip): one wave per corner, the 49 x 49 tile and its blur in LDS.
  *   vo_brief_default_pattern  out[1024]: the default table; needs no context.
  *   vo_brief_params           n_bits must be 256; the rest is room to grow and must be 0.  vo_brief_default_params fills it.
@@ -674,6 +675,72 @@ int32_t vo_homography_ransac(vo_ctx* ctx, const float* pts1, const float* pts2, 
  * kps [batch][max_out]; desc [batch][max_out][128] f32; n_out [batch].  VO_E_CAPACITY if max_out is too small. */
 int32_t vo_sift_detect_compute(vo_ctx* ctx, const uint8_t* img, int32_t stride, const uint8_t* mask, int32_t nfeatures,
                                int32_t max_out, vo_sift_kp* kps, float* desc, int32_t* n_out);
+
+/* ---- multi-scale ORB features -------------------------------------------------------------------
+ * The reference's Extractor names two feature methods, 'sift' and 'orb' (src/extractor/extractor.py:26-33: cv2.ORB_create(); :114-122 detect +
+ * compute; :144-145 the 1-NN Hamming match).  This is the 'orb' one: FAST-9/16 corners on a scale pyramid, Harris re-ranking, per-level quotas,
+ * orientation by intensity centroid and the steered 256-bit BRIEF of the section above.  Neither OpenCV nor its learned table is part of this
+ * project: parity with cv2.ORB is not pinned, the numpy model tests/orb_model.py is the definition, and the kernels equal it bit for bit
+ * (integer arithmetic or single IEEE operations in a fixed order).
+ *   geometry   float64 on the host: s_l = scale_factor^l (pow), w_l = rint(w / s_l), h_l = rint(h / s_l), half to even; the reported scale is
+ *              (float)s_l.  A level with w_l < 1 or h_l < 1 has no pixels.
+ *   quotas     OpenCV's rule in float64: f = 1 / scale_factor, nd = nfeatures (1 - f) / (1 - f^nlevels); levels 0 .. nlevels-2 get rint(nd) and
+ *              nd *= f after each; the last level gets max(nfeatures - sum, 0).  nlevels = 1: the single level gets nfeatures.
+ *   pyramid    level 0 is the image, level l is resized from level l-1 by fixed-point bilinear interpolation: per axis destination d samples
+ *              the source at fx = (d + 0.5) (src / dst) - 0.5 in float64, i0 = floor(fx), a = rint((fx - i0) 2048), both taps i0 and i0 + 1
+ *              clamped to [0, src-1]; pixel = (sum of the four products of the (2048 - a, a) weights + 2^21) >> 22.  The (tap, weight) tables
+ *              are made on the host (like the undistortion map and the CLAHE table), so no float enters the kernel.
+ *   candidates strict 3 x 3 maxima of the FAST score (section "Shi-Tomasi re-detection": fast_threshold) of the level with 31 <= lx < w_l - 31
+ *              and 31 <= ly < h_l - 31 (edge_threshold = 31, fixed); under a mask those with
+ *              mask[min(h-1, rint((float)ly * (float)s_l))][min(w-1, rint((float)lx * (float)s_l))] != 0.
+ *   retention  OpenCV's retainBest, ties kept, both rules sets: keep i iff fewer than 2 quota_l candidates of the level have a strictly greater
+ *              FAST score; then, among those, iff fewer than quota_l have a strictly greater Harris response.  A level can return more than
+ *              its quota.
+ *   Harris     ORB's HarrisResponses over the 7 x 7 block centred on the keypoint: Ix = 2 (I(x+1,y) - I(x-1,y)) + (I(x+1,y-1) - I(x-1,y-1)) +
+ *              (I(x+1,y+1) - I(x-1,y+1)), Iy its transpose; a = sum Ix^2, b = sum Iy^2, c = sum Ix Iy in int32; in float32, every operation
+ *              rounded on its own, ((fa fb - fc fc) - (0.04f (fa + fb)) (fa + fb)) * sc4, sc4 = (float)((1 / (4 * 7 * 255))^4); harris_k = 0.04f, fixed.
+ *   describe   angle and descriptor of the section above on the level image at (lx, ly); the 31-pixel edge implies its 24-pixel margin.
+ *   output     per sequence by level ascending, response descending, ly ascending, lx ascending; x = (float)lx * (float)s_l, y likewise,
+ *              size = 31.0f * (float)s_l, octave = l.
+ * Not cv2.ORB: the sampling table (the caller's, or the generated default), no fastAtan2 (the angle is atan2 in float64 and never enters the
+ * descriptor), the integer 7-tap Gaussian in place of GaussianBlur(7 x 7, 2), plain fixed-point bilinear resizing in place of INTER_LINEAR_EXACT,
+ * and the mask sampled at the keypoint's level-0 position instead of being resized per level.
+ * Kernels (csrc/vo_orb.hip): one resize launch per level above 0; then a fixed number of launches, each covering every level and sequence
+ * through a tile-to-level table: FAST score, strict maxima into candidate lists and a 256-bin score histogram per (sequence, level), the FAST
+ * cut read off the histogram, Harris of the survivors, retention and output position by counting over all pairs of a (sequence, level), one
+ * wave per keypoint to describe.  Capacities: 65536 candidates and 8192 rows behind the FAST cut per (sequence, level); beyond either, and
+ * when a sequence has more than max_out keypoints, the call returns VO_E_CAPACITY and writes none of its outputs.  Nothing is truncated.
+ *   vo_orb_params          nfeatures >= 1 (500); scale_factor in (1, 2] (1.2); nlevels 1..8 (8); fast_threshold 1..254 (20); edge_threshold
+ *                          must be 31 and harris_k 0.04f.  vo_orb_default_params fills it.  Anything else: VO_E_INVALID, nothing enqueued.
+ *   vo_orb_detect_compute  synchronous.  img [batch][height][stride] u8 (the context's image size), mask the same layout or NULL; prm NULL = the
+ *                          defaults; pattern NULL = the default table, else checked as vo_set_brief checks it; kps [batch][max_out],
+ *                          desc [batch][max_out][32] u8, n_out [batch].  The pyramid (about 3.3 w h bytes per sequence at 1.2, every level inside
+ *                          a 32-pixel border so that no tile load leaves the allocation) is reserved by the first call.
+ *   vo_orb_levels_read     of the last call: w_l, h_l, scale_l, quota_l [8] each (zeros beyond nlevels), n_l [batch][8] the keypoints each level
+ *                          returned (any may be NULL).  VO_E_STATE before the first successful call.
+ *   vo_orb_level_image_read  level `level` of sequence `seq` of the last call's pyramid, out [h_l][w_l] u8. */
+typedef struct {
+  int32_t nfeatures;         /* 500 */
+  int32_t nlevels;           /* 8 */
+  double  scale_factor;      /* 1.2 */
+  int32_t fast_threshold;    /* 20 */
+  int32_t edge_threshold;    /* 31, fixed */
+  float   harris_k;          /* 0.04f, fixed */
+  int32_t _pad;
+} vo_orb_params;             /* 32 bytes */
+typedef struct {
+  float   x, y;              /* pt, pixels of the input image */
+  float   size;              /* 31 * scale of the level */
+  float   angle;             /* degrees, [0, 360) */
+  float   response;          /* Harris response on the level */
+  int32_t octave;            /* pyramid level */
+  int32_t lx, ly;            /* integer pixel on the level */
+} vo_orb_kp;                 /* 32 bytes */
+int32_t vo_orb_default_params(vo_orb_params* p);
+int32_t vo_orb_detect_compute(vo_ctx* ctx, const uint8_t* img, int32_t stride, const uint8_t* mask, const vo_orb_params* prm,
+                              const int8_t* pattern, int32_t max_out, vo_orb_kp* kps, uint8_t* desc, int32_t* n_out);
+int32_t vo_orb_levels_read(vo_ctx* ctx, int32_t* w_l, int32_t* h_l, float* scale_l, int32_t* quota_l, int32_t* n_l);
+int32_t vo_orb_level_image_read(vo_ctx* ctx, int32_t seq, int32_t level, uint8_t* out);
 
 /* ---- descriptor matching (SURVEY.md 8f "next" row 4, matching part) -----------------------------
  * Replaces cv2.BFMatcher().knnMatch(desc_1, desc_2, k=2) in Extractor.match (src/extractor/extractor.py:134-145;
@@ -924,9 +991,12 @@ int32_t vo_step_layout(vo_ctx* ctx, int32_t* layout, int32_t* gate_groups, int32
  * recorded regions since vo_profile_enable(ctx, mask); mask = OR of (1 << region), 0 = off.
  * VO_PROF_CLAHE_LUT / VO_PROF_CLAHE_APPLY bracket the k_clahe_lut / k_clahe_apply launch of a pyramid build (inside its VO_PROF_FRAME bracket).
  * VO_PROF_HOM_SOLVE / _SCORE / _SELECT / _FINISH bracket the k_h4_solve / k_h4_score / k_h4_select launch of every round of
- * vo_homography_ransac and its k_h4_finish launch (tools/homography_timing.py). */
+ * vo_homography_ransac and its k_h4_finish launch (tools/homography_timing.py).
+ * VO_PROF_ORB_PYRAMID / _CANDIDATES / _RETAIN / _DESCRIBE bracket the stages of vo_orb_detect_compute: the k_orb_resize launches; k_orb_score,
+ * k_orb_nms and k_orb_cut; k_orb_harris and k_orb_rank; k_orb_describe (tools/orb_timing.py). */
 enum { VO_PROF_FRAME = 0, VO_PROF_KLT = 1, VO_PROF_ST = 2, VO_PROF_DLT = 3, VO_PROF_BA = 4, VO_PROF_CLAHE_LUT = 5, VO_PROF_CLAHE_APPLY = 6,
-       VO_PROF_HOM_SOLVE = 7, VO_PROF_HOM_SCORE = 8, VO_PROF_HOM_SELECT = 9, VO_PROF_HOM_FINISH = 10, VO_PROF_COUNT = 11 };
+       VO_PROF_HOM_SOLVE = 7, VO_PROF_HOM_SCORE = 8, VO_PROF_HOM_SELECT = 9, VO_PROF_HOM_FINISH = 10, VO_PROF_ORB_PYRAMID = 11,
+       VO_PROF_ORB_CANDIDATES = 12, VO_PROF_ORB_RETAIN = 13, VO_PROF_ORB_DESCRIBE = 14, VO_PROF_COUNT = 15 };
 int32_t vo_profile_enable(vo_ctx* ctx, int32_t region_mask);
 int32_t vo_profile_read(vo_ctx* ctx, int32_t region, double* total_ms, int32_t* count);
 /* diagnostic: shader-clock stamps (s_memtime deltas, cycles) of the phases of the last launch of a

@@ -17,17 +17,15 @@
 // One wave per corner (a 64-thread workgroup), grid (corners, batch).  The 49 x 49 raw tile goes to LDS once, the blur runs in LDS over the
 // 43 x 43 pixels a rotated sample can reach, the moments are a wave butterfly, and the 256 tests are four per lane: four ballots are the
 // four 64-bit words of the descriptor.  A per-corner tile instead of a blurred image: a corner is described once in its life and a
-// steady-state detection spawns few of them.
+// steady-state detection spawns few of them.  The per-corner body, brief_describe_px, lives in vo_brief_dev.h: k_orb_describe of vo_orb.hip runs it on
+// the levels of its pyramid.
 #include "vo_internal.h"
 #include "vo_brief_pattern.h"
+#include "vo_brief_dev.h"
 
 #include <math.h>
 #include <string.h>
 
-#define BRIEF_M 24                      // margin: 21 + 3
-#define BRIEF_TW (2 * BRIEF_M + 1)      // 49: raw tile
-#define BRIEF_R 21                      // furthest rotated sample: rint(15 * sqrt(2))
-#define BRIEF_SW (2 * BRIEF_R + 1)      // 43: blurred tile
 #define BRIEF_CAP 4096                  // corners a Shi-Tomasi launch can put out (ST_OUT_CAP)
 
 struct brief_args {
@@ -37,14 +35,6 @@ struct brief_args {
   int cap;                     // corner slots per sequence this launch covers
   int8_t pat[1024];            // [256][4]
 };
-
-__device__ __constant__ static const unsigned char brief_umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
-
-__device__ __forceinline__ int brief_wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 // corners: sequence-0 rows [n][2] f32, `rows_seq` bytes apart; desc [cap][32] u8, angle [cap] f32, flags [cap] u8: sequence-0 rows `out_seq`
 // bytes apart; counts: per-sequence corner count as the selection kernel left it (word 2 of the sequence's st_scalars, 0xFFFFFFFF = none),
@@ -83,63 +73,9 @@ __global__ void __launch_bounds__(64) k_brief_describe(brief_args A, const float
     return;
   }
   x = __builtin_amdgcn_readfirstlane(x); y = __builtin_amdgcn_readfirstlane(y);
-  // ---- the raw tile: rows y-24 .. y+24, columns x-24 .. x+24, all inside the image ----
-  const uint8_t* const img = A.img + (size_t)bseq * A.img_seq + (size_t)(VO_PAD + y - BRIEF_M) * A.pitch + (VO_PAD + x - BRIEF_M);
-  for (int k = lane; k < BRIEF_TW * BRIEF_TW; k += 64) {
-    const int r = k / BRIEF_TW, q = k - r * BRIEF_TW;
-    raw[k] = img[(size_t)r * A.pitch + q];
-  }
-  __syncthreads();
-  // ---- orientation: the intensity centroid of the disc of radius 15 ----
-  int m10 = 0, m01 = 0;
-  for (int k = lane; k < 31 * 31; k += 64) {
-    const int r = k / 31, q = k - r * 31;
-    const int v = r - 15, u = q - 15;
-    if (abs(u) <= (int)brief_umax[abs(v)]) {
-      const int I = raw[(v + BRIEF_M) * BRIEF_TW + (u + BRIEF_M)];
-      m10 += u * I; m01 += v * I;
-    }
-  }
-  m10 = brief_wave_sum(m10); m01 = brief_wave_sum(m01);
-  float c = 1.f, s = 0.f, ang = 0.f;
-  if (m10 != 0 || m01 != 0) {
-    const double dx = (double)m10, dy = (double)m01;
-    const double r = sqrt(dx * dx + dy * dy);
-    c = (float)(dx / r); s = (float)(dy / r);
-    double a = atan2(dy, dx) * (180.0 / 3.14159265358979323846);
-    if (a < 0.0) a = a + 360.0;
-    ang = (float)a;
-    if (ang >= 360.f) ang = 0.f;
-  }
-  // ---- blur: horizontal sums of the 49 rows over the 43 middle columns, then the vertical pass ----
-  for (int k = lane; k < BRIEF_TW * BRIEF_SW; k += 64) {
-    const int r = k / BRIEF_SW, q = k - r * BRIEF_SW;
-    const uint8_t* const p = raw + r * BRIEF_TW + q;            // tile column q .. q + 6 = centre q + 3
-    hs[k] = (uint16_t)(18 * (p[0] + p[6]) + 33 * (p[1] + p[5]) + 49 * (p[2] + p[4]) + 56 * p[3]);
-  }
-  __syncthreads();
-  for (int k = lane; k < BRIEF_SW * BRIEF_SW; k += 64) {
-    const int r = k / BRIEF_SW, q = k - r * BRIEF_SW;
-    const uint16_t* const p = hs + r * BRIEF_SW + q;            // rows r .. r + 6 = centre r + 3
-    const int v = 18 * ((int)p[0] + (int)p[6 * BRIEF_SW]) + 33 * ((int)p[BRIEF_SW] + (int)p[5 * BRIEF_SW]) +
-                  49 * ((int)p[2 * BRIEF_SW] + (int)p[4 * BRIEF_SW]) + 56 * (int)p[3 * BRIEF_SW];
-    S[k] = (uint8_t)((v + 32768) >> 16);
-  }
-  __syncthreads();
-  // ---- the tests: lane l runs tests l, l + 64, l + 128, l + 192; ballot t is descriptor word t ----
-  unsigned long long word = 0ull;
-#pragma unroll
-  for (int t = 0; t < 4; t++) {
-    const char4 p = reinterpret_cast<const char4*>(A.pat)[t * 64 + lane];
-    const float x1 = (float)p.x, y1 = (float)p.y, x2 = (float)p.z, y2 = (float)p.w;
-    const int ix1 = (int)rintf(__fsub_rn(__fmul_rn(x1, c), __fmul_rn(y1, s))), iy1 = (int)rintf(__fadd_rn(__fmul_rn(x1, s), __fmul_rn(y1, c)));
-    const int ix2 = (int)rintf(__fsub_rn(__fmul_rn(x2, c), __fmul_rn(y2, s))), iy2 = (int)rintf(__fadd_rn(__fmul_rn(x2, s), __fmul_rn(y2, c)));
-    // (|ix|, |iy| <= 21 for coordinates in +-15, which the host checked; the clamp keeps a table it did not see inside the tile)
-    const int a0 = (min(max(iy1, -BRIEF_R), BRIEF_R) + BRIEF_R) * BRIEF_SW + (min(max(ix1, -BRIEF_R), BRIEF_R) + BRIEF_R);
-    const int a1 = (min(max(iy2, -BRIEF_R), BRIEF_R) + BRIEF_R) * BRIEF_SW + (min(max(ix2, -BRIEF_R), BRIEF_R) + BRIEF_R);
-    const unsigned long long b = __ballot(S[a0] < S[a1]);
-    if (lane == t) word = b;
-  }
+  float ang;
+  const unsigned long long word = brief_describe_px(A.img + (size_t)bseq * A.img_seq + (size_t)VO_PAD * A.pitch + VO_PAD, A.pitch, A.W, A.H, x, y, A.pat,
+                                                    lane, raw, hs, S, ang);
   if (lane < 4) o_desc[lane] = word;
   if (lane == 0) { *o_ang = ang; *o_fl = 0; }
 }
@@ -182,6 +118,11 @@ extern "C" int32_t vo_brief_default_params(vo_brief_params* p) {
 // every rule that refuses a parameter set or a pattern; nothing is enqueued
 static int32_t brief_check(vo_ctx* c, const vo_brief_params* p, const int8_t* pattern) {
   VO_CHECK(c, p->n_bits == 256, VO_E_INVALID, "n_bits must be 256");
+  return vo_brief_check_pattern(c, pattern);
+}
+
+// (shared with vo_orb_detect_compute) null = the default table
+int32_t vo_brief_check_pattern(vo_ctx* c, const int8_t* pattern) {
   if (pattern)
     for (int i = 0; i < 256; i++) {
       const int8_t* r = pattern + 4 * i;

@@ -360,6 +360,7 @@ extern "C" int32_t vo_ctx_destroy(vo_ctx* c) {
   vo_guess_destroy(c);
   vo_subpix_destroy(c);
   vo_brief_destroy(c);
+  vo_orb_destroy(c);
   vo_ingest_free(&c->und_on, &c->d_und, (void**)&c->d_und_tab);
   vo_ingest_free(&c->cl_on, &c->d_clahe, (void**)&c->d_clahe_lut);
   for (int f = 0; f < 2; f++)

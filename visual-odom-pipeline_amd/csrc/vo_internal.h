@@ -146,6 +146,7 @@ struct vo_ctx {
   vo_st_ws* st = nullptr;
   struct vo_pnp_ws* pnp = nullptr;   // PnP-RANSAC workspace (vo_pnp.hip)
   struct vo_sift_ws* sift = nullptr;     // SIFT scale space and lists (vo_sift.hip)
+  struct vo_orb_ws* orb = nullptr;       // ORB pyramid, score maps and lists (vo_orb.hip), made by the first vo_orb_detect_compute
   struct vo_match_ws* match = nullptr;   // descriptor matcher buffers (vo_match.hip)
   struct vo_ess_ws* ess = nullptr;   // essential-matrix RANSAC workspace (vo_essential.hip)
   struct vo_hom_ws* hom = nullptr;   // homography RANSAC workspace (vo_homography.hip)
@@ -340,6 +341,8 @@ void vo_subpix_destroy(vo_ctx* c);
 // flag per corner row of st_out into the side buffer; off, it only notes that the last detection did not describe
 int32_t vo_brief_describe_detected(vo_ctx* c, hipStream_t q, int max_corners);
 void vo_brief_destroy(vo_ctx* c);
+int32_t vo_brief_check_pattern(vo_ctx* c, const int8_t* pattern);    // a caller's sampling table: VO_OK or VO_E_INVALID; null = the default table
+void vo_orb_destroy(vo_ctx* c);                                      // the ORB pyramid and lists (vo_orb.hip)
 // The ingest chain (vo_frame.hip): the optional stages vo_build_pyramid runs in front of level 0, in this order: lens undistortion
 // (vo_undistort.hip), then CLAHE (vo_clahe.hip).  A stage's enqueue takes the frames (k_pad_level0's triple) to its own tight [batch][h][w]
 // staging image on q; the next stage, and at last the level-0 kernel, read that image as their raw frame.

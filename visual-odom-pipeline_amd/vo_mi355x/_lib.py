@@ -108,6 +108,22 @@ class SiftKp(C.Structure):
                 ("octave", C.c_int32)]
 
 
+class OrbParams(C.Structure):
+    """vo_orb_params (32 bytes): edge_threshold and harris_k are fixed at 31 and 0.04f"""
+    _fields_ = [("nfeatures", C.c_int32), ("nlevels", C.c_int32), ("scale_factor", C.c_double), ("fast_threshold", C.c_int32),
+                ("edge_threshold", C.c_int32), ("harris_k", C.c_float), ("_pad", C.c_int32)]
+
+
+class OrbKp(C.Structure):
+    """vo_orb_kp (32 bytes)"""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("size", C.c_float), ("angle", C.c_float), ("response", C.c_float),
+                ("octave", C.c_int32), ("lx", C.c_int32), ("ly", C.c_int32)]
+
+
+ORB_KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"),
+                         ("lx", "<i4"), ("ly", "<i4")])
+
+
 class BaStats(C.Structure):
     _fields_ = [("cost0", C.c_double), ("cost", C.c_double), ("lam", C.c_double), ("iters", C.c_int32),
                 ("accepted", C.c_int32), ("status", C.c_int32), ("n_obs", C.c_int32)]
@@ -233,6 +249,10 @@ SIGNATURES = {
     "vo_homography_default_params": (C.c_int32, [C.POINTER(HomParams)]),
     "vo_homography_ransac": (C.c_int32, [_ctx, _f32p, _f32p, C.c_int32, C.POINTER(HomParams), _f64p, _f64p, _u8p, C.POINTER(HomStats)]),
     "vo_sift_detect_compute": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32, C.POINTER(SiftKp), _f32p, _i32p]),
+    "vo_orb_default_params": (C.c_int32, [C.POINTER(OrbParams)]),
+    "vo_orb_detect_compute": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.POINTER(OrbParams), _i8p, C.c_int32, C.POINTER(OrbKp), _u8p, _i32p]),
+    "vo_orb_levels_read": (C.c_int32, [_ctx, _i32p, _i32p, _f32p, _i32p, _i32p]),
+    "vo_orb_level_image_read": (C.c_int32, [_ctx, C.c_int32, C.c_int32, _u8p]),
     "vo_match_knn2": (C.c_int32, [_ctx, _f32p, C.c_int32, _f32p, C.c_int32, C.c_int32, _i32p, _f32p]),
     "vo_match_hamming_knn2": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32, _i32p, _i32p]),
     "vo_pnp_upload": (C.c_int32, [_ctx, _f64p, _f32p, _f32p, C.c_int32]),

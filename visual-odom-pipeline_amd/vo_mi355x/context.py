@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, HomParams, HomStats, KltParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
+from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, HomParams, HomStats, KltParams, OrbKp, OrbParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
 
 # vo_set_klt_predict modes (include/vo_mi355x.h)
 KLT_PREDICT_MODES = {"off": 0, "constant_velocity": 1}
@@ -764,6 +764,7 @@ class VoContext:
     # -- in-stream timing -----------------------------------------------------------------------
     PROF_FRAME, PROF_KLT, PROF_ST, PROF_DLT, PROF_BA, PROF_CLAHE_LUT, PROF_CLAHE_APPLY = range(7)
     PROF_HOM_SOLVE, PROF_HOM_SCORE, PROF_HOM_SELECT, PROF_HOM_FINISH = range(7, 11)
+    PROF_ORB_PYRAMID, PROF_ORB_CANDIDATES, PROF_ORB_RETAIN, PROF_ORB_DESCRIBE = range(11, 15)
 
     def profile_enable(self, regions=(0, 1, 2, 3, 4)):
         """regions: iterable of PROF_* ids to time with hipEvent pairs on the ctx stream; () switches timing off"""
@@ -904,6 +905,52 @@ class VoContext:
             k = np.stack([r["x"], r["y"], r["size"], r["angle"], r["response"], r["octave"]], 1).astype(np.float64).reshape(-1, 6)
             outs.append((k, desc[b, :n_out[b]].copy()))
         return outs[0] if B == 1 else outs
+
+    # -- ORB ----------------------------------------------------------------------------------------
+    def orb_params(self, nfeatures=500, scale_factor=1.2, nlevels=8, fast_threshold=20):
+        p = OrbParams()
+        self._L.vo_orb_default_params(C.byref(p))
+        p.nfeatures, p.scale_factor, p.nlevels, p.fast_threshold = int(nfeatures), float(scale_factor), int(nlevels), int(fast_threshold)
+        return p
+
+    def orb_detect_compute(self, img, mask=None, nfeatures=500, scale_factor=1.2, nlevels=8, fast_threshold=20, pattern=None, max_out=None):
+        """multi-scale ORB (vo_orb_detect_compute; the definition is tests/orb_model.py, not cv2.ORB).  img (h, w) u8 [leading batch dim if
+        batch > 1], mask the same shape or None; pattern as in brief_compute -> keypoints (n,) structured [x, y, size, angle, response, octave,
+        lx, ly] (_lib.ORB_KP_DTYPE), descriptors (n, 32) uint8   [lists over the batch].  max_out: output rows per sequence (default
+        2 * nfeatures + 64, at most 65536); VoError VO_E_CAPACITY when a sequence has more."""
+        B = self.batch
+        im = np.ascontiguousarray(img, np.uint8).reshape(B, self.height, self.width)
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(B, self.height, self.width)
+        cap = int(max_out) if max_out is not None else min(2 * int(nfeatures) + 64, 1 << 16)
+        prm = self.orb_params(nfeatures, scale_factor, nlevels, fast_threshold)
+        pat = self._brief_pattern(pattern)
+        n = max(cap, 1)
+        kps = np.zeros((B, n), _lib.ORB_KP_DTYPE)
+        desc = np.zeros((B, n, 32), np.uint8)
+        n_out = np.zeros(B, np.int32)
+        self._ck(self._L.vo_orb_detect_compute(self._h, ptr(im, C.c_uint8), self.width, None if mk is None else ptr(mk, C.c_uint8), C.byref(prm),
+                                               ptr(pat, C.c_int8), cap, kps.ctypes.data_as(C.POINTER(OrbKp)), ptr(desc, C.c_uint8),
+                                               ptr(n_out, C.c_int32)))
+        outs = [(kps[b, :n_out[b]].copy(), desc[b, :n_out[b]].copy()) for b in range(B)]
+        return outs[0] if B == 1 else outs
+
+    def orb_levels(self):
+        """the pyramid of the last orb_detect_compute (vo_orb_levels_read / vo_orb_level_image_read) -> dict(w_l, h_l, scale_l f32, quota_l: [8],
+        zeros beyond nlevels; n_l (batch, 8): keypoints each level returned; images: per sequence, the level images (h_l, w_l) u8)"""
+        w_l, h_l, q_l = np.zeros(8, np.int32), np.zeros(8, np.int32), np.zeros(8, np.int32)
+        s_l, n_l = np.zeros(8, np.float32), np.zeros((self.batch, 8), np.int32)
+        self._ck(self._L.vo_orb_levels_read(self._h, ptr(w_l, C.c_int32), ptr(h_l, C.c_int32), ptr(s_l, C.c_float), ptr(q_l, C.c_int32),
+                                            ptr(n_l, C.c_int32)))
+        nlevels = int(np.count_nonzero(s_l))
+        images = []
+        for b in range(self.batch):
+            lv = []
+            for l in range(nlevels):
+                out = np.zeros((h_l[l], w_l[l]), np.uint8)
+                self._ck(self._L.vo_orb_level_image_read(self._h, b, l, ptr(out, C.c_uint8)))
+                lv.append(out)
+            images.append(lv)
+        return dict(w_l=w_l, h_l=h_l, scale_l=s_l, quota_l=q_l, n_l=n_l, nlevels=nlevels, images=images)
 
     # -- descriptor matching ----------------------------------------------------------------------
     def match_knn2(self, desc1, desc2):

@@ -28,7 +28,8 @@ class DMatch:
 
 class Extractor:
     def __init__(self, cfg=None, min_kp_dist=10, ctx=None, device=0, max_pts=8192, lazy=None, lazy_backend=None, bidir="reference",
-                 predict="off", subpix=None, undistort=None, clahe=None, fast_threshold=20, descriptor=None, brief_pattern=None):
+                 predict="off", subpix=None, undistort=None, clahe=None, fast_threshold=20, descriptor=None, brief_pattern=None, feature_method='sift',
+                 orb_params=None):
         """lazy (default: on unless VO_LAZY=0): once a frame has come through the reference's call order (pipeline.py:98-156) the state moves
         into device tables and the lists this class hands out are views of them (vo_mi355x/lazy.py); lazy_backend: test hook
         (ctx, K, params, width, height) -> backend, default the GPU one.  max_pts: keypoints per call AND the capacity of those tables (<= 8192).
@@ -61,7 +62,18 @@ class Extractor:
         the reference's cv2.ORB_create() branch, extractor.py:30-31, 119-122) and returns Keypoints whose `des` is the (32, 1) uint8 column;
         corners within 24 pixels of a border are dropped, as cv2.ORB.compute drops border keypoints.  brief_pattern: 256 rows
         (x1, y1, x2, y2) in [-15, 15], None = the default table.  match / match_lists on uint8 descriptors take the reference's 'orb' branch
-        (1-NN under the Hamming distance, extractor.py:144-145).  A lazy session does not describe: such a call takes the plain path."""
+        (1-NN under the Hamming distance, extractor.py:144-145).  A lazy session does not describe: such a call takes the plain path.
+        feature_method: what extract(detector='custom') runs, the reference's two feature methods (extractor.py:26-33).  'sift' (default):
+        cv2.SIFT_create(nfeatures=1000).  'orb': the multi-scale ORB detector (VoContext.orb_detect_compute; cv2.ORB_create()'s defaults
+        nfeatures=500, scaleFactor=1.2, nlevels=8, fastThreshold=20, any of them replaced through orb_params=dict(...)): Keypoints at (x, y) of
+        the input image whose `des`, with describe=True, is the (32, 1) uint8 column; brief_pattern is its sampling table too."""
+        if feature_method not in ('sift', 'orb'):
+            raise ValueError("feature_method must be 'sift' or 'orb'")
+        self._feature_method = feature_method
+        unknown = set(orb_params or {}) - {"nfeatures", "scale_factor", "nlevels", "fast_threshold"}
+        if unknown:
+            raise ValueError("orb_params: unknown keys %r" % sorted(unknown))
+        self._orb_params = dict(orb_params or {})
         if descriptor not in (None, 'brief'):
             raise ValueError("descriptor must be None or 'brief'")
         self._descriptor = descriptor
@@ -271,6 +283,9 @@ class Extractor:
     # -- re-detection ---------------------------------------------------------------------------
     def extract(self, img, t, current_kp=[], detector='custom', mask_radius=5, describe=False):
         if detector == 'custom':
+            if self._feature_method == 'orb':
+                self._plain("extract_orb")
+                return self._extract_orb(img, t, current_kp, describe)
             self._plain("extract_sift")
             return self._extract_sift(img, t, current_kp, describe)
         if detector not in ('shi-tomasi', 'fast'):
@@ -428,6 +443,19 @@ class Extractor:
         self._context(img)
         kps, desc = self._ctx.sift_detect_compute(img, nfeatures=1000)
         kp = np.ascontiguousarray(kps[:, :2], np.float32)          # cv2.KeyPoint_convert: (n, 2) float32
+        if not describe:
+            desc = np.zeros((kp.shape[0], 1))
+        return [Keypoint(t_first=t, t_total=1, uv_first=kp[i, :].reshape((2, 1)), uv=kp[i, :].reshape((2, 1)),
+                         des=desc[i, :].reshape((-1, 1)), uv_history=[kp[i, :].reshape((2, 1))]) for i in range(len(kp))]
+
+    def _extract_orb(self, img, t, current_kp, describe):
+        """detector='custom' with feature_method='orb' (reference extractor.py:30-31, 114-131): cv2.ORB_create().detect(img, mask) and, with
+        describe=True, .compute(img, kps) -> Keypoints whose `des` is the (32, 1) uint8 descriptor column (a (1, 1) zero column without)."""
+        if len(current_kp):
+            raise NotImplementedError("ORB detection with a keypoint mask is not used by the reference pipeline")
+        self._context(img)
+        kps, desc = self._ctx.orb_detect_compute(img, pattern=self._brief_pattern, **self._orb_params)
+        kp = np.ascontiguousarray(np.stack([kps["x"], kps["y"]], axis=1), np.float32).reshape(-1, 2)
         if not describe:
             desc = np.zeros((kp.shape[0], 1))
         return [Keypoint(t_first=t, t_total=1, uv_first=kp[i, :].reshape((2, 1)), uv=kp[i, :].reshape((2, 1)),
