@@ -11,29 +11,9 @@ import numpy as np
 import pytest
 
 import pipe_helpers as ph
+from tracks_model import fb_np as _fb_np, occlude as _occlude, oracle_fb as _oracle_fb      # (shared with tests/test_gpu_tracks_chunks.py)
 
 pytestmark = pytest.mark.gpu
-
-
-def _fb_np(p0, p0r, max_err):
-    e = np.abs(np.asarray(p0, np.float32) - np.asarray(p0r, np.float32)).reshape(-1, 2).max(-1)
-    return e, e < np.float32(max_err)
-
-
-def _oracle_fb(im0, im1, p0, **kw):
-    import vo_oracle as o
-    q1, qs, qe = o.klt(im0, im1, p0, **kw)
-    r0 = o.klt(im1, im0, q1, **kw)[0]
-    return q1, qs, qe, r0
-
-
-def _occlude(img, x0, y0, size, seed):
-    """an occluder that appears in this frame only: a block of unrelated texture pasted over the scene"""
-    rng = np.random.default_rng(seed)
-    out = img.copy()
-    blk = rng.integers(0, 256, (size // 4 + 1, size // 4 + 1)).astype(np.uint8)
-    out[y0:y0 + size, x0:x0 + size] = np.kron(blk, np.ones((4, 4), np.uint8))[:size, :size]
-    return out
 
 
 def _check_pair(c, im0, im1, p0, max_err, **kw):
@@ -174,7 +154,7 @@ def test_tracks_table_with_the_check_equals_list_model():
             assert np.array_equal(r["uv"], np.array([k["uv"] for k in tr]).reshape(-1, 2)), t
             assert np.array_equal(r["uv_first"], np.array([k["first"] for k in tr]).reshape(-1, 2)), t
             assert np.array_equal(r["t_total"], [k["tt"] for k in tr]) and np.array_equal(r["t_first"], [k["tf"] for k in tr]), t
-            assert sorted(r["dead_tag"].tolist()) == sorted(dead), t
+            assert r["dead_tag"].tolist() == dead, t               # in list order
             for i, k in enumerate(tr):
                 for s in range(8):
                     if t - s in k["hist"]:
