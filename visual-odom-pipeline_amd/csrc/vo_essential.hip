@@ -13,8 +13,10 @@
 // refinement of every root on the ten cubics; all of it in
 // per-lane scratch arrays, it runs 256 x once per call -- then a WAVE per (hypothesis, root) for the consensus count,
 // one workgroup per sequence for the running best / iteration bound, and one for the cheirality vote.
-// The arithmetic follows the oracle operation by operation (this library is built with -ffp-contract=off).
+// The arithmetic follows the oracle operation by operation (this library is built with -ffp-contract=off).  The sample generator, the
+// iteration bound, the head of the control block and the host's round loop are the ones all three searches share: vo_ransac.h.
 #include "vo_internal.h"
+#include "vo_ransac.h"
 
 #include <math.h>
 #include <string.h>
@@ -23,7 +25,9 @@
 #define E5_MAXSOL 10
 
 struct e5_hyp { double E[E5_MAXSOL][9]; int count[E5_MAXSOL]; int nsol; int h; };
-struct e5_ctrl { int niters, h_done, done, best_h, best_k, best_count; double E[9]; };
+struct e5_ctrl { vo_ransac_state s; int best_h, best_k, best_count; double E[9]; };
+static_assert(sizeof(e5_ctrl) == 96 && offsetof(e5_ctrl, best_h) == 12 && offsetof(e5_ctrl, best_k) == 16 && offsetof(e5_ctrl, best_count) == 20 &&
+              offsetof(e5_ctrl, E) == 24, "e5_ctrl layout");
 
 struct vo_ess_ws {
   int cap = 0, n = 0;
@@ -41,28 +45,6 @@ struct vo_ess_ws {
 __constant__ int c_mul11[4][4] = {{0, 3, 4, 6}, {3, 1, 5, 7}, {4, 5, 2, 8}, {6, 7, 8, 9}};
 __constant__ int c_mul21[10][4] = {{0, 2, 4, 5}, {3, 1, 6, 7}, {10, 13, 16, 17}, {2, 3, 8, 9}, {4, 8, 10, 11}, {8, 6, 13, 14}, {5, 9, 11, 12},
                                    {9, 7, 14, 15}, {11, 14, 17, 18}, {12, 15, 18, 19}};
-
-__device__ __forceinline__ unsigned long long e5_splitmix64(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  unsigned long long z = x;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ inline void e5_sample5(unsigned seed, unsigned h, int n, int idx[5]) {
-  int cnt = 0;
-  unsigned k = 0;
-  while (cnt < 5) {
-    const unsigned long long r = (k < 256) ? e5_splitmix64(((unsigned long long)(seed & 0xFFFFFFu) << 40) ^ ((unsigned long long)h << 8) ^ (unsigned long long)(k & 0xFFu))
-                                           : e5_splitmix64((unsigned long long)k);
-    const int i = (int)((r >> 11) % (unsigned long long)n);
-    k++;
-    bool dup = false;
-    for (int j = 0; j < cnt; j++) dup = dup || (idx[j] == i);
-    if (!dup) idx[cnt++] = i;
-  }
-}
 
 // polynomial helpers on the bases of the oracle: p1 = [x y z 1], p2 (10), p3 (20 = the matrix columns)
 __device__ inline void e5_mul11(const double* a, const double* b, double* o) {
@@ -416,7 +398,8 @@ __global__ void __launch_bounds__(256) k_e5_prep(const double* __restrict__ Kall
 
 __global__ void k_e5_init(e5_ctrl* ctrl, int max_iters) {
   e5_ctrl* c = ctrl + blockIdx.x;
-  c->niters = max_iters; c->h_done = 0; c->done = 0; c->best_h = -1; c->best_k = -1; c->best_count = 4;
+  vo_ransac_reset(&c->s, max_iters);
+  c->best_h = -1; c->best_k = -1; c->best_count = 4;
   for (int i = 0; i < 9; i++) c->E[i] = 0;
 }
 
@@ -425,13 +408,13 @@ __global__ void __launch_bounds__(64) k_e5_solve(const double* __restrict__ q, i
   const int b = blockIdx.y, slot = blockIdx.x * 64 + threadIdx.x;
   const e5_ctrl cs = ctrl[b];
   e5_hyp* out = hyps + (size_t)b * E5_BATCH + slot;
-  const int h = cs.h_done + slot;
+  const int h = cs.s.h_done + slot;
   out->h = h;
-  if (cs.done) { out->nsol = 0; return; }
+  if (cs.s.done) { out->nsol = 0; return; }
   const double* qa = q + ((size_t)b * 2) * cap * 2;
   const double* qb = qa + (size_t)cap * 2;
   int idx[5];
-  e5_sample5(seed, (unsigned)h, n, idx);
+  vo_ransac_sample<5>(seed, (unsigned)h, n, idx);
   double q1[5][2], q2[5][2];
   for (int i = 0; i < 5; i++) {
     q1[i][0] = qa[2 * idx[i]]; q1[i][1] = qa[2 * idx[i] + 1];
@@ -462,22 +445,13 @@ __global__ void __launch_bounds__(64 * E5_MAXSOL) k_e5_score(const double* __res
   if (lane == 0) hp->count[k] = cnt;
 }
 
-__device__ inline int e5_update_iters(double p, double ep, int model_points, int max_iters) {   // OpenCV RANSACUpdateNumIters
-  p = fmin(fmax(p, 0.0), 1.0); ep = fmin(fmax(ep, 0.0), 1.0);
-  double num = fmax(1.0 - p, 2.2250738585072014e-308);
-  double denom = 1.0 - pow(1.0 - ep, (double)model_points);
-  if (denom < 2.2250738585072014e-308) return 0;
-  num = log(num); denom = log(denom);
-  return (denom >= 0 || -num >= max_iters * (-denom)) ? max_iters : (int)rint(num / denom);
-}
-
 // grid (batch): running best (most inliers; ties to the smallest h, then the smallest root) and the iteration bound
 __global__ void __launch_bounds__(E5_BATCH) k_e5_select(const e5_hyp* __restrict__ hyps, e5_ctrl* __restrict__ ctrl, int n, double prob, int max_iters) {
   __shared__ int s_cnt[E5_BATCH];
   __shared__ int s_k[E5_BATCH];
   const int b = blockIdx.x, tid = threadIdx.x;
   e5_ctrl* c = ctrl + b;
-  if (c->done) return;
+  if (c->s.done) return;
   const e5_hyp* H = hyps + (size_t)b * E5_BATCH;
   {
     int bc = -1, bk = 0;
@@ -486,18 +460,12 @@ __global__ void __launch_bounds__(E5_BATCH) k_e5_select(const e5_hyp* __restrict
   }
   __syncthreads();
   if (tid == 0) {
-    int bi = -1, bc = c->best_count;
-    for (int i = 0; i < E5_BATCH; i++) if (s_cnt[i] > bc) { bc = s_cnt[i]; bi = i; }     // batch order = ascending h
+    const int bi = vo_ransac_best_slot(s_cnt, E5_BATCH, c->best_count);
     if (bi >= 0) {
-      c->best_count = bc; c->best_h = H[bi].h; c->best_k = s_k[bi];
+      c->best_count = s_cnt[bi]; c->best_h = H[bi].h; c->best_k = s_k[bi];
       for (int i = 0; i < 9; i++) c->E[i] = H[bi].E[s_k[bi]][i];
     }
-    c->h_done += E5_BATCH;
-    if (c->best_h >= 0) {
-      const int ni = e5_update_iters(prob, (double)(n - c->best_count) / (double)n, 5, max_iters);
-      if (ni < c->niters) c->niters = ni;
-    }
-    c->done = (c->h_done >= c->niters) ? 1 : 0;
+    vo_ransac_advance(&c->s, E5_BATCH, n, c->best_count, c->best_h >= 0, prob, 5, max_iters);
   }
 }
 
@@ -747,17 +715,12 @@ extern "C" int32_t vo_essential_ransac(vo_ctx* c, const double* K, const float* 
   VO_HIP(c, hipMemcpy2DAsync(w->d_p + (size_t)cap * 2, pitch, pts2, row, row, B, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_e5_prep, dim3(vo_div_up(n, 256), (unsigned)B), dim3(256), 0, c->stream, w->d_K, w->d_p, w->d_q, cap, n);
   hipLaunchKernelGGL(k_e5_init, dim3((unsigned)B), dim3(1), 0, c->stream, w->d_ctrl, prm->max_iters);
-  for (int guard = 0; guard < (prm->max_iters + E5_BATCH - 1) / E5_BATCH; guard++) {
+  r = vo_ransac_rounds(c, c->stream, w->d_ctrl, w->h_ctrl, B, (prm->max_iters + E5_BATCH - 1) / E5_BATCH, [&](int) {
     hipLaunchKernelGGL(k_e5_solve, dim3(E5_BATCH / 64, (unsigned)B), dim3(64), 0, c->stream, w->d_q, cap, n, (unsigned)prm->seed, w->d_hyp, w->d_ctrl);
     hipLaunchKernelGGL(k_e5_score, dim3(E5_BATCH, (unsigned)B), dim3(64 * E5_MAXSOL), 0, c->stream, w->d_q, cap, n, d_thr2, w->d_hyp);
     hipLaunchKernelGGL(k_e5_select, dim3((unsigned)B), dim3(E5_BATCH), 0, c->stream, w->d_hyp, w->d_ctrl, n, prm->prob, prm->max_iters);
-    VO_HIP(c, hipGetLastError());
-    VO_HIP(c, hipMemcpyAsync(w->h_ctrl, w->d_ctrl, sizeof(e5_ctrl) * B, hipMemcpyDeviceToHost, c->stream));
-    VO_HIP(c, hipStreamSynchronize(c->stream));
-    bool all = true;
-    for (size_t b = 0; b < B; b++) all = all && w->h_ctrl[b].done;
-    if (all) break;
-  }
+  });
+  if (r != VO_OK) return r;
   hipLaunchKernelGGL(k_e5_finish, dim3((unsigned)B), dim3(256), 0, c->stream, w->d_q, cap, n, d_thr2, prm->distance_thresh, w->d_ctrl, w->d_mask, w->d_out);
   VO_HIP(c, hipGetLastError());
   VO_HIP(c, hipMemcpyAsync(w->h_out, w->d_out, sizeof(double) * 32 * B, hipMemcpyDeviceToHost, c->stream));
@@ -770,7 +733,7 @@ extern "C" int32_t vo_essential_ransac(vo_ctx* c, const double* K, const float* 
     for (int k = 0; k < 3; k++) t[3 * b + k] = o[18 + k];
     if (stats) {
       stats[b].n_inliers = (int32_t)o[21]; stats[b].n_good = (int32_t)o[22];
-      stats[b].hypotheses = w->h_ctrl[b].h_done; stats[b].best = w->h_ctrl[b].best_h;
+      stats[b].hypotheses = w->h_ctrl[b].s.h_done; stats[b].best = w->h_ctrl[b].best_h;
       stats[b].status = (w->h_ctrl[b].best_h < 0) ? VO_E_NUMERIC : 0;
       stats[b].pad = 0;
     }

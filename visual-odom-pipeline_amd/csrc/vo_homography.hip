@@ -17,7 +17,8 @@
 //              the inliers (smallest eigenvector of the 9 x 9 normal matrix by Jacobi) and up to refine_iters Levenberg-Marquardt steps on
 //              the forward transfer error in the 8 parameters of the normalised frame (its scale is isotropic, so the minimiser is the
 //              pixel error's); cost = sum of squared pixel errors over the mask at the returned H
-// Rounds of 256 hypotheses, a control block per sequence, [batch] everywhere, everything on ctx->stream -- the shape of vo_essential.hip.
+// Rounds of 256 hypotheses, a control block per sequence, [batch] everywhere, everything on ctx->stream -- the shape of vo_essential.hip;
+// what the two and vo_pnp.hip share (generator, bound, control head, select tail, the host's round loop) is vo_ransac.h.
 // This library is built with -ffp-contract=off: the sign tests of checkSubset evaluate exactly as the model's float64 expressions do.
 #include "vo_internal.h"
 #include "vo_ransac.h"
@@ -30,7 +31,9 @@
 #define H4_NSUM 45             // sums of one reduction pass: the 45 distinct entries of a 9 x 9 normal matrix, or 36 + 8 + 1 of an LM step
 
 struct h4_hyp { double H[9]; int count; int ok; int h; int pad; };
-struct h4_ctrl { int niters, h_done, done, best_h, best_count, pad; double H[9]; };
+struct h4_ctrl { vo_ransac_state s; int best_h, best_count, pad; double H[9]; };
+static_assert(sizeof(h4_ctrl) == 96 && offsetof(h4_ctrl, best_h) == 12 && offsetof(h4_ctrl, best_count) == 16 && offsetof(h4_ctrl, pad) == 20 &&
+              offsetof(h4_ctrl, H) == 24, "h4_ctrl layout");
 
 struct vo_hom_ws {
   int cap = 0;
@@ -164,7 +167,8 @@ __device__ __forceinline__ bool h4_inlier(const double* H, double x, double y, d
 // ------------------------------------------------------------------------------------------------
 __global__ void k_h4_init(h4_ctrl* ctrl, int max_iters) {
   h4_ctrl* c = ctrl + blockIdx.x;
-  c->niters = max_iters; c->h_done = 0; c->done = 0; c->best_h = -1; c->best_count = 3; c->pad = 0;
+  vo_ransac_reset(&c->s, max_iters);
+  c->best_h = -1; c->best_count = 3; c->pad = 0;
   for (int i = 0; i < 9; i++) c->H[i] = 0;
 }
 
@@ -174,9 +178,9 @@ __global__ void __launch_bounds__(64) k_h4_solve(const float* __restrict__ p, in
   const int b = blockIdx.y, slot = blockIdx.x * 64 + threadIdx.x;
   const h4_ctrl* cs = ctrl + b;
   h4_hyp* out = hyps + (size_t)b * H4_BATCH + slot;
-  const int h = cs->h_done + slot;
+  const int h = cs->s.h_done + slot;
   out->h = h; out->count = 0; out->ok = 0;
-  if (cs->done) return;
+  if (cs->s.done) return;
   const float* pa = p + ((size_t)b * 2) * cap * 2;
   const float* pb = pa + (size_t)cap * 2;
   int idx[4];
@@ -223,23 +227,17 @@ __global__ void __launch_bounds__(H4_BATCH) k_h4_select(const h4_hyp* __restrict
   __shared__ int s_cnt[H4_BATCH];
   const int b = blockIdx.x, tid = threadIdx.x;
   h4_ctrl* c = ctrl + b;
-  if (c->done) return;
+  if (c->s.done) return;
   const h4_hyp* H = hyps + (size_t)b * H4_BATCH;
   s_cnt[tid] = H[tid].ok ? H[tid].count : -1;
   __syncthreads();
   if (tid == 0) {
-    int bi = -1, bc = c->best_count;
-    for (int i = 0; i < H4_BATCH; i++) if (s_cnt[i] > bc) { bc = s_cnt[i]; bi = i; }     // batch order = ascending h
+    const int bi = vo_ransac_best_slot(s_cnt, H4_BATCH, c->best_count);
     if (bi >= 0) {
-      c->best_count = bc; c->best_h = H[bi].h;
+      c->best_count = s_cnt[bi]; c->best_h = H[bi].h;
       for (int i = 0; i < 9; i++) c->H[i] = H[bi].H[i];
     }
-    c->h_done += H4_BATCH;
-    if (c->best_h >= 0) {
-      const int ni = vo_ransac_update_iters(conf, (double)(n - c->best_count) / (double)n, 4, max_iters);
-      if (ni < c->niters) c->niters = ni;
-    }
-    c->done = (c->h_done >= c->niters) ? 1 : 0;
+    vo_ransac_advance(&c->s, H4_BATCH, n, c->best_count, c->best_h >= 0, conf, 4, max_iters);
   }
 }
 
@@ -551,7 +549,7 @@ extern "C" int32_t vo_homography_ransac(vo_ctx* c, const float* pts1, const floa
   VO_HIP(c, hipMemcpy2DAsync(w->d_p, pitch, pts1, row, row, B, hipMemcpyHostToDevice, c->stream));
   VO_HIP(c, hipMemcpy2DAsync(w->d_p + (size_t)cap * 2, pitch, pts2, row, row, B, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_h4_init, dim3((unsigned)B), dim3(1), 0, c->stream, w->d_ctrl, prm->max_iters);
-  for (int guard = 0; guard < (prm->max_iters + H4_BATCH - 1) / H4_BATCH; guard++) {
+  r = vo_ransac_rounds(c, c->stream, w->d_ctrl, w->h_ctrl, B, (prm->max_iters + H4_BATCH - 1) / H4_BATCH, [&](int) {
     {
       vo_prof_scope prof(c, c->stream, VO_PROF_HOM_SOLVE);
       hipLaunchKernelGGL(k_h4_solve, dim3(H4_BATCH / 64, (unsigned)B), dim3(64), 0, c->stream, w->d_p, cap, n, (unsigned)prm->seed, w->d_hyp, w->d_ctrl);
@@ -564,13 +562,8 @@ extern "C" int32_t vo_homography_ransac(vo_ctx* c, const float* pts1, const floa
       vo_prof_scope prof(c, c->stream, VO_PROF_HOM_SELECT);
       hipLaunchKernelGGL(k_h4_select, dim3((unsigned)B), dim3(H4_BATCH), 0, c->stream, w->d_hyp, w->d_ctrl, n, prm->confidence, prm->max_iters);
     }
-    VO_HIP(c, hipGetLastError());
-    VO_HIP(c, hipMemcpyAsync(w->h_ctrl, w->d_ctrl, sizeof(h4_ctrl) * B, hipMemcpyDeviceToHost, c->stream));
-    VO_HIP(c, hipStreamSynchronize(c->stream));
-    bool all = true;
-    for (size_t b = 0; b < B; b++) all = all && w->h_ctrl[b].done;
-    if (all) break;
-  }
+  });
+  if (r != VO_OK) return r;
   {
     vo_prof_scope prof(c, c->stream, VO_PROF_HOM_FINISH);
     hipLaunchKernelGGL(k_h4_finish, dim3((unsigned)B), dim3(256), 0, c->stream, w->d_p, cap, n, thr2, prm->refine_iters, w->d_ctrl, w->d_mask, w->d_out);
@@ -586,7 +579,7 @@ extern "C" int32_t vo_homography_ransac(vo_ctx* c, const float* pts1, const floa
     if (H0) for (int k = 0; k < 9; k++) H0[9 * b + k] = o[9 + k];
     if (stats) {
       stats[b].cost = o[18];
-      stats[b].n_inliers = none ? 0 : (int32_t)o[19]; stats[b].hypotheses = w->h_ctrl[b].h_done; stats[b].best = w->h_ctrl[b].best_h;
+      stats[b].n_inliers = none ? 0 : (int32_t)o[19]; stats[b].hypotheses = w->h_ctrl[b].s.h_done; stats[b].best = w->h_ctrl[b].best_h;
       stats[b].status = none ? VO_E_NUMERIC : 0;
       stats[b].lm_iters = none ? 0 : (int32_t)o[20]; stats[b]._pad = 0;
     }

@@ -23,6 +23,7 @@
 // What such a kernel costs is its number of DEPENDENT trips to global memory: extend, prune and promote read the lists, then every row field
 // and the heads of the free lists in one trip each, and keep their bookkeeping (elections, counts, the growing list) in LDS.
 #include "vo_internal.h"
+#include "vo_ransac.h"
 
 #include <math.h>
 #include <string.h>
@@ -1096,8 +1097,8 @@ __global__ void __launch_bounds__(PIPE_TPB) k_pipe_spawn(pipe_ptrs Pall, int do_
     r.n_landmarks = nl; r.n_candidates = nc; r.n_dead = nd; r.n_dead_total = nd + P.cnt[C_NINERT];
     r.n_tracked = P.cnt[C_NKLT];
     const double n_in = pnp_out[8 * (size_t)b + 7];
-    r.pnp_inliers = (n_in == n_in) ? (int)n_in : 0; r.pnp_hypotheses = pnp_ctrl[(size_t)b * pnp_ctrl_stride + 1];
-    r.pnp_bound_reached = pnp_ctrl[(size_t)b * pnp_ctrl_stride + 2];
+    r.pnp_inliers = (n_in == n_in) ? (int)n_in : 0; r.pnp_hypotheses = pnp_ctrl[(size_t)b * pnp_ctrl_stride + VO_RANSAC_WORD_H_DONE];
+    r.pnp_bound_reached = pnp_ctrl[(size_t)b * pnp_ctrl_stride + VO_RANSAC_WORD_DONE];
     r.n_ripe = P.cnt[C_NRIPE]; r.n_new = P.cnt[C_NNEW]; r.n_resurrected = P.cnt[C_NRES]; r.n_detected = n_det;
     P.cnt[C_NDET] = n_det; P.cnt[C_OVERFLOW] = overflow;       // (H, H_final, t_final and the ba_* fields: k_pipe_writeback)
   }

@@ -17,6 +17,7 @@
 // stride over the points).  32 (first batch of a search) or 256 hypotheses x batch sequences per launch; a one-workgroup-per-sequence kernel keeps the running best and the
 // iteration bound on the device, another one refines.
 #include "vo_internal.h"
+#include "vo_ransac.h"
 
 #include <math.h>
 #include <string.h>
@@ -30,7 +31,8 @@
 #endif
 
 struct pnp_hyp { double R[9]; double t[3]; int count; int h; };
-struct pnp_ctrl { int niters; int h_done; int done; int pad; pnp_hyp best; };
+struct pnp_ctrl { vo_ransac_state s; int pad; pnp_hyp best; };
+static_assert(sizeof(pnp_hyp) == 104 && sizeof(pnp_ctrl) == 120 && offsetof(pnp_ctrl, pad) == 12 && offsetof(pnp_ctrl, best) == 16, "pnp_ctrl layout");
 
 struct vo_pnp_ws {
   int cap = 0;
@@ -47,30 +49,8 @@ struct vo_pnp_ws {
 };
 
 // ------------------------------------------------------------------------------------------------
-// device helpers (mirror oracle/pnp_oracle.py line by line)
+// device helpers (P3P as in oracle/pnp_oracle.py, operation by operation; the sample generator and the iteration bound: vo_ransac.h)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long pnp_splitmix64(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  unsigned long long z = x;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ inline void pnp_sample4(unsigned seed, unsigned h, int n, int idx[4]) {
-  int cnt = 0;
-  unsigned k = 0;
-  while (cnt < 4) {
-    const unsigned long long r = (k < 256) ? pnp_splitmix64(((unsigned long long)(seed & 0xFFFFFFu) << 40) ^ ((unsigned long long)h << 8) ^ (unsigned long long)(k & 0xFFu))
-                                           : pnp_splitmix64((unsigned long long)k);
-    const int i = (int)((r >> 11) % (unsigned long long)n);
-    k++;
-    bool dup = false;
-    for (int j = 0; j < cnt; j++) dup = dup || (idx[j] == i);
-    if (!dup) idx[cnt++] = i;
-  }
-}
-
 __device__ inline double pnp_cubic_root(double A, double B, double C) {   // largest real root of z^3 + A z^2 + B z + C
   const double P = B - A * A / 3.0;
   const double Q = 2.0 * A * A * A / 27.0 - A * B / 3.0 + C;
@@ -347,7 +327,7 @@ __global__ void __launch_bounds__(64) k_pnp_solve(const double* __restrict__ Kal
   if (counts) n = counts[b];
   // first = 1: the first batch of a search -- the control block is taken as freshly initialised (k_pnp_select of this batch writes it),
   // which saves the closed loop the k_pnp_init launch in front of every frame's search
-  const int h_done = first ? 0 : ctrl[b].h_done, done = first ? 0 : ctrl[b].done;
+  const int h_done = first ? 0 : ctrl[b].s.h_done, done = first ? 0 : ctrl[b].s.done;
   pnp_hyp* out = hyps + (size_t)b * PNP_BATCH + slot;
   const int h = h_done + slot;
   out->h = h;
@@ -359,7 +339,7 @@ __global__ void __launch_bounds__(64) k_pnp_solve(const double* __restrict__ Kal
   for (int i = 0; i < 9; i++) K[i] = Kp[i];
   pnp_inv3(K, Kinv);
   int idx[4];
-  pnp_sample4(seed, (unsigned)h, n, idx);
+  vo_ransac_sample<4>(seed, (unsigned)h, n, idx);
   double P[4][3], q[4][2];
   for (int i = 0; i < 4; i++) {
     for (int c = 0; c < 3; c++) P[i][c] = (double)X[3 * idx[i] + c];
@@ -401,21 +381,12 @@ __global__ void __launch_bounds__(PNP_SCORE_THREADS) k_pnp_score(const double* _
   if (lane == 0) { int tot = 0; for (int w = 0; w < PNP_SCORE_THREADS / 64; w++) tot += s_part[w]; hp->count = tot; }
 }
 
-// OpenCV RANSACUpdateNumIters (calib3d/ptsetreg.cpp)
-__device__ inline int pnp_update_iters(double p, double ep, int model_points, int max_iters) {
-  p = fmin(fmax(p, 0.0), 1.0); ep = fmin(fmax(ep, 0.0), 1.0);
-  double num = fmax(1.0 - p, 2.2250738585072014e-308);
-  double denom = 1.0 - pow(1.0 - ep, (double)model_points);
-  if (denom < 2.2250738585072014e-308) return 0;
-  num = log(num); denom = log(denom);
-  return (denom >= 0 || -num >= max_iters * (-denom)) ? max_iters : (int)rint(num / denom);
-}
-
 // ------------------------------------------------------------------------------------------------
 // k_pnp_select : grid (batch): running best (most inliers, ties to the smallest h) and the iteration bound
 // ------------------------------------------------------------------------------------------------
 __device__ inline void pnp_ctrl_reset(pnp_ctrl* c, int max_iters) {
-  c->niters = max_iters; c->h_done = 0; c->done = 0; c->pad = 0;
+  vo_ransac_reset(&c->s, max_iters);
+  c->pad = 0;
   c->best.count = 0; c->best.h = -1;
   for (int i = 0; i < 9; i++) c->best.R[i] = 0;
   for (int i = 0; i < 3; i++) c->best.t[i] = 0;
@@ -427,22 +398,16 @@ __global__ void __launch_bounds__(PNP_BATCH) k_pnp_select(const pnp_hyp* __restr
   const int b = blockIdx.x, tid = threadIdx.x;
   if (counts) n = counts[b];
   pnp_ctrl* c = ctrl + b;
-  if (!first && c->done) return;
-  if (n < 4) { if (tid == 0) { if (first) pnp_ctrl_reset(c, max_iters); c->done = 1; } return; }
+  if (!first && c->s.done) return;
+  if (n < 4) { if (tid == 0) { if (first) pnp_ctrl_reset(c, max_iters); c->s.done = 1; } return; }
   const pnp_hyp* H = hyps + (size_t)b * PNP_BATCH;
   s_cnt[tid] = tid < nb ? H[tid].count : -1;
   __syncthreads();
   if (tid == 0) {
     if (first) pnp_ctrl_reset(c, max_iters);               // (see k_pnp_solve)
-    int bi = -1, bc = c->best.count;
-    for (int i = 0; i < nb; i++) if (s_cnt[i] > bc) { bc = s_cnt[i]; bi = i; }    // batch order = ascending h
+    const int bi = vo_ransac_best_slot(s_cnt, nb, c->best.count);
     if (bi >= 0) c->best = H[bi];
-    c->h_done += nb;
-    if (c->best.count > 0) {
-      const int ni = pnp_update_iters(conf, (double)(n - c->best.count) / (double)n, 4, max_iters);
-      if (ni < c->niters) c->niters = ni;
-    }
-    c->done = (c->h_done >= c->niters) ? 1 : 0;
+    vo_ransac_advance(&c->s, nb, n, c->best.count, c->best.count > 0, conf, 4, max_iters);
   }
 }
 
@@ -934,9 +899,9 @@ extern "C" int32_t vo_pnp_fetch(vo_ctx* c, double* rvec, double* tvec, uint8_t* 
     if (rvec) for (int k = 0; k < 3; k++) rvec[3 * b + k] = out[k];
     if (tvec) for (int k = 0; k < 3; k++) tvec[3 * b + k] = out[3 + k];
     if (stats) {
-      stats[b].n_inliers = (int32_t)out[7]; stats[b].hypotheses = w->h_ctrl[b].h_done; stats[b].best = w->h_ctrl[b].best.h;
+      stats[b].n_inliers = (int32_t)out[7]; stats[b].hypotheses = w->h_ctrl[b].s.h_done; stats[b].best = w->h_ctrl[b].best.h;
       stats[b].cost = out[6];
-      stats[b].status = !(out[7] >= 4) ? VO_E_NUMERIC : (w->h_ctrl[b].done ? 0 : VO_E_CAPACITY);
+      stats[b].status = !(out[7] >= 4) ? VO_E_NUMERIC : (w->h_ctrl[b].s.done ? 0 : VO_E_CAPACITY);
     }
   }
   return VO_OK;
@@ -958,14 +923,9 @@ extern "C" int32_t vo_pnp_ransac(vo_ctx* c, const double* K, const float* pts3d,
   hipLaunchKernelGGL(k_pnp_init, dim3((unsigned)B), dim3(1), 0, c->stream, w->d_ctrl, prm->max_iters);
   // batches of 32, then 256 hypotheses per sequence until every sequence has reached its iteration bound (typically one or
   // two batches: the bound is 33 iterations at 70 % inliers, 145 at 50 %)
-  for (int guard = 0; guard < (prm->max_iters + PNP_BATCH - 1) / PNP_BATCH + 1; guard++) {
-    pnp_enqueue_batch(c, c->stream, prm, guard);
-    VO_HIP(c, hipMemcpyAsync(w->h_ctrl, w->d_ctrl, sizeof(pnp_ctrl) * B, hipMemcpyDeviceToHost, c->stream));
-    VO_HIP(c, hipStreamSynchronize(c->stream));
-    bool all = true;
-    for (size_t b = 0; b < B; b++) all = all && w->h_ctrl[b].done;
-    if (all) break;
-  }
+  r = vo_ransac_rounds(c, c->stream, w->d_ctrl, w->h_ctrl, B, (prm->max_iters + PNP_BATCH - 1) / PNP_BATCH + 1,
+                       [&](int round) { pnp_enqueue_batch(c, c->stream, prm, round); });
+  if (r != VO_OK) return r;
   r = pnp_enqueue_refine(c, c->stream, prm);
   if (r != VO_OK) return r;
   r = vo_pnp_fetch(c, rvec, tvec, inlier_mask, stats);
