@@ -186,6 +186,26 @@ typedef struct {
   int32_t _pad;
 } vo_hom_stats;
 
+/* cv2.findFundamentalMat(p1, p2, cv2.FM_RANSAC, 3.0, 0.99): the two-view model that needs no intrinsics */
+typedef struct {
+  double  threshold;         /* 3.0 px: consensus threshold on the distance of a point to its epipolar line, in either view */
+  double  confidence;        /* 0.99 */
+  int32_t max_iters;         /* 1000 */
+  int32_t seed;              /* of the counter-based sample generator */
+  int32_t refit;             /* 0: F is the winning sample's model, as cv2 returns it; 1: the normalised eight-point re-fit on the inliers */
+  int32_t _pad;
+} vo_fund_params;
+
+typedef struct {
+  double  cost;              /* sum of err = max(d1^2, d2^2) in px^2 over the mask at the returned F */
+  int32_t n_inliers;         /* consensus set of F0 */
+  int32_t hypotheses;        /* seven-point samples evaluated */
+  int32_t best;              /* index of the winning sample */
+  int32_t status;            /* 0, or VO_E_NUMERIC when no model with >= 7 inliers was found */
+  int32_t n_roots;           /* real roots (models) of the winning sample: 1 or 3 */
+  int32_t models;            /* models scored over the whole search */
+} vo_fund_stats;
+
 /* the fields of cv2.KeyPoint that cv2.SIFT fills (the reference reads pt through cv2.KeyPoint_convert and hands the
  * objects back to compute(), src/extractor/extractor.py:114-122) */
 typedef struct {
@@ -657,6 +677,30 @@ int32_t vo_homography_default_params(vo_hom_params* p);
 int32_t vo_homography_ransac(vo_ctx* ctx, const float* pts1, const float* pts2, int32_t n, const vo_hom_params* prm,
                              double* H, double* H0, uint8_t* inlier_mask, vo_hom_stats* stats);
 
+/* ---- fundamental matrix: epipolar verification of matches without intrinsics ----------------------
+ * cv2.findFundamentalMat(p1, p2, cv2.FM_RANSAC, 3.0, 0.99) of OpenCV 4.4, next to vo_essential_ransac (which needs K) and
+ * vo_homography_ransac.  Rounds of 256 seven-point samples: hypothesis h draws sample7(seed, h, n), the generator of the other
+ * searches, with no subset check (OpenCV's FMEstimatorCallback has none: a degenerate sample yields poor models and still counts); a
+ * lane per sample Hartley-normalises the seven points, finds the two-dimensional null space of the 7 x 9 system, and keeps every
+ * real root of det(a F1 + (1 - a) F2) = 0 (1 or 3) as a model; a system with a larger null space (a repeated point, a sample on a
+ * line) has none.  A wave per model counts err <= threshold^2, err = max(d1^2 s1, d2^2 s2) the larger squared point-to-epiline
+ * distance; most inliers win, ties to the smallest h, between the models of one sample to the smaller sum of err over the consensus
+ * set, at least 7; the bound is RANSACUpdateNumIters with 7 model points.  The mask is the winner F0's and is not recomputed.
+ * refit = 0: F = F0; refit = 1 with at least 8 inliers: the normalised eight-point algorithm on the consensus set, rank 2 enforced.
+ * Stated deviations from cv2: err in float64 (cv2: float32); for 7 < n < 15 cv2 silently switches to LMedS, this runs RANSAC for
+ * every n >= 8; for n = 7 cv2 returns every root stacked as 9 x 3, this returns the winner by the tie rule; cv2 scales F to f33 = 1,
+ * this returns unit Frobenius norm (the Python layer divides by f33).  Sample draws differ from OpenCV's: statistical parity; the
+ * algorithm is defined by tests/fundamental_model.py.
+ * pts1, pts2 [batch][n][2] f32 pixels (NaN rows, and points whose epipolar line has a^2 + b^2 = 0 or a value that is not finite in
+ * either view, are never inliers); F, F0 [batch][9] row-major, unit Frobenius norm, the entry of the largest magnitude positive,
+ * x2^T F x1 = 0 (F0 may be NULL); inlier_mask [batch][n] u8 (may be NULL); stats [batch] (may be NULL).  A sequence without a model:
+ * status VO_E_NUMERIC, NaN F and F0, an empty mask; the call returns VO_OK.
+ * VO_E_INVALID with nothing enqueued: n < 7, threshold <= 0 or not finite, confidence outside (0, 1), max_iters < 1, refit outside
+ * 0..1. */
+int32_t vo_fundamental_default_params(vo_fund_params* p);
+int32_t vo_fundamental_ransac(vo_ctx* ctx, const float* pts1, const float* pts2, int32_t n, const vo_fund_params* prm,
+                              double* F, double* F0, uint8_t* inlier_mask, vo_fund_stats* stats);
+
 /* ---- SIFT features (SURVEY.md 8f "next" row 4, feature part) -----------------------------------
  * Replaces cv2.SIFT_create(nfeatures=1000).detect(img, mask) + .compute(img, kps) in
  * Extractor.extract(detector='custom', describe=True) (src/extractor/extractor.py:26-28, 114-122; the two bootstrap
@@ -993,10 +1037,13 @@ int32_t vo_step_layout(vo_ctx* ctx, int32_t* layout, int32_t* gate_groups, int32
  * VO_PROF_HOM_SOLVE / _SCORE / _SELECT / _FINISH bracket the k_h4_solve / k_h4_score / k_h4_select launch of every round of
  * vo_homography_ransac and its k_h4_finish launch (tools/homography_timing.py).
  * VO_PROF_ORB_PYRAMID / _CANDIDATES / _RETAIN / _DESCRIBE bracket the stages of vo_orb_detect_compute: the k_orb_resize launches; k_orb_score,
- * k_orb_nms and k_orb_cut; k_orb_harris and k_orb_rank; k_orb_describe (tools/orb_timing.py). */
+ * k_orb_nms and k_orb_cut; k_orb_harris and k_orb_rank; k_orb_describe (tools/orb_timing.py).
+ * VO_PROF_FUND_SOLVE / _SCORE / _SELECT / _FINISH bracket the k_f7_solve / k_f7_score / k_f7_select launch of every round of
+ * vo_fundamental_ransac and its k_f7_finish launch (tools/fundamental_timing.py). */
 enum { VO_PROF_FRAME = 0, VO_PROF_KLT = 1, VO_PROF_ST = 2, VO_PROF_DLT = 3, VO_PROF_BA = 4, VO_PROF_CLAHE_LUT = 5, VO_PROF_CLAHE_APPLY = 6,
        VO_PROF_HOM_SOLVE = 7, VO_PROF_HOM_SCORE = 8, VO_PROF_HOM_SELECT = 9, VO_PROF_HOM_FINISH = 10, VO_PROF_ORB_PYRAMID = 11,
-       VO_PROF_ORB_CANDIDATES = 12, VO_PROF_ORB_RETAIN = 13, VO_PROF_ORB_DESCRIBE = 14, VO_PROF_COUNT = 15 };
+       VO_PROF_ORB_CANDIDATES = 12, VO_PROF_ORB_RETAIN = 13, VO_PROF_ORB_DESCRIBE = 14,
+       VO_PROF_FUND_SOLVE = 15, VO_PROF_FUND_SCORE = 16, VO_PROF_FUND_SELECT = 17, VO_PROF_FUND_FINISH = 18, VO_PROF_COUNT = 19 };
 int32_t vo_profile_enable(vo_ctx* ctx, int32_t region_mask);
 int32_t vo_profile_read(vo_ctx* ctx, int32_t region, double* total_ms, int32_t* count);
 /* diagnostic: shader-clock stamps (s_memtime deltas, cycles) of the phases of the last launch of a

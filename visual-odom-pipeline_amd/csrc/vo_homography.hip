@@ -28,7 +28,7 @@
 
 #define H4_BATCH 256
 #define H4_OUT 24              // doubles per sequence: H (9), H0 (9), cost, n_inliers, lm_iters, 3 spare
-#define H4_NSUM 45             // sums of one reduction pass: the 45 distinct entries of a 9 x 9 normal matrix, or 36 + 8 + 1 of an LM step
+#define H4_NSUM VO_NSUM        // sums of one reduction pass: the 45 distinct entries of a 9 x 9 normal matrix, or 36 + 8 + 1 of an LM step
 
 struct h4_hyp { double H[9]; int count; int ok; int h; int pad; };
 struct h4_ctrl { vo_ransac_state s; int best_h, best_count, pad; double H[9]; };
@@ -244,45 +244,6 @@ __global__ void __launch_bounds__(H4_BATCH) k_h4_select(const h4_hyp* __restrict
 // ------------------------------------------------------------------------------------------------
 // finish: mask, DLT re-fit, Levenberg-Marquardt
 // ------------------------------------------------------------------------------------------------
-// sum of every acc[k] over the 256 threads -> s_tot[k], the same order every time (wave shuffles, then the four waves in order)
-__device__ inline void h4_block_sum(double (&acc)[H4_NSUM], double (*s_part)[H4_NSUM], double* s_tot) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  __syncthreads();                                       // the previous totals have been read
-#pragma unroll
-  for (int k = 0; k < H4_NSUM; k++) {
-    double v = acc[k];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (lane == 0) s_part[wave][k] = v;
-  }
-  __syncthreads();
-  if (tid < H4_NSUM) s_tot[tid] = (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]);
-  __syncthreads();
-}
-
-// eigenvector of the smallest eigenvalue of the symmetric 9 x 9 M (destroyed) by cyclic Jacobi rotations; one thread, arrays in LDS
-__device__ inline void h4_smallest_eigenvector(double (*M)[9], double (*V)[9], double* out) {
-  for (int i = 0; i < 9; i++) for (int j = 0; j < 9; j++) V[i][j] = (i == j) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 60; sweep++) {
-    bool changed = false;
-    for (int p = 0; p < 8; p++)
-      for (int q = p + 1; q < 9; q++) {
-        const double apq = M[p][q];
-        if (!(apq * apq > 4.930380657631324e-32 * fabs(M[p][p] * M[q][q]))) continue;      // |a_pq| <= 2^-52 sqrt(a_pp a_qq): converged
-        changed = true;
-        const double zeta = (M[q][q] - M[p][p]) / (2.0 * apq);
-        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-        for (int k = 0; k < 9; k++) { const double a = M[k][p], bq = M[k][q]; M[k][p] = c * a - s * bq; M[k][q] = s * a + c * bq; }
-        for (int k = 0; k < 9; k++) { const double a = M[p][k], bq = M[q][k]; M[p][k] = c * a - s * bq; M[q][k] = s * a + c * bq; }
-        for (int k = 0; k < 9; k++) { const double a = V[k][p], bq = V[k][q]; V[k][p] = c * a - s * bq; V[k][q] = s * a + c * bq; }
-      }
-    if (!changed) break;
-  }
-  int j = 0;
-  for (int k = 1; k < 9; k++) if (M[k][k] < M[j][j]) j = k;
-  for (int k = 0; k < 9; k++) out[k] = V[k][j];
-}
-
 // (A + lam diag A) d = -g for the 8 x 8 normal matrix packed in s (upper triangle, row by row, then g): Cholesky.  -> false on a
 // non-positive pivot
 __device__ inline bool h4_lm_step(const double* s, double lam, double* d) {
@@ -348,7 +309,7 @@ __global__ void __launch_bounds__(256) k_h4_finish(const float* __restrict__ p, 
     mask[i] = in ? 1 : 0;
     if (in) { acc[0] += 1.0; acc[1] += (double)a.x; acc[2] += (double)a.y; acc[3] += (double)c.x; acc[4] += (double)c.y; }
   }
-  h4_block_sum(acc, s_part, s_tot);
+  vo_block_sum(acc, s_part, s_tot);
   const double m = s_tot[0];
   const double c1x = s_tot[1] / m, c1y = s_tot[2] / m, c2x = s_tot[3] / m, c2y = s_tot[4] / m;
   if (tid == 0) { for (int k = 0; k < 9; k++) s_H[k] = H0[k]; s_lm = 0; s_flag = 0; }
@@ -362,7 +323,7 @@ __global__ void __launch_bounds__(256) k_h4_finish(const float* __restrict__ p, 
       const double dx1 = (double)a.x - c1x, dy1 = (double)a.y - c1y, dx2 = (double)c.x - c2x, dy2 = (double)c.y - c2y;
       acc[0] += sqrt(dx1 * dx1 + dy1 * dy1); acc[1] += sqrt(dx2 * dx2 + dy2 * dy2);
     }
-    h4_block_sum(acc, s_part, s_tot);
+    vo_block_sum(acc, s_part, s_tot);
     const double s1 = 1.4142135623730951 / (s_tot[0] / m), s2 = 1.4142135623730951 / (s_tot[1] / m);
     // ---- normal matrix of the DLT rows (-x -y -1 0 0 0 ux uy u), (0 0 0 -x -y -1 vx vy v)
 #pragma unroll
@@ -378,12 +339,12 @@ __global__ void __launch_bounds__(256) k_h4_finish(const float* __restrict__ p, 
 #pragma unroll
         for (int ib = ia; ib < 9; ib++, k++) acc[k] += r1[ia] * r1[ib] + r2[ia] * r2[ib];
     }
-    h4_block_sum(acc, s_part, s_tot);
+    vo_block_sum(acc, s_part, s_tot);
     if (tid == 0) {
       for (int ia = 0, k = 0; ia < 9; ia++)
         for (int ib = ia; ib < 9; ib++, k++) { s_M[ia][ib] = s_tot[k]; s_M[ib][ia] = s_tot[k]; }
       double hn[9];
-      h4_smallest_eigenvector(s_M, s_V, hn);
+      vo_smallest_eigenvector9(s_M, s_V, hn);
       bool ok = true;
       for (int k = 0; k < 9; k++) ok = ok && (fabs(hn[k]) < __builtin_inf());
       for (int k = 0; k < 8; k++) { s_p[k] = hn[k] / hn[8]; ok = ok && (fabs(s_p[k]) < __builtin_inf()); }
@@ -426,7 +387,7 @@ __global__ void __launch_bounds__(256) k_h4_finish(const float* __restrict__ p, 
           for (int ia = 0; ia < 8; ia++) acc[36 + ia] += jx[ia] * rx + jy[ia] * ry;
           acc[44] += rx * rx + ry * ry;
         }
-        h4_block_sum(acc, s_part, s_tot);
+        vo_block_sum(acc, s_part, s_tot);
         if (tid == 0) {
           bool stop = false;
           const double cnew = s_tot[44];
@@ -482,7 +443,7 @@ __global__ void __launch_bounds__(256) k_h4_finish(const float* __restrict__ p, 
     const double dx = (double)c.x - ((H[0] * x + H[1] * y) + H[2]) / w, dy = (double)c.y - ((H[3] * x + H[4] * y) + H[5]) / w;
     acc[0] += dx * dx + dy * dy;
   }
-  h4_block_sum(acc, s_part, s_tot);
+  vo_block_sum(acc, s_part, s_tot);
   if (tid == 0) {
     for (int k = 0; k < 9; k++) { out[k] = H[k]; out[9 + k] = H0[k]; }
     out[18] = s_tot[0]; out[19] = m; out[20] = (double)s_lm; out[21] = 0.0; out[22] = 0.0; out[23] = 0.0;

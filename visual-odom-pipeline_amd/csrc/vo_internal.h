@@ -150,6 +150,7 @@ struct vo_ctx {
   struct vo_match_ws* match = nullptr;   // descriptor matcher buffers (vo_match.hip)
   struct vo_ess_ws* ess = nullptr;   // essential-matrix RANSAC workspace (vo_essential.hip)
   struct vo_hom_ws* hom = nullptr;   // homography RANSAC workspace (vo_homography.hip)
+  struct vo_fund_ws* fund = nullptr; // fundamental-matrix RANSAC workspace (vo_fundamental.hip)
   struct vo_trk_ws* trk = nullptr;   // device-resident track table (vo_tracks.hip)
   struct vo_pipe_ws* pipe = nullptr; // closed-loop Pipeline.step on the device (vo_pipeline.hip)
   const int32_t* d_pt_counts = nullptr;   // vo_tracks_* only (set by vo_tracks_seed, cleared by vo_trk_destroy): per-sequence number of live tracks the
@@ -404,6 +405,7 @@ int32_t vo_dlt_enqueue(vo_ctx* c, hipStream_t q, int n);     // the uploaded pai
 void vo_pnp_destroy(vo_ctx* c);
 void vo_ess_destroy(vo_ctx* c);
 void vo_hom_destroy(vo_ctx* c);
+void vo_fund_destroy(vo_ctx* c);
 void vo_match_destroy(vo_ctx* c);
 void vo_sift_destroy(vo_ctx* c);
 // sub-workspace lifetime hooks

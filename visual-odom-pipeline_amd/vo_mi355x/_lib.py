@@ -103,6 +103,16 @@ class HomStats(C.Structure):
                 ("status", C.c_int32), ("lm_iters", C.c_int32), ("_pad", C.c_int32)]
 
 
+class FundParams(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("max_iters", C.c_int32), ("seed", C.c_int32),
+                ("refit", C.c_int32), ("_pad", C.c_int32)]
+
+
+class FundStats(C.Structure):
+    _fields_ = [("cost", C.c_double), ("n_inliers", C.c_int32), ("hypotheses", C.c_int32), ("best", C.c_int32),
+                ("status", C.c_int32), ("n_roots", C.c_int32), ("models", C.c_int32)]
+
+
 class SiftKp(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("size", C.c_float), ("angle", C.c_float), ("response", C.c_float),
                 ("octave", C.c_int32)]
@@ -248,6 +258,8 @@ SIGNATURES = {
                                         C.POINTER(EssStats)]),
     "vo_homography_default_params": (C.c_int32, [C.POINTER(HomParams)]),
     "vo_homography_ransac": (C.c_int32, [_ctx, _f32p, _f32p, C.c_int32, C.POINTER(HomParams), _f64p, _f64p, _u8p, C.POINTER(HomStats)]),
+    "vo_fundamental_default_params": (C.c_int32, [C.POINTER(FundParams)]),
+    "vo_fundamental_ransac": (C.c_int32, [_ctx, _f32p, _f32p, C.c_int32, C.POINTER(FundParams), _f64p, _f64p, _u8p, C.POINTER(FundStats)]),
     "vo_sift_detect_compute": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32, C.POINTER(SiftKp), _f32p, _i32p]),
     "vo_orb_default_params": (C.c_int32, [C.POINTER(OrbParams)]),
     "vo_orb_detect_compute": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.POINTER(OrbParams), _i8p, C.c_int32, C.POINTER(OrbKp), _u8p, _i32p]),

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, HomParams, HomStats, KltParams, OrbKp, OrbParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
+from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, FundParams, FundStats, HomParams, HomStats, KltParams, OrbKp, OrbParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
 
 # vo_set_klt_predict modes (include/vo_mi355x.h)
 KLT_PREDICT_MODES = {"off": 0, "constant_velocity": 1}
@@ -765,6 +765,7 @@ class VoContext:
     PROF_FRAME, PROF_KLT, PROF_ST, PROF_DLT, PROF_BA, PROF_CLAHE_LUT, PROF_CLAHE_APPLY = range(7)
     PROF_HOM_SOLVE, PROF_HOM_SCORE, PROF_HOM_SELECT, PROF_HOM_FINISH = range(7, 11)
     PROF_ORB_PYRAMID, PROF_ORB_CANDIDATES, PROF_ORB_RETAIN, PROF_ORB_DESCRIBE = range(11, 15)
+    PROF_FUND_SOLVE, PROF_FUND_SCORE, PROF_FUND_SELECT, PROF_FUND_FINISH = range(15, 19)
 
     def profile_enable(self, regions=(0, 1, 2, 3, 4)):
         """regions: iterable of PROF_* ids to time with hipEvent pairs on the ctx stream; () switches timing off"""
@@ -1031,6 +1032,36 @@ class VoContext:
         if B == 1:
             return H[0], inl[0], stats[0], H0[0]
         return H, inl, stats, H0
+
+    def find_fundamental(self, pts1, pts2, threshold=3.0, confidence=0.99, max_iters=1000, seed=0, refit=0):
+        """cv2.findFundamentalMat(pts1, pts2, cv2.FM_RANSAC, threshold, confidence) (vo_fundamental_ransac).  pts1, pts2 (n,2) pixels, n >= 7
+        [leading batch dim if batch > 1] -> F (3,3) with x2^T F x1 = 0 (refit=0: the winning seven-point sample's model, as cv2 returns it;
+        refit=1: the normalised eight-point re-fit on the inliers, rank 2), inlier indices (ascending, the consensus set of F0), stats dict,
+        F0 (3,3) the winning sample's own model.  F and F0 are divided by f33 as cv2 returns them; where |f33| is under 1e-12 of the norm they
+        stay at unit Frobenius norm.  Without a model: stats['status'] != 0, NaN matrices, no inliers."""
+        B = self.batch
+        p1 = np.ascontiguousarray(pts1, np.float32).reshape(B, -1, 2)
+        p2 = np.ascontiguousarray(pts2, np.float32).reshape(B, -1, 2)
+        n = p1.shape[1]
+        assert p2.shape[1] == n
+        prm = FundParams()
+        self._L.vo_fundamental_default_params(C.byref(prm))
+        prm.threshold, prm.confidence, prm.max_iters, prm.seed, prm.refit = threshold, confidence, int(max_iters), int(seed), int(refit)
+        F, F0 = np.zeros((B, 3, 3)), np.zeros((B, 3, 3))
+        mask = np.zeros((B, n), np.uint8)
+        st = (FundStats * B)()
+        self._ck(self._L.vo_fundamental_ransac(self._h, ptr(p1, C.c_float), ptr(p2, C.c_float), n, C.byref(prm), ptr(F, C.c_double),
+                                               ptr(F0, C.c_double), ptr(mask, C.c_uint8), st))
+        for M in (F, F0):
+            for b in range(B):
+                if abs(M[b, 2, 2]) >= 1e-12 * np.linalg.norm(M[b]):      # (False for NaN: left as it is)
+                    M[b] /= M[b, 2, 2]
+        stats = [dict(cost=s.cost, n_inliers=s.n_inliers, hypotheses=s.hypotheses, best=s.best, status=s.status, n_roots=s.n_roots,
+                      models=s.models) for s in st]
+        inl = [np.nonzero(mask[b])[0] for b in range(B)]
+        if B == 1:
+            return F[0], inl[0], stats[0], F0[0]
+        return F, inl, stats, F0
 
     def pnp_params(self, reproj_err=2.0, confidence=0.9999, max_iters=1000000, seed=0):
         prm = PnpParams()

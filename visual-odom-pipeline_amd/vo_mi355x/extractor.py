@@ -552,6 +552,15 @@ class Extractor:
         H, inliers, st, H0 = self._ctx.find_homography(*self._uv_pairs(list_1, list_2), **kw)
         return H, inliers.reshape((-1,)).tolist(), st, H0
 
+    def find_fundamental(self, list_1, list_2, **kw):
+        """cv2.findFundamentalMat(FM_RANSAC) between the `uv` of two lists of keypoints (the lists camera_pose takes): the epipolar
+        verification of matches that needs no K -> (F 3x3 with x2^T F x1 = 0 and f33 = 1, inlier indices as a list, stats dict, F0);
+        keywords as VoContext.find_fundamental"""
+        if self._ctx is None:
+            raise RuntimeError("find_fundamental needs the device context: track a frame first (or pass ctx=)")
+        F, inliers, st, F0 = self._ctx.find_fundamental(*self._uv_pairs(list_1, list_2), **kw)
+        return F, inliers.reshape((-1,)).tolist(), st, F0
+
     def bootstrap_check(self, K, list_1, list_2, threshold=1.0, max_h_ratio=0.8, seed=0):
         """Is this frame pair fit for the 2D-2D bootstrap?  One essential_ransac and one find_homography call at the same pixel threshold;
         -> dict e_inliers, h_inliers, h_ratio = h_inliers / max(e_inliers, 1), degenerate = h_ratio > max_h_ratio (COLMAP's
