@@ -1263,25 +1263,35 @@ extern "C" int32_t vo_ba_upload(vo_ctx* c, const double* K, const double* poses,
   return VO_OK;
 }
 
+// the instance of the wave-walk kernels for the geometry fixed at the upload (ba_geometry): f(RT, SPL, LPP, factored) with integral constants.
+// The build and the update launch of an iteration both choose here.  factored: the pair of vo_ba_factored.hip, wherever the rule took the
+// <4, 2, 5> geometry (v2 == 2) with the Huber set
+template <int V> using ba_ic = std::integral_constant<int, V>;
+template <class F>
+static void ba_with_geometry(const vo_ba_ws* b, bool huber, F&& f) {
+  if (huber && b->v2 == 2) f(ba_ic<4>(), ba_ic<2>(), ba_ic<5>(), std::true_type());
+  else if (b->v2_spl == 2 && b->v2_lpp == 5) f(ba_ic<4>(), ba_ic<2>(), ba_ic<5>(), std::false_type());
+  else if (b->v2_spl == 2) f(ba_ic<4>(), ba_ic<2>(), ba_ic<8>(), std::false_type());
+  else if (b->v2_rt == 4) f(ba_ic<4>(), ba_ic<1>(), ba_ic<8>(), std::false_type());
+  else if (b->v2_rt == 3) f(ba_ic<3>(), ba_ic<1>(), ba_ic<8>(), std::false_type());
+  else if (b->v2_rt == 2 && b->v2_lpp == 4) f(ba_ic<2>(), ba_ic<1>(), ba_ic<4>(), std::false_type());
+  else if (b->v2_rt == 2) f(ba_ic<2>(), ba_ic<1>(), ba_ic<8>(), std::false_type());
+  else if (b->v2_lpp == 4) f(ba_ic<1>(), ba_ic<1>(), ba_ic<4>(), std::false_type());
+  else f(ba_ic<1>(), ba_ic<1>(), ba_ic<8>(), std::false_type());
+}
+
 template <int LOSS>
 static int32_t ba_launch_iter_t(vo_ctx* c, hipStream_t q, const ba_ptrs& P, const ba_params_dev& prm, int it, double probe_lambda,
                                 double* probe_S, double* hpp_out, double* probe_dl) {
   vo_ba_ws* b = c->ba;
   const int B = c->batch;
-  // the factored kernels (vo_ba_factored.hip) wherever the rule took the <4, 2, 5> geometry (v2 == 2, fixed at the upload by ba_geometry) with the Huber set
-  const bool fac = LOSS == VO_LOSS_HUBER && b->v2 == 2;
+  const dim3 g2(b->v2_g0 * B);
+  const int g0 = b->v2_g0, gc = b->v2_gcap;
   if (b->v2) {
-    const dim3 g(b->v2_g0 * B);
-    const int g0 = b->v2_g0, gc = b->v2_gcap;
-    if (fac) vo_ba_f_launch_build(g, b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
-    else if (b->v2_spl == 2 && b->v2_lpp == 5) hipLaunchKernelGGL((k_ba_build_w<4, 2, 5, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
-    else if (b->v2_spl == 2) hipLaunchKernelGGL((k_ba_build_w<4, 2, 8, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
-    else if (b->v2_rt == 4) hipLaunchKernelGGL((k_ba_build_w<4, 1, 8, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
-    else if (b->v2_rt == 3) hipLaunchKernelGGL((k_ba_build_w<3, 1, 8, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
-    else if (b->v2_rt == 2 && b->v2_lpp == 4) hipLaunchKernelGGL((k_ba_build_w<2, 1, 4, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
-    else if (b->v2_rt == 2) hipLaunchKernelGGL((k_ba_build_w<2, 1, 8, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
-    else if (b->v2_lpp == 4) hipLaunchKernelGGL((k_ba_build_w<1, 1, 4, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
-    else hipLaunchKernelGGL((k_ba_build_w<1, 1, 8, LOSS>), g, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
+    ba_with_geometry(b, LOSS == VO_LOSS_HUBER, [&](auto rt, auto spl, auto lpp, auto factored) {
+      if constexpr (decltype(factored)::value) vo_ba_f_launch_build(g2, b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
+      else hipLaunchKernelGGL((k_ba_build_w<decltype(rt)::value, decltype(spl)::value, decltype(lpp)::value, LOSS>), g2, dim3(256), b->v2_lds, q, P, prm, it, probe_lambda, g0, gc);
+    });
   } else if (b->tpb == 256 && b->LPP == 8) hipLaunchKernelGGL((k_ba_build<256, 8, LOSS>), dim3(P.nset, B), dim3(256), b->build_lds, q, P, prm, it, probe_lambda);
   else if (b->tpb == 256) hipLaunchKernelGGL((k_ba_build<256, 0, LOSS>), dim3(P.nset, B), dim3(256), b->build_lds, q, P, prm, it, probe_lambda);
   else if (b->tpb == 512) hipLaunchKernelGGL((k_ba_build<512, 0, LOSS>), dim3(b->nblk, B), dim3(512), b->build_lds, q, P, prm, it, probe_lambda);
@@ -1296,11 +1306,10 @@ static int32_t ba_launch_iter_t(vo_ctx* c, hipStream_t q, const ba_ptrs& P, cons
   }
   hipLaunchKernelGGL(k_ba_solve, dim3(B), dim3(BA_SOLVE_THREADS), b->solve_lds, q, P, prm, it, probe_S, hpp_out);
   if (b->v2) {
-    if (fac) vo_ba_f_launch_update(dim3(b->v2_g0 * B), q, P, prm, it, probe_dl, b->v2_g0, b->v2_gcap);
-    else if (b->v2_spl == 2 && b->v2_lpp == 5) hipLaunchKernelGGL((k_ba_update_w<2, 5, LOSS>), dim3(b->v2_g0 * B), dim3(256), 0, q, P, prm, it, probe_dl, b->v2_g0, b->v2_gcap);
-    else if (b->v2_spl == 2) hipLaunchKernelGGL((k_ba_update_w<2, 8, LOSS>), dim3(b->v2_g0 * B), dim3(256), 0, q, P, prm, it, probe_dl, b->v2_g0, b->v2_gcap);
-    else if (b->v2_lpp == 4) hipLaunchKernelGGL((k_ba_update_w<1, 4, LOSS>), dim3(b->v2_g0 * B), dim3(256), 0, q, P, prm, it, probe_dl, b->v2_g0, b->v2_gcap);
-    else hipLaunchKernelGGL((k_ba_update_w<1, 8, LOSS>), dim3(b->v2_g0 * B), dim3(256), 0, q, P, prm, it, probe_dl, b->v2_g0, b->v2_gcap);
+    ba_with_geometry(b, LOSS == VO_LOSS_HUBER, [&](auto, auto spl, auto lpp, auto factored) {
+      if constexpr (decltype(factored)::value) vo_ba_f_launch_update(g2, q, P, prm, it, probe_dl, g0, gc);
+      else hipLaunchKernelGGL((k_ba_update_w<decltype(spl)::value, decltype(lpp)::value, LOSS>), g2, dim3(256), 0, q, P, prm, it, probe_dl, g0, gc);
+    });
   } else if (b->tpb == 256 && b->LPP == 8) hipLaunchKernelGGL((k_ba_update<256, 8, LOSS>), dim3(b->nblk, B), dim3(256), 0, q, P, prm, it, probe_dl);
   else if (b->tpb == 256) hipLaunchKernelGGL((k_ba_update<256, 0, LOSS>), dim3(b->nblk, B), dim3(256), 0, q, P, prm, it, probe_dl);
   else if (b->tpb == 512) hipLaunchKernelGGL((k_ba_update<512, 0, LOSS>), dim3(b->nblk, B), dim3(512), 0, q, P, prm, it, probe_dl);

@@ -1,7 +1,11 @@
 // Bundle adjustment, windows of 9 and 10 slots: the FACTORED form of the wave-private build / update kernels of vo_ba_wave.h.
 //
-// Same reference lines, algorithm, wave walk, lane maps, work assignment (ba2_select_work), aux record, gmax, partial-set layout and fixed
-// summation orders as k_ba_build_w / k_ba_update_w.  What changes is where the per-CAMERA constants of the camera block are applied.  With
+// Same reference lines and algorithm as k_ba_build_w / k_ba_update_w, and for the build the SAME TEXT around pass 2: the geometry, the chunk
+// prefetch, the camera staging, the observation, the landmark factor with its aux record and gmax, the Gram phase and the fold of the four waves
+// are the shared phases of vo_ba_wave.h ("The phases of the wave walk"), called from both forms -- lane maps, partial-set layout and summation
+// orders agree because they are defined once.  This file's own: the head (the text of k_ba_build_w's), pass 2 of the build, its rotation
+// epilogue, and the update (k_ba_update_w's text with another Jp d_pose; its observations and its trial cost go through ba2_observe too).  What changes is where the per-CAMERA constants of the camera block
+// are applied.  With
 // Jl_k = a_k K R (row k of the landmark block) the camera block of an observation of slot s is
 //     Jp_k = j_k^T T_s,   j_k = [X x Jl_k ; Jl_k],   T_s = blockdiag(Jr_s, R_s^T)
 // -- the wave-private kernels multiply by Jr_s and form a_k K = Jl_k R_s^T once per OBSERVATION (5.12 M per launch at 256 x 2 000 x 10).
@@ -21,7 +25,7 @@
 
 #pragma clang fp contract(fast)
 
-#include "vo_ba_wave.h"      // lane maps, ba2_select_work, ba2_stage_camera, group sums
+#include "vo_ba_wave.h"      // lane maps, group sums and the shared phases of the wave walk
 
 #define BA3_CAM 18           // update: per window slot in LDS: K R (9), K t (3), R^T d_trans (3), Jr d_rot (3)
 
@@ -54,15 +58,11 @@ __device__ __forceinline__ int ba3_tile_index(int a, int b) {
 // ------------------------------------------------------------------------------------------------
 // k_ba_build_f
 // ------------------------------------------------------------------------------------------------
-// template arguments, grid and partial sets as k_ba_build_w
+// template arguments (ba2_geom), grid and partial sets as k_ba_build_w
 template <int RT, int SPL, int LPP, int LOSS>
 __global__ void __launch_bounds__(256, 2) k_ba_build_f(ba_ptrs Pall, ba_params_dev prm, int it, double probe_lambda, int G0, int Gcap) {
-  constexpr int LPC = ba2_map<LPP>::LPC;     // landmarks of a chunk
-  constexpr int LEAD = ba2_map<LPP>::LEAD;   // the lane of a landmark's group that holds its sums
-  constexpr int ROWS = 3 * LPC;              // panel rows of a chunk
-  constexpr int RP = 16 * RT, PITCH = RP + (LPP != 5 ? 16 : 0);
-  constexpr int NT = RT * (RT + 1) / 2;
-  constexpr int REGION = ROWS * PITCH;       // doubles of LDS a wave owns
+  using GEO = ba2_geom<RT, SPL, LPP>;
+  constexpr int LPC = GEO::LPC, LEAD = GEO::LEAD, PITCH = GEO::PITCH, NT = GEO::NT, REGION = GEO::REGION, WMAX = GEO::WMAX, CAMV = GEO::CAMV, TPR = GEO::TPR;
   ba2_work wk = ba2_select_work<true>(Pall, it, G0, Gcap);
   wk.prob = ba2_uniform(wk.prob); wk.part = ba2_uniform(wk.part); wk.G = ba2_uniform(wk.G);
   if (wk.prob < 0) return;                   // (uniform) more workgroups than the running problems can use
@@ -74,7 +74,7 @@ __global__ void __launch_bounds__(256, 2) k_ba_build_f(ba_ptrs Pall, ba_params_d
   __shared__ ba_state s_st;
   __shared__ double s_esum[4];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int n_live_ld = ba2_uniform(Pall.n_live ? *P.n_live : P.N);
+  const int n_live = ba2_uniform(Pall.n_live ? *P.n_live : P.N);
   ba_state prev;
   ba_info inf;
   if (it > 0) {
@@ -102,7 +102,6 @@ __global__ void __launch_bounds__(256, 2) k_ba_build_f(ba_ptrs Pall, ba_params_d
   const int pl = mp.pl, q = mp.q;
   const int lead4 = 4 * (lane - q + LEAD);        // (LPP = 5) ds_bpermute source: the leader of this lane's group
   const int nchunk = (N + LPC - 1) / LPC;
-  const int n_live = n_live_ld;
   const int nchunk_live = min(nchunk, (n_live + LPC - 1) / LPC);
   const bool seed_x = it == 0;
   double* const pan = dyn + wave * REGION;
@@ -113,44 +112,12 @@ __global__ void __launch_bounds__(256, 2) k_ba_build_f(ba_ptrs Pall, ba_params_d
 #pragma unroll
   for (int t = 0; t < 7 * SPL; t++) camacc[t] = 0.0;
   double gm = 0.0;
-  const double lam = st.lambda, delta = prm.delta;
-  const double id2 = LOSS == VO_LOSS_HUBER ? 0.0 : 1.0 / (delta * delta);
-  // this lane's landmark and observations of a chunk; the NEXT chunk's are requested before the Gram phase of this one
+  const double lam = st.lambda;
+  const ba2_scale sc = ba2_loss_scale<LOSS>(prm.delta);
   double Xn[3], uon[SPL], von[SPL];
-  auto fetch = [&](const int ch) {
-    const int jn = ch * LPC + pl;
-    Xn[0] = Xn[1] = Xn[2] = 0.0;
-    if (ch < nchunk && jn < N && !mp.idle) { Xn[0] = pts[3 * jn]; Xn[1] = pts[3 * jn + 1]; Xn[2] = pts[3 * jn + 2]; }
-#pragma unroll
-    for (int i = 0; i < SPL; i++) {
-      const int s = q + LPP * i;
-      uon[i] = __builtin_nan(""); von[i] = 0.0;
-      if (ch < nchunk_live && s < W && jn < N && !mp.idle) { const double2 ob = *reinterpret_cast<const double2*>(P.obs + ((size_t)s * N + jn) * 2); uon[i] = ob.x; von[i] = ob.y; }
-    }
-  };
+  const ba2_fetch<SPL, LPP> fetch{P, pts, mp, pl, q, W, N, nchunk, nchunk_live, Xn, uon, von};     // (references, in the order of ba2_fetch's members)
   fetch(part * 4 + wave);
-  // cameras: [R | t | Jr] from the poses (iteration 0) or as k_ba_solve left them, then K R, K t per camera (Jr waits in LDS for the epilogue)
-  if (tid < W) {
-    double c[BA_CAM];
-    if (it == 0) d_camera(poses + 6 * tid, c);
-    else {
-      const double* cg = P.cams + ((size_t)st.cur * W + tid) * BA_CAM;
-#pragma unroll
-      for (int k = 0; k < BA_CAM; k++) c[k] = cg[k];
-    }
-    ba2_stage_camera(P.K, c, s_cam + BA2_CAM * tid);
-    if (it == 0 && part == 0) {
-#pragma unroll
-      for (int k = 0; k < BA_CAM; k++) P.cams[(size_t)tid * BA_CAM + k] = c[k];   // cams[0] <-> x[0]
-    }
-  }
-  if (it == 0 && part == 0 && tid < 6 * W) P.xa[tid] = poses[tid];
-  // the padding columns behind 6 W + 1 start as zeros and are never written afterwards
-  {
-    const int npad = RP - (6 * W + 1);
-    for (int i = tid; i < 4 * ROWS * npad; i += 256) { const int r = i / npad; dyn[r * PITCH + 6 * W + 1 + (i - r * npad)] = 0.0; }
-    if (PITCH > RP) for (int i = tid; i < 4 * ROWS * (PITCH - RP); i += 256) { const int r = i / (PITCH - RP); dyn[r * PITCH + RP + (i - r * (PITCH - RP))] = 0.0; }
-  }
+  ba2_stage_build<GEO>(P, st, it, part, poses, dyn);      // (Jr waits in LDS for the epilogue)
   __syncthreads();
   int nwalk = 0;
 #pragma unroll 1
@@ -167,67 +134,34 @@ __global__ void __launch_bounds__(256, 2) k_ba_build_f(ba_ptrs Pall, ba_params_d
     // ---- pass 1: residual, weight and landmark block of this lane's observations; landmark sums over its slots.  Pass 2 needs the slot's own
     //      landmark block and nothing else: P (6), gamma (3) and rho are kept per slot ----
     double kP[SPL][6], kg[SPL][3], krho[SPL];
-    double h00 = 0, h10 = 0, h11 = 0, h20 = 0, h21 = 0, h22 = 0, g0 = 0, g1 = 0, g2 = 0;
+    double h[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
 #pragma unroll
     for (int i = 0; i < SPL; i++) {
       const int s = min(q + LPP * i, W - 1);      // (a lane without an i-th slot computes zeros on a valid camera)
-      const double* cam = s_cam + BA2_CAM * s;
-      const bool have = uo[i] == uo[i];
-      const double p0 = fma(cam[0], X[0], fma(cam[1], X[1], fma(cam[2], X[2], cam[9])));
-      const double p1 = fma(cam[3], X[0], fma(cam[4], X[1], fma(cam[5], X[2], cam[10])));
-      const double p2 = fma(cam[6], X[0], fma(cam[7], X[1], fma(cam[8], X[2], cam[11])));
-      const double ip2 = have ? rcp_nr(p2) : 0.0;             // an unobserved slot: zero Jacobians, zero residual (w = 1, rho = 0)
-      const double u = p0 * ip2, v = p1 * ip2;
-      const double e0 = u - (have ? uo[i] : 0.0), e1 = v - (have ? vo[i] : 0.0);
-      const double sq = e0 * e0 + e1 * e1;
-      const double d2 = delta * delta;
-      double w, rho;
-      ba_loss<LOSS>(sq, delta, d2, id2, w, rho);
-      krho[i] = rho;
-      double l0[3], l1[3];
-#pragma unroll
-      for (int c = 0; c < 3; c++) { l0[c] = (cam[c] - u * cam[6 + c]) * ip2; l1[c] = (cam[3 + c] - v * cam[6 + c]) * ip2; }
-      const double wl0[3] = {w * l0[0], w * l0[1], w * l0[2]};
-      const double wl1[3] = {w * l1[0], w * l1[1], w * l1[2]};
+      ba2_obs o;
+      ba2_observe<LOSS>(s_cam + BA2_CAM * s, X, uo[i], vo[i], sc, o);
+      krho[i] = o.rho;
+      const double* l0 = o.Jl[0];
+      const double* l1 = o.Jl[1];
+      const double wl0[3] = {o.w * l0[0], o.w * l0[1], o.w * l0[2]};
+      const double wl1[3] = {o.w * l1[0], o.w * l1[1], o.w * l1[2]};
       kP[i][0] = wl0[0] * l0[0] + wl1[0] * l1[0];
       kP[i][1] = wl0[1] * l0[0] + wl1[1] * l1[0];
       kP[i][2] = wl0[1] * l0[1] + wl1[1] * l1[1];
       kP[i][3] = wl0[2] * l0[0] + wl1[2] * l1[0];
       kP[i][4] = wl0[2] * l0[1] + wl1[2] * l1[1];
       kP[i][5] = wl0[2] * l0[2] + wl1[2] * l1[2];
-      kg[i][0] = wl0[0] * e0 + wl1[0] * e1;
-      kg[i][1] = wl0[1] * e0 + wl1[1] * e1;
-      kg[i][2] = wl0[2] * e0 + wl1[2] * e1;
-      h00 += kP[i][0]; h10 += kP[i][1]; h11 += kP[i][2]; h20 += kP[i][3]; h21 += kP[i][4]; h22 += kP[i][5];
-      g0 += kg[i][0]; g1 += kg[i][1]; g2 += kg[i][2];
+      kg[i][0] = wl0[0] * o.e0 + wl1[0] * o.e1;
+      kg[i][1] = wl0[1] * o.e0 + wl1[1] * o.e1;
+      kg[i][2] = wl0[2] * o.e0 + wl1[2] * o.e1;
+#pragma unroll
+      for (int k = 0; k < 6; k++) h[k] += kP[i][k];
+#pragma unroll
+      for (int k = 0; k < 3; k++) g[k] += kg[i][k];
     }
-    h00 = ba2_group_sum<LPP>(h00); h10 = ba2_group_sum<LPP>(h10); h11 = ba2_group_sum<LPP>(h11);
-    h20 = ba2_group_sum<LPP>(h20); h21 = ba2_group_sum<LPP>(h21); h22 = ba2_group_sum<LPP>(h22);
-    g0 = ba2_group_sum<LPP>(g0); g1 = ba2_group_sum<LPP>(g1); g2 = ba2_group_sum<LPP>(g2);
-    // ---- damped 3x3 block: Cholesky C C^T, Cinv = C^-1 (lower), y = Cinv g, z = Cinv^T y = M g ----
-    const double a00 = h00 + lam * fmax(h00, 1e-12), a11 = h11 + lam * fmax(h11, 1e-12), a22 = h22 + lam * fmax(h22, 1e-12);
-    double i00 = rsqrt_nr(a00);
-    const double c10 = h10 * i00, c20 = h20 * i00;
-    double i11 = rsqrt_nr(a11 - c10 * c10);
-    const double c21 = (h21 - c20 * c10) * i11;
-    double i22 = rsqrt_nr(a22 - c20 * c20 - c21 * c21);
-    double i10 = -c10 * i00 * i11;
-    double i21 = -c21 * i11 * i22;
-    double i20 = -(c20 * i00 + c21 * i10) * i22;
-    const double y0 = i00 * g0, y1 = i10 * g0 + i11 * g1, y2 = i20 * g0 + i21 * g1 + i22 * g2;
-    if (nwalk == 2) VO_STAMP(dbgb, 2);   // pass 1 + factor
-    if (q == LEAD && inr) {
-      double2* ax = reinterpret_cast<double2*>(P.aux + (size_t)j * BA_AUX);
-      ax[0] = make_double2(h00, h10); ax[1] = make_double2(h11, h20); ax[2] = make_double2(h21, h22);
-      ax[3] = make_double2(g0, g1); ax[4] = make_double2(g2, i00); ax[5] = make_double2(i10, i11);
-      ax[6] = make_double2(i20, i21); ax[7] = make_double2(i22, i00 * y0 + i10 * y1 + i20 * y2);
-      ax[8] = make_double2(i11 * y1 + i21 * y2, i22 * y2);
-    }
-    if (inr && (LPP != 5 || q == LEAD)) gm = fmax(gm, fmax(fabs(g0), fmax(fabs(g1), fabs(g2))));
-    if (LPP == 5) {      // the factor of the landmark to every lane of its group
-      i00 = ba2_from_leader<LPP>(i00, lead4); i10 = ba2_from_leader<LPP>(i10, lead4); i11 = ba2_from_leader<LPP>(i11, lead4);
-      i20 = ba2_from_leader<LPP>(i20, lead4); i21 = ba2_from_leader<LPP>(i21, lead4); i22 = ba2_from_leader<LPP>(i22, lead4);
-    }
+    double ci[6], y[3];
+    gm = ba2_factor_landmark<LPP>(h, g, lam, P.aux, j, inr, q == LEAD, lead4, dbgb, nwalk, gm, ci, y);
+    const double i00 = ci[0], i10 = ci[1], i11 = ci[2], i20 = ci[3], i21 = ci[4], i22 = ci[5];
     // ---- pass 2, slot by slot, in the basis of j_k = [X x Jl_k ; Jl_k]: the slot's camera sums from M = [X]x P, M [X]x^T, P, X x gamma, gamma;
     //      the landmark's panel rows [X]x Q, Q with Q = P Cinv^T;  column 6 W = y ----
     double* const rw0 = pan + (3 * pl) * PITCH;
@@ -275,25 +209,11 @@ __global__ void __launch_bounds__(256, 2) k_ba_build_f(ba_ptrs Pall, ba_params_d
         }
       }
     }
-    if (q == LEAD && !mp.idle) { rw0[6 * W] = inr ? y0 : 0.0; rw1[6 * W] = inr ? y1 : 0.0; rw2[6 * W] = inr ? y2 : 0.0; }
-    // ---- Gram matrix of the chunk's panel into the accumulators: one operand fetch per column block and k-step ----
+    if (q == LEAD && !mp.idle) { rw0[6 * W] = inr ? y[0] : 0.0; rw1[6 * W] = inr ? y[1] : 0.0; rw2[6 * W] = inr ? y[2] : 0.0; }
     __builtin_amdgcn_wave_barrier();
     if (nwalk == 2) VO_STAMP(dbgb, 3);   // first chunk: pass 2, panel written
     fetch(chunk + 4 * G);
-    {
-      const double* base = pan + (lane >> 4) * PITCH + (lane & 15);
-#pragma unroll
-      for (int k0 = 0; k0 < ROWS; k0 += 4) {
-        double op[RT];
-#pragma unroll
-        for (int c = 0; c < RT; c++) op[c] = base[k0 * PITCH + 16 * c];
-        int t = 0;
-#pragma unroll
-        for (int ta = 0; ta < RT; ta++)
-#pragma unroll
-          for (int tb = ta; tb < RT; tb++, t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(op[ta], op[tb], acc[t], 0, 0, 0);
-      }
-    }
+    ba2_gram<GEO, RT>(pan, lane, acc);
     __builtin_amdgcn_wave_barrier();
     if (nwalk == 2) VO_STAMP(dbgb, 4);
     nwalk++;   // first chunk: Gram
@@ -313,54 +233,19 @@ __global__ void __launch_bounds__(256, 2) k_ba_build_f(ba_ptrs Pall, ba_params_d
       for (int k = 0; k < 9; k++) Rc[k] = cg[k];
     }
   }
-  // ---- after the walk: the landmark bits the chunk stages left, then the four waves' sums through LDS in wave order (k_ba_build_w's order) ----
-#pragma unroll
-  for (int t = 0; t < 7 * SPL; t++) camacc[t] = ba2_finish_landmark_sum<LPP>(camacc[t]);
-  for (int ofs = 32; ofs > 0; ofs >>= 1) gm = fmax(gm, __shfl_xor(gm, ofs));
-  if (lane == 0) s_gmax[wave] = gm;
-  constexpr int WMAX = (RP - 1) / 6 < LPP * SPL ? (RP - 1) / 6 : LPP * SPL;   // largest window this instance serves
-  constexpr int CAMV = WMAX * BA_POSE_VALS;                  // room for the camera sums behind the tiles of a round
-  constexpr int TPR = (REGION - CAMV) / 256 < NT ? (REGION - CAMV) / 256 : NT;   // tiles per round
-  static_assert(TPR >= 1, "a wave's LDS region holds at least one tile beside the camera sums");
+  // ---- after the walk: the landmark bits the chunk stages left, then the four waves' sums through LDS in wave order ----
+  ba2_finish_walk<GEO, SPL, LPP>(camacc, gm, mp, W, lane, pan, s_gmax + wave);
   constexpr int NCS = (CAMV + 255) / 256;                    // camera sums a lane folds
-  double* const camsum = pan + TPR * 256;
-  {
-    const int b5 = lane >> 5, b4 = (lane >> 4) & 1;
-    const bool wr = (LPP == 8) ? ((lane & 8) == 0) : (LPP == 4) ? ((lane & 12) == 0) : ((lane & 15) < 5);
-    if (wr) {
-#pragma unroll
-      for (int i = 0; i < SPL; i++) {
-        const int s = q + LPP * i;
-        if (s < W) {
-#pragma unroll
-          for (int n = 0; n < 7; n++) camsum[s * BA_POSE_VALS + 4 * n + 2 * b4 + b5] = camacc[7 * i + n];
-        }
-      }
-    }
-  }
   // the folded set stays in registers (a lane: element tid of every tile, camera sums tid and tid + 256) until every round has been read
   double fsum[NT], csum[NCS];
 #pragma unroll
   for (int t0 = 0; t0 < NT; t0 += TPR) {
-    if (t0 > 0) __syncthreads();                            // the previous round has been read
+    ba2_tiles_to_lds<GEO>(acc, pan, lane, t0);
 #pragma unroll
-    for (int t = t0; t < NT && t < t0 + TPR; t++) {
-      double2* o2 = reinterpret_cast<double2*>(pan + (t - t0) * 256 + lane * 4);
-      o2[0] = make_double2(acc[t][0], acc[t][1]);
-      o2[1] = make_double2(acc[t][2], acc[t][3]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = t0; t < NT && t < t0 + TPR; t++) {
-      const int e = (t - t0) * 256 + tid;
-      fsum[t] = (dyn[e] + dyn[REGION + e]) + (dyn[2 * REGION + e] + dyn[3 * REGION + e]);
-    }
+    for (int t = t0; t < NT && t < t0 + TPR; t++) fsum[t] = ba2_fold4<GEO>(dyn, (t - t0) * 256 + tid);
     if (t0 == 0) {
 #pragma unroll
-      for (int k = 0; k < NCS; k++) {
-        const int o = TPR * 256 + min(tid + 256 * k, CAMV - 1);
-        csum[k] = (dyn[o] + dyn[REGION + o]) + (dyn[2 * REGION + o] + dyn[3 * REGION + o]);
-      }
+      for (int k = 0; k < NCS; k++) csum[k] = ba2_fold4<GEO>(dyn, TPR * 256 + min(tid + 256 * k, CAMV - 1));
     }
   }
   __syncthreads();                                          // the last round has been read: the panels' LDS is free
@@ -515,6 +400,7 @@ __global__ void __launch_bounds__(256, 2) k_ba_update_f(ba_ptrs Pall, ba_params_
   const int nchunk_live = min(nchunk, (n_live + LPC - 1) / LPC);
   const double lam = st.lambda, delta = prm.delta, d2 = delta * delta;
   const double id2 = LOSS == VO_LOSS_HUBER ? 0.0 : 1.0 / d2;
+  const ba2_scale sc{delta, d2, id2};
   double e0 = 0, e1 = 0, e2 = 0, e3 = 0;
 #pragma unroll 1
   for (int chunk = part * 4 + wave; chunk < nchunk_live; chunk += 4 * G) {
@@ -544,18 +430,11 @@ __global__ void __launch_bounds__(256, 2) k_ba_update_f(ba_ptrs Pall, ba_params_
     for (int i = 0; i < SPL; i++) {
       const int s = min(q + LPP * i, W - 1);
       const double* cam = s_cam + BA3_CAM * s;
-      const bool have = uo[i] == uo[i];
-      const double p0 = fma(cam[0], X[0], fma(cam[1], X[1], fma(cam[2], X[2], cam[9])));
-      const double p1 = fma(cam[3], X[0], fma(cam[4], X[1], fma(cam[5], X[2], cam[10])));
-      const double p2 = fma(cam[6], X[0], fma(cam[7], X[1], fma(cam[8], X[2], cam[11])));
-      const double ip2 = have ? rcp_nr(p2) : 0.0;
-      const double u = p0 * ip2, v = p1 * ip2;
-      const double r0 = u - (have ? uo[i] : 0.0), r1 = v - (have ? vo[i] : 0.0);
-      double w, rho;
-      ba_loss<LOSS>(r0 * r0 + r1 * r1, delta, d2, id2, w, rho);
-      double l0[3], l1[3];
-#pragma unroll
-      for (int c = 0; c < 3; c++) { l0[c] = (cam[c] - u * cam[6 + c]) * ip2; l1[c] = (cam[3 + c] - v * cam[6 + c]) * ip2; }
+      ba2_obs o;
+      ba2_observe<LOSS>(cam, X, uo[i], vo[i], sc, o);
+      const double w = o.w;
+      const double* l0 = o.Jl[0];
+      const double* l1 = o.Jl[1];
       const double z0 = cam[12] + (cam[16] * X[2] - cam[17] * X[1]);
       const double z1 = cam[13] + (cam[17] * X[0] - cam[15] * X[2]);
       const double z2 = cam[14] + (cam[15] * X[1] - cam[16] * X[0]);
@@ -574,17 +453,9 @@ __global__ void __launch_bounds__(256, 2) k_ba_update_f(ba_ptrs Pall, ba_params_
 #pragma unroll
     for (int i = 0; i < SPL; i++) {
       const int s = min(q + LPP * i, W - 1);
-      const double* cam = s_camt + 12 * s;
-      const bool have = uo[i] == uo[i];
-      const double p0 = fma(cam[0], Xt[0], fma(cam[1], Xt[1], fma(cam[2], Xt[2], cam[9])));
-      const double p1 = fma(cam[3], Xt[0], fma(cam[4], Xt[1], fma(cam[5], Xt[2], cam[10])));
-      const double p2 = fma(cam[6], Xt[0], fma(cam[7], Xt[1], fma(cam[8], Xt[2], cam[11])));
-      const double ip2 = have ? rcp_nr(p2) : 0.0;
-      const double r0 = p0 * ip2 - (have ? uo[i] : 0.0), r1 = p1 * ip2 - (have ? vo[i] : 0.0);
-      const double sq = r0 * r0 + r1 * r1;
-      double wt, rho;
-      ba_loss<LOSS>(sq, delta, d2, id2, wt, rho);
-      e0 += 0.5 * rho;
+      ba2_obs o;      // (only rho is used: the trial cost)
+      ba2_observe<LOSS>(s_camt + 12 * s, Xt, uo[i], vo[i], sc, o);
+      e0 += 0.5 * o.rho;
     }
     if (q == LEAD && inr) {
       tpts[3 * j] = Xt[0]; tpts[3 * j + 1] = Xt[1]; tpts[3 * j + 2] = Xt[2];

@@ -1,4 +1,5 @@
-// Bundle adjustment, windows of <= 10 slots: the WAVE-PRIVATE form of k_ba_build / k_ba_update (round 5).  Included by vo_ba.hip.
+// Bundle adjustment, windows of <= 10 slots: the WAVE-PRIVATE form of k_ba_build / k_ba_update (round 5).  Included by vo_ba.hip, and by
+// vo_ba_factored.hip for the phases of the wave walk that its kernels share with the ones here ("The phases of the wave walk" below).
 //
 // Replaces (same reference lines as vo_ba.hip: bundle_adjuster.py:18-65, :189-194) the lane-per-observation kernels for the shapes the
 // path is quoted on (BASELINE configs[2]: window 10; the reference's own window: 4).  What the old form paid for at a batch of 256
@@ -154,51 +155,244 @@ __device__ __forceinline__ double ba2_uniform(double v) {
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
-struct ba2_lin {
-  double e0, e1, w, rho;
-  double Jl[2][3];
-  double A[2][3];      // d(u, v) / d(camera-frame point) = the translation block of Jp
+// (K in SCALAR registers: as vector registers its nine values were 18 of the 256, eight of them spilled and reloaded twice per chunk)
+__device__ __forceinline__ void ba2_uniform_K(const double* __restrict__ K, double Kk[9]) {
+#pragma unroll
+  for (int k = 0; k < 9; k++) Kk[k] = ba2_uniform(K[k]);
+}
+
+// ================================================================================================
+// The phases of the wave walk.  The two BUILD kernels, k_ba_build_w (below) and k_ba_build_f (vo_ba_factored.hip), call the SAME functions
+// for the geometry, the chunk prefetch, the camera staging, the observation, the landmark factor, the Gram phase and the fold of the four
+// waves: their operation and summation orders agree because there is one text of them.  The two update kernels share the observation
+// (ba2_observe: their slot loops and their trial-cost loops) and nothing else: the heads of all four kernels and the rest of the updates keep
+// a text of their own in both forms (shared, their scalar and vector register counts moved off the pinned ones: EXPERIMENTS.md).
+// ================================================================================================
+
+// ---- the geometry of an instance ----
+// RT = 16-column blocks of the panel (RP = 16 RT >= 6 W + 1), SPL = window slots per lane (W <= LPP SPL), LPP = lanes per landmark
+template <int RT, int SPL, int LPP> struct ba2_geom {
+  static constexpr int LPC = ba2_map<LPP>::LPC;     // landmarks of a chunk
+  static constexpr int LEAD = ba2_map<LPP>::LEAD;   // the lane of a landmark's group that holds its sums
+  static constexpr int ROWS = 3 * LPC;              // panel rows of a chunk
+  static constexpr int RP = 16 * RT, PITCH = RP + (LPP != 5 ? 16 : 0);   // + 16: the four rows an MFMA operand fetch touches lie on disjoint banks (12 landmarks
+                                                                         // per wave: no room for it -- two workgroups of 4 x 36 x 64 doubles fill a CU's LDS)
+  static constexpr int NT = RT * (RT + 1) / 2;      // upper Gram tiles
+  static constexpr int REGION = ROWS * PITCH;       // doubles of LDS a wave owns
+  static constexpr int WMAX = (RP - 1) / 6 < LPP * SPL ? (RP - 1) / 6 : LPP * SPL;   // largest window this instance serves
+  static constexpr int CAMV = WMAX * BA_POSE_VALS;                  // room for the camera sums behind the tiles of a round
+  static constexpr int TPR = (REGION - CAMV) / 256 < NT ? (REGION - CAMV) / 256 : NT;   // tiles per round
+  static_assert(TPR >= 1, "a wave's LDS region holds at least one tile beside the camera sums");
 };
 
-// residual, weight, landmark block and translation block of one observation; an unobserved slot (uo = NaN) comes out as all zeros
-// (zero Jacobians, w = 1, rho = 0) without a branch: 1 / p_2 and the measurement are replaced, nothing else.  id2 = 1 / delta^2 (robust losses)
+// delta, delta^2 and 1 / delta^2 (robust losses only) of ba_loss
+struct ba2_scale { double delta, d2, id2; };
 template <int LOSS>
-__device__ __forceinline__ void ba2_linearize(const double* __restrict__ K, const double* __restrict__ cam, const double X[3],
-                                              double uo, double vo, double delta, double id2, ba2_lin& o) {
+__device__ __forceinline__ ba2_scale ba2_loss_scale(double delta) {
+  ba2_scale s;
+  s.delta = delta; s.d2 = delta * delta; s.id2 = LOSS == VO_LOSS_HUBER ? 0.0 : 1.0 / s.d2;
+  return s;
+}
+
+// ---- one observation ----
+// p = (K R) X + K t, 1 / p_2, (u, v), the residual e, weight and rho of the loss, the landmark block Jl = d(u, v)/dX.  An unobserved slot
+// (uo = NaN) comes out as all zeros (zero Jacobians, zero residual, w = 1, rho = 0) without a branch: 1 / p_2 and the measurement are
+// replaced, nothing else.  cam = K R (9), K t (3) of the slot's camera.
+struct ba2_obs {
+  double u, v, ip2, e0, e1, w, rho;
+  double Jl[2][3];
+};
+template <int LOSS>
+__device__ __forceinline__ void ba2_observe(const double* cam, const double X[3], double uo, double vo, const ba2_scale& sc, ba2_obs& o) {
   const bool have = uo == uo;
   const double p0 = fma(cam[0], X[0], fma(cam[1], X[1], fma(cam[2], X[2], cam[9])));
   const double p1 = fma(cam[3], X[0], fma(cam[4], X[1], fma(cam[5], X[2], cam[10])));
   const double p2 = fma(cam[6], X[0], fma(cam[7], X[1], fma(cam[8], X[2], cam[11])));
-  const double ip2 = have ? rcp_nr(p2) : 0.0;
-  const double u = p0 * ip2, v = p1 * ip2;
-  o.e0 = u - (have ? uo : 0.0); o.e1 = v - (have ? vo : 0.0);
-  const double s = o.e0 * o.e0 + o.e1 * o.e1;
-  ba_loss<LOSS>(s, delta, delta * delta, id2, o.w, o.rho);
+  o.ip2 = have ? rcp_nr(p2) : 0.0;
+  o.u = p0 * o.ip2; o.v = p1 * o.ip2;
+  o.e0 = o.u - (have ? uo : 0.0); o.e1 = o.v - (have ? vo : 0.0);
+  ba_loss<LOSS>(o.e0 * o.e0 + o.e1 * o.e1, sc.delta, sc.d2, sc.id2, o.w, o.rho);
 #pragma unroll
-  for (int c = 0; c < 3; c++) {
-    o.Jl[0][c] = (cam[c] - u * cam[6 + c]) * ip2;
-    o.Jl[1][c] = (cam[3 + c] - v * cam[6 + c]) * ip2;
-    o.A[0][c] = (K[c] - u * K[6 + c]) * ip2;
-    o.A[1][c] = (K[3 + c] - v * K[6 + c]) * ip2;
+  for (int c = 0; c < 3; c++) { o.Jl[0][c] = (cam[c] - o.u * cam[6 + c]) * o.ip2; o.Jl[1][c] = (cam[3 + c] - o.v * cam[6 + c]) * o.ip2; }
+}
+
+// ... and the translation block of Jp, A = d(u, v) / d(camera-frame point).  id2 = 1 / delta^2 (robust losses)
+struct ba2_lin : ba2_obs { double A[2][3]; };
+template <int LOSS>
+__device__ __forceinline__ void ba2_linearize(const double* __restrict__ K, const double* __restrict__ cam, const double X[3],
+                                              double uo, double vo, double delta, double id2, ba2_lin& o) {
+  ba2_observe<LOSS>(cam, X, uo, vo, ba2_scale{delta, delta * delta, id2}, o);
+#pragma unroll
+  for (int c = 0; c < 3; c++) { o.A[0][c] = (K[c] - o.u * K[6 + c]) * o.ip2; o.A[1][c] = (K[3 + c] - o.v * K[6 + c]) * o.ip2; }
+}
+
+// ---- chunk prefetch ----
+// this lane's landmark and observations of a chunk; the build requests the NEXT chunk's before the Gram phase of this one (a trip to HBM / L2
+// at the head of every chunk otherwise, with one other wave on the SIMD to cover it).  A chunk behind the table, a landmark behind N and an
+// idle lane read nothing: X = 0, unobserved; behind the live part of the table only the landmark is read.
+// A closure over the kernel's own variables (what a [&] lambda in the kernel would capture, written out so that both builds use one body;
+// as a function of values the compiler merged the guards into other exec-mask regions than the kernels had).  Not forced inline, like a lambda.
+// Every member is a reference bound by aggregate initialisation: a new member goes to the END, and both construction sites change with it.
+template <int SPL, int LPP> struct ba2_fetch {
+  const ba_ptrs& P; const double* const& pts; const ba2_map<LPP>& mp; const int& pl; const int& q; const int& W; const int& N; const int& nchunk; const int& nchunk_live;
+  double (&Xn)[3]; double (&uon)[SPL]; double (&von)[SPL];
+  __device__ void operator()(const int ch) const {
+    const int jn = ch * ba2_map<LPP>::LPC + pl;
+    Xn[0] = Xn[1] = Xn[2] = 0.0;
+    if (ch < nchunk && jn < N && !mp.idle) { Xn[0] = pts[3 * jn]; Xn[1] = pts[3 * jn + 1]; Xn[2] = pts[3 * jn + 2]; }
+#pragma unroll
+    for (int i = 0; i < SPL; i++) {
+      const int s = q + LPP * i;
+      uon[i] = __builtin_nan(""); von[i] = 0.0;
+      if (ch < nchunk_live && s < W && jn < N && !mp.idle) { const double2 ob = *reinterpret_cast<const double2*>(P.obs + ((size_t)s * N + jn) * 2); uon[i] = ob.x; von[i] = ob.y; }
+    }
   }
+};
+
+// ---- camera staging of the build ----
+// cameras: [R | t | Jr] from the poses (iteration 0) or as k_ba_solve left them, then K R, K t, Jr per camera into s_cam = dyn + 4 REGION;
+// iteration 0 also seeds cams[0] and the poses of xa (part 0); the padding columns of the four panels are zeroed
+template <class GEO>
+__device__ __forceinline__ void ba2_stage_build(const ba_ptrs& P, const ba_state& st, int it, int part, const double* poses, double* dyn) {
+  constexpr int ROWS = GEO::ROWS, RP = GEO::RP, PITCH = GEO::PITCH;
+  const int tid = threadIdx.x, W = P.W;
+  double* const s_cam = dyn + 4 * GEO::REGION;
+  if (tid < W) {
+    double c[BA_CAM];
+    if (it == 0) d_camera(poses + 6 * tid, c);
+    else {
+      const double* cg = P.cams + ((size_t)st.cur * W + tid) * BA_CAM;
+#pragma unroll
+      for (int k = 0; k < BA_CAM; k++) c[k] = cg[k];
+    }
+    ba2_stage_camera(P.K, c, s_cam + BA2_CAM * tid);
+    if (it == 0 && part == 0) {
+#pragma unroll
+      for (int k = 0; k < BA_CAM; k++) P.cams[(size_t)tid * BA_CAM + k] = c[k];   // cams[0] <-> x[0]
+    }
+  }
+  if (it == 0 && part == 0 && tid < 6 * W) P.xa[tid] = poses[tid];
+  // the padding columns behind 6 W + 1 start as zeros and are never written afterwards (every chunk rewrites the columns before them in
+  // every row: a lane without a landmark writes zeros)
+  const int npad = RP - (6 * W + 1);
+  for (int i = tid; i < 4 * ROWS * npad; i += 256) { const int r = i / npad; dyn[r * PITCH + 6 * W + 1 + (i - r * npad)] = 0.0; }
+  if constexpr (PITCH > RP) for (int i = tid; i < 4 * ROWS * (PITCH - RP); i += 256) { const int r = i / (PITCH - RP); dyn[r * PITCH + RP + (i - r * (PITCH - RP))] = 0.0; }
+}
+
+// ---- landmark factor ----
+// h = (h00, h10, h11, h20, h21, h22), g: the lane's sums over its slots of the landmark blocks w Jl^T Jl and w Jl^T e.  Summed over the
+// lanes of the landmark; damped 3x3 block: Cholesky C C^T, ci = Cinv = C^-1 (lower: i00, i10, i11, i20, i21, i22), y = Cinv g,
+// z = Cinv^T y = M g; the aux record of landmark j (what k_ba_update_* reads) and the gradient maximum from the landmark's leader lane;
+// ci comes back in every lane of the group (LPP = 5: from the leader); returns the gradient maximum gm brought up to date
+template <int LPP>
+__device__ __forceinline__ double ba2_factor_landmark(double (&h)[6], double (&g)[3], double lam, double* aux, int j, bool inr, bool leader, int lead4,
+                                                    unsigned long long* dbgb, int nwalk, double gm, double (&ci)[6], double (&y)[3]) {
+#pragma unroll
+  for (int k = 0; k < 6; k++) h[k] = ba2_group_sum<LPP>(h[k]);
+#pragma unroll
+  for (int k = 0; k < 3; k++) g[k] = ba2_group_sum<LPP>(g[k]);
+  const double h00 = h[0], h10 = h[1], h11 = h[2], h20 = h[3], h21 = h[4], h22 = h[5], g0 = g[0], g1 = g[1], g2 = g[2];
+  const double a00 = h00 + lam * fmax(h00, 1e-12), a11 = h11 + lam * fmax(h11, 1e-12), a22 = h22 + lam * fmax(h22, 1e-12);
+  double i00 = rsqrt_nr(a00);
+  const double c10 = h10 * i00, c20 = h20 * i00;
+  double i11 = rsqrt_nr(a11 - c10 * c10);
+  const double c21 = (h21 - c20 * c10) * i11;
+  double i22 = rsqrt_nr(a22 - c20 * c20 - c21 * c21);
+  double i10 = -c10 * i00 * i11;
+  double i21 = -c21 * i11 * i22;
+  double i20 = -(c20 * i00 + c21 * i10) * i22;
+  const double y0 = i00 * g0, y1 = i10 * g0 + i11 * g1, y2 = i20 * g0 + i21 * g1 + i22 * g2;
+  if (nwalk == 2) VO_STAMP(dbgb, 2);   // pass 1 + factor
+  if (leader && inr) {
+    double2* ax = reinterpret_cast<double2*>(aux + (size_t)j * BA_AUX);
+    ax[0] = make_double2(h00, h10); ax[1] = make_double2(h11, h20); ax[2] = make_double2(h21, h22);
+    ax[3] = make_double2(g0, g1); ax[4] = make_double2(g2, i00); ax[5] = make_double2(i10, i11);
+    ax[6] = make_double2(i20, i21); ax[7] = make_double2(i22, i00 * y0 + i10 * y1 + i20 * y2);
+    ax[8] = make_double2(i11 * y1 + i21 * y2, i22 * y2);
+  }
+  if (inr && (LPP != 5 || leader)) gm = fmax(gm, fmax(fabs(g0), fmax(fabs(g1), fabs(g2))));
+  if (LPP == 5) {      // the factor of the landmark to every lane of its group
+    i00 = ba2_from_leader<LPP>(i00, lead4); i10 = ba2_from_leader<LPP>(i10, lead4); i11 = ba2_from_leader<LPP>(i11, lead4);
+    i20 = ba2_from_leader<LPP>(i20, lead4); i21 = ba2_from_leader<LPP>(i21, lead4); i22 = ba2_from_leader<LPP>(i22, lead4);
+  }
+  ci[0] = i00; ci[1] = i10; ci[2] = i11; ci[3] = i20; ci[4] = i21; ci[5] = i22;
+  y[0] = y0; y[1] = y1; y[2] = y2;
+  return gm;
+}
+
+// ---- Gram phase ----
+// Gram matrix of the chunk's panel into the accumulators: one operand fetch per column block and k-step feeds every tile that uses it
+//   A[i][k] = panel[k0 + k][16 ta + i]  (lane: i = l & 15, k = l >> 4),  B[k][j] = panel[k0 + k][16 tb + j]
+//   D layout: col = lane & 15, row = (lane >> 4) + 4 * reg
+template <class GEO, int RT>
+__device__ __forceinline__ void ba2_gram(const double* pan, int lane, d4 (&acc)[GEO::NT]) {
+  const double* base = pan + (lane >> 4) * GEO::PITCH + (lane & 15);
+#pragma unroll
+  for (int k0 = 0; k0 < GEO::ROWS; k0 += 4) {
+    double op[RT];
+#pragma unroll
+    for (int c = 0; c < RT; c++) op[c] = base[k0 * GEO::PITCH + 16 * c];
+    int t = 0;
+#pragma unroll
+    for (int ta = 0; ta < RT; ta++)
+#pragma unroll
+      for (int tb = ta; tb < RT; tb++, t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(op[ta], op[tb], acc[t], 0, 0, 0);
+  }
+}
+
+// ---- after the walk ----
+// the landmark bits of the camera sums the chunk stages left, the wave's gradient maximum, and the camera sums into the wave's LDS region
+// behind the tiles of a round
+template <class GEO, int SPL, int LPP>
+__device__ __forceinline__ void ba2_finish_walk(double (&camacc)[7 * SPL], double gm, const ba2_map<LPP>& mp, int W, int lane, double* pan, double* s_gmax_wave) {
+#pragma unroll
+  for (int t = 0; t < 7 * SPL; t++) camacc[t] = ba2_finish_landmark_sum<LPP>(camacc[t]);
+  for (int ofs = 32; ofs > 0; ofs >>= 1) gm = fmax(gm, __shfl_xor(gm, ofs));
+  if (lane == 0) *s_gmax_wave = gm;
+  double* const camsum = pan + GEO::TPR * 256;
+  // writer lanes: the remaining landmark bits clear (every lane of a (b5, b4, q) class holds the same total)
+  const int b5 = lane >> 5, b4 = (lane >> 4) & 1;
+  const bool wr = (LPP == 8) ? ((lane & 8) == 0) : (LPP == 4) ? ((lane & 12) == 0) : ((lane & 15) < 5);
+  if (wr) {
+#pragma unroll
+    for (int i = 0; i < SPL; i++) {
+      const int s = mp.q + LPP * i;
+      if (s < W) {
+#pragma unroll
+        for (int n = 0; n < 7; n++) camsum[s * BA_POSE_VALS + 4 * n + 2 * b4 + b5] = camacc[7 * i + n];
+      }
+    }
+  }
+}
+// one round of the fold of the four waves' tiles: tiles t0 .. t0 + TPR - 1 of this wave into its LDS region, between two workgroup barriers
+template <class GEO>
+__device__ __forceinline__ void ba2_tiles_to_lds(const d4 (&acc)[GEO::NT], double* pan, int lane, int t0) {
+  if (t0 > 0) __syncthreads();                            // the previous round has been read
+#pragma unroll
+  for (int t = t0; t < GEO::NT && t < t0 + GEO::TPR; t++) {
+    double2* o2 = reinterpret_cast<double2*>(pan + (t - t0) * 256 + lane * 4);
+    o2[0] = make_double2(acc[t][0], acc[t][1]);
+    o2[1] = make_double2(acc[t][2], acc[t][3]);
+  }
+  __syncthreads();
+}
+// element e of the four waves' regions added in the fixed order of every partial set
+template <class GEO>
+__device__ __forceinline__ double ba2_fold4(const double* dyn, int e) {
+  return (dyn[e] + dyn[GEO::REGION + e]) + (dyn[2 * GEO::REGION + e] + dyn[3 * GEO::REGION + e]);
 }
 
 // ------------------------------------------------------------------------------------------------
 // k_ba_build_w
 // ------------------------------------------------------------------------------------------------
-// RT = 16-column blocks of the panel (RP = 16 RT >= 6 W + 1), SPL = window slots per lane (W <= LPP SPL), LPP = lanes per landmark,
-// LOSS = VO_LOSS_* (ba_loss: the weight of an observation; everything else is the same for every loss).  The robust losses leave the cost
-// value of the camera sums at 0: k_ba_cost_r adds it after this kernel (their log1p / atan in the slot loop spilled the accumulators).
+// RT, SPL, LPP: ba2_geom; LOSS = VO_LOSS_* (ba_loss: the weight of an observation; everything else is the same for every loss).  The robust
+// losses leave the cost value of the camera sums at 0: k_ba_cost_r adds it after this kernel (their log1p / atan in the slot loop spilled
+// the accumulators).
 // grid (G0 * batch), 256 lanes; partial set = the part of the problem a workgroup serves (ba2_select_work)
 template <int RT, int SPL, int LPP, int LOSS>
 __global__ void __launch_bounds__(256, 2) k_ba_build_w(ba_ptrs Pall, ba_params_dev prm, int it, double probe_lambda, int G0, int Gcap) {
-  constexpr int LPC = ba2_map<LPP>::LPC;     // landmarks of a chunk
-  constexpr int LEAD = ba2_map<LPP>::LEAD;   // the lane of a landmark's group that holds its sums
-  constexpr int ROWS = 3 * LPC;              // panel rows of a chunk
-  constexpr int RP = 16 * RT, PITCH = RP + (LPP != 5 ? 16 : 0);   // + 16: the four rows an MFMA operand fetch touches lie on disjoint banks (12 landmarks
-                                                                  // per wave: no room for it -- two workgroups of 4 x 36 x 64 doubles fill a CU's LDS)
-  constexpr int NT = RT * (RT + 1) / 2;
-  constexpr int REGION = ROWS * PITCH;       // doubles of LDS a wave owns
+  using GEO = ba2_geom<RT, SPL, LPP>;
+  constexpr int LPC = GEO::LPC, LEAD = GEO::LEAD, PITCH = GEO::PITCH, NT = GEO::NT, REGION = GEO::REGION, TPR = GEO::TPR;
   ba2_work wk = ba2_select_work<true>(Pall, it, G0, Gcap);
   wk.prob = ba2_uniform(wk.prob); wk.part = ba2_uniform(wk.part); wk.G = ba2_uniform(wk.G);
   if (wk.prob < 0) return;                   // (uniform) more workgroups than the running problems can use
@@ -212,7 +406,7 @@ __global__ void __launch_bounds__(256, 2) k_ba_build_w(ba_ptrs Pall, ba_params_d
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   // what the decision reads -- the previous state, k_ba_solve's record, the live-slot count -- is requested BEFORE the step statistics are
   // summed: one trip to memory instead of three dependent ones at the head of every workgroup
-  const int n_live_ld = ba2_uniform(Pall.n_live ? *P.n_live : P.N);
+  const int n_live = ba2_uniform(Pall.n_live ? *P.n_live : P.N);
   ba_state prev;
   ba_info inf;
   if (it > 0) {
@@ -236,12 +430,10 @@ __global__ void __launch_bounds__(256, 2) k_ba_build_w(ba_ptrs Pall, ba_params_d
   const int W = P.W, N = P.N;
   const double* poses = (it == 0) ? P.x0 : ba_x(P, st.cur);
   const double* pts = poses + 6 * W;
-  // (the first chunk's landmark and observations are requested before the cameras are staged: two trips to memory overlap)
   const ba2_map<LPP> mp(lane);
   const int pl = mp.pl, q = mp.q;
   const int lead4 = 4 * (lane - q + LEAD);        // (LPP = 5) ds_bpermute source: the leader of this lane's group
   const int nchunk = (N + LPC - 1) / LPC;
-  const int n_live = n_live_ld;
   const int nchunk_live = min(nchunk, (n_live + LPC - 1) / LPC);
   const bool seed_x = it == 0;
   double* const pan = dyn + wave * REGION;
@@ -252,49 +444,15 @@ __global__ void __launch_bounds__(256, 2) k_ba_build_w(ba_ptrs Pall, ba_params_d
 #pragma unroll
   for (int t = 0; t < 7 * SPL; t++) camacc[t] = 0.0;
   double gm = 0.0;
-  const double lam = st.lambda, delta = prm.delta;
-  const double id2 = LOSS == VO_LOSS_HUBER ? 0.0 : 1.0 / (delta * delta);
-  // (K in SCALAR registers: as vector registers its nine values were 18 of the 256, eight of them spilled and reloaded twice per chunk)
-  const double Kk[9] = {ba2_uniform(P.K[0]), ba2_uniform(P.K[1]), ba2_uniform(P.K[2]), ba2_uniform(P.K[3]), ba2_uniform(P.K[4]), ba2_uniform(P.K[5]),
-                        ba2_uniform(P.K[6]), ba2_uniform(P.K[7]), ba2_uniform(P.K[8])};
-  // this lane's landmark and observations of a chunk; the NEXT chunk's are requested before the Gram phase of this one (a trip to HBM / L2
-  // at the head of every chunk otherwise, with one other wave on the SIMD to cover it)
+  const double lam = st.lambda;
+  const ba2_scale sc = ba2_loss_scale<LOSS>(prm.delta);
+  double Kk[9];
+  ba2_uniform_K(P.K, Kk);
+  // (the first chunk's landmark and observations are requested before the cameras are staged: two trips to memory overlap)
   double Xn[3], uon[SPL], von[SPL];
-  auto fetch = [&](const int ch) {
-    const int jn = ch * LPC + pl;
-    Xn[0] = Xn[1] = Xn[2] = 0.0;
-    if (ch < nchunk && jn < N && !mp.idle) { Xn[0] = pts[3 * jn]; Xn[1] = pts[3 * jn + 1]; Xn[2] = pts[3 * jn + 2]; }
-#pragma unroll
-    for (int i = 0; i < SPL; i++) {
-      const int s = q + LPP * i;
-      uon[i] = __builtin_nan(""); von[i] = 0.0;
-      if (ch < nchunk_live && s < W && jn < N && !mp.idle) { const double2 ob = *reinterpret_cast<const double2*>(P.obs + ((size_t)s * N + jn) * 2); uon[i] = ob.x; von[i] = ob.y; }
-    }
-  };
+  const ba2_fetch<SPL, LPP> fetch{P, pts, mp, pl, q, W, N, nchunk, nchunk_live, Xn, uon, von};     // (references, in the order of ba2_fetch's members)
   fetch(part * 4 + wave);
-  // cameras: [R | t | Jr] from the poses (iteration 0) or as k_ba_solve left them, then K R, K t per camera
-  if (tid < W) {
-    double c[BA_CAM];
-    if (it == 0) d_camera(poses + 6 * tid, c);
-    else {
-      const double* cg = P.cams + ((size_t)st.cur * W + tid) * BA_CAM;
-#pragma unroll
-      for (int k = 0; k < BA_CAM; k++) c[k] = cg[k];
-    }
-    ba2_stage_camera(P.K, c, s_cam + BA2_CAM * tid);
-    if (it == 0 && part == 0) {
-#pragma unroll
-      for (int k = 0; k < BA_CAM; k++) P.cams[(size_t)tid * BA_CAM + k] = c[k];   // cams[0] <-> x[0]
-    }
-  }
-  if (it == 0 && part == 0 && tid < 6 * W) P.xa[tid] = poses[tid];
-  // the padding columns behind 6 W + 1 start as zeros and are never written afterwards (every chunk rewrites the columns before them in
-  // every row: a lane without a landmark writes zeros)
-  {
-    const int npad = RP - (6 * W + 1);
-    for (int i = tid; i < 4 * ROWS * npad; i += 256) { const int r = i / npad; dyn[r * PITCH + 6 * W + 1 + (i - r * npad)] = 0.0; }
-    if (PITCH > RP) for (int i = tid; i < 4 * ROWS * (PITCH - RP); i += 256) { const int r = i / (PITCH - RP); dyn[r * PITCH + RP + (i - r * (PITCH - RP))] = 0.0; }
-  }
+  ba2_stage_build<GEO>(P, st, it, part, poses, dyn);
   __syncthreads();
   int nwalk = 0;
 #pragma unroll 1
@@ -312,67 +470,32 @@ __global__ void __launch_bounds__(256, 2) k_ba_build_w(ba_ptrs Pall, ba_params_d
     //      kept per slot as 7 values (u, v, 1 / p_2, w, e, rho): the Jacobian blocks of ALL slots of a lane (36 values each) do not fit the
     //      256 registers beside the 80 accumulators, and d(u, v)/dX is 12 operations to form again ----
     double ku[SPL], kv[SPL], kip[SPL], kw[SPL], ke0[SPL], ke1[SPL], krho[SPL];
-    double h00 = 0, h10 = 0, h11 = 0, h20 = 0, h21 = 0, h22 = 0, g0 = 0, g1 = 0, g2 = 0;
+    double h[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
 #pragma unroll
     for (int i = 0; i < SPL; i++) {
       const int s = min(q + LPP * i, W - 1);      // (a lane without an i-th slot computes zeros on a valid camera)
-      const double* cam = s_cam + BA2_CAM * s;
-      const bool have = uo[i] == uo[i];
-      const double p0 = fma(cam[0], X[0], fma(cam[1], X[1], fma(cam[2], X[2], cam[9])));
-      const double p1 = fma(cam[3], X[0], fma(cam[4], X[1], fma(cam[5], X[2], cam[10])));
-      const double p2 = fma(cam[6], X[0], fma(cam[7], X[1], fma(cam[8], X[2], cam[11])));
-      const double ip2 = have ? rcp_nr(p2) : 0.0;             // an unobserved slot: zero Jacobians, zero residual (w = 1, rho = 0)
-      const double u = p0 * ip2, v = p1 * ip2;
-      const double e0 = u - (have ? uo[i] : 0.0), e1 = v - (have ? vo[i] : 0.0);
-      const double sq = e0 * e0 + e1 * e1;
-      const double d2 = delta * delta;
-      double w, rho;
-      ba_loss<LOSS>(sq, delta, d2, id2, w, rho);     // (robust losses: rho is not used here, k_ba_cost_r sums the cost)
-      ku[i] = u; kv[i] = v; kip[i] = ip2; kw[i] = w;
-      ke0[i] = e0; ke1[i] = e1;
-      krho[i] = rho;
-      double l0[3], l1[3];
-#pragma unroll
-      for (int c = 0; c < 3; c++) { l0[c] = (cam[c] - u * cam[6 + c]) * ip2; l1[c] = (cam[3 + c] - v * cam[6 + c]) * ip2; }
-      const double wl0[3] = {w * l0[0], w * l0[1], w * l0[2]};
-      const double wl1[3] = {w * l1[0], w * l1[1], w * l1[2]};
-      h00 += wl0[0] * l0[0] + wl1[0] * l1[0];
-      h10 += wl0[1] * l0[0] + wl1[1] * l1[0];
-      h11 += wl0[1] * l0[1] + wl1[1] * l1[1];
-      h20 += wl0[2] * l0[0] + wl1[2] * l1[0];
-      h21 += wl0[2] * l0[1] + wl1[2] * l1[1];
-      h22 += wl0[2] * l0[2] + wl1[2] * l1[2];
-      g0 += wl0[0] * e0 + wl1[0] * e1;
-      g1 += wl0[1] * e0 + wl1[1] * e1;
-      g2 += wl0[2] * e0 + wl1[2] * e1;
+      ba2_obs o;
+      ba2_observe<LOSS>(s_cam + BA2_CAM * s, X, uo[i], vo[i], sc, o);     // (robust losses: rho is not used here, k_ba_cost_r sums the cost)
+      ku[i] = o.u; kv[i] = o.v; kip[i] = o.ip2; kw[i] = o.w;
+      ke0[i] = o.e0; ke1[i] = o.e1;
+      krho[i] = o.rho;
+      const double* l0 = o.Jl[0];
+      const double* l1 = o.Jl[1];
+      const double wl0[3] = {o.w * l0[0], o.w * l0[1], o.w * l0[2]};
+      const double wl1[3] = {o.w * l1[0], o.w * l1[1], o.w * l1[2]};
+      h[0] += wl0[0] * l0[0] + wl1[0] * l1[0];
+      h[1] += wl0[1] * l0[0] + wl1[1] * l1[0];
+      h[2] += wl0[1] * l0[1] + wl1[1] * l1[1];
+      h[3] += wl0[2] * l0[0] + wl1[2] * l1[0];
+      h[4] += wl0[2] * l0[1] + wl1[2] * l1[1];
+      h[5] += wl0[2] * l0[2] + wl1[2] * l1[2];
+      g[0] += wl0[0] * o.e0 + wl1[0] * o.e1;
+      g[1] += wl0[1] * o.e0 + wl1[1] * o.e1;
+      g[2] += wl0[2] * o.e0 + wl1[2] * o.e1;
     }
-    h00 = ba2_group_sum<LPP>(h00); h10 = ba2_group_sum<LPP>(h10); h11 = ba2_group_sum<LPP>(h11);
-    h20 = ba2_group_sum<LPP>(h20); h21 = ba2_group_sum<LPP>(h21); h22 = ba2_group_sum<LPP>(h22);
-    g0 = ba2_group_sum<LPP>(g0); g1 = ba2_group_sum<LPP>(g1); g2 = ba2_group_sum<LPP>(g2);
-    // ---- damped 3x3 block: Cholesky C C^T, Cinv = C^-1 (lower), y = Cinv g, z = Cinv^T y = M g ----
-    const double a00 = h00 + lam * fmax(h00, 1e-12), a11 = h11 + lam * fmax(h11, 1e-12), a22 = h22 + lam * fmax(h22, 1e-12);
-    double i00 = rsqrt_nr(a00);
-    const double c10 = h10 * i00, c20 = h20 * i00;
-    double i11 = rsqrt_nr(a11 - c10 * c10);
-    const double c21 = (h21 - c20 * c10) * i11;
-    double i22 = rsqrt_nr(a22 - c20 * c20 - c21 * c21);
-    double i10 = -c10 * i00 * i11;
-    double i21 = -c21 * i11 * i22;
-    double i20 = -(c20 * i00 + c21 * i10) * i22;
-    const double y0 = i00 * g0, y1 = i10 * g0 + i11 * g1, y2 = i20 * g0 + i21 * g1 + i22 * g2;
-    if (nwalk == 2) VO_STAMP(dbgb, 2);   // pass 1 + factor
-    if (q == LEAD && inr) {
-      double2* ax = reinterpret_cast<double2*>(P.aux + (size_t)j * BA_AUX);
-      ax[0] = make_double2(h00, h10); ax[1] = make_double2(h11, h20); ax[2] = make_double2(h21, h22);
-      ax[3] = make_double2(g0, g1); ax[4] = make_double2(g2, i00); ax[5] = make_double2(i10, i11);
-      ax[6] = make_double2(i20, i21); ax[7] = make_double2(i22, i00 * y0 + i10 * y1 + i20 * y2);
-      ax[8] = make_double2(i11 * y1 + i21 * y2, i22 * y2);
-    }
-    if (inr && (LPP != 5 || q == LEAD)) gm = fmax(gm, fmax(fabs(g0), fmax(fabs(g1), fabs(g2))));
-    if (LPP == 5) {      // the factor of the landmark to every lane of its group
-      i00 = ba2_from_leader<LPP>(i00, lead4); i10 = ba2_from_leader<LPP>(i10, lead4); i11 = ba2_from_leader<LPP>(i11, lead4);
-      i20 = ba2_from_leader<LPP>(i20, lead4); i21 = ba2_from_leader<LPP>(i21, lead4); i22 = ba2_from_leader<LPP>(i22, lead4);
-    }
+    double ci[6], y[3];
+    gm = ba2_factor_landmark<LPP>(h, g, lam, P.aux, j, inr, q == LEAD, lead4, dbgb, nwalk, gm, ci, y);
+    const double i00 = ci[0], i10 = ci[1], i11 = ci[2], i20 = ci[3], i21 = ci[4], i22 = ci[5];
     // ---- pass 2, slot by slot: the camera block Jp = [(X x Jl_k)^T Jr | A], the slot's camera sums, the landmark's panel rows
     //      Y[a][c] = sum_k Jp[k][a] (w Z[k][c]),  Z = Jl Cinv^T;  column 6 W = y ----
     double* const rw0 = pan + (3 * pl) * PITCH;
@@ -411,8 +534,8 @@ __global__ void __launch_bounds__(256, 2) k_ba_build_w(ba_ptrs Pall, ba_params_d
 #pragma unroll
       for (int n = 0; n < 7; n++) {
         camacc[7 * i + n] += rs16_sum(rs32_sum(term(4 * n), term(4 * n + 1)), rs32_sum(term(4 * n + 2), term(4 * n + 3)));
-        // the sum is taken HERE: left to itself the compiler carries the 14 reduce-scatter results through the Gram phase to the loop's latch and
-        // spills half of the accumulators to make room for them (7 x 8 bytes of scratch stored and reloaded per chunk)
+        // the sum is taken HERE (in both forms of the build): left to itself the compiler carries the 14 reduce-scatter results through the Gram
+        // phase to the loop's latch and spills half of the accumulators to make room for them (7 x 8 bytes of scratch stored and reloaded per chunk)
         asm volatile("" : "+v"(camacc[7 * i + n]));
       }
       if (sr < W && !mp.idle) {
@@ -432,76 +555,26 @@ __global__ void __launch_bounds__(256, 2) k_ba_build_w(ba_ptrs Pall, ba_params_d
         }
       }
     }
-    if (q == LEAD && !mp.idle) { rw0[6 * W] = inr ? y0 : 0.0; rw1[6 * W] = inr ? y1 : 0.0; rw2[6 * W] = inr ? y2 : 0.0; }
-    // ---- Gram matrix of the chunk's panel into the accumulators: one operand fetch per column block and k-step ----
-    //   A[i][k] = panel[k0 + k][16 ta + i]  (lane: i = l & 15, k = l >> 4),  B[k][j] = panel[k0 + k][16 tb + j]
-    //   D layout: col = lane & 15, row = (lane >> 4) + 4 * reg
+    if (q == LEAD && !mp.idle) { rw0[6 * W] = inr ? y[0] : 0.0; rw1[6 * W] = inr ? y[1] : 0.0; rw2[6 * W] = inr ? y[2] : 0.0; }
     __builtin_amdgcn_wave_barrier();
     if (nwalk == 2) VO_STAMP(dbgb, 3);   // first chunk: pass 2, panel written
     fetch(chunk + 4 * G);
-    {
-      const double* base = pan + (lane >> 4) * PITCH + (lane & 15);
-#pragma unroll
-      for (int k0 = 0; k0 < ROWS; k0 += 4) {
-        double op[RT];
-#pragma unroll
-        for (int c = 0; c < RT; c++) op[c] = base[k0 * PITCH + 16 * c];
-        int t = 0;
-#pragma unroll
-        for (int ta = 0; ta < RT; ta++)
-#pragma unroll
-          for (int tb = ta; tb < RT; tb++, t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(op[ta], op[tb], acc[t], 0, 0, 0);
-      }
-    }
+    ba2_gram<GEO, RT>(pan, lane, acc);
     __builtin_amdgcn_wave_barrier();
     if (nwalk == 2) VO_STAMP(dbgb, 4);
     nwalk++;   // first chunk: Gram
   }
   VO_STAMP(dbgb, 5);   // walk
   // ---- after the walk: the landmark bits the chunk stages left, then the four waves' sums through LDS in wave order ----
-#pragma unroll
-  for (int t = 0; t < 7 * SPL; t++) camacc[t] = ba2_finish_landmark_sum<LPP>(camacc[t]);
-  for (int ofs = 32; ofs > 0; ofs >>= 1) gm = fmax(gm, __shfl_xor(gm, ofs));
-  if (lane == 0) s_gmax[wave] = gm;
-  constexpr int WMAX = (RP - 1) / 6 < LPP * SPL ? (RP - 1) / 6 : LPP * SPL;   // largest window this instance serves
-  constexpr int CAMV = WMAX * BA_POSE_VALS;                  // room for the camera sums behind the tiles of a round
-  constexpr int TPR = (REGION - CAMV) / 256 < NT ? (REGION - CAMV) / 256 : NT;   // tiles per round
-  static_assert(TPR >= 1, "a wave's LDS region holds at least one tile beside the camera sums");
-  double* const camsum = pan + TPR * 256;
-  {
-    // writer lanes: the remaining landmark bits clear (every lane of a (b5, b4, q) class holds the same total)
-    const int b5 = lane >> 5, b4 = (lane >> 4) & 1;
-    const bool wr = (LPP == 8) ? ((lane & 8) == 0) : (LPP == 4) ? ((lane & 12) == 0) : ((lane & 15) < 5);
-    if (wr) {
-#pragma unroll
-      for (int i = 0; i < SPL; i++) {
-        const int s = q + LPP * i;
-        if (s < W) {
-#pragma unroll
-          for (int n = 0; n < 7; n++) camsum[s * BA_POSE_VALS + 4 * n + 2 * b4 + b5] = camacc[7 * i + n];
-        }
-      }
-    }
-  }
+  ba2_finish_walk<GEO, SPL, LPP>(camacc, gm, mp, W, lane, pan, s_gmax + wave);
 #pragma unroll
   for (int t0 = 0; t0 < NT; t0 += TPR) {
-    if (t0 > 0) __syncthreads();                            // the previous round has been read
-#pragma unroll
-    for (int t = t0; t < NT && t < t0 + TPR; t++) {
-      double2* o2 = reinterpret_cast<double2*>(pan + (t - t0) * 256 + lane * 4);
-      o2[0] = make_double2(acc[t][0], acc[t][1]);
-      o2[1] = make_double2(acc[t][2], acc[t][3]);
-    }
-    __syncthreads();
+    ba2_tiles_to_lds<GEO>(acc, pan, lane, t0);
     const int nel = (NT - t0 < TPR ? NT - t0 : TPR) * 256;
     double* out = P.tiles + ((size_t)part * NT + t0) * 256;
-    for (int e = tid; e < nel; e += 256)
-      out[e] = (dyn[e] + dyn[REGION + e]) + (dyn[2 * REGION + e] + dyn[3 * REGION + e]);
+    for (int e = tid; e < nel; e += 256) out[e] = ba2_fold4<GEO>(dyn, e);
     if (t0 == 0) {
-      for (int t = tid; t < W * BA_POSE_VALS; t += 256) {
-        const int o = TPR * 256 + t;
-        P.posepart[(size_t)part * W * BA_POSE_VALS + t] = (dyn[o] + dyn[REGION + o]) + (dyn[2 * REGION + o] + dyn[3 * REGION + o]);
-      }
+      for (int t = tid; t < W * BA_POSE_VALS; t += 256) P.posepart[(size_t)part * W * BA_POSE_VALS + t] = ba2_fold4<GEO>(dyn, TPR * 256 + t);
       if (tid == 0) P.gmax[part] = fmax(fmax(s_gmax[0], s_gmax[1]), fmax(s_gmax[2], s_gmax[3]));
     }
   }
@@ -559,8 +632,9 @@ __global__ void __launch_bounds__(256, 2) k_ba_update_w(ba_ptrs Pall, ba_params_
   const int nchunk_live = min(nchunk, (n_live + LPC - 1) / LPC);
   const double lam = st.lambda, delta = prm.delta, d2 = delta * delta;
   const double id2 = LOSS == VO_LOSS_HUBER ? 0.0 : 1.0 / d2;
-  const double Kk[9] = {ba2_uniform(P.K[0]), ba2_uniform(P.K[1]), ba2_uniform(P.K[2]), ba2_uniform(P.K[3]), ba2_uniform(P.K[4]), ba2_uniform(P.K[5]),
-                        ba2_uniform(P.K[6]), ba2_uniform(P.K[7]), ba2_uniform(P.K[8])};
+  const ba2_scale sc{delta, d2, id2};
+  double Kk[9];
+  ba2_uniform_K(P.K, Kk);
   double e0 = 0, e1 = 0, e2 = 0, e3 = 0;
 #pragma unroll 1
   for (int chunk = part * 4 + wave; chunk < nchunk_live; chunk += 4 * G) {
@@ -613,17 +687,9 @@ __global__ void __launch_bounds__(256, 2) k_ba_update_w(ba_ptrs Pall, ba_params_
 #pragma unroll
     for (int i = 0; i < SPL; i++) {
       const int s = min(q + LPP * i, W - 1);
-      const double* cam = s_camt + 12 * s;
-      const bool have = uo[i] == uo[i];
-      const double p0 = fma(cam[0], Xt[0], fma(cam[1], Xt[1], fma(cam[2], Xt[2], cam[9])));
-      const double p1 = fma(cam[3], Xt[0], fma(cam[4], Xt[1], fma(cam[5], Xt[2], cam[10])));
-      const double p2 = fma(cam[6], Xt[0], fma(cam[7], Xt[1], fma(cam[8], Xt[2], cam[11])));
-      const double ip2 = have ? rcp_nr(p2) : 0.0;
-      const double r0 = p0 * ip2 - (have ? uo[i] : 0.0), r1 = p1 * ip2 - (have ? vo[i] : 0.0);
-      const double sq = r0 * r0 + r1 * r1;
-      double wt, rho;
-      ba_loss<LOSS>(sq, delta, d2, id2, wt, rho);
-      e0 += 0.5 * rho;
+      ba2_obs o;      // (only rho is used: the trial cost)
+      ba2_observe<LOSS>(s_camt + 12 * s, Xt, uo[i], vo[i], sc, o);
+      e0 += 0.5 * o.rho;
     }
     if (q == LEAD && inr) {
       tpts[3 * j] = Xt[0]; tpts[3 * j + 1] = Xt[1]; tpts[3 * j + 2] = Xt[2];
