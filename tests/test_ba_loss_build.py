@@ -111,7 +111,7 @@ def test_model_huber_is_the_oracle_bit_for_bit(golden_dir):
     import ba_oracle as bo
     from helpers import golden_ba_problem, ref_stub_cv2
     cv2 = ref_stub_cv2()
-    paths = sorted(glob.glob(os.path.join(golden_dir, "ba_*.npz")))
+    paths = sorted(glob.glob(os.path.join(golden_dir, "ba_s[0-9]*.npz")))      # the reference's vectors ba_s<seed>_n<N>_w<W> (not the model's ba_so3_<case>)
     assert paths
     for path in paths:
         K, poses, points, obs, _ = golden_ba_problem(np.load(path), lambda R: cv2.Rodrigues(R)[0])

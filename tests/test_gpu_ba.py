@@ -36,7 +36,7 @@ def ctx():
 
 
 def _goldens(golden_dir):
-    return sorted(glob.glob(golden_dir + "/ba_*.npz"))
+    return sorted(glob.glob(golden_dir + "/ba_s[0-9]*.npz"))      # the reference's vectors ba_s<seed>_n<N>_w<W> (not the model's ba_so3_<case>: tests/test_gpu_ba_so3.py)
 
 
 def test_ba_residual_matches_reference(ctx, golden_dir):

@@ -14,8 +14,15 @@ pytestmark = pytest.mark.gpu
 W_IMG, H_IMG = 256, 160
 
 
-def _random_state(rng, cap, t_step, n_l, n_c, n_d, share=0.3, long_hist=False):
-    """State + dead lists with object sharing like the reference produces (and a little worse)"""
+def _z_turn_pose(t):
+    H = np.eye(4)
+    ang = 0.01 * t
+    H[:2, :2] = [[np.cos(ang), -np.sin(ang)], [np.sin(ang), np.cos(ang)]]; H[:3, 3] = [0.1 * t, 0.02 * t, -0.05 * t]
+    return H
+
+
+def _random_state(rng, cap, t_step, n_l, n_c, n_d, share=0.3, long_hist=False, pose_fn=_z_turn_pose):
+    """State + dead lists with object sharing like the reference produces (and a little worse); pose_fn(t) -> H 4 x 4 of trajectory entry t"""
     from vo_mi355x import Keypoint, Landmark, State, Trajectory
 
     def kp(t_first=None, border=False):
@@ -49,10 +56,7 @@ def _random_state(rng, cap, t_step, n_l, n_c, n_d, share=0.3, long_hist=False):
             k = kp(); dead.append(lm(k)); dead_kp.append(k)
     traj = Trajectory({})
     for t in range(t_step + 1):
-        H = np.eye(4)
-        ang = 0.01 * t
-        H[:2, :2] = [[np.cos(ang), -np.sin(ang)], [np.sin(ang), np.cos(ang)]]; H[:3, 3] = [0.1 * t, 0.02 * t, -0.05 * t]
-        traj.append(t, H)
+        traj.append(t, pose_fn(t))
     return State(lms, kps, cands, traj), dead, dead_kp
 
 
@@ -129,3 +133,99 @@ def test_random_states_stage_by_stage(cap):
                 _same(model, rp, what)
             assert rec["overflow"] == model.info.get("overflow", 0), (what, rec["overflow"], model.info)
     ca.close(); cb.close()
+
+
+# ---- the closed loop's own log and exp (pipe_log_so3 / pipe_rodrigues, csrc/vo_pipeline.hip) at their edges -------------------------------
+def _edge_pose(t):
+    """trajectory entry t: the rotation exp(r_t), r_t = so3_model.PIPE_ANGLES[t % 7] about an axis of its own with every component >= 0.3 in
+    magnitude (the host's SVD projection cannot flip one of the sign tests of the near-pi branch).  so3.rodrigues_vec_to_mat is within
+    so3_model.SO3_EXP_DEV of the 60-digit exp entry by entry (tests/test_so3_model.py)"""
+    import so3_model as sm
+    from vo_mi355x import so3
+    k = t % len(sm.PIPE_ANGLES)
+    H = np.eye(4)
+    H[:3, :3] = so3.rodrigues_vec_to_mat(sm.PIPE_ANGLES[k] * sm.AXES[k])
+    H[:3, 3] = np.array([0.1 * t, 0.02 * t, 12.0 - 0.05 * t]) - H[:3, :3] @ [0.0, 0.0, 12.0]      # the landmark cloud N((0, 0, 12), 3^2) stays in front
+    return H
+
+
+def _reproject_histories(rng, K, state, dead, dead_kp, t_step, pose_fn):
+    """every history entry of every (landmark, keypoint) pair becomes the landmark's projection by the pose of its frame + 0.5 px (float32): the
+    window problem has a minimum, so that the solve carries the ~1e-12 by which two correct logs differ near th = pi - 1e-4 to the positions
+    as ~1e-12 and not, as six LM iterations on _random_state's unrelated points and tracks do, as 1e-3 (measured with oracle/ba_oracle.py)"""
+    for L, k in list(zip(state._landmarks, state._landmarks_kp)) + list(zip(dead, dead_kp)):
+        n = len(k.uv_history)
+        for idx in range(n):
+            t = L.t_latest - (n - 1) + idx                       # the frame PipeModel.ba_problem reads this entry for
+            if 0 <= t <= t_step:
+                q = K @ (pose_fn(t)[:3] @ np.append(np.asarray(L.p, np.float64).reshape(3), 1.0))
+                k.uv_history[idx] = np.float32(q[:2] / q[2] + rng.normal(0.0, 0.5, 2)).reshape(2, 1)
+        k.uv, k.uv_first = k.uv_history[-1].copy(), k.uv_history[0].copy()
+
+
+def _angle_between(Ra, Rb):
+    D = Ra @ Rb.T
+    return 0.5 * np.sqrt((D[2, 1] - D[1, 2]) ** 2 + (D[0, 2] - D[2, 0]) ** 2 + (D[1, 0] - D[0, 1]) ** 2) if np.trace(D) > 0 else np.pi
+
+
+@pytest.mark.parametrize("cap,W", [(64, 4), (64, 10), (1100, 4), (1100, 10)])
+def test_adjust_stage_with_edge_rotations(cap, W):
+    """The ADJUST stage alone on windows whose poses are rotations by 1e-6 and 1e-4 (either side of the snap to zero, sin th < 1e-5), 0.3, 2.5,
+    pi - 1e-4 and pi - 1e-6 (either side of the near-pi branch: axis from the diagonal, signs from the first row), pi + 0.2 -- every other
+    pipeline test turns by <= 0.3 rad about one axis.  t_step = 13 puts all seven into a window of 10; windows of 4 see them in two states
+    (t_step 10: the first four, t_step 13: the last four).
+    (1) against PipeModel.adjust through _same: lists equal, positions and the window's poses to 1e-6, the poses outside the window equal;
+    (2) with an LM budget of 0 the stage writes exp(log(R)) of every window pose back: against R itself, as a rotation angle, 8 x what the host
+        twin so3.rodrigues_mat_to_vec achieves against the exact log (so3_model.SO3_LOG_DEV) outside the snap zones, OpenCV's 2e-5 rad inside
+        them; translations equal."""
+    import pipe_oracle as po
+    import so3_model as sm
+    from vo_mi355x import VoContext
+    from vo_mi355x.resident import ResidentPipeline, ADJUST
+    rng = np.random.default_rng(7000 + cap + W)
+    sc = {"K": np.array([[260.0, 0, (W_IMG - 1) / 2], [0, 260.0, (H_IMG - 1) / 2], [0, 0, 1]])}      # (the other test's camera; no frames: ADJUST reads none)
+    ca, cb = VoContext(W_IMG, H_IMG, max_pts=cap), VoContext(W_IMG, H_IMG, max_pts=cap)
+    try:
+        for t_step in ((10, 13) if W == 4 else (13,)):
+            n_l, n_c, n_d = int(rng.integers(cap // 4, cap // 2)), int(rng.integers(0, cap // 3)), int(rng.integers(0, cap // 2))
+            state, dead, dead_kp = _random_state(rng, cap, t_step, n_l, n_c, n_d, pose_fn=_edge_pose)
+            _reproject_histories(rng, sc["K"], state, dead, dead_kp, t_step, _edge_pose)
+            what = "cap %d W %d t_step %d edge rotations" % (cap, W, t_step)
+            # (1) six LM iterations against the table model
+            st2, d2, dk2 = copy.deepcopy((state, dead, dead_kp))
+            model = po.PipeModel(ca, sc["K"], W_IMG, H_IMG, cap=cap, params=po.Params(ba_window=W, ba_max_iters=6))
+            model.seed(st2, d2, dk2, t_step)
+            rp = ResidentPipeline(cb, sc["K"], ba_window=W, ba_max_iters=6)
+            st3, d3, dk3 = copy.deepcopy((state, dead, dead_kp))
+            rp.seed(st3, d3, dk3, t_step=t_step)
+            model.adjust()
+            rp.step(-1, ADJUST)
+            rec = rp.fetch()
+            assert model.status == 0 and rec["ba_iters"] >= 1, (what, model.status, rec)
+            _same(model, rp, what, p_tol=1e-6)
+            assert rec["n_resurrected"] == model.info["n_resurrected"] and rec["overflow"] == model.info.get("overflow", 0), what
+            got = rp.entries()["poses"]
+            for t in range(t_step + 1):
+                d = np.abs(got[t] - model.poses[t]).max()
+                assert d <= (1e-6 * max(1.0, np.abs(model.poses[t]).max()) if t > t_step - W else 0.0), (what, t, d)
+            # (2) budget 0: the window's poses go through the device's log and exp and nothing else
+            rp = ResidentPipeline(cb, sc["K"], ba_window=W, ba_max_iters=6, ba_budget=0)
+            st4, d4, dk4 = copy.deepcopy((state, dead, dead_kp))
+            rp.seed(st4, d4, dk4, t_step=t_step)
+            rp.step(-1, ADJUST)
+            rec = rp.fetch()
+            assert rec["status"] == 0 and rec["ba_iters"] == 0, (what, rec)
+            got = rp.entries()["poses"]
+            for t in range(t_step + 1):
+                H, th = _edge_pose(t), sm.PIPE_ANGLES[t % len(sm.PIPE_ANGLES)]
+                if t <= t_step - W:
+                    assert np.array_equal(got[t], H), (what, t)
+                    continue
+                ang = _angle_between(got[t][:3, :3], H[:3, :3])
+                tol = 2e-5 if abs(np.sin(th)) < 1e-5 else 8 * sm.SO3_LOG_DEV[th]
+                print("%s t %d th %.9g: exp(log(R)) is %.2e rad from R (tolerance %.2e)" % (what, t, th, ang, tol))
+                assert ang <= tol, (what, t, th, ang, tol)
+                assert np.array_equal(got[t][:3, 3], H[:3, 3]) and np.array_equal(got[t][3], [0, 0, 0, 1]), (what, t)
+                assert np.abs(got[t][:3, :3] @ got[t][:3, :3].T - np.eye(3)).max() <= 8 * sm.EPS, (what, t)
+    finally:
+        ca.close(); cb.close()
