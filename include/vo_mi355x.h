@@ -800,6 +800,51 @@ int32_t vo_match_knn2(vo_ctx* ctx, const float* desc1, int32_t n1, const float* 
 int32_t vo_match_hamming_knn2(vo_ctx* ctx, const uint8_t* desc1, int32_t n1, const uint8_t* desc2, int32_t n2, int32_t nbytes,
                               int32_t* idx, int32_t* dist);
 
+/* ---- guided descriptor matching: window and epipolar gates, ratio test, cross-check ---------------
+ * The second matching pass of a detect / match / verify front end: the two matchers above, with every pair outside a search window or an
+ * epipolar band excluded before a descriptor byte is touched, and the decisions on which neighbour to keep (Lowe's ratio test, a distance
+ * ceiling, cv2.BFMatcher(crossCheck=True)'s mutual-nearest rule) made on the device.  OpenCV has no guided matcher: the numpy model
+ * tests/gmatch_model.py is the definition, and the kernels (csrc/vo_match_guided.hip) equal it bit for bit.
+ *   admitted(i, j), for i < counts1[b] and j < counts2[b]:
+ *     window (gate bit 0)    c = centers[i], or pts1[i] where centers is NULL; dx = (double)pts2[j].x - (double)c.x, dy likewise;
+ *                            (dx dx + dy dy) <= radius radius.  Any NaN makes it false.
+ *     epipolar (gate bit 1)  both squared point-to-epiline distances of (pts1[i], pts2[j]) under F are at most epi_dist epi_dist, in the
+ *                            float64 expressions of the consensus test of vo_fundamental_ransac (one device function, vo_epi_dev.h): a pair
+ *                            admitted at epi_dist = t is a pair that search counts as an inlier of F at threshold t.  A value that is not
+ *                            finite (a NaN position, a line with a^2 + b^2 = 0) is never admitted.
+ *     both bits: both hold.  gate 0: every existing pair is admitted.
+ *   distances  those of the matchers above, bit for bit: the popcount; sqrtf((float)acc), acc the float64 sum in ascending k.
+ *   per query i   idx[i][0..1], dist[i][0..1]: the two nearest admitted train rows by (distance, train index); an empty slot is -1 with
+ *                 INT32_MAX or +inf.  n_admitted[i]: the number of admitted train rows.
+ *   per train row j, with cross_check   rbest[j]: the nearest admitted query by (distance, query index), or -1.  Without: -1.
+ *   match[i] = idx[i][0] iff  a nearest row exists,  (double)d0 <= max_dist,  ratio == 1 or there is no second admitted neighbour or
+ *              (double)d0 < ratio * (double)d1 (one float64 product: Extractor.match's comparison),  and cross_check == 0 or
+ *              rbest[idx[i][0]] == i;  else -1.  The ratio test is not applied on the reverse side.
+ * desc1 [batch][n1][nbytes | dim], desc2 [batch][n2][nbytes | dim] as above; pts1 [batch][n1][2], pts2 [batch][n2][2], centers
+ * [batch][n1][2] f32 pixels; F [batch][9] row-major with x2^T F x1 = 0 (vo_fundamental_ransac's convention); counts1, counts2 [batch]: rows
+ * at or beyond a sequence's count do not exist for it (their outputs are the empty ones), NULL = n1 / n2 for every sequence, 0 is valid.
+ * prm NULL = the defaults.  idx, dist [batch][n1][2], n_admitted, match [batch][n1], rbest [batch][n2]; all but match may be NULL.
+ * Synchronous on the context's stream.  VO_E_INVALID with nothing enqueued and no output written: a NULL descriptor set or match, n1 < 1,
+ * n2 < 1, nbytes / dim outside the rules above, gate outside 0..3, cross_check outside 0..1, a gate bit whose distance is <= 0 or not
+ * finite, gate != 0 without pts1 and pts2, bit 1 without F, ratio outside (0, 1], max_dist NaN or negative, a count outside 0..n. */
+typedef struct {
+  int32_t gate;         /* bit 0: window, bit 1: epipolar; 0 = every pair admitted */
+  int32_t cross_check;  /* 0 / 1 */
+  double  radius;       /* window gate, pixels */
+  double  epi_dist;     /* epipolar gate, pixels */
+  double  ratio;        /* (0, 1]; 1 = no ratio test */
+  double  max_dist;     /* keep only d0 <= max_dist; +inf = off */
+} vo_gmatch_params;     /* 40 bytes */
+int32_t vo_gmatch_default_params(vo_gmatch_params* p);   /* gate 0, cross_check 0, radius 0, epi_dist 0, ratio 1, max_dist +inf */
+int32_t vo_match_guided_hamming(vo_ctx* ctx, const uint8_t* desc1, int32_t n1, const uint8_t* desc2, int32_t n2, int32_t nbytes,
+                                const float* pts1, const float* pts2, const float* centers, const double* F,
+                                const int32_t* counts1, const int32_t* counts2, const vo_gmatch_params* prm,
+                                int32_t* match, int32_t* idx, int32_t* dist, int32_t* n_admitted, int32_t* rbest);
+int32_t vo_match_guided_l2(vo_ctx* ctx, const float* desc1, int32_t n1, const float* desc2, int32_t n2, int32_t dim,
+                           const float* pts1, const float* pts2, const float* centers, const double* F,
+                           const int32_t* counts1, const int32_t* counts2, const vo_gmatch_params* prm,
+                           int32_t* match, int32_t* idx, float* dist, int32_t* n_admitted, int32_t* rbest);
+
 /* ---- device-resident track table (SURVEY.md 8f "next" row 3) -----------------------------------
  * The bookkeeping Extractor.extend_tracks / extend_landmarks / extract do on Python lists of Keypoint objects
  * (src/extractor/extractor.py:38-88, 90-132; src/state/keypoint.py:4-21), as a structure of arrays in HBM: per
@@ -1039,11 +1084,14 @@ int32_t vo_step_layout(vo_ctx* ctx, int32_t* layout, int32_t* gate_groups, int32
  * VO_PROF_ORB_PYRAMID / _CANDIDATES / _RETAIN / _DESCRIBE bracket the stages of vo_orb_detect_compute: the k_orb_resize launches; k_orb_score,
  * k_orb_nms and k_orb_cut; k_orb_harris and k_orb_rank; k_orb_describe (tools/orb_timing.py).
  * VO_PROF_FUND_SOLVE / _SCORE / _SELECT / _FINISH bracket the k_f7_solve / k_f7_score / k_f7_select launch of every round of
- * vo_fundamental_ransac and its k_f7_finish launch (tools/fundamental_timing.py). */
+ * vo_fundamental_ransac and its k_f7_finish launch (tools/fundamental_timing.py).
+ * VO_PROF_GMATCH_FORWARD / _REVERSE / _ACCEPT bracket the forward pass, the cross-check's reverse pass and the k_gmatch_accept launch of
+ * vo_match_guided_hamming / vo_match_guided_l2 (tools/guided_match_timing.py). */
 enum { VO_PROF_FRAME = 0, VO_PROF_KLT = 1, VO_PROF_ST = 2, VO_PROF_DLT = 3, VO_PROF_BA = 4, VO_PROF_CLAHE_LUT = 5, VO_PROF_CLAHE_APPLY = 6,
        VO_PROF_HOM_SOLVE = 7, VO_PROF_HOM_SCORE = 8, VO_PROF_HOM_SELECT = 9, VO_PROF_HOM_FINISH = 10, VO_PROF_ORB_PYRAMID = 11,
        VO_PROF_ORB_CANDIDATES = 12, VO_PROF_ORB_RETAIN = 13, VO_PROF_ORB_DESCRIBE = 14,
-       VO_PROF_FUND_SOLVE = 15, VO_PROF_FUND_SCORE = 16, VO_PROF_FUND_SELECT = 17, VO_PROF_FUND_FINISH = 18, VO_PROF_COUNT = 19 };
+       VO_PROF_FUND_SOLVE = 15, VO_PROF_FUND_SCORE = 16, VO_PROF_FUND_SELECT = 17, VO_PROF_FUND_FINISH = 18,
+       VO_PROF_GMATCH_FORWARD = 19, VO_PROF_GMATCH_REVERSE = 20, VO_PROF_GMATCH_ACCEPT = 21, VO_PROF_COUNT = 22 };
 int32_t vo_profile_enable(vo_ctx* ctx, int32_t region_mask);
 int32_t vo_profile_read(vo_ctx* ctx, int32_t region, double* total_ms, int32_t* count);
 /* diagnostic: shader-clock stamps (s_memtime deltas, cycles) of the phases of the last launch of a

@@ -1,0 +1,17 @@
+// The symmetric epipolar error shared by the fundamental-matrix search (vo_fundamental.hip: the consensus of a model) and the guided
+// matcher (vo_match_guided.hip: the epipolar gate of a pair), so that a pair the gate admits at epi_dist = t is a pair the search counts as
+// an inlier at threshold t.  The numpy restatement is tests/fundamental_model.py (err_parts).
+#pragma once
+#include "vo_internal.h"
+
+// OpenCV's FMEstimatorCallback::computeError in float64: the larger of the two squared distances of a point to its epipolar line.
+// -> true (and err) if both are within thr2; a NaN coordinate, or an epipolar line with a^2 + b^2 = 0 or a value that is not finite, is never an inlier
+__device__ __forceinline__ bool f7_inlier(const double* F, double x, double y, double u, double v, double thr2, double& err) {
+  const double a2 = (F[0] * x + F[1] * y) + F[2], b2 = (F[3] * x + F[4] * y) + F[5], c2 = (F[6] * x + F[7] * y) + F[8];
+  const double s2 = 1.0 / (a2 * a2 + b2 * b2), d2 = (u * a2 + v * b2) + c2;
+  const double a1 = (F[0] * u + F[3] * v) + F[6], b1 = (F[1] * u + F[4] * v) + F[7], c1 = (F[2] * u + F[5] * v) + F[8];
+  const double s1 = 1.0 / (a1 * a1 + b1 * b1), d1 = (x * a1 + y * b1) + c1;
+  const double e1 = (d1 * d1) * s1, e2 = (d2 * d2) * s2;
+  err = e1 > e2 ? e1 : e2;
+  return (e1 <= thr2) && (e2 <= thr2);
+}

@@ -1,0 +1,408 @@
+// Guided 2-nearest-neighbour descriptor matching: the two matchers of vo_match.hip with a per-pair gate in front of the distance, and the
+// accept rule (distance ceiling, Lowe's ratio, cross-check) on the device.  Definition: include/vo_mi355x.h, section "guided descriptor
+// matching"; numpy model: tests/gmatch_model.py, which the kernels equal bit for bit.
+//
+// The gate decides per (query, train row) pair whether the distance is computed at all:
+//   window    (dx dx + dy dy) <= radius^2 in float64 between the train position and the query's centre;
+//   epipolar  f7_inlier of vo_epi_dev.h, the consensus test of the fundamental-matrix search, at epi_dist^2.
+// GPU mapping, as in vo_match.hip: a wave per query, four queries per 256-thread workgroup, grid y = batch; the train rows are scanned 64 at
+// a time and the 64 lane results merged by shuffles under the same (distance, index) order.  The train positions of a tile are staged in LDS
+// as float2 (twice where the window and the epipolar gate read different arrays: the reverse pass with centres); what belongs to the query
+// (its centre, its epipolar line) does not depend on the lane and is hoisted out of the scan by the compiler.
+//   Hamming  the descriptor tile sits in LDS as in k_match_hamming_knn2; a rejected row's popcounts are skipped.  Gate 0 has an instance of its
+//            own without the position tiles.
+//   L2       a rejected row's 4 dim bytes are never loaded: the lanes ballot the predicate, append the admitted row indices to a ring of 128 in
+//            LDS that the wave owns, and whenever it holds 64 every lane takes one and computes its whole row exactly as k_match_knn2 does
+//            (float64 sum in ascending k, one sqrtf).  The order in which rows reach knn_insert does not matter: (distance, index) is a total
+//            order over the rows that can enter (a NaN distance never does).
+// The cross-check's reverse pass is the same kernel with the sets swapped: the window's dx changes sign, which its square does not see, and
+// the host passes F^T, under which f7_inlier evaluates the same two squared distances in the other order.  k_gmatch_accept applies the rule.
+// Rows at or beyond counts[b] do not exist: as queries they get the empty result, as train rows they are never scanned.
+#include "vo_internal.h"
+#include "vo_epi_dev.h"
+
+#include <math.h>
+#include <string.h>
+
+#define GM_MAX_WORDS 16
+#define GM_TILE_WORDS 9216                // the Hamming descriptor tile, as HAM_TILE_WORDS of vo_match.hip
+#define GM_POS_ROWS 1024                  // train positions staged at once; a tile holds min(GM_POS_ROWS, GM_TILE_WORDS / (nw + 1)) rows
+#define GM_RING 128                       // admitted row indices a wave holds (L2): under 64 left over + 64 appended
+
+// Beside the two descriptor sets the call moves two slabs: every gate input in one upload from a pinned mirror, every output in one read-back
+// into a pinned mirror (a copy per array from and to the caller's pageable memory costs more than the kernels at these sizes).
+struct vo_gmatch_ws {
+  struct buf { void* p = nullptr; size_t cap = 0; };
+  buf a, b;                               // descriptors
+  buf in, out, rev;                       // gate inputs; match | idx | dist | n_admitted | rbest; the reverse pass's idx | dist
+  buf h_in, h_out;                        // pinned mirrors of in and out
+};
+
+struct gm_gate {
+  int gate;                               // bit 0 window, bit 1 epipolar
+  double r2, e2;                          // radius^2, epi_dist^2
+  const double* F;                        // [batch][2][9]
+  int f_off;                              // 0: F (forward), 9: F^T (reverse)
+  const float2* qw; const float2* qe;     // query side: window centre / epipolar point, [batch][nq]
+  const float2* tw; const float2* te;     // train side, [batch][nt]
+};
+
+// the pair predicate; qw, tw are read under bit 0 and qe, te under bit 1 only
+__device__ __forceinline__ bool gm_admit(int gate, double r2, double e2, const double* F, float2 qw, float2 qe, float2 tw, float2 te) {
+  bool ok = true;
+  if (gate & 1) {
+    const double dx = (double)tw.x - (double)qw.x, dy = (double)tw.y - (double)qw.y;
+    ok = (dx * dx + dy * dy) <= r2;
+  }
+  if (gate & 2) {
+    double err;
+    ok = f7_inlier(F, (double)qe.x, (double)qe.y, (double)te.x, (double)te.y, e2, err) && ok;
+  }
+  return ok;
+}
+
+struct gknn2 { float d0, d1; int i0, i1; };
+struct gknn2i { int d0, d1; int i0, i1; };
+
+__device__ __forceinline__ bool gknn_less(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
+__device__ __forceinline__ bool gknn_less(int da, int ia, int db, int ib) { return da < db || (da == db && ia < ib); }
+
+template <class S, class D> __device__ __forceinline__ void gknn_insert(S& s, D d, int i) {
+  if (gknn_less(d, i, s.d0, s.i0)) { s.d1 = s.d0; s.i1 = s.i0; s.d0 = d; s.i0 = i; }
+  else if (gknn_less(d, i, s.d1, s.i1)) { s.d1 = d; s.i1 = i; }
+}
+
+template <class S> __device__ __forceinline__ void gknn_merge(S& s) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const auto od0 = __shfl_xor(s.d0, o), od1 = __shfl_xor(s.d1, o);
+    const int oi0 = __shfl_xor(s.i0, o), oi1 = __shfl_xor(s.i1, o);
+    gknn_insert(s, od0, oi0);
+    gknn_insert(s, od1, oi1);
+  }
+}
+
+// A [batch][nq][nw], Bm [batch][nt][nw] words; idx, dist [batch][nq][2]; nadm [batch][nq] or null.  grid (ceil(nq / 4), batch), 256 threads.
+// GATED = false is the instance of gate 0: no position tiles in LDS and no gate state in registers, the resources of k_match_hamming_knn2
+template <bool GATED>
+__global__ void __launch_bounds__(256) k_gmatch_hamming(const uint32_t* __restrict__ A, const uint32_t* __restrict__ Bm, int nq, int nt, int nw,
+                                                        const int32_t* __restrict__ cntq, const int32_t* __restrict__ cntt, gm_gate g,
+                                                        int32_t* __restrict__ idx, int32_t* __restrict__ dist, int32_t* __restrict__ nadm) {
+  __shared__ uint32_t tile[GM_TILE_WORDS];
+  __shared__ uint32_t qs[4][GM_MAX_WORDS];
+  __shared__ float2 posw[GATED ? GM_POS_ROWS : 1], pose[GATED ? GM_POS_ROWS : 1];
+  const int gate = GATED ? g.gate : 0;
+  const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int qi = blockIdx.x * 4 + wave;
+  const int nq_b = cntq ? cntq[b] : nq, nt_b = cntt ? cntt[b] : nt;
+  const bool live = qi < nq;                       // the wave has an output row
+  const bool active = qi < nq_b;                   // ... and a query (a wave without one still loads tiles and meets the barriers)
+  if (active && lane < nw) qs[wave][lane] = A[((size_t)b * nq + qi) * nw + lane];
+  const float2 zero = make_float2(0.f, 0.f);
+  float2 qw = zero, qe = zero;
+  if (active && (gate & 1)) qw = g.qw[(size_t)b * nq + qi];
+  if (active && (gate & 2)) qe = g.qe[(size_t)b * nq + qi];
+  double F[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) F[k] = (gate & 2) ? g.F[(size_t)b * 18 + g.f_off + k] : 0.0;
+  const uint32_t* const T = Bm + (size_t)b * nt * nw;
+  const int pitch = nw + 1, rows_tile = min(GM_TILE_WORDS / pitch, GM_POS_ROWS);
+  gknn2i s;
+  s.d0 = s.d1 = 0x7fffffff; s.i0 = s.i1 = 0x7fffffff;
+  int na = 0;
+  for (int j0 = 0; j0 < nt_b; j0 += rows_tile) {
+    const int rows = min(rows_tile, nt_b - j0);
+    __syncthreads();                               // the previous tile has been read (first pass: the queries are written)
+    for (int k = threadIdx.x; k < rows * nw; k += 256) {
+      const int r = k / nw, q = k - r * nw;
+      tile[r * pitch + q] = T[(size_t)j0 * nw + k];
+    }
+    for (int r = threadIdx.x; r < rows; r += 256) {
+      if (gate & 1) posw[r] = g.tw[(size_t)b * nt + j0 + r];
+      if (gate & 2) pose[r] = g.te[(size_t)b * nt + j0 + r];
+    }
+    __syncthreads();
+    if (active)
+      for (int j = lane; j < rows; j += 64) {
+        float2 tw = zero, te = zero;
+        if (gate & 1) tw = posw[j];
+        if (gate & 2) te = pose[j];
+        if (gm_admit(gate, g.r2, g.e2, F, qw, qe, tw, te)) {
+          na++;
+          const uint32_t* const r = tile + j * pitch;
+          const uint32_t* const q = qs[wave];
+          int d = 0, k = 0;
+          for (; k + 1 < nw; k += 2) d += __popcll(((unsigned long long)(q[k + 1] ^ r[k + 1]) << 32) | (unsigned long long)(q[k] ^ r[k]));
+          if (k < nw) d += __popc(q[k] ^ r[k]);
+          gknn_insert(s, d, j0 + j);
+        }
+      }
+  }
+  gknn_merge(s);
+  for (int o = 32; o > 0; o >>= 1) na += __shfl_xor(na, o);
+  if (live && lane == 0) {
+    const size_t o = (size_t)b * nq + qi;
+    idx[o * 2] = (s.i0 == 0x7fffffff) ? -1 : s.i0; idx[o * 2 + 1] = (s.i1 == 0x7fffffff) ? -1 : s.i1;
+    dist[o * 2] = s.d0; dist[o * 2 + 1] = s.d1;
+    if (nadm) nadm[o] = na;
+  }
+}
+
+// the distance of k_match_knn2: float64 sum of the squared float32 differences in ascending k, rounded to float32 once, sqrtf
+__device__ __forceinline__ float gm_l2(const float* __restrict__ q, const float* __restrict__ r, int dim) {
+  double acc = 0.0;
+  int k = 0;
+  if ((dim & 3) == 0) {
+    for (; k < dim; k += 4) {
+      const float4 x = *reinterpret_cast<const float4*>(r + k);
+      const float4 y = *reinterpret_cast<const float4*>(q + k);
+      const double e0 = (double)y.x - (double)x.x, e1 = (double)y.y - (double)x.y, e2 = (double)y.z - (double)x.z, e3 = (double)y.w - (double)x.w;
+      acc += e0 * e0; acc += e1 * e1; acc += e2 * e2; acc += e3 * e3;
+    }
+  }
+  for (; k < dim; k++) { const double e = (double)q[k] - (double)r[k]; acc += e * e; }
+  return sqrtf((float)acc);
+}
+
+// A [batch][nq][dim], Bm [batch][nt][dim] f32; idx, dist [batch][nq][2]; nadm [batch][nq] or null.  grid (ceil(nq / 4), batch), 256 threads
+__global__ void __launch_bounds__(256) k_gmatch_l2(const float* __restrict__ A, const float* __restrict__ Bm, int nq, int nt, int dim,
+                                                   const int32_t* __restrict__ cntq, const int32_t* __restrict__ cntt, gm_gate g,
+                                                   int32_t* __restrict__ idx, float* __restrict__ dist, int32_t* __restrict__ nadm) {
+  __shared__ float2 posw[GM_POS_ROWS], pose[GM_POS_ROWS];
+  __shared__ int ring[4][GM_RING];
+  const int b = blockIdx.y, lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // uniform: the query's row is read by scalar loads
+  const int qi = blockIdx.x * 4 + wave;
+  const int nq_b = cntq ? cntq[b] : nq, nt_b = cntt ? cntt[b] : nt;
+  const bool live = qi < nq, active = qi < nq_b;
+  const float* const q = A + ((size_t)b * nq + (active ? qi : 0)) * dim;
+  const float* const T = Bm + (size_t)b * nt * dim;
+  const float2 zero = make_float2(0.f, 0.f);
+  float2 qw = zero, qe = zero;
+  if (active && (g.gate & 1)) qw = g.qw[(size_t)b * nq + qi];
+  if (active && (g.gate & 2)) qe = g.qe[(size_t)b * nq + qi];
+  double F[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) F[k] = (g.gate & 2) ? g.F[(size_t)b * 18 + g.f_off + k] : 0.0;
+  volatile int* const rg = ring[wave];
+  gknn2 s;
+  s.d0 = s.d1 = __builtin_inff(); s.i0 = s.i1 = 0x7fffffff;
+  int head = 0, tail = 0;                          // wave-uniform; tail - head entries wait in the ring
+  for (int j0 = 0; j0 < nt_b; j0 += GM_POS_ROWS) {
+    const int rows = min(GM_POS_ROWS, nt_b - j0);
+    __syncthreads();                               // the previous tile's positions have been read
+    for (int r = threadIdx.x; r < rows; r += 256) {
+      if (g.gate & 1) posw[r] = g.tw[(size_t)b * nt + j0 + r];
+      if (g.gate & 2) pose[r] = g.te[(size_t)b * nt + j0 + r];
+    }
+    __syncthreads();
+    if (active)
+      for (int c0 = 0; c0 < rows; c0 += 64) {
+        const int r = c0 + lane;
+        bool adm = r < rows;
+        if (adm) {
+          float2 tw = zero, te = zero;
+          if (g.gate & 1) tw = posw[r];
+          if (g.gate & 2) te = pose[r];
+          adm = gm_admit(g.gate, g.r2, g.e2, F, qw, qe, tw, te);
+        }
+        const unsigned long long m = __ballot(adm);
+        if (adm) rg[(tail + __popcll(m & ((1ull << lane) - 1ull))) & (GM_RING - 1)] = j0 + r;
+        tail += __popcll(m);
+        __builtin_amdgcn_wave_barrier();
+        if (tail - head >= 64) {
+          const int j = rg[(head + lane) & (GM_RING - 1)];
+          head += 64;
+          gknn_insert(s, gm_l2(q, T + (size_t)j * dim, dim), j);
+          __builtin_amdgcn_wave_barrier();
+        }
+      }
+  }
+  if (lane < tail - head) {
+    const int j = rg[(head + lane) & (GM_RING - 1)];
+    gknn_insert(s, gm_l2(q, T + (size_t)j * dim, dim), j);
+  }
+  gknn_merge(s);
+  if (live && lane == 0) {
+    const size_t o = (size_t)b * nq + qi;
+    idx[o * 2] = (s.i0 == 0x7fffffff) ? -1 : s.i0; idx[o * 2 + 1] = (s.i1 == 0x7fffffff) ? -1 : s.i1;
+    dist[o * 2] = s.d0; dist[o * 2 + 1] = s.d1;
+    if (nadm) nadm[o] = tail;
+  }
+}
+
+// the accept rule, a thread per query, and rbest = column 0 of the reverse pass, a thread per train row.  grid (ceil(max(n1, n2) / 256), batch)
+template <class D>
+__global__ void __launch_bounds__(256) k_gmatch_accept(const int32_t* __restrict__ idx, const D* __restrict__ dist, const int32_t* __restrict__ ridx,
+                                                       int n1, int n2, int cross, double ratio, double max_dist, int32_t* __restrict__ match,
+                                                       int32_t* __restrict__ rbest) {
+  const int b = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+  if (t < n1) {
+    const size_t o = (size_t)b * n1 + t;
+    const int i0 = idx[o * 2], i1 = idx[o * 2 + 1];
+    bool ok = i0 >= 0;
+    if (ok) {
+      const double d0 = (double)dist[o * 2], d1 = (double)dist[o * 2 + 1];
+      ok = d0 <= max_dist;
+      ok = ok && (ratio == 1.0 || i1 < 0 || d0 < ratio * d1);
+      ok = ok && (!cross || ridx[((size_t)b * n2 + i0) * 2] == t);
+    }
+    match[o] = ok ? i0 : -1;
+  }
+  if (t < n2) rbest[(size_t)b * n2 + t] = cross ? ridx[((size_t)b * n2 + t) * 2] : -1;
+}
+
+void vo_gmatch_destroy(vo_ctx* c) {
+  if (!c->gmatch) return;
+  vo_gmatch_ws* w = c->gmatch;
+  for (vo_gmatch_ws::buf* p : {&w->a, &w->b, &w->in, &w->out, &w->rev}) if (p->p) (void)hipFree(p->p);
+  for (vo_gmatch_ws::buf* p : {&w->h_in, &w->h_out}) if (p->p) (void)hipHostFree(p->p);
+  delete w;
+  c->gmatch = nullptr;
+}
+
+// every buffer is laid out for the call at hand ([batch][n] packed) and only ever grows; the calls are synchronous, so nothing is in flight
+static int32_t gm_reserve(vo_ctx* c, vo_gmatch_ws::buf& b, size_t need, bool pinned = false) {
+  if (b.cap >= need) return VO_OK;
+  if (b.p) { (void)(pinned ? hipHostFree(b.p) : hipFree(b.p)); b.p = nullptr; b.cap = 0; }
+  if (pinned) VO_HIP(c, hipHostMalloc(&b.p, need, hipHostMallocDefault));
+  else VO_HIP(c, hipMalloc(&b.p, need));
+  b.cap = need;
+  return VO_OK;
+}
+
+#define GM_RESERVE(buf, bytes, pinned) do { const int32_t _rc = gm_reserve(c, (buf), (bytes), (pinned)); if (_rc != VO_OK) return _rc; } while (0)
+
+extern "C" int32_t vo_gmatch_default_params(vo_gmatch_params* p) {
+  if (!p) return VO_E_INVALID;
+  p->gate = 0; p->cross_check = 0; p->radius = 0.0; p->epi_dist = 0.0; p->ratio = 1.0; p->max_dist = (double)INFINITY;
+  return VO_OK;
+}
+
+// width: words per row (Hamming) or floats per row (L2); DT: the distance type
+template <bool HAM, class DT>
+static int32_t gm_run(vo_ctx* c, const void* desc1, int32_t n1, const void* desc2, int32_t n2, int32_t width, const float* pts1, const float* pts2,
+                      const float* centers, const double* F, const int32_t* counts1, const int32_t* counts2, const vo_gmatch_params* prm,
+                      int32_t* match, int32_t* idx, DT* dist, int32_t* n_admitted, int32_t* rbest) {
+  vo_gmatch_params P;
+  vo_gmatch_default_params(&P);
+  if (prm) P = *prm;
+  VO_CHECK(c, P.gate >= 0 && P.gate <= 3, VO_E_INVALID, "gate must be in 0..3");
+  VO_CHECK(c, P.cross_check == 0 || P.cross_check == 1, VO_E_INVALID, "cross_check must be 0 or 1");
+  VO_CHECK(c, !(P.gate & 1) || (P.radius > 0 && std::isfinite(P.radius)), VO_E_INVALID, "the window gate needs a finite radius > 0");
+  VO_CHECK(c, !(P.gate & 2) || (P.epi_dist > 0 && std::isfinite(P.epi_dist)), VO_E_INVALID, "the epipolar gate needs a finite epi_dist > 0");
+  VO_CHECK(c, P.gate == 0 || (pts1 && pts2), VO_E_INVALID, "a gate needs pts1 and pts2");
+  VO_CHECK(c, !(P.gate & 2) || F, VO_E_INVALID, "the epipolar gate needs F");
+  VO_CHECK(c, P.ratio > 0 && P.ratio <= 1, VO_E_INVALID, "ratio must be in (0, 1]");
+  VO_CHECK(c, P.max_dist >= 0, VO_E_INVALID, "max_dist must be >= 0 (inf = off)");
+  const size_t B = c->batch;
+  for (size_t b = 0; b < B; b++) {
+    VO_CHECK(c, !counts1 || (counts1[b] >= 0 && counts1[b] <= n1), VO_E_INVALID, "counts1 outside 0..n1");
+    VO_CHECK(c, !counts2 || (counts2[b] >= 0 && counts2[b] <= n2), VO_E_INVALID, "counts2 outside 0..n2");
+  }
+  VO_HIP(c, hipSetDevice(c->device));
+  if (!c->gmatch) c->gmatch = new vo_gmatch_ws();
+  vo_gmatch_ws* w = c->gmatch;
+  const size_t N1 = (size_t)n1 * B, N2 = (size_t)n2 * B, row = 4 * (size_t)width;
+  const int cross = P.cross_check;
+  // the input slab: F and F^T [batch][2][9] f64 | pts1 | pts2 | centers (float2 each) | counts1 | counts2
+  const size_t o_p1 = B * 18 * sizeof(double), o_p2 = o_p1 + N1 * sizeof(float2), o_ce = o_p2 + N2 * sizeof(float2),
+               o_c1 = o_ce + N1 * sizeof(float2), o_c2 = o_c1 + B * sizeof(int32_t), in_bytes = o_c2 + B * sizeof(int32_t);
+  // the output slab: match | idx | dist | n_admitted | rbest
+  const size_t o_idx = N1 * sizeof(int32_t), o_dist = o_idx + N1 * 2 * sizeof(int32_t), o_nadm = o_dist + N1 * 2 * sizeof(DT),
+               o_rbest = o_nadm + N1 * sizeof(int32_t), out_bytes = o_rbest + N2 * sizeof(int32_t);
+  GM_RESERVE(w->a, N1 * row, false);
+  GM_RESERVE(w->b, N2 * row, false);
+  GM_RESERVE(w->in, in_bytes, false);
+  GM_RESERVE(w->h_in, in_bytes, true);
+  GM_RESERVE(w->out, out_bytes, false);
+  GM_RESERVE(w->h_out, out_bytes, true);
+  if (cross) GM_RESERVE(w->rev, N2 * 2 * (sizeof(int32_t) + sizeof(DT)), false);
+  VO_HIP(c, hipMemcpyAsync(w->a.p, desc1, N1 * row, hipMemcpyHostToDevice, c->stream));
+  VO_HIP(c, hipMemcpyAsync(w->b.p, desc2, N2 * row, hipMemcpyHostToDevice, c->stream));
+  const bool use_ce = (P.gate & 1) && centers;
+  if (P.gate || counts1 || counts2) {
+    char* const h = (char*)w->h_in.p;
+    if (P.gate & 2) {
+      double* hF = (double*)h;
+      for (size_t b = 0; b < B; b++)
+        for (int i = 0; i < 3; i++)
+          for (int j = 0; j < 3; j++) {
+            hF[b * 18 + i * 3 + j] = F[b * 9 + i * 3 + j];
+            hF[b * 18 + 9 + i * 3 + j] = F[b * 9 + j * 3 + i];
+          }
+    }
+    if (P.gate) { memcpy(h + o_p1, pts1, N1 * sizeof(float2)); memcpy(h + o_p2, pts2, N2 * sizeof(float2)); }
+    if (use_ce) memcpy(h + o_ce, centers, N1 * sizeof(float2));
+    if (counts1) memcpy(h + o_c1, counts1, B * sizeof(int32_t));
+    if (counts2) memcpy(h + o_c2, counts2, B * sizeof(int32_t));
+    VO_HIP(c, hipMemcpyAsync(w->in.p, h, in_bytes, hipMemcpyHostToDevice, c->stream));
+  }
+  char* const din = (char*)w->in.p; char* const dout = (char*)w->out.p;
+  const float2* const dp1 = (const float2*)(din + o_p1); const float2* const dp2 = (const float2*)(din + o_p2);
+  const float2* const dc = use_ce ? (const float2*)(din + o_ce) : dp1;
+  const int32_t* const dc1 = counts1 ? (const int32_t*)(din + o_c1) : nullptr; const int32_t* const dc2 = counts2 ? (const int32_t*)(din + o_c2) : nullptr;
+  int32_t* const d_match = (int32_t*)dout; int32_t* const d_idx = (int32_t*)(dout + o_idx); DT* const d_dist = (DT*)(dout + o_dist);
+  int32_t* const d_nadm = (int32_t*)(dout + o_nadm); int32_t* const d_rbest = (int32_t*)(dout + o_rbest);
+  int32_t* const d_ridx = (int32_t*)w->rev.p; DT* const d_rdist = (DT*)((char*)w->rev.p + N2 * 2 * sizeof(int32_t));
+  gm_gate g;
+  g.gate = P.gate; g.r2 = P.radius * P.radius; g.e2 = P.epi_dist * P.epi_dist; g.F = (const double*)din;
+  g.f_off = 0; g.qw = dc; g.qe = dp1; g.tw = dp2; g.te = dp2;
+  gm_gate gr = g;                                  // the reverse pass: the train rows ask, the queries answer
+  gr.f_off = 9; gr.qw = dp2; gr.qe = dp2; gr.tw = dc; gr.te = dp1;
+  const dim3 gf(vo_div_up(n1, 4), (unsigned)B), gv(vo_div_up(n2, 4), (unsigned)B);
+  {
+    vo_prof_scope prof(c, c->stream, VO_PROF_GMATCH_FORWARD);
+    if (HAM)
+      hipLaunchKernelGGL(P.gate ? k_gmatch_hamming<true> : k_gmatch_hamming<false>, gf, dim3(256), 0, c->stream, (const uint32_t*)w->a.p, (const uint32_t*)w->b.p, n1, n2, width, dc1, dc2, g,
+                         d_idx, (int32_t*)d_dist, d_nadm);
+    else
+      hipLaunchKernelGGL(k_gmatch_l2, gf, dim3(256), 0, c->stream, (const float*)w->a.p, (const float*)w->b.p, n1, n2, width, dc1, dc2, g,
+                         d_idx, (float*)d_dist, d_nadm);
+  }
+  VO_HIP(c, hipGetLastError());
+  if (cross) {
+    vo_prof_scope prof(c, c->stream, VO_PROF_GMATCH_REVERSE);
+    if (HAM)
+      hipLaunchKernelGGL(P.gate ? k_gmatch_hamming<true> : k_gmatch_hamming<false>, gv, dim3(256), 0, c->stream, (const uint32_t*)w->b.p, (const uint32_t*)w->a.p, n2, n1, width, dc2, dc1, gr,
+                         d_ridx, (int32_t*)d_rdist, (int32_t*)nullptr);
+    else
+      hipLaunchKernelGGL(k_gmatch_l2, gv, dim3(256), 0, c->stream, (const float*)w->b.p, (const float*)w->a.p, n2, n1, width, dc2, dc1, gr,
+                         d_ridx, (float*)d_rdist, (int32_t*)nullptr);
+  }
+  VO_HIP(c, hipGetLastError());
+  {
+    vo_prof_scope prof(c, c->stream, VO_PROF_GMATCH_ACCEPT);
+    hipLaunchKernelGGL(k_gmatch_accept<DT>, dim3(vo_div_up(n1 > n2 ? n1 : n2, 256), (unsigned)B), dim3(256), 0, c->stream, (const int32_t*)d_idx,
+                       (const DT*)d_dist, (const int32_t*)d_ridx, n1, n2, cross, P.ratio, P.max_dist, d_match, d_rbest);
+  }
+  VO_HIP(c, hipGetLastError());
+  VO_HIP(c, hipMemcpyAsync(w->h_out.p, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP(c, hipStreamSynchronize(c->stream));
+  const char* const ho = (const char*)w->h_out.p;
+  memcpy(match, ho, N1 * sizeof(int32_t));
+  if (idx) memcpy(idx, ho + o_idx, N1 * 2 * sizeof(int32_t));
+  if (dist) memcpy(dist, ho + o_dist, N1 * 2 * sizeof(DT));
+  if (n_admitted) memcpy(n_admitted, ho + o_nadm, N1 * sizeof(int32_t));
+  if (rbest) memcpy(rbest, ho + o_rbest, N2 * sizeof(int32_t));
+  return VO_OK;
+}
+
+extern "C" int32_t vo_match_guided_hamming(vo_ctx* c, const uint8_t* desc1, int32_t n1, const uint8_t* desc2, int32_t n2, int32_t nbytes,
+                                           const float* pts1, const float* pts2, const float* centers, const double* F, const int32_t* counts1,
+                                           const int32_t* counts2, const vo_gmatch_params* prm, int32_t* match, int32_t* idx, int32_t* dist,
+                                           int32_t* n_admitted, int32_t* rbest) {
+  if (!c) return VO_E_INVALID;
+  VO_CHECK(c, desc1 && desc2 && match, VO_E_INVALID, "null buffer");
+  VO_CHECK(c, n1 >= 1 && n2 >= 1, VO_E_INVALID, "empty descriptor set");
+  VO_CHECK(c, nbytes >= 4 && nbytes <= 4 * GM_MAX_WORDS && nbytes % 4 == 0, VO_E_INVALID, "nbytes must be a multiple of 4 in 4..64");
+  return gm_run<true, int32_t>(c, desc1, n1, desc2, n2, nbytes / 4, pts1, pts2, centers, F, counts1, counts2, prm, match, idx, dist, n_admitted, rbest);
+}
+
+extern "C" int32_t vo_match_guided_l2(vo_ctx* c, const float* desc1, int32_t n1, const float* desc2, int32_t n2, int32_t dim, const float* pts1,
+                                      const float* pts2, const float* centers, const double* F, const int32_t* counts1, const int32_t* counts2,
+                                      const vo_gmatch_params* prm, int32_t* match, int32_t* idx, float* dist, int32_t* n_admitted, int32_t* rbest) {
+  if (!c) return VO_E_INVALID;
+  VO_CHECK(c, desc1 && desc2 && match, VO_E_INVALID, "null buffer");
+  VO_CHECK(c, n1 >= 1 && n2 >= 1 && dim >= 1, VO_E_INVALID, "empty descriptor set");
+  return gm_run<false, float>(c, desc1, n1, desc2, n2, dim, pts1, pts2, centers, F, counts1, counts2, prm, match, idx, dist, n_admitted, rbest);
+}

@@ -113,6 +113,11 @@ class FundStats(C.Structure):
                 ("status", C.c_int32), ("n_roots", C.c_int32), ("models", C.c_int32)]
 
 
+class GMatchParams(C.Structure):
+    _fields_ = [("gate", C.c_int32), ("cross_check", C.c_int32), ("radius", C.c_double), ("epi_dist", C.c_double), ("ratio", C.c_double),
+                ("max_dist", C.c_double)]
+
+
 class SiftKp(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("size", C.c_float), ("angle", C.c_float), ("response", C.c_float),
                 ("octave", C.c_int32)]
@@ -267,6 +272,11 @@ SIGNATURES = {
     "vo_orb_level_image_read": (C.c_int32, [_ctx, C.c_int32, C.c_int32, _u8p]),
     "vo_match_knn2": (C.c_int32, [_ctx, _f32p, C.c_int32, _f32p, C.c_int32, C.c_int32, _i32p, _f32p]),
     "vo_match_hamming_knn2": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32, _i32p, _i32p]),
+    "vo_gmatch_default_params": (C.c_int32, [C.POINTER(GMatchParams)]),
+    "vo_match_guided_hamming": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32, _f32p, _f32p, _f32p, _f64p, _i32p, _i32p,
+                                            C.POINTER(GMatchParams), _i32p, _i32p, _i32p, _i32p, _i32p]),
+    "vo_match_guided_l2": (C.c_int32, [_ctx, _f32p, C.c_int32, _f32p, C.c_int32, C.c_int32, _f32p, _f32p, _f32p, _f64p, _i32p, _i32p,
+                                       C.POINTER(GMatchParams), _i32p, _i32p, _f32p, _i32p, _i32p]),
     "vo_pnp_upload": (C.c_int32, [_ctx, _f64p, _f32p, _f32p, C.c_int32]),
     "vo_pnp_solve_resident": (C.c_int32, [_ctx, C.POINTER(PnpParams), C.c_int32]),
     "vo_pnp_fetch": (C.c_int32, [_ctx, _f64p, _f64p, _u8p, C.POINTER(PnpStats)]),

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, FundParams, FundStats, HomParams, HomStats, KltParams, OrbKp, OrbParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
+from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, FundParams, FundStats, GMatchParams, HomParams, HomStats, KltParams, OrbKp, OrbParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
 
 # vo_set_klt_predict modes (include/vo_mi355x.h)
 KLT_PREDICT_MODES = {"off": 0, "constant_velocity": 1}
@@ -766,6 +766,7 @@ class VoContext:
     PROF_HOM_SOLVE, PROF_HOM_SCORE, PROF_HOM_SELECT, PROF_HOM_FINISH = range(7, 11)
     PROF_ORB_PYRAMID, PROF_ORB_CANDIDATES, PROF_ORB_RETAIN, PROF_ORB_DESCRIBE = range(11, 15)
     PROF_FUND_SOLVE, PROF_FUND_SCORE, PROF_FUND_SELECT, PROF_FUND_FINISH = range(15, 19)
+    PROF_GMATCH_FORWARD, PROF_GMATCH_REVERSE, PROF_GMATCH_ACCEPT = range(19, 22)
 
     def profile_enable(self, regions=(0, 1, 2, 3, 4)):
         """regions: iterable of PROF_* ids to time with hipEvent pairs on the ctx stream; () switches timing off"""
@@ -980,6 +981,50 @@ class VoContext:
         self._ck(self._L.vo_match_hamming_knn2(self._h, ptr(d1, C.c_uint8), n1, ptr(d2, C.c_uint8), n2, nb, ptr(idx, C.c_int32),
                                                ptr(dist, C.c_int32)))
         return (idx[0], dist[0]) if B == 1 else (idx, dist)
+
+    def match_guided(self, desc1, desc2, pts1=None, pts2=None, F=None, centers=None, radius=None, epi_dist=None, ratio=1.0, max_dist=None,
+                     cross_check=False, counts1=None, counts2=None):
+        """guided matching (vo_match_guided_hamming for uint8 descriptors, vo_match_guided_l2 otherwise): the two nearest train rows of every
+        query among the pairs a gate admits, and the accept rule on the device.  radius (pixels) sets the window gate: pts2[j] within radius of
+        centers[i] (pts1[i] without centers); epi_dist (pixels) sets the epipolar gate under F (3,3), x2^T F x1 = 0: the pairs find_fundamental
+        counts as inliers of F at that threshold.  ratio < 1: Lowe's test d0 < ratio d1; max_dist: d0 <= max_dist; cross_check: the match must be
+        mutual.  desc1 (n1,w), desc2 (n2,w), pts1 / centers (n1,2), pts2 (n2,2) [leading batch dim if batch > 1]; counts1, counts2 (batch,):
+        rows at or beyond a sequence's count do not exist.  -> dict match (n1,) train index or -1, idx (n1,2), dist (n1,2), n_admitted (n1,),
+        rbest (n2,) the nearest admitted query of every train row under cross_check, else -1"""
+        B = self.batch
+        ham = np.asarray(desc1).dtype == np.uint8 and np.asarray(desc2).dtype == np.uint8
+        dt, ct = (np.uint8, C.c_uint8) if ham else (np.float32, C.c_float)
+        wd = np.shape(desc1)[-1]
+        d1 = np.ascontiguousarray(desc1, dt).reshape(B, -1, wd)
+        d2 = np.ascontiguousarray(desc2, dt).reshape(B, -1, wd)
+        n1, n2 = d1.shape[1], d2.shape[1]
+
+        def pos(p, n):
+            return None if p is None else np.ascontiguousarray(p, np.float32).reshape(B, n, 2)
+
+        def cnt(k):
+            return None if k is None else np.ascontiguousarray(np.broadcast_to(np.asarray(k, np.int32).reshape(-1), (B,)), np.int32)
+        p1, p2, ce = pos(pts1, n1), pos(pts2, n2), pos(centers, n1)
+        Fm = None if F is None else np.ascontiguousarray(F, np.float64).reshape(B, 9)
+        c1, c2 = cnt(counts1), cnt(counts2)
+        prm = GMatchParams()
+        self._L.vo_gmatch_default_params(C.byref(prm))
+        prm.gate = (1 if radius is not None else 0) | (2 if epi_dist is not None else 0)
+        prm.radius = 0.0 if radius is None else float(radius)
+        prm.epi_dist = 0.0 if epi_dist is None else float(epi_dist)
+        prm.ratio = float(ratio)
+        if max_dist is not None:
+            prm.max_dist = float(max_dist)
+        prm.cross_check = int(cross_check)
+        match = np.zeros((B, n1), np.int32); idx = np.zeros((B, n1, 2), np.int32)
+        dist = np.zeros((B, n1, 2), np.int32 if ham else np.float32)
+        nadm = np.zeros((B, n1), np.int32); rbest = np.zeros((B, n2), np.int32)
+        fn = self._L.vo_match_guided_hamming if ham else self._L.vo_match_guided_l2
+        self._ck(fn(self._h, ptr(d1, ct), n1, ptr(d2, ct), n2, wd, ptr(p1, C.c_float), ptr(p2, C.c_float), ptr(ce, C.c_float),
+                    ptr(Fm, C.c_double), ptr(c1, C.c_int32), ptr(c2, C.c_int32), C.byref(prm), ptr(match, C.c_int32), ptr(idx, C.c_int32),
+                    ptr(dist, C.c_int32 if ham else C.c_float), ptr(nadm, C.c_int32), ptr(rbest, C.c_int32)))
+        out = dict(match=match, idx=idx, dist=dist, n_admitted=nadm, rbest=rbest)
+        return {k: v[0] for k, v in out.items()} if B == 1 else out
 
     # -- 2D-2D bootstrap pose ---------------------------------------------------------------------
     def essential_ransac(self, K, pts1, pts2, threshold=1.0, prob=0.9999, max_iters=1000, seed=0, distance_thresh=50.0):

@@ -495,6 +495,22 @@ class Extractor:
         rows = [np.stack([np.ravel(o.des) for o in lst]) for lst in (list_1, list_2)]
         return self.match(rows[0], rows[1])
 
+    def match_guided(self, list_1, list_2, F=None, centers=None, **kw):
+        """the second matching pass between two lists of objects with `.uv` and `.des` (keypoints, landmarks): VoContext.match_guided over
+        their descriptor rows and positions -> the list of DMatch of the accepted queries (m.queryIdx indexes list_1, m.trainIdx list_2).
+        F (3,3) with epi_dist=, or centers (n1,2) / the queries' own positions with radius=, narrow the search; ratio=, max_dist= and
+        cross_check= as VoContext.match_guided.  Float descriptors take the L2 kernel, uint8 ones the Hamming kernel."""
+        if self._ctx is None:
+            raise RuntimeError("match_guided needs the device context: track a frame first (or pass ctx=)")
+        if len(list_1) == 0 or len(list_2) == 0:
+            return []
+        rows = [np.stack([np.ravel(o.des) for o in lst]) for lst in (list_1, list_2)]
+        if not (rows[0].dtype == np.uint8 and rows[1].dtype == np.uint8):
+            rows = [np.ascontiguousarray(r, np.float32) for r in rows]
+        p1, p2 = self._uv_pairs(list_1, list_2)
+        r = self._ctx.match_guided(rows[0], rows[1], pts1=p1, pts2=p2, F=F, centers=centers, **kw)
+        return [DMatch(q, int(j), r["dist"][q, 0]) for q, j in enumerate(r["match"]) if j >= 0]
+
     def match_list(self, kp_1, desc_1, keypoints):
         # the reference's match_list (extractor.py:156-160) calls self.match with four arguments and always raises
         raise TypeError("match() takes 3 positional arguments but 5 were given")
