@@ -804,7 +804,7 @@ int32_t vo_match_hamming_knn2(vo_ctx* ctx, const uint8_t* desc1, int32_t n1, con
  * The second matching pass of a detect / match / verify front end: the two matchers above, with every pair outside a search window or an
  * epipolar band excluded before a descriptor byte is touched, and the decisions on which neighbour to keep (Lowe's ratio test, a distance
  * ceiling, cv2.BFMatcher(crossCheck=True)'s mutual-nearest rule) made on the device.  OpenCV has no guided matcher: the numpy model
- * tests/gmatch_model.py is the definition, and the kernels (csrc/vo_match_guided.hip) equal it bit for bit.
+ * tests/gmatch_model.py is the definition, and the kernels (csrc/vo_match.hip) equal it bit for bit.
  *   admitted(i, j), for i < counts1[b] and j < counts2[b]:
  *     window (gate bit 0)    c = centers[i], or pts1[i] where centers is NULL; dx = (double)pts2[j].x - (double)c.x, dy likewise;
  *                            (dx dx + dy dy) <= radius radius.  Any NaN makes it false.
@@ -1085,7 +1085,7 @@ int32_t vo_step_layout(vo_ctx* ctx, int32_t* layout, int32_t* gate_groups, int32
  * k_orb_nms and k_orb_cut; k_orb_harris and k_orb_rank; k_orb_describe (tools/orb_timing.py).
  * VO_PROF_FUND_SOLVE / _SCORE / _SELECT / _FINISH bracket the k_f7_solve / k_f7_score / k_f7_select launch of every round of
  * vo_fundamental_ransac and its k_f7_finish launch (tools/fundamental_timing.py).
- * VO_PROF_GMATCH_FORWARD / _REVERSE / _ACCEPT bracket the forward pass, the cross-check's reverse pass and the k_gmatch_accept launch of
+ * VO_PROF_GMATCH_FORWARD / _REVERSE / _ACCEPT bracket the forward pass, the cross-check's reverse pass and the k_match_accept launch of
  * vo_match_guided_hamming / vo_match_guided_l2 (tools/guided_match_timing.py). */
 enum { VO_PROF_FRAME = 0, VO_PROF_KLT = 1, VO_PROF_ST = 2, VO_PROF_DLT = 3, VO_PROF_BA = 4, VO_PROF_CLAHE_LUT = 5, VO_PROF_CLAHE_APPLY = 6,
        VO_PROF_HOM_SOLVE = 7, VO_PROF_HOM_SCORE = 8, VO_PROF_HOM_SELECT = 9, VO_PROF_HOM_FINISH = 10, VO_PROF_ORB_PYRAMID = 11,

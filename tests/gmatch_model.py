@@ -1,5 +1,5 @@
 """gmatch_model.py -- the definition of guided descriptor matching (include/vo_mi355x.h, section "guided descriptor matching"; kernels in
-csrc/vo_match_guided.hip), restated in numpy.  OpenCV has no guided matcher, so this model is what the kernels are compared with, for equality.
+csrc/vo_match.hip), restated in numpy.  OpenCV has no guided matcher, so this model is what the kernels are compared with, for equality.
 
 One sequence at a time.  Every float64 expression below is a single IEEE operation per step in the order the kernels use (the library is built
 with -ffp-contract=off), so results are equal bit for bit, not within a tolerance."""

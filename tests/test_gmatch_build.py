@@ -1,5 +1,5 @@
-"""CPU-only: what hipcc makes of the guided matcher (csrc/vo_match_guided.hip) -- gfx950 cross-compile, no GPU needed -- and its place in
-the build and the C ABI.  What is asserted of the kernels' resources is what the build shows, with its reason."""
+"""CPU-only: what hipcc makes of the descriptor matchers, plain and guided (csrc/vo_match.hip) -- gfx950 cross-compile, no GPU needed -- and
+their place in the build and the C ABI.  What is asserted of the kernels' resources is what the build shows, with its reason."""
 import ctypes
 import os
 import re
@@ -19,42 +19,50 @@ def _one(res, name):
     return next(iter(m.values()))
 
 
+def _definitions(pattern):
+    """the files of csrc that define what `pattern` matches, one entry per definition"""
+    csrc = os.path.join(ROOT, "visual-odom-pipeline_amd", "csrc")
+    return [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")) for _ in re.findall(pattern, open(os.path.join(csrc, f)).read())]
+
+
 def test_the_unit_and_the_shared_header_are_in_the_makefile():
     mk = open(os.path.join(ROOT, "visual-odom-pipeline_amd", "csrc", "Makefile")).read()
     srcs = re.search(r"^SRCS := (.*)$", mk, re.M).group(1).split()
-    assert "vo_match_guided.hip" in srcs and "vo_match.hip" in srcs
+    assert "vo_match.hip" in srcs and "vo_match_guided.hip" not in srcs            # one unit for the plain and the guided matchers
     deps = re.search(r"^\$\(OBJDIR\)/%\.o: (.*)$", mk, re.M).group(1).split()
     assert "vo_epi_dev.h" in deps
     # one definition of the epipolar test, included by both users
+    assert _definitions(r"bool\s+f7_inlier\s*\(") == ["vo_epi_dev.h"]
     csrc = os.path.join(ROOT, "visual-odom-pipeline_amd", "csrc")
-    defs = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")) and re.search(r"bool\s+f7_inlier\s*\(", open(os.path.join(csrc, f)).read())]
-    assert defs == ["vo_epi_dev.h"], defs
-    for user in ("vo_fundamental.hip", "vo_match_guided.hip"):
+    for user in ("vo_fundamental.hip", "vo_match.hip"):
         assert '#include "vo_epi_dev.h"' in open(os.path.join(csrc, user)).read()
+    # one two-best insert and one L2 row distance for the plain and the guided scans
+    assert _definitions(r"void\s+knn_insert\s*\(") == ["vo_match.hip"]
+    assert _definitions(r"float\s+match_l2\s*\(") == ["vo_match.hip"]
 
 
 def test_kernel_resources():
-    res = kernel_resources("vo_match_guided.hip")
+    res = kernel_resources("vo_match.hip")
     for name, r in sorted(res.items()):
         print(name, r)
         assert r["ScratchSize"] == 0 and r["LDS"] <= 64 * 1024, (name, r)
-    plain = kernel_resources("vo_match.hip")
-    h, h0, hp = _one(res, "k_gmatch_hammingILb1E"), _one(res, "k_gmatch_hammingILb0E"), _one(plain, "k_match_hamming_knn2")
-    l, lp = _one(res, "k_gmatch_l2"), _one(plain, "k_match_knn2")
-    print("k_gmatch_hamming<gated>", h, "<gate 0>", h0, "beside k_match_hamming_knn2", hp)
-    print("k_gmatch_l2", l, "beside k_match_knn2", lp)
-    # Hamming with a gate: the 36 KiB descriptor tile and the four queries of the plain kernel plus two float2 position tiles of 1024 rows
-    # (16 KiB): 53 504 bytes, three workgroups in a CU's 160 KiB where the plain kernel has four.  The nine entries of F, the query's two
-    # points and its epipolar line sit in float64 registers beside the scan (116 VGPRs in this build against 63): under 128 they do not lower
-    # the three workgroups (12 waves per CU) that LDS allows.
+    assert len(res) == 5, sorted(res)                                               # one scan per distance kind (Hamming: two instances), two accepts
+    h, h0, l = _one(res, "k_match_hammingILb1E"), _one(res, "k_match_hammingILb0E"), _one(res, "k_match_l2")
+    print("k_match_hamming<gated>", h, "<gate 0>", h0)
+    print("k_match_l2", l)
+    # Hamming with a gate: the 36 KiB descriptor tile and the four queries of the ungated instance plus two float2 position tiles of 1024
+    # rows (16 KiB): 53 504 bytes, three workgroups in a CU's 160 KiB where the ungated instance has four.  The nine entries of F, the
+    # query's two points and its epipolar line sit in float64 registers beside the scan (116 VGPRs in this build against 63): under 128 they
+    # do not lower the three workgroups (12 waves per CU) that LDS allows.
     assert h["LDS"] == 4 * 9216 + 4 * 4 * 16 + 2 * 8 * 1024 and h["VGPRs"] <= 128 and h["Occupancy"] == 3, h
-    # Hamming at gate 0: an instance without the position tiles and the gate state -- the plain kernel's LDS and occupancy (66 VGPRs against 63:
-    # the admitted-row counter and the counts)
-    assert h0["LDS"] == hp["LDS"] == 4 * 9216 + 4 * 4 * 16 and h0["VGPRs"] <= 72 and h0["Occupancy"] == hp["Occupancy"] == 4, (h0, hp)
-    # L2: no descriptor tile; the two position tiles and the four rings of 128 indices (18 432 bytes: eight workgroups per CU).  56 VGPRs in
-    # this build (the plain kernel: 40, no gate): 64 is the most that keeps the plain kernel's 8 waves per SIMD, which hide the row loads.
-    assert l["LDS"] == 2 * 8 * 1024 + 4 * 4 * 128 and l["VGPRs"] <= 64 and l["Occupancy"] == 8 == lp["Occupancy"], (l, lp)
-    accept = [v for k, v in res.items() if "k_gmatch_accept" in k]
+    # Hamming at gate 0, which also serves vo_match_hamming_knn2: no position tiles, no gate state, no count of admitted rows.  The bounds are
+    # those held against the plain kernel k_match_hamming_knn2 this instance replaced, whose recorded values were 63 VGPRs, 37 120 B of LDS
+    # and 4 workgroups per CU; this instance builds to the same three numbers.
+    assert h0["LDS"] == 4 * 9216 + 4 * 4 * 16 and h0["VGPRs"] <= 72 and h0["Occupancy"] == 4, h0
+    # L2, every gate and vo_match_knn2: no descriptor tile; the two position tiles and the four rings of 128 indices (18 432 bytes: eight
+    # workgroups per CU).  56 VGPRs in this build: 64 is the most that keeps 8 waves per SIMD, which hide the row loads.
+    assert l["LDS"] == 2 * 8 * 1024 + 4 * 4 * 128 and l["VGPRs"] <= 64 and l["Occupancy"] == 8, l
+    accept = [v for k, v in res.items() if "k_match_accept" in k]
     assert len(accept) == 2 and all(r["LDS"] == 0 and r["Occupancy"] == 8 for r in accept), accept    # int32 and float distances
 
 

@@ -3,7 +3,7 @@ matcher (vo_match_hamming_knn2) through every layer.
 
 The contract is the numpy model tests/brief_model.py (shown against brute-force loops and exact rotations by tests/test_brief_model.py):
 descriptors and flags of k_brief_describe equal it bit for bit, the angle -- float32 from two different atan2s, nothing depends on it --
-within 1e-3 degrees; k_match_hamming_knn2 equals the model exactly.  The resident detections -- the track table's and the closed loop's --
+within 1e-3 degrees; vo_match_hamming_knn2 equals the model exactly.  The resident detections -- the track table's and the closed loop's --
 are pinned against the model at the integer corners they spawned, and everything else those detections write must be identical with the
 setting on and off."""
 import copy

@@ -1,6 +1,7 @@
-"""GPU: guided descriptor matching (vo_match_guided_hamming / vo_match_guided_l2, csrc/vo_match_guided.hip) against its numpy definition
+"""GPU: guided descriptor matching (vo_match_guided_hamming / vo_match_guided_l2, csrc/vo_match.hip) against its numpy definition
 tests/gmatch_model.py -- match, idx, dist, n_admitted and rbest for equality, no tolerances -- at the smallest shapes at which the kernels can
-go wrong, the properties that hold by construction, and one pass over real ORB descriptors."""
+go wrong, the properties that hold by construction, and one pass over real ORB descriptors.  The plain matchers (vo_match_knn2 /
+vo_match_hamming_knn2) are the same scans at gate 0 on the same workspace: they are held to the model here as well."""
 import ctypes as C
 
 import numpy as np
@@ -14,7 +15,8 @@ from test_gmatch_model import check_property_a, mutual_pairs
 pytestmark = pytest.mark.gpu
 
 KEYS = ("match", "idx", "dist", "n_admitted", "rbest")
-HAM_TILE_ROWS = {4: 1024, 32: 1024, 64: 542}            # min(1024 staged positions, 9216 words / (nbytes / 4 + 1)) rows per LDS tile
+HAM_TILE_ROWS = {4: 1024, 32: 1024, 64: 542}            # min(1024 staged positions, 9216 words / (nbytes / 4 + 1)) rows per LDS tile under a gate
+HAM_TILE_ROWS_GATE_0 = {4: 4608}                        # gate 0 stages no positions: 9216 words / (nbytes / 4 + 1)
 
 
 @pytest.fixture(scope="module")
@@ -52,6 +54,14 @@ def test_hamming_shapes(ctx, nbytes, n2):
     for n1 in (1, 5, 9):
         d1, d2 = gc.hamming_sets(n1, n2, nbytes, 1)
         _all_gates(ctx, d1, d2, n1)
+
+
+def test_hamming_gate_0_beyond_one_tile_of_four_byte_rows(ctx):
+    """the ungated instance's tile is not cut at the 1024 staged positions: at nbytes = 4 a second tile begins at row 4608"""
+    d1, d2 = gc.hamming_sets(5, HAM_TILE_ROWS_GATE_0[4] + 1, 4, 1)
+    d2[-1] = d1[3]                                                      # the one row of the second tile is query 3's nearest
+    got, _ = _check(ctx, d1, d2)
+    assert got["idx"][3, 0] == len(d2) - 1 and got["dist"][3, 0] == 0 and (got["n_admitted"] == len(d2)).all()
 
 
 @pytest.mark.parametrize("dim", [6, 128])
@@ -136,6 +146,12 @@ def test_ties(ctx, ham):
     assert list(got["idx"][0]) == [33, 70]
 
 
+def _plain_is_the_model(idx, dist, d1, d2, what=""):
+    want = gm.match_guided(d1, d2)
+    assert idx.dtype == want["idx"].dtype and np.array_equal(idx, want["idx"]), (what, idx, want["idx"])
+    assert dist.dtype == want["dist"].dtype and np.array_equal(dist, want["dist"]), (what, dist, want["dist"])
+
+
 def test_gate_0_is_the_plain_matcher_bit_for_bit(ctx):
     rng = np.random.default_rng(12)
     for dim, n1, n2 in ((128, 130, 300), (6, 9, 70)):
@@ -145,11 +161,13 @@ def test_gate_0_is_the_plain_matcher_bit_for_bit(ctx):
         got = ctx.match_guided(d1, d2)
         assert np.array_equal(got["idx"], idx) and np.array_equal(got["dist"].view(np.uint32), dist.view(np.uint32))
         assert np.array_equal(got["match"], idx[:, 0]) and (got["n_admitted"] == n2).all()
+        _plain_is_the_model(idx, dist, d1, d2)                          # both sides run one kernel: the model is the independent pin
     for nb, n1, n2 in ((32, 130, 1100), (4, 9, 70)):
         d1 = rng.integers(0, 256, (n1, nb), dtype=np.uint8); d2 = rng.integers(0, 256, (n2, nb), dtype=np.uint8)
         idx, dist = ctx.match_hamming_knn2(d1, d2)
         got = ctx.match_guided(d1, d2)
         assert np.array_equal(got["idx"], idx) and np.array_equal(got["dist"], dist) and got["dist"].dtype == dist.dtype
+        _plain_is_the_model(idx, dist, d1, d2)
 
 
 @pytest.mark.parametrize("ham", [True, False])
@@ -189,6 +207,28 @@ def test_the_workspace_grows_then_shrinks(ham):
             p1, p2 = gc.positions(n1, n2, n1 + n2)
             _check(c, d1, d2, cross_check=True, ratio=0.9, **gc.gate_kwargs(3, 0.5, p1, p2, F=gc.F_FORWARD))
             _check(c, d1, d2)
+
+
+def test_the_four_entry_points_share_one_workspace():
+    """one context, batch 2: the plain and the guided calls of both kinds take turns over sets that grow, shrink and grow on one side only,
+    at two row widths each.  A buffer sized by one kind and read by another, or a capacity left stale by a smaller call, would show."""
+    from vo_mi355x import VoContext
+    Fs = np.stack([gc.F_FORWARD, gc.F_GENERAL])
+    with VoContext(64, 64, max_pts=64, batch=2) as c:
+        for n1, n2 in ((5, 9), (70, 300), (5, 9), (3, 400)):
+            for dim, nbytes in ((6, 32), (128, 4)):
+                fs = [gc.l2_sets(n1, n2, dim, 60 + b, integer=False) for b in range(2)]
+                hs = [gc.hamming_sets(n1, n2, nbytes, 60 + b) for b in range(2)]
+                pos = [gc.positions(n1, n2, 60 + b) for b in range(2)]
+                f1, f2, h1, h2, p1, p2 = (np.stack([x[k] for x in xs]) for xs in (fs, hs, pos) for k in (0, 1))
+                kw = dict(pts1=p1, pts2=p2, radius=60.0, epi_dist=25.0, F=Fs, cross_check=True, ratio=0.9)
+                for d1, d2, plain in ((f1, f2, c.match_knn2), (h1, h2, c.match_hamming_knn2)):
+                    idx, dist = plain(d1, d2)
+                    guided = c.match_guided(d1, d2, **kw)
+                    for b in range(2):
+                        what = (n1, n2, d1.shape[-1], str(d1.dtype), b)
+                        _plain_is_the_model(idx[b], dist[b], d1[b], d2[b], what)
+                        _same({k: guided[k][b] for k in KEYS}, gm.match_guided(d1[b], d2[b], **{k: (v[b] if np.ndim(v) > 0 else v) for k, v in kw.items()}), what)
 
 
 def _raw(c, ham, **over):

@@ -1,5 +1,5 @@
 // The symmetric epipolar error shared by the fundamental-matrix search (vo_fundamental.hip: the consensus of a model) and the guided
-// matcher (vo_match_guided.hip: the epipolar gate of a pair), so that a pair the gate admits at epi_dist = t is a pair the search counts as
+// matcher (vo_match.hip: the epipolar gate of a pair), so that a pair the gate admits at epi_dist = t is a pair the search counts as
 // an inlier at threshold t.  The numpy restatement is tests/fundamental_model.py (err_parts).
 #pragma once
 #include "vo_internal.h"

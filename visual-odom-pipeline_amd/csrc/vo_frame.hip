@@ -354,7 +354,6 @@ extern "C" int32_t vo_ctx_destroy(vo_ctx* c) {
   vo_hom_destroy(c);
   vo_fund_destroy(c);
   vo_match_destroy(c);
-  vo_gmatch_destroy(c);
   vo_sift_destroy(c);
   vo_st_destroy(c);
   vo_ba_destroy(c);

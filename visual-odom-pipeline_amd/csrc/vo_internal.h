@@ -147,8 +147,7 @@ struct vo_ctx {
   struct vo_pnp_ws* pnp = nullptr;   // PnP-RANSAC workspace (vo_pnp.hip)
   struct vo_sift_ws* sift = nullptr;     // SIFT scale space and lists (vo_sift.hip)
   struct vo_orb_ws* orb = nullptr;       // ORB pyramid, score maps and lists (vo_orb.hip), made by the first vo_orb_detect_compute
-  struct vo_match_ws* match = nullptr;   // descriptor matcher buffers (vo_match.hip)
-  struct vo_gmatch_ws* gmatch = nullptr; // guided matcher buffers (vo_match_guided.hip)
+  struct vo_match_ws* match = nullptr;   // descriptor matcher buffers, plain and guided (vo_match.hip)
   struct vo_ess_ws* ess = nullptr;   // essential-matrix RANSAC workspace (vo_essential.hip)
   struct vo_hom_ws* hom = nullptr;   // homography RANSAC workspace (vo_homography.hip)
   struct vo_fund_ws* fund = nullptr; // fundamental-matrix RANSAC workspace (vo_fundamental.hip)
@@ -408,7 +407,6 @@ void vo_ess_destroy(vo_ctx* c);
 void vo_hom_destroy(vo_ctx* c);
 void vo_fund_destroy(vo_ctx* c);
 void vo_match_destroy(vo_ctx* c);
-void vo_gmatch_destroy(vo_ctx* c);
 void vo_sift_destroy(vo_ctx* c);
 // sub-workspace lifetime hooks
 void vo_st_destroy(vo_ctx* c);
