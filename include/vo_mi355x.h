@@ -206,6 +206,28 @@ typedef struct {
   int32_t models;            /* models scored over the whole search */
 } vo_fund_stats;
 
+/* cv2.decomposeHomographyMat(H, K) with cv2.filterHomographyDecompByVisibleRefpoints' two tests counted as votes, a ranking and an
+ * ambiguity verdict (vo_homography_decompose, vo_homography_pose) */
+typedef struct {
+  double  ratio;             /* 0.75 (ORB-SLAM): a candidate is viable if n_good >= ratio x the largest n_good; in (0, 1] */
+  double  threshold;         /* 1.0 px: Sampson threshold of the points outside the mask (divided by (fx + fy) / 2 internally) */
+  double  hint[3];           /* plane-normal prior in view-1 camera coordinates (a ground plane: 0, 1, 0); read when use_hint != 0 */
+  int32_t min_off;           /* 8: the best candidate is unambiguous once its n_off leads its rival's by this many points */
+  int32_t use_hint;          /* 0 */
+} vo_hpose_params;
+
+typedef struct {
+  double  sigma[3];          /* singular values of K^-1 H K divided by the middle one: s1 >= 1 >= s3; NaN without a solution */
+  int32_t n_solutions;       /* 4; 1 for a rotation-only H (s1 - s3 <= 2^-26: t = n = 0); 0 without a solution */
+  int32_t n_distinct;        /* 1, 2 or 4: entries that differ by 2^-20 or more in R, t or n (2: t || n, the two pairs coincide) */
+  int32_t ambiguous;         /* 1: a distinct viable rival lies fewer than min_off behind the best in n_off and no hint was given */
+  int32_t status;            /* 0, or VO_E_NUMERIC: det H = 0, a zero focal length or an entry that is not finite (a NaN H: no homography) */
+  int32_t n_mask;            /* points with finite coordinates in the mask */
+  int32_t n_good[4];         /* per ranked candidate: mask points in front of the plane in both views */
+  int32_t n_off[4];          /* per ranked candidate: points outside the mask within the Sampson threshold of E = [t]x R */
+  int32_t _pad;
+} vo_hpose_stats;
+
 /* the fields of cv2.KeyPoint that cv2.SIFT fills (the reference reads pt through cv2.KeyPoint_convert and hands the
  * objects back to compute(), src/extractor/extractor.py:114-122) */
 typedef struct {
@@ -677,6 +699,42 @@ int32_t vo_homography_default_params(vo_hom_params* p);
 int32_t vo_homography_ransac(vo_ctx* ctx, const float* pts1, const float* pts2, int32_t n, const vo_hom_params* prm,
                              double* H, double* H0, uint8_t* inlier_mask, vo_hom_stats* stats);
 
+/* ---- pose from the homography: what the bootstrap does when the degeneracy check fires ---------------
+ * cv2.decomposeHomographyMat(H, K) followed by cv2.filterHomographyDecompByVisibleRefpoints, with the two visibility tests counted
+ * per candidate instead of all-or-nothing (an outlier does not veto a candidate), a ranking, and a verdict on whether the pair can
+ * decide (ORB-SLAM ReconstructH, COLMAP).  The algorithm is defined by tests/hpose_model.py.
+ * G = K^-1 H K (K read as fx, fy, cx, cy), negated if det G < 0: both cameras on the same side of the plane, a property of H alone, so
+ * H may come at any scale and sign.  One-sided Jacobi SVD of G in float64 (the condition is never squared; s^2 - 1 enters as
+ * (s - 1)(s + 1)), singular values divided by the middle one: s1 >= 1 >= s3.  The solutions of G / s2 = R + (t / d) n^T with R in
+ * SO(3), |n| = 1 are two pairs {(R, t, n), (R, -t, -n)}: four entries, also where the pairs coincide (t || n: s1 = 1 or s3 = 1;
+ * n_distinct = 2).  s1 - s3 <= 2^-26 (below it the directions of t and n carry fewer than about 26 bits) is a rotation: one solution,
+ * R the rotation nearest G / s2, t = n = 0, every vote 0.
+ * Votes over the points i < n with finite coordinates, m = ((p - c) / f, 1) in float64 as vo_essential_ransac normalises:
+ * n_good[k] counts the points of the mask with n_k . m1 > 0 and (R_k n_k) . m2 > 0; n_off[k] the points outside the mask whose
+ * squared Sampson distance under E_k = [t_k / |t_k|]x R_k is <= (threshold / ((fx + fy) / 2))^2 (off-plane points tell the true
+ * candidate from the false one; with a NULL mask there are none).  Rank: the viable candidates (n_good >= ratio x max n_good) first;
+ * then n_off descending; then, with a hint, n_k . hint descending; then n_good descending; then trace R, n_z, n_y, n_x descending,
+ * properties of the solution, so the labelling of the SVD never shows.  ambiguous = 1 iff no hint was given and the best candidate
+ * has a viable rival distinct from it (the first in rank order) fewer than min_off behind it in n_off: a plane seen by a moving camera
+ * without off-plane points has two solutions that pass every point in both views, and only a prior or a third view tells them apart.
+ * vo_homography_decompose: K, H [batch][9] row-major (x2 ~ H x1, pixels); pts1, pts2 [batch][n][2] f32 pixels (NULL with n = 0: the
+ * pure cv2.decomposeHomographyMat, every vote 0); mask [batch][n] u8 (NULL: every point is in it); prm NULL: the defaults; R
+ * [batch][4][9], t [batch][4][3] (t / d, as cv2 returns it), nrm [batch][4][3] in rank order, entries beyond n_solutions NaN (each
+ * may be NULL); stats [batch] (may be NULL).  A sequence without a solution: status VO_E_NUMERIC, NaN outputs; the call returns VO_OK.
+ * vo_homography_pose: vo_homography_ransac(pts1, pts2, n, hom_prm) -> H, H0, inlier_mask, hom_stats as that call returns them, with
+ * the decomposition of the refined H against the winner's mask enqueued behind the search's last kernel on the same stream: H and
+ * the mask are read where they lie on the device, there is one read-back and no host synchronisation in between; the result is that
+ * of vo_homography_decompose on the returned H and mask, bit for bit.  A sequence without a homography reports VO_E_NUMERIC in both.
+ * VO_E_INVALID with nothing enqueued: ratio outside (0, 1], threshold <= 0 or not finite, min_off < 0, use_hint with a hint that is
+ * zero or not finite, n < 0, n > 0 with NULL points, a NULL K or H; for vo_homography_pose also what vo_homography_ransac rejects. */
+int32_t vo_homography_pose_default_params(vo_hpose_params* p);
+int32_t vo_homography_decompose(vo_ctx* ctx, const double* K, const double* H, const float* pts1, const float* pts2,
+                                const uint8_t* mask, int32_t n, const vo_hpose_params* prm, double* R, double* t, double* nrm,
+                                vo_hpose_stats* stats);
+int32_t vo_homography_pose(vo_ctx* ctx, const double* K, const float* pts1, const float* pts2, int32_t n,
+                           const vo_hom_params* hom_prm, const vo_hpose_params* pose_prm, double* H, uint8_t* inlier_mask,
+                           double* R, double* t, double* nrm, vo_hom_stats* hom_stats, vo_hpose_stats* pose_stats);
+
 /* ---- fundamental matrix: epipolar verification of matches without intrinsics ----------------------
  * cv2.findFundamentalMat(p1, p2, cv2.FM_RANSAC, 3.0, 0.99) of OpenCV 4.4, next to vo_essential_ransac (which needs K) and
  * vo_homography_ransac.  Rounds of 256 seven-point samples: hypothesis h draws sample7(seed, h, n), the generator of the other
@@ -1086,12 +1144,14 @@ int32_t vo_step_layout(vo_ctx* ctx, int32_t* layout, int32_t* gate_groups, int32
  * VO_PROF_FUND_SOLVE / _SCORE / _SELECT / _FINISH bracket the k_f7_solve / k_f7_score / k_f7_select launch of every round of
  * vo_fundamental_ransac and its k_f7_finish launch (tools/fundamental_timing.py).
  * VO_PROF_GMATCH_FORWARD / _REVERSE / _ACCEPT bracket the forward pass, the cross-check's reverse pass and the k_match_accept launch of
- * vo_match_guided_hamming / vo_match_guided_l2 (tools/guided_match_timing.py). */
+ * vo_match_guided_hamming / vo_match_guided_l2 (tools/guided_match_timing.py).
+ * VO_PROF_HPOSE brackets the k_hpose launch of vo_homography_decompose and vo_homography_pose (tools/hpose_timing.py). */
 enum { VO_PROF_FRAME = 0, VO_PROF_KLT = 1, VO_PROF_ST = 2, VO_PROF_DLT = 3, VO_PROF_BA = 4, VO_PROF_CLAHE_LUT = 5, VO_PROF_CLAHE_APPLY = 6,
        VO_PROF_HOM_SOLVE = 7, VO_PROF_HOM_SCORE = 8, VO_PROF_HOM_SELECT = 9, VO_PROF_HOM_FINISH = 10, VO_PROF_ORB_PYRAMID = 11,
        VO_PROF_ORB_CANDIDATES = 12, VO_PROF_ORB_RETAIN = 13, VO_PROF_ORB_DESCRIBE = 14,
        VO_PROF_FUND_SOLVE = 15, VO_PROF_FUND_SCORE = 16, VO_PROF_FUND_SELECT = 17, VO_PROF_FUND_FINISH = 18,
-       VO_PROF_GMATCH_FORWARD = 19, VO_PROF_GMATCH_REVERSE = 20, VO_PROF_GMATCH_ACCEPT = 21, VO_PROF_COUNT = 22 };
+       VO_PROF_GMATCH_FORWARD = 19, VO_PROF_GMATCH_REVERSE = 20, VO_PROF_GMATCH_ACCEPT = 21, VO_PROF_HPOSE = 22,
+       VO_PROF_COUNT = 23 };
 int32_t vo_profile_enable(vo_ctx* ctx, int32_t region_mask);
 int32_t vo_profile_read(vo_ctx* ctx, int32_t region, double* total_ms, int32_t* count);
 /* diagnostic: shader-clock stamps (s_memtime deltas, cycles) of the phases of the last launch of a

@@ -492,6 +492,11 @@ static int32_t hom_alloc(vo_ctx* c, int n) {
 // Frobenius norm with h33 >= 0 and x2 ~ H x1; inlier_mask [batch][n] u8 (of H0), stats [batch].
 extern "C" int32_t vo_homography_ransac(vo_ctx* c, const float* pts1, const float* pts2, int32_t n, const vo_hom_params* prm, double* H, double* H0,
                                         uint8_t* inlier_mask, vo_hom_stats* stats) {
+  return vo_hom_ransac_tail(c, pts1, pts2, n, prm, H, H0, inlier_mask, stats, nullptr);
+}
+
+int32_t vo_hom_ransac_tail(vo_ctx* c, const float* pts1, const float* pts2, int32_t n, const vo_hom_params* prm, double* H, double* H0,
+                           uint8_t* inlier_mask, vo_hom_stats* stats, const vo_hom_tail* tail) {
   if (!c) return VO_E_INVALID;
   vo_hom_params def;
   if (!prm) { vo_homography_default_params(&def); prm = &def; }
@@ -530,6 +535,10 @@ extern "C" int32_t vo_homography_ransac(vo_ctx* c, const float* pts1, const floa
     hipLaunchKernelGGL(k_h4_finish, dim3((unsigned)B), dim3(256), 0, c->stream, w->d_p, cap, n, thr2, prm->refine_iters, w->d_ctrl, w->d_mask, w->d_out);
   }
   VO_HIP(c, hipGetLastError());
+  if (tail) {
+    r = tail->enqueue(c, c->stream, w->d_p, cap, n, w->d_out, H4_OUT, w->d_mask, tail->user);
+    if (r != VO_OK) return r;
+  }
   VO_HIP(c, hipMemcpyAsync(w->h_out, w->d_out, sizeof(double) * H4_OUT * B, hipMemcpyDeviceToHost, c->stream));
   if (inlier_mask) VO_HIP(c, hipMemcpy2DAsync(inlier_mask, n, w->d_mask, cap, n, B, hipMemcpyDeviceToHost, c->stream));
   VO_HIP(c, hipStreamSynchronize(c->stream));

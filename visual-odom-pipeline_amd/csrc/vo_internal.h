@@ -151,6 +151,7 @@ struct vo_ctx {
   struct vo_ess_ws* ess = nullptr;   // essential-matrix RANSAC workspace (vo_essential.hip)
   struct vo_hom_ws* hom = nullptr;   // homography RANSAC workspace (vo_homography.hip)
   struct vo_fund_ws* fund = nullptr; // fundamental-matrix RANSAC workspace (vo_fundamental.hip)
+  struct vo_hpose_ws* hpose = nullptr; // pose-from-homography workspace (vo_hpose.hip)
   struct vo_trk_ws* trk = nullptr;   // device-resident track table (vo_tracks.hip)
   struct vo_pipe_ws* pipe = nullptr; // closed-loop Pipeline.step on the device (vo_pipeline.hip)
   const int32_t* d_pt_counts = nullptr;   // vo_tracks_* only (set by vo_tracks_seed, cleared by vo_trk_destroy): per-sequence number of live tracks the
@@ -406,6 +407,16 @@ void vo_pnp_destroy(vo_ctx* c);
 void vo_ess_destroy(vo_ctx* c);
 void vo_hom_destroy(vo_ctx* c);
 void vo_fund_destroy(vo_ctx* c);
+void vo_hpose_destroy(vo_ctx* c);
+// vo_homography_ransac with work enqueued behind k_h4_finish on the same stream, in front of the one read-back (vo_homography_pose):
+// `enqueue` gets the search's device buffers -- points [batch][2][cap][2], the refined H of sequence b at d_H + b * h_stride (NaN
+// without a model), the winner's mask [batch][cap] -- and what it copies to pinned memory on q is complete when the call returns
+struct vo_hom_tail {
+  int32_t (*enqueue)(vo_ctx* c, hipStream_t q, const float* d_p, int cap, int n, const double* d_H, int h_stride, const uint8_t* d_mask, void* user);
+  void* user;
+};
+int32_t vo_hom_ransac_tail(vo_ctx* c, const float* pts1, const float* pts2, int32_t n, const vo_hom_params* prm, double* H, double* H0,
+                           uint8_t* inlier_mask, vo_hom_stats* stats, const vo_hom_tail* tail);
 void vo_match_destroy(vo_ctx* c);
 void vo_sift_destroy(vo_ctx* c);
 // sub-workspace lifetime hooks

@@ -113,6 +113,15 @@ class FundStats(C.Structure):
                 ("status", C.c_int32), ("n_roots", C.c_int32), ("models", C.c_int32)]
 
 
+class HposeParams(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("threshold", C.c_double), ("hint", C.c_double * 3), ("min_off", C.c_int32), ("use_hint", C.c_int32)]
+
+
+class HposeStats(C.Structure):
+    _fields_ = [("sigma", C.c_double * 3), ("n_solutions", C.c_int32), ("n_distinct", C.c_int32), ("ambiguous", C.c_int32),
+                ("status", C.c_int32), ("n_mask", C.c_int32), ("n_good", C.c_int32 * 4), ("n_off", C.c_int32 * 4), ("_pad", C.c_int32)]
+
+
 class GMatchParams(C.Structure):
     _fields_ = [("gate", C.c_int32), ("cross_check", C.c_int32), ("radius", C.c_double), ("epi_dist", C.c_double), ("ratio", C.c_double),
                 ("max_dist", C.c_double)]
@@ -263,6 +272,11 @@ SIGNATURES = {
                                         C.POINTER(EssStats)]),
     "vo_homography_default_params": (C.c_int32, [C.POINTER(HomParams)]),
     "vo_homography_ransac": (C.c_int32, [_ctx, _f32p, _f32p, C.c_int32, C.POINTER(HomParams), _f64p, _f64p, _u8p, C.POINTER(HomStats)]),
+    "vo_homography_pose_default_params": (C.c_int32, [C.POINTER(HposeParams)]),
+    "vo_homography_decompose": (C.c_int32, [_ctx, _f64p, _f64p, _f32p, _f32p, _u8p, C.c_int32, C.POINTER(HposeParams), _f64p, _f64p, _f64p,
+                                            C.POINTER(HposeStats)]),
+    "vo_homography_pose": (C.c_int32, [_ctx, _f64p, _f32p, _f32p, C.c_int32, C.POINTER(HomParams), C.POINTER(HposeParams), _f64p, _u8p,
+                                       _f64p, _f64p, _f64p, C.POINTER(HomStats), C.POINTER(HposeStats)]),
     "vo_fundamental_default_params": (C.c_int32, [C.POINTER(FundParams)]),
     "vo_fundamental_ransac": (C.c_int32, [_ctx, _f32p, _f32p, C.c_int32, C.POINTER(FundParams), _f64p, _f64p, _u8p, C.POINTER(FundStats)]),
     "vo_sift_detect_compute": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32, C.POINTER(SiftKp), _f32p, _i32p]),

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, FundParams, FundStats, GMatchParams, HomParams, HomStats, KltParams, OrbKp, OrbParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
+from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, FundParams, FundStats, GMatchParams, HomParams, HomStats, HposeParams, HposeStats, KltParams, OrbKp, OrbParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
 
 # vo_set_klt_predict modes (include/vo_mi355x.h)
 KLT_PREDICT_MODES = {"off": 0, "constant_velocity": 1}
@@ -767,6 +767,7 @@ class VoContext:
     PROF_ORB_PYRAMID, PROF_ORB_CANDIDATES, PROF_ORB_RETAIN, PROF_ORB_DESCRIBE = range(11, 15)
     PROF_FUND_SOLVE, PROF_FUND_SCORE, PROF_FUND_SELECT, PROF_FUND_FINISH = range(15, 19)
     PROF_GMATCH_FORWARD, PROF_GMATCH_REVERSE, PROF_GMATCH_ACCEPT = range(19, 22)
+    PROF_HPOSE = 22
 
     def profile_enable(self, regions=(0, 1, 2, 3, 4)):
         """regions: iterable of PROF_* ids to time with hipEvent pairs on the ctx stream; () switches timing off"""
@@ -1077,6 +1078,83 @@ class VoContext:
         if B == 1:
             return H[0], inl[0], stats[0], H0[0]
         return H, inl, stats, H0
+
+    def _hpose_params(self, ratio, threshold, min_off, normal_hint):
+        prm = HposeParams()
+        self._L.vo_homography_pose_default_params(C.byref(prm))
+        prm.ratio, prm.threshold, prm.min_off = float(ratio), float(threshold), int(min_off)
+        if normal_hint is not None:
+            prm.use_hint = 1
+            prm.hint[:] = [float(x) for x in np.asarray(normal_hint, np.float64).reshape(3)]
+        return prm
+
+    def _hpose_out(self, R, t, nrm, st):
+        stats = [dict(n_solutions=s.n_solutions, n_distinct=s.n_distinct, ambiguous=s.ambiguous, status=s.status, n_mask=s.n_mask,
+                      n_good=list(s.n_good), n_off=list(s.n_off), sigma=np.array(s.sigma), rotation_only=s.n_solutions == 1) for s in st]
+        if self.batch == 1:
+            return R[0], t[0], nrm[0], stats[0]
+        return R, t, nrm, stats
+
+    def decompose_homography(self, K, H, pts1=None, pts2=None, mask=None, ratio=0.75, threshold=1.0, min_off=8, normal_hint=None):
+        """cv2.decomposeHomographyMat(H, K) with cv2.filterHomographyDecompByVisibleRefpoints' two visibility tests counted as votes, a ranking
+        and an ambiguity verdict (vo_homography_decompose; the algorithm: tests/hpose_model.py).  K (3,3); H (3,3) with x2 ~ H x1 at any scale
+        and sign; pts1, pts2 (n,2) pixels or None (the pure decomposition, every vote 0); mask (n,) nonzero = on the plane, None = every
+        point [leading batch dim if batch > 1; one K serves every sequence].  threshold (px) is the Sampson threshold of the points outside
+        the mask; normal_hint (3,) a plane-normal prior in view-1 camera coordinates.
+        -> R (4,3,3), t (4,3) = t / d as cv2 returns it, n (4,3), best first, NaN beyond stats['n_solutions'] (4; 1 for a rotation-only H,
+        then t = n = 0 and stats['rotation_only']; 0 with stats['status'] != 0 for an H without a solution), stats dict with n_distinct,
+        ambiguous, n_mask, n_good, n_off (per ranked candidate), sigma."""
+        B = self.batch
+        Kc = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (B, 3, 3)))
+        Hc = self._in(H, np.float64, (3, 3))
+        p1 = p2 = m = None
+        n = 0
+        if pts1 is not None:
+            p1 = np.ascontiguousarray(pts1, np.float32).reshape(B, -1, 2)
+            p2 = np.ascontiguousarray(pts2, np.float32).reshape(B, -1, 2)
+            n = p1.shape[1]
+            assert p2.shape[1] == n
+            if mask is not None:
+                m = np.ascontiguousarray(np.asarray(mask).reshape(B, n) != 0, np.uint8)
+        prm = self._hpose_params(ratio, threshold, min_off, normal_hint)
+        R, t, nrm = np.zeros((B, 4, 3, 3)), np.zeros((B, 4, 3)), np.zeros((B, 4, 3))
+        st = (HposeStats * B)()
+        self._ck(self._L.vo_homography_decompose(self._h, ptr(Kc, C.c_double), ptr(Hc, C.c_double), ptr(p1, C.c_float), ptr(p2, C.c_float),
+                                                 ptr(m, C.c_uint8), n, C.byref(prm), ptr(R, C.c_double), ptr(t, C.c_double),
+                                                 ptr(nrm, C.c_double), st))
+        return self._hpose_out(R, t, nrm, st)
+
+    def homography_pose(self, K, pts1, pts2, threshold=3.0, confidence=0.995, max_iters=2000, seed=0, refine_iters=10, ratio=0.75,
+                        pose_threshold=1.0, min_off=8, normal_hint=None):
+        """find_homography(pts1, pts2, threshold, ...) and decompose_homography of its H against its inliers in one call
+        (vo_homography_pose): the decomposition runs behind the search on the device, on the H and the mask where they lie; the result is
+        that of the two calls, bit for bit.  pose_threshold is decompose_homography's threshold.
+        -> H (3,3) divided by h33, inlier indices, the search's stats dict, then R, t, n, stats as decompose_homography returns them."""
+        B = self.batch
+        p1 = np.ascontiguousarray(pts1, np.float32).reshape(B, -1, 2)
+        p2 = np.ascontiguousarray(pts2, np.float32).reshape(B, -1, 2)
+        n = p1.shape[1]
+        assert p2.shape[1] == n
+        Kc = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (B, 3, 3)))
+        hp = HomParams()
+        self._L.vo_homography_default_params(C.byref(hp))
+        hp.threshold, hp.confidence, hp.max_iters, hp.seed, hp.refine_iters = threshold, confidence, int(max_iters), int(seed), int(refine_iters)
+        prm = self._hpose_params(ratio, pose_threshold, min_off, normal_hint)
+        H = np.zeros((B, 3, 3))
+        mask = np.zeros((B, n), np.uint8)
+        R, t, nrm = np.zeros((B, 4, 3, 3)), np.zeros((B, 4, 3)), np.zeros((B, 4, 3))
+        hs, st = (HomStats * B)(), (HposeStats * B)()
+        self._ck(self._L.vo_homography_pose(self._h, ptr(Kc, C.c_double), ptr(p1, C.c_float), ptr(p2, C.c_float), n, C.byref(hp), C.byref(prm),
+                                            ptr(H, C.c_double), ptr(mask, C.c_uint8), ptr(R, C.c_double), ptr(t, C.c_double),
+                                            ptr(nrm, C.c_double), hs, st))
+        for b in range(B):
+            if abs(H[b, 2, 2]) >= 1e-12 * np.linalg.norm(H[b]):
+                H[b] /= H[b, 2, 2]
+        hstats = [dict(cost=s.cost, n_inliers=s.n_inliers, hypotheses=s.hypotheses, best=s.best, status=s.status, lm_iters=s.lm_iters) for s in hs]
+        inl = [np.nonzero(mask[b])[0] for b in range(B)]
+        if B == 1:
+            return (H[0], inl[0], hstats[0]) + self._hpose_out(R, t, nrm, st)
+        return (H, inl, hstats) + self._hpose_out(R, t, nrm, st)
 
     def find_fundamental(self, pts1, pts2, threshold=3.0, confidence=0.99, max_iters=1000, seed=0, refit=0):
         """cv2.findFundamentalMat(pts1, pts2, cv2.FM_RANSAC, threshold, confidence) (vo_fundamental_ransac).  pts1, pts2 (n,2) pixels, n >= 7

@@ -589,3 +589,68 @@ class Extractor:
         h_st = self._ctx.find_homography(p1, p2, threshold=threshold, seed=seed)[2]
         ratio = h_st["n_inliers"] / max(e_st["n_inliers"], 1)
         return dict(e_inliers=e_st["n_inliers"], h_inliers=h_st["n_inliers"], h_ratio=ratio, degenerate=bool(ratio > max_h_ratio))
+
+    @staticmethod
+    def _planar_info(K, Hm, R, t, nrm, st, min_parallax_px):
+        """the ranked candidates of VoContext.homography_pose -> (H 4x4 of the best with |t| = 1, or t = 0 for a rotation; info dict)"""
+        ns = st["n_solutions"]
+        f = (float(K[0][0]) + float(K[1][1])) / 2.0
+        # a plane-induced parallax f |t / d| = f (s1 - s3) under min_parallax_px moves no point by more than that: at this pixel scale the
+        # homography cannot be told from a rotation, and the direction of its t is noise
+        rot = bool(ns == 1 or (st["sigma"][0] - st["sigma"][2]) * f <= min_parallax_px)
+        alts = []
+        for k in range(ns):
+            tn = float(np.linalg.norm(t[k]))
+            alts.append(dict(R=R[k].copy(), t=(t[k] / tn if tn > 0 else np.zeros(3)), t_over_d=t[k].copy(), n=nrm[k].copy(),
+                             n_good=st["n_good"][k], n_off=st["n_off"][k]))
+        H4 = np.eye(4)
+        H4[:3, :3] = alts[0]["R"]
+        if not rot:
+            H4[:3, 3] = alts[0]["t"]
+        info = dict(alternatives=alts, n_good=st["n_good"][:ns], n_off=st["n_off"][:ns], n_mask=st["n_mask"], n_solutions=ns,
+                    n_distinct=st["n_distinct"], ambiguous=bool(st["ambiguous"]) and not rot, rotation_only=rot, sigma=st["sigma"], homography=Hm)
+        return H4, info
+
+    def camera_pose_planar(self, K, list_1, list_2, threshold=3.0, seed=0, normal_hint=None, min_parallax_px=1.0, **kw):
+        """Pose from the homography of a planar scene or a pair without a baseline, where camera_pose(corr='2D-2D') has nothing to offer:
+        cv2.findHomography(RANSAC, threshold) + cv2.decomposeHomographyMat, ranked by the visibility of the inliers, the Sampson support of the
+        points off the plane and the optional plane-normal prior normal_hint (view-1 camera coordinates; a ground plane is (0, 1, 0)).
+        -> (inlier indices as a list, H 4x4 view-1 -> view-2 with |t| = 1, info).  info: `alternatives` (every candidate in rank order: R, t
+        of unit length, t_over_d, n, n_good, n_off), `ambiguous` (two candidates pass and nothing tells them apart: a plane without
+        off-plane points and without a hint -- take the alternatives to the next view), `rotation_only` (the parallax f (s1 - s3) is under
+        min_parallax_px: H's t is 0), n_good, n_off, n_mask, n_solutions, n_distinct, sigma, homography.  Further keywords as
+        VoContext.homography_pose."""
+        if self._ctx is None:
+            raise RuntimeError("camera_pose_planar needs the device context: track a frame first (or pass ctx=)")
+        Kc = np.asarray(K, np.float64)
+        Hm, inliers, hst, R, t, nrm, st = self._ctx.homography_pose(Kc, *self._uv_pairs(list_1, list_2), threshold=threshold, seed=seed,
+                                                                   normal_hint=normal_hint, **kw)
+        if hst["status"] != 0 or st["status"] != 0:
+            raise RuntimeError("findHomography found no model to decompose")
+        H4, info = self._planar_info(Kc, Hm, R, t, nrm, st, min_parallax_px)
+        return inliers.reshape((-1,)).tolist(), H4, info
+
+    def bootstrap_pose(self, K, list_1, list_2, threshold=1.0, max_h_ratio=0.8, seed=0, normal_hint=None):
+        """bootstrap_check's verdict followed by the right model.  -> dict `model`: 'essential' (the pair has structure and a baseline: the
+        pose of camera_pose(corr='2D-2D')), 'homography' (planar scene: the best candidate of camera_pose_planar, |t| = 1) or 'rotation' (no
+        baseline to speak of: t = 0); `inliers` (a list, of the model used), `H` 4x4 view-1 -> view-2, `ambiguous` (True only for
+        'homography': see camera_pose_planar; `info` then holds the alternatives), `check` (bootstrap_check's dict)."""
+        if self._ctx is None:
+            raise RuntimeError("bootstrap_pose needs the device context: track a frame first (or pass ctx=)")
+        Kc = np.asarray(K, np.float64)
+        p1, p2 = self._uv_pairs(list_1, list_2)
+        _E, Re, te, e_inl, e_st = self._ctx.essential_ransac(Kc, p1, p2, threshold=threshold, prob=0.9999, seed=seed)
+        Hm, h_inl, h_st, R, t, nrm, st = self._ctx.homography_pose(Kc, p1, p2, threshold=threshold, seed=seed, pose_threshold=threshold,
+                                                                  normal_hint=normal_hint)
+        ratio = h_st["n_inliers"] / max(e_st["n_inliers"], 1)
+        check = dict(e_inliers=e_st["n_inliers"], h_inliers=h_st["n_inliers"], h_ratio=ratio, degenerate=bool(ratio > max_h_ratio))
+        if not check["degenerate"] or h_st["status"] != 0 or st["status"] != 0:
+            if e_st["status"] != 0:
+                raise RuntimeError("findEssentialMat found no model")
+            H4 = np.eye(4)
+            H4[:3, :3] = Re
+            H4[:3, 3] = te.reshape((3,))
+            return dict(model='essential', inliers=e_inl.reshape((-1,)).tolist(), H=H4, ambiguous=False, check=check, info=None)
+        H4, info = self._planar_info(Kc, Hm, R, t, nrm, st, threshold)
+        return dict(model='rotation' if info["rotation_only"] else 'homography', inliers=h_inl.reshape((-1,)).tolist(), H=H4,
+                    ambiguous=info["ambiguous"], check=check, info=info)
