@@ -1,6 +1,8 @@
 // The symmetric epipolar error shared by the fundamental-matrix search (vo_fundamental.hip: the consensus of a model) and the guided
 // matcher (vo_match.hip: the epipolar gate of a pair), so that a pair the gate admits at epi_dist = t is a pair the search counts as
 // an inlier at threshold t.  The numpy restatement is tests/fundamental_model.py (err_parts).
+// And the squared Sampson distance shared by the essential-matrix search (vo_essential.hip: consensus and mask) and the pose from a
+// homography (vo_hpose.hip: the vote of the points off the plane); oracle/essential_oracle.py and tests/hpose_model.py restate it.
 #pragma once
 #include "vo_internal.h"
 
@@ -14,4 +16,12 @@ __device__ __forceinline__ bool f7_inlier(const double* F, double x, double y, d
   const double e1 = (d1 * d1) * s1, e2 = (d2 * d2) * s2;
   err = e1 > e2 ? e1 : e2;
   return (e1 <= thr2) && (e2 <= thr2);
+}
+
+// squared Sampson distance of the normalised correspondence (x1, y1) <-> (x2, y2) to E
+__device__ __forceinline__ double vo_sampson(const double* E, double x1, double y1, double x2, double y2) {
+  const double a0 = E[0] * x1 + E[1] * y1 + E[2], a1 = E[3] * x1 + E[4] * y1 + E[5], a2 = E[6] * x1 + E[7] * y1 + E[8];   // E x1
+  const double b0 = E[0] * x2 + E[3] * y2 + E[6], b1 = E[1] * x2 + E[4] * y2 + E[7];                                       // E^T x2
+  const double num = x2 * a0 + y2 * a1 + a2;
+  return num * num / (a0 * a0 + a1 * a1 + b0 * b0 + b1 * b1);
 }

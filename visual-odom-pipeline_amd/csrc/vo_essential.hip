@@ -14,32 +14,28 @@
 // per-lane scratch arrays, it runs 256 x once per call -- then a WAVE per (hypothesis, root) for the consensus count,
 // one workgroup per sequence for the running best / iteration bound, and one for the cheirality vote.
 // The arithmetic follows the oracle operation by operation (this library is built with -ffp-contract=off).  The sample generator, the
-// iteration bound, the head of the control block and the host's round loop are the ones all three searches share: vo_ransac.h.
+// iteration bound, the head of the control block and the host's round loop are the ones all four searches share: vo_ransac.h.  The
+// workspace, the upload of the two views, the read-back, a sequence's pointers and the no-winner exit are the two-view units':
+// vo_twoview.h; the squared Sampson distance is vo_sampson of vo_epi_dev.h, which the pose from a homography votes with too.
 #include "vo_internal.h"
-#include "vo_ransac.h"
+#include "vo_twoview.h"
+#include "vo_epi_dev.h"
 
 #include <math.h>
 #include <string.h>
 
 #define E5_BATCH 256
 #define E5_MAXSOL 10
+#define E5_OUT 32              // doubles per sequence: E (9), R (9), t (3), n_inliers, n_good, good (4), 5 spare
 
 struct e5_hyp { double E[E5_MAXSOL][9]; int count[E5_MAXSOL]; int nsol; int h; };
 struct e5_ctrl { vo_ransac_state s; int best_h, best_k, best_count; double E[9]; };
 static_assert(sizeof(e5_ctrl) == 96 && offsetof(e5_ctrl, best_h) == 12 && offsetof(e5_ctrl, best_k) == 16 && offsetof(e5_ctrl, best_count) == 20 &&
               offsetof(e5_ctrl, E) == 24, "e5_ctrl layout");
 
-struct vo_ess_ws {
-  int cap = 0, n = 0;
-  double* d_K = nullptr;       // [B][9]
-  float* d_p = nullptr;        // [B][2][cap][2] pixel coordinates of the two views
+struct vo_ess_ws : vo_tv_search_ws<e5_hyp, e5_ctrl, E5_BATCH> {      // h_out: [B][E5_OUT], then 10 staging doubles per sequence
+  double* d_K = nullptr;       // [B][9] K, then [B] squared thresholds
   double* d_q = nullptr;       // [B][2][cap][2] normalised
-  e5_hyp* d_hyp = nullptr;     // [B][E5_BATCH]
-  e5_ctrl* d_ctrl = nullptr;   // [B]
-  uint8_t* d_mask = nullptr;   // [B][cap]
-  double* d_out = nullptr;     // [B][32]: E(9) R(9) t(3) n_inliers n_good good[4]
-  e5_ctrl* h_ctrl = nullptr;   // pinned
-  double* h_out = nullptr;     // pinned
 };
 
 __constant__ int c_mul11[4][4] = {{0, 3, 4, 6}, {3, 1, 5, 7}, {4, 5, 2, 8}, {6, 7, 8, 9}};
@@ -375,13 +371,6 @@ __device__ inline int e5_five_point(const double q1[5][2], const double q2[5][2]
   return ns;
 }
 
-__device__ __forceinline__ double e5_sampson(const double* E, double x1, double y1, double x2, double y2) {
-  const double a0 = E[0] * x1 + E[1] * y1 + E[2], a1 = E[3] * x1 + E[4] * y1 + E[5], a2 = E[6] * x1 + E[7] * y1 + E[8];   // E x1
-  const double b0 = E[0] * x2 + E[3] * y2 + E[6], b1 = E[1] * x2 + E[4] * y2 + E[7];                                       // E^T x2
-  const double num = x2 * a0 + y2 * a1 + a2;
-  return num * num / (a0 * a0 + a1 * a1 + b0 * b0 + b1 * b1);
-}
-
 // ------------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------------
@@ -411,8 +400,7 @@ __global__ void __launch_bounds__(64) k_e5_solve(const double* __restrict__ q, i
   const int h = cs.s.h_done + slot;
   out->h = h;
   if (cs.s.done) { out->nsol = 0; return; }
-  const double* qa = q + ((size_t)b * 2) * cap * 2;
-  const double* qb = qa + (size_t)cap * 2;
+  const auto [qa, qb] = vo_tv_seq_views<double>(q, cap, b);
   int idx[5];
   vo_ransac_sample<5>(seed, (unsigned)h, n, idx);
   double q1[5][2], q2[5][2];
@@ -433,14 +421,13 @@ __global__ void __launch_bounds__(64 * E5_MAXSOL) k_e5_score(const double* __res
   const int b = blockIdx.y, lane = threadIdx.x & 63, k = threadIdx.x >> 6;
   e5_hyp* hp = hyps + (size_t)b * E5_BATCH + blockIdx.x;
   if (k >= hp->nsol) { if (lane == 0) hp->count[k] = 0; return; }
-  const double* qa = q + ((size_t)b * 2) * cap * 2;
-  const double* qb = qa + (size_t)cap * 2;
+  const auto [qa, qb] = vo_tv_seq_views<double>(q, cap, b);
   const double thr2 = thr2_all[b];
   double E[9];
   for (int i = 0; i < 9; i++) E[i] = hp->E[k][i];
   int cnt = 0;
   for (int i = lane; i < n; i += 64)
-    cnt += (e5_sampson(E, qa[2 * i], qa[2 * i + 1], qb[2 * i], qb[2 * i + 1]) <= thr2) ? 1 : 0;
+    cnt += (vo_sampson(E, qa[2 * i], qa[2 * i + 1], qb[2 * i], qb[2 * i + 1]) <= thr2) ? 1 : 0;
   for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
   if (lane == 0) hp->count[k] = cnt;
 }
@@ -575,23 +562,16 @@ __global__ void __launch_bounds__(256) k_e5_finish(const double* __restrict__ q,
   __shared__ double s_R[2][9], s_t[3];
   __shared__ int s_cnt[4][5];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const double* qa = q + ((size_t)b * 2) * cap * 2;
-  const double* qb = qa + (size_t)cap * 2;
-  uint8_t* mask = mask_all + (size_t)b * cap;
-  double* out = out_all + 32 * b;
+  const auto [qa, qb, mask, out] = vo_tv_seq_rows<double>(q, cap, b, mask_all, out_all, E5_OUT);
   const e5_ctrl cs = ctrl[b];
-  if (cs.best_h < 0) {
-    for (int i = tid; i < n; i += 256) mask[i] = 0;
-    if (tid < 32) out[tid] = (tid < 21) ? __builtin_nan("") : 0.0;
-    return;
-  }
+  if (cs.best_h < 0) { vo_tv_no_winner(mask, n, out, E5_OUT, 21); return; }
   const double thr2 = thr2_all[b];
   if (tid == 0) e5_decompose(cs.E, s_R[0], s_R[1], s_t);
   __syncthreads();
   int cnt[5] = {0, 0, 0, 0, 0};
   for (int i = tid; i < n; i += 256) {
     const double x1 = qa[2 * i], y1 = qa[2 * i + 1], x2 = qb[2 * i], y2 = qb[2 * i + 1];
-    const uint8_t m = (e5_sampson(cs.E, x1, y1, x2, y2) <= thr2) ? 1 : 0;
+    const uint8_t m = (vo_sampson(cs.E, x1, y1, x2, y2) <= thr2) ? 1 : 0;
     mask[i] = m;
     if (!m) continue;
     cnt[4]++;
@@ -646,14 +626,9 @@ __global__ void __launch_bounds__(256) k_e5_finish(const double* __restrict__ q,
 // host
 // ================================================================================================
 void vo_ess_destroy(vo_ctx* c) {
-  if (!c->ess) return;
-  vo_ess_ws* w = c->ess;
-  void* bufs[] = {w->d_K, w->d_p, w->d_q, w->d_hyp, w->d_ctrl, w->d_mask, w->d_out};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  if (w->h_ctrl) (void)hipHostFree(w->h_ctrl);
-  if (w->h_out) (void)hipHostFree(w->h_out);
-  delete w;
-  c->ess = nullptr;
+  if (c->ess && c->ess->d_K) (void)hipFree(c->ess->d_K);
+  if (c->ess && c->ess->d_q) (void)hipFree(c->ess->d_q);
+  vo_tv_free(c->ess);
 }
 
 extern "C" int32_t vo_essential_default_params(vo_ess_params* p) {
@@ -663,22 +638,11 @@ extern "C" int32_t vo_essential_default_params(vo_ess_params* p) {
 }
 
 static int32_t ess_alloc(vo_ctx* c, int n) {
-  const size_t B = c->batch;
-  if (c->ess && c->ess->cap < n) vo_ess_destroy(c);
-  if (!c->ess) {
-    vo_ess_ws* w = new vo_ess_ws();
-    c->ess = w;
-    w->cap = n > c->max_pts ? n : c->max_pts;
-    VO_HIP(c, hipMalloc((void**)&w->d_K, sizeof(double) * (9 + 1) * B));           // [B][9] K, then [B] squared thresholds
-    VO_HIP(c, hipMalloc((void**)&w->d_p, sizeof(float) * 4 * B * w->cap));
-    VO_HIP(c, hipMalloc((void**)&w->d_q, sizeof(double) * 4 * B * w->cap));
-    VO_HIP(c, hipMalloc((void**)&w->d_hyp, sizeof(e5_hyp) * B * E5_BATCH));
-    VO_HIP(c, hipMalloc((void**)&w->d_ctrl, sizeof(e5_ctrl) * B));
-    VO_HIP(c, hipMalloc((void**)&w->d_mask, B * w->cap));
-    VO_HIP(c, hipMalloc((void**)&w->d_out, sizeof(double) * 32 * B));
-    VO_HIP(c, hipHostMalloc((void**)&w->h_ctrl, sizeof(e5_ctrl) * B, hipHostMallocDefault));
-    VO_HIP(c, hipHostMalloc((void**)&w->h_out, sizeof(double) * (32 + 10) * B, hipHostMallocDefault));
-  }
+  int32_t r = vo_tv_alloc(c, c->ess, vo_ess_destroy, n, E5_OUT, 10);
+  if (r != VO_OK) return r;
+  vo_ess_ws* w = c->ess;
+  if (!w->d_K) VO_HIP(c, hipMalloc((void**)&w->d_K, sizeof(double) * (9 + 1) * c->batch));
+  if (!w->d_q) VO_HIP(c, hipMalloc((void**)&w->d_q, sizeof(double) * 4 * c->batch * w->cap));
   return VO_OK;
 }
 
@@ -699,8 +663,7 @@ extern "C" int32_t vo_essential_ransac(vo_ctx* c, const double* K, const float* 
   vo_ess_ws* w = c->ess;
   const size_t B = c->batch;
   const int cap = w->cap;
-  w->n = n;
-  double* h_K = w->h_out + 32 * B;                       // staging for K and the squared normalised thresholds
+  double* h_K = w->h_out + E5_OUT * B;                   // staging for K and the squared normalised thresholds
   double* d_thr2 = w->d_K + 9 * B;
   for (size_t b = 0; b < B; b++) {
     const double* Kb = K + 9 * b;
@@ -710,9 +673,8 @@ extern "C" int32_t vo_essential_ransac(vo_ctx* c, const double* K, const float* 
   }
   VO_HIP(c, hipMemcpyAsync(w->d_K, K, sizeof(double) * 9 * B, hipMemcpyHostToDevice, c->stream));
   VO_HIP(c, hipMemcpyAsync(d_thr2, h_K, sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
-  const size_t row = sizeof(float) * 2 * n, pitch = sizeof(float) * 2 * 2 * (size_t)cap;
-  VO_HIP(c, hipMemcpy2DAsync(w->d_p, pitch, pts1, row, row, B, hipMemcpyHostToDevice, c->stream));
-  VO_HIP(c, hipMemcpy2DAsync(w->d_p + (size_t)cap * 2, pitch, pts2, row, row, B, hipMemcpyHostToDevice, c->stream));
+  r = vo_tv_upload(c, c->stream, w, pts1, pts2, n);
+  if (r != VO_OK) return r;
   hipLaunchKernelGGL(k_e5_prep, dim3(vo_div_up(n, 256), (unsigned)B), dim3(256), 0, c->stream, w->d_K, w->d_p, w->d_q, cap, n);
   hipLaunchKernelGGL(k_e5_init, dim3((unsigned)B), dim3(1), 0, c->stream, w->d_ctrl, prm->max_iters);
   r = vo_ransac_rounds(c, c->stream, w->d_ctrl, w->h_ctrl, B, (prm->max_iters + E5_BATCH - 1) / E5_BATCH, [&](int) {
@@ -723,11 +685,10 @@ extern "C" int32_t vo_essential_ransac(vo_ctx* c, const double* K, const float* 
   if (r != VO_OK) return r;
   hipLaunchKernelGGL(k_e5_finish, dim3((unsigned)B), dim3(256), 0, c->stream, w->d_q, cap, n, d_thr2, prm->distance_thresh, w->d_ctrl, w->d_mask, w->d_out);
   VO_HIP(c, hipGetLastError());
-  VO_HIP(c, hipMemcpyAsync(w->h_out, w->d_out, sizeof(double) * 32 * B, hipMemcpyDeviceToHost, c->stream));
-  if (inlier_mask) VO_HIP(c, hipMemcpy2DAsync(inlier_mask, n, w->d_mask, cap, n, B, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP(c, hipStreamSynchronize(c->stream));
+  r = vo_tv_readback(c, c->stream, w, E5_OUT, inlier_mask, n);
+  if (r != VO_OK) return r;
   for (size_t b = 0; b < B; b++) {
-    const double* o = w->h_out + 32 * b;
+    const double* o = w->h_out + E5_OUT * b;
     if (E) for (int k = 0; k < 9; k++) E[9 * b + k] = o[k];
     for (int k = 0; k < 9; k++) R[9 * b + k] = o[9 + k];
     for (int k = 0; k < 3; k++) t[3 * b + k] = o[18 + k];

@@ -22,10 +22,11 @@
 // Stated deviations from cv2: err is evaluated in float64 (OpenCV: float32); for 7 < n < 15 cv2 silently switches to LMedS, this search runs
 // RANSAC for every n >= 8; for n = 7 cv2 returns all roots stacked as 9 x 3, this search evaluates the one possible sample and returns the
 // winner by the tie rule above; cv2 scales F to f33 = 1, the C ABI returns unit norm (the Python layer divides by f33).
-// Rounds of 256 hypotheses, a control block per sequence, [batch] everywhere -- the shape of vo_homography.hip; what the searches share is
-// vo_ransac.h.
+// Rounds of 256 hypotheses, a control block per sequence, [batch] everywhere.  What the searches share on the sampling side is vo_ransac.h;
+// what the two-view units share beyond it (workspace, upload and read-back, a sequence's pointers, the mask, Hartley and Gram passes of the
+// finish kernel, which the homography's finish kernel runs too) is vo_twoview.h.
 #include "vo_internal.h"
-#include "vo_ransac.h"
+#include "vo_twoview.h"
 #include "vo_epi_dev.h"
 
 #include <math.h>
@@ -42,16 +43,7 @@ struct f7_hyp { double F[F7_ROOTS][9]; double sum[F7_ROOTS]; int count[F7_ROOTS]
 struct f7_ctrl { vo_ransac_state s; int best_h, best_count, n_roots, models, pad; double best_sum; double F[9]; };
 static_assert(sizeof(f7_ctrl) == 112 && offsetof(f7_ctrl, best_h) == 12 && offsetof(f7_ctrl, best_sum) == 32 && offsetof(f7_ctrl, F) == 40, "f7_ctrl layout");
 
-struct vo_fund_ws {
-  int cap = 0;
-  float* d_p = nullptr;        // [B][2][cap][2] pixel coordinates of the two views
-  f7_hyp* d_hyp = nullptr;     // [B][F7_BATCH]
-  f7_ctrl* d_ctrl = nullptr;   // [B]
-  uint8_t* d_mask = nullptr;   // [B][cap]
-  double* d_out = nullptr;     // [B][F7_OUT]
-  f7_ctrl* h_ctrl = nullptr;   // pinned
-  double* h_out = nullptr;     // pinned
-};
+struct vo_fund_ws : vo_tv_search_ws<f7_hyp, f7_ctrl, F7_BATCH> {};
 
 // ------------------------------------------------------------------------------------------------
 // the minimal problem
@@ -72,13 +64,8 @@ __device__ inline void f7_normalise7(double (&x)[7], double (&y)[7], double& cx,
 // Fn (normalised frame) -> T2^T Fn T1 with T = [[s 0 -s cx] [0 s -s cy] [0 0 1]], scaled to unit Frobenius norm, the entry of the largest
 // magnitude positive.  -> false if an entry is not finite or the norm is 0
 __device__ inline bool f7_denormalise(const double* Fn, double c1x, double c1y, double s1, double c2x, double c2y, double s2, double* F) {
-  double M[9];
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    M[3 * r] = Fn[3 * r] * s1; M[3 * r + 1] = Fn[3 * r + 1] * s1;
-    M[3 * r + 2] = Fn[3 * r + 2] - (M[3 * r] * c1x + M[3 * r + 1] * c1y);
-  }
-  double nn = 0.0, big = 0.0, sgn = 1.0;
+  double M[9], nn = 0.0, big = 0.0, sgn = 1.0;
+  vo_tv_right_factor(Fn, c1x, c1y, s1, M);
 #pragma unroll
   for (int k = 0; k < 3; k++) {
     F[k] = M[k] * s2; F[3 + k] = M[3 + k] * s2;
@@ -300,8 +287,7 @@ __global__ void __launch_bounds__(64) k_f7_solve(const float* __restrict__ p, in
 #pragma unroll
   for (int k = 0; k < F7_ROOTS; k++) { out->count[k] = 0; out->sum[k] = 0.0; }
   if (cs->s.done) return;
-  const float* pa = p + ((size_t)b * 2) * cap * 2;
-  const float* pb = pa + (size_t)cap * 2;
+  const auto [pa, pb] = vo_tv_seq_views<float>(p, cap, b);
   int idx[7];
   vo_ransac_sample<7>(seed, (unsigned)h, n, idx);
   double x1[7], y1[7], x2[7], y2[7];
@@ -326,8 +312,7 @@ __global__ void __launch_bounds__(256) k_f7_score(const float* __restrict__ p, i
   const int model = blockIdx.x * 4 + (threadIdx.x >> 6), slot = model / F7_ROOTS, root = model - slot * F7_ROOTS;
   f7_hyp* hp = hyps + (size_t)b * F7_BATCH + slot;
   if (root >= hp->nroots) return;                        // count and sum stay 0 (k_f7_solve)
-  const float2* pa = (const float2*)(p + ((size_t)b * 2) * cap * 2);
-  const float2* pb = pa + cap;
+  const auto [pa, pb] = vo_tv_seq_views<float2>(p, cap, b);
   const double* Fp = hp->F[root];
   const double F0 = Fp[0], F1 = Fp[1], F2 = Fp[2], F3 = Fp[3], F4 = Fp[4], F5 = Fp[5], F6 = Fp[6], F7 = Fp[7], F8 = Fp[8];
   const double F[9] = {F0, F1, F2, F3, F4, F5, F6, F7, F8};
@@ -422,63 +407,25 @@ __global__ void __launch_bounds__(256) k_f7_finish(const float* __restrict__ p, 
   __shared__ double s_M[9][9], s_V[9][9];
   __shared__ double s_F[9];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const float2* pa = (const float2*)(p + ((size_t)b * 2) * cap * 2);
-  const float2* pb = pa + cap;
-  uint8_t* mask = mask_all + (size_t)b * cap;
-  double* out = out_all + F7_OUT * b;
+  const auto [pa, pb, mask, out] = vo_tv_seq_rows<float2>(p, cap, b, mask_all, out_all, F7_OUT);
   const f7_ctrl* cs = ctrl + b;
-  if (cs->best_h < 0) {
-    for (int i = tid; i < n; i += 256) mask[i] = 0;
-    if (tid < F7_OUT) out[tid] = (tid < 19) ? __builtin_nan("") : 0.0;
-    return;
-  }
+  if (cs->best_h < 0) { vo_tv_no_winner(mask, n, out, F7_OUT, 19); return; }
   double F0[9];
   for (int k = 0; k < 9; k++) F0[k] = cs->F[k];
   double acc[VO_NSUM];
-  // ---- the winner's mask (each thread re-reads below what it wrote itself), the inliers' count and centroids
-#pragma unroll
-  for (int k = 0; k < VO_NSUM; k++) acc[k] = 0.0;
-  for (int i = tid; i < n; i += 256) {
-    const float2 a = pa[i], c = pb[i];
-    double err;
-    const bool in = f7_inlier(F0, (double)a.x, (double)a.y, (double)c.x, (double)c.y, thr2, err);
-    mask[i] = in ? 1 : 0;
-    if (in) { acc[0] += 1.0; acc[1] += (double)a.x; acc[2] += (double)a.y; acc[3] += (double)c.x; acc[4] += (double)c.y; }
-  }
-  vo_block_sum(acc, s_part, s_tot);
-  const double m = s_tot[0];
-  const double c1x = s_tot[1] / m, c1y = s_tot[2] / m, c2x = s_tot[3] / m, c2y = s_tot[4] / m;
+  // ---- the winner's mask, the inliers' count and centroids
+  const vo_tv_centroids g = vo_tv_mask_pass(pa, pb, mask, n, [&](double x, double y, double u, double v) { double err; return f7_inlier(F0, x, y, u, v, thr2, err); },
+                                            acc, s_part, s_tot);
+  const double m = g.m, c1x = g.c1x, c1y = g.c1y, c2x = g.c2x, c2y = g.c2y;
   if (tid == 0) for (int k = 0; k < 9; k++) s_F[k] = F0[k];
   if (refit && m >= 8.0) {
-    // ---- Hartley scales of the inliers
-#pragma unroll
-    for (int k = 0; k < VO_NSUM; k++) acc[k] = 0.0;
-    for (int i = tid; i < n; i += 256) {
-      if (!mask[i]) continue;
-      const float2 a = pa[i], c = pb[i];
-      const double dx1 = (double)a.x - c1x, dy1 = (double)a.y - c1y, dx2 = (double)c.x - c2x, dy2 = (double)c.y - c2y;
-      acc[0] += sqrt(dx1 * dx1 + dy1 * dy1); acc[1] += sqrt(dx2 * dx2 + dy2 * dy2);
-    }
-    vo_block_sum(acc, s_part, s_tot);
-    const double s1 = 1.4142135623730951 / (s_tot[0] / m), s2 = 1.4142135623730951 / (s_tot[1] / m);
-    // ---- Gram matrix of the epipolar rows (u x, u y, u, v x, v y, v, x, y, 1)
-#pragma unroll
-    for (int k = 0; k < VO_NSUM; k++) acc[k] = 0.0;
-    for (int i = tid; i < n; i += 256) {
-      if (!mask[i]) continue;
-      const float2 a = pa[i], c = pb[i];
-      const double x = ((double)a.x - c1x) * s1, y = ((double)a.y - c1y) * s1, u = ((double)c.x - c2x) * s2, v = ((double)c.y - c2y) * s2;
-      const double r[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
-      int k = 0;
-#pragma unroll
-      for (int ia = 0; ia < 9; ia++)
-#pragma unroll
-        for (int ib = ia; ib < 9; ib++, k++) acc[k] += r[ia] * r[ib];
-    }
-    vo_block_sum(acc, s_part, s_tot);
+    // ---- Hartley scales of the inliers, then the Gram matrix of the epipolar rows (u x, u y, u, v x, v y, v, x, y, 1)
+    const auto [s1, s2] = vo_tv_scale_pass(pa, pb, mask, n, g, acc, s_part, s_tot);
+    vo_tv_gram_pass(pa, pb, mask, n, g, s1, s2, [](double x, double y, double u, double v) {
+      return vo_tv_rows<1>{{{u * x, u * y, u, v * x, v * y, v, x, y, 1.0}}};
+    }, acc, s_part, s_tot);
     if (tid == 0) {
-      for (int ia = 0, k = 0; ia < 9; ia++)
-        for (int ib = ia; ib < 9; ib++, k++) { s_M[ia][ib] = s_tot[k]; s_M[ib][ia] = s_tot[k]; }
+      vo_tv_unpack_sym9(s_tot, s_M);
       double fn[9], Fd[9], w[3];
       vo_smallest_eigenvector9(s_M, s_V, fn);
       // rank 2: the right singular vector w of the smallest singular value is the smallest eigenvector of Fn^T Fn; Fn <- Fn - (Fn w) w^T
@@ -518,38 +465,11 @@ __global__ void __launch_bounds__(256) k_f7_finish(const float* __restrict__ p, 
 // ================================================================================================
 // host
 // ================================================================================================
-void vo_fund_destroy(vo_ctx* c) {
-  if (!c->fund) return;
-  vo_fund_ws* w = c->fund;
-  void* bufs[] = {w->d_p, w->d_hyp, w->d_ctrl, w->d_mask, w->d_out};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  if (w->h_ctrl) (void)hipHostFree(w->h_ctrl);
-  if (w->h_out) (void)hipHostFree(w->h_out);
-  delete w;
-  c->fund = nullptr;
-}
+void vo_fund_destroy(vo_ctx* c) { vo_tv_free(c->fund); }
 
 extern "C" int32_t vo_fundamental_default_params(vo_fund_params* p) {
   if (!p) return VO_E_INVALID;
   p->threshold = 3.0; p->confidence = 0.99; p->max_iters = 1000; p->seed = 0; p->refit = 0; p->_pad = 0;
-  return VO_OK;
-}
-
-static int32_t fund_alloc(vo_ctx* c, int n) {
-  const size_t B = c->batch;
-  if (c->fund && c->fund->cap < n) vo_fund_destroy(c);
-  if (!c->fund) {
-    vo_fund_ws* w = new vo_fund_ws();
-    c->fund = w;
-    w->cap = n > c->max_pts ? n : c->max_pts;
-    VO_HIP(c, hipMalloc((void**)&w->d_p, sizeof(float) * 4 * B * w->cap));
-    VO_HIP(c, hipMalloc((void**)&w->d_hyp, sizeof(f7_hyp) * B * F7_BATCH));
-    VO_HIP(c, hipMalloc((void**)&w->d_ctrl, sizeof(f7_ctrl) * B));
-    VO_HIP(c, hipMalloc((void**)&w->d_mask, B * w->cap));
-    VO_HIP(c, hipMalloc((void**)&w->d_out, sizeof(double) * F7_OUT * B));
-    VO_HIP(c, hipHostMalloc((void**)&w->h_ctrl, sizeof(f7_ctrl) * B, hipHostMallocDefault));
-    VO_HIP(c, hipHostMalloc((void**)&w->h_out, sizeof(double) * F7_OUT * B, hipHostMallocDefault));
-  }
   return VO_OK;
 }
 
@@ -559,11 +479,10 @@ static int32_t fund_search(vo_ctx* c, hipStream_t q, const float* pts1, const fl
   const size_t B = c->batch;
   const int cap = w->cap;
   const double thr2 = prm->threshold * prm->threshold;
-  const size_t row = sizeof(float) * 2 * n, pitch = sizeof(float) * 2 * 2 * (size_t)cap;
-  VO_HIP(c, hipMemcpy2DAsync(w->d_p, pitch, pts1, row, row, B, hipMemcpyHostToDevice, q));
-  VO_HIP(c, hipMemcpy2DAsync(w->d_p + (size_t)cap * 2, pitch, pts2, row, row, B, hipMemcpyHostToDevice, q));
+  int32_t r = vo_tv_upload(c, q, w, pts1, pts2, n);
+  if (r != VO_OK) return r;
   hipLaunchKernelGGL(k_f7_init, dim3((unsigned)B), dim3(1), 0, q, w->d_ctrl, prm->max_iters);
-  int32_t r = vo_ransac_rounds(c, q, w->d_ctrl, w->h_ctrl, B, (prm->max_iters + F7_BATCH - 1) / F7_BATCH, [&](int) {
+  r = vo_ransac_rounds(c, q, w->d_ctrl, w->h_ctrl, B, (prm->max_iters + F7_BATCH - 1) / F7_BATCH, [&](int) {
     {
       vo_prof_scope prof(c, q, VO_PROF_FUND_SOLVE);
       hipLaunchKernelGGL(k_f7_solve, dim3(F7_BATCH / 64, (unsigned)B), dim3(64), 0, q, w->d_p, cap, n, (unsigned)prm->seed, w->d_hyp, w->d_ctrl);
@@ -583,10 +502,7 @@ static int32_t fund_search(vo_ctx* c, hipStream_t q, const float* pts1, const fl
     hipLaunchKernelGGL(k_f7_finish, dim3((unsigned)B), dim3(256), 0, q, w->d_p, cap, n, thr2, prm->refit, w->d_ctrl, w->d_mask, w->d_out);
   }
   VO_HIP(c, hipGetLastError());
-  VO_HIP(c, hipMemcpyAsync(w->h_out, w->d_out, sizeof(double) * F7_OUT * B, hipMemcpyDeviceToHost, q));
-  if (inlier_mask) VO_HIP(c, hipMemcpy2DAsync(inlier_mask, n, w->d_mask, cap, n, B, hipMemcpyDeviceToHost, q));
-  VO_HIP(c, hipStreamSynchronize(q));
-  return VO_OK;
+  return vo_tv_readback(c, q, w, F7_OUT, inlier_mask, n);
 }
 
 // pts1 / pts2 [batch][n][2] f32 (pixels, view 1 / view 2) -> F [batch][9] (the winner's, or the eight-point re-fit), F0 [batch][9] (the
@@ -602,7 +518,7 @@ extern "C" int32_t vo_fundamental_ransac(vo_ctx* c, const float* pts1, const flo
   VO_CHECK(c, prm->threshold > 0 && prm->threshold < __builtin_inf() && prm->confidence > 0 && prm->confidence < 1 && prm->max_iters >= 1 &&
            prm->refit >= 0 && prm->refit <= 1, VO_E_INVALID, "bad parameters");
   VO_HIP(c, hipSetDevice(c->device));
-  int32_t r = fund_alloc(c, n);
+  int32_t r = vo_tv_alloc(c, c->fund, vo_fund_destroy, n, F7_OUT);
   if (r != VO_OK) return r;
   r = fund_search(c, c->stream, pts1, pts2, n, prm, inlier_mask);
   if (r != VO_OK) return r;

@@ -17,11 +17,12 @@
 //              the inliers (smallest eigenvector of the 9 x 9 normal matrix by Jacobi) and up to refine_iters Levenberg-Marquardt steps on
 //              the forward transfer error in the 8 parameters of the normalised frame (its scale is isotropic, so the minimiser is the
 //              pixel error's); cost = sum of squared pixel errors over the mask at the returned H
-// Rounds of 256 hypotheses, a control block per sequence, [batch] everywhere, everything on ctx->stream -- the shape of vo_essential.hip;
-// what the two and vo_pnp.hip share (generator, bound, control head, select tail, the host's round loop) is vo_ransac.h.
+// Rounds of 256 hypotheses, a control block per sequence, [batch] everywhere, everything on ctx->stream.  What the searches share on the
+// sampling side (generator, bound, control head, select tail, the host's round loop) is vo_ransac.h; what the two-view units share beyond
+// it (workspace, upload and read-back, a sequence's pointers, the mask, Hartley and Gram passes of the finish kernel) is vo_twoview.h.
 // This library is built with -ffp-contract=off: the sign tests of checkSubset evaluate exactly as the model's float64 expressions do.
 #include "vo_internal.h"
-#include "vo_ransac.h"
+#include "vo_twoview.h"
 
 #include <math.h>
 #include <string.h>
@@ -35,16 +36,7 @@ struct h4_ctrl { vo_ransac_state s; int best_h, best_count, pad; double H[9]; };
 static_assert(sizeof(h4_ctrl) == 96 && offsetof(h4_ctrl, best_h) == 12 && offsetof(h4_ctrl, best_count) == 16 && offsetof(h4_ctrl, pad) == 20 &&
               offsetof(h4_ctrl, H) == 24, "h4_ctrl layout");
 
-struct vo_hom_ws {
-  int cap = 0;
-  float* d_p = nullptr;        // [B][2][cap][2] pixel coordinates of the two views
-  h4_hyp* d_hyp = nullptr;     // [B][H4_BATCH]
-  h4_ctrl* d_ctrl = nullptr;   // [B]
-  uint8_t* d_mask = nullptr;   // [B][cap]
-  double* d_out = nullptr;     // [B][H4_OUT]
-  h4_ctrl* h_ctrl = nullptr;   // pinned
-  double* h_out = nullptr;     // pinned
-};
+struct vo_hom_ws : vo_tv_search_ws<h4_hyp, h4_ctrl, H4_BATCH> {};
 
 // ------------------------------------------------------------------------------------------------
 // the minimal problem
@@ -90,13 +82,8 @@ __device__ inline void h4_normalise4(double (&x)[4], double (&y)[4], double& cx,
 // Hn (normalised frame) -> T2^-1 Hn T1 with T = [[s 0 -s cx] [0 s -s cy] [0 0 1]], scaled to unit Frobenius norm with h33 >= 0.
 // -> false if an entry is not finite or the norm is 0
 __device__ inline bool h4_denormalise(const double* Hn, double c1x, double c1y, double s1, double c2x, double c2y, double s2, double* H) {
-  double M[9];
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    M[3 * r] = Hn[3 * r] * s1; M[3 * r + 1] = Hn[3 * r + 1] * s1;
-    M[3 * r + 2] = Hn[3 * r + 2] - (M[3 * r] * c1x + M[3 * r + 1] * c1y);
-  }
-  double nn = 0.0;
+  double M[9], nn = 0.0;
+  vo_tv_right_factor(Hn, c1x, c1y, s1, M);
 #pragma unroll
   for (int k = 0; k < 3; k++) {
     H[k] = M[k] / s2 + c2x * M[6 + k];
@@ -181,8 +168,7 @@ __global__ void __launch_bounds__(64) k_h4_solve(const float* __restrict__ p, in
   const int h = cs->s.h_done + slot;
   out->h = h; out->count = 0; out->ok = 0;
   if (cs->s.done) return;
-  const float* pa = p + ((size_t)b * 2) * cap * 2;
-  const float* pb = pa + (size_t)cap * 2;
+  const auto [pa, pb] = vo_tv_seq_views<float>(p, cap, b);
   int idx[4];
   vo_ransac_sample<4>(seed, (unsigned)h, n, idx);
   const int i0 = idx[0], i1 = idx[1], i2 = idx[2], i3 = idx[3];
@@ -209,8 +195,7 @@ __global__ void __launch_bounds__(256) k_h4_score(const float* __restrict__ p, i
   const int b = blockIdx.y, lane = threadIdx.x & 63;
   h4_hyp* hp = hyps + (size_t)b * H4_BATCH + blockIdx.x * 4 + (threadIdx.x >> 6);
   if (!hp->ok) return;                                   // count stays 0 (k_h4_solve)
-  const float2* pa = (const float2*)(p + ((size_t)b * 2) * cap * 2);
-  const float2* pb = pa + cap;
+  const auto [pa, pb] = vo_tv_seq_views<float2>(p, cap, b);
   const double H0 = hp->H[0], H1 = hp->H[1], H2 = hp->H[2], H3 = hp->H[3], H4 = hp->H[4], H5 = hp->H[5], H6 = hp->H[6], H7 = hp->H[7], H8 = hp->H[8];
   const double H[9] = {H0, H1, H2, H3, H4, H5, H6, H7, H8};
   int cnt = 0;
@@ -287,62 +272,25 @@ __global__ void __launch_bounds__(256) k_h4_finish(const float* __restrict__ p, 
   __shared__ double s_p[8], s_try[8], s_H[9];
   __shared__ int s_flag, s_lm;
   const int b = blockIdx.x, tid = threadIdx.x;
-  const float2* pa = (const float2*)(p + ((size_t)b * 2) * cap * 2);
-  const float2* pb = pa + cap;
-  uint8_t* mask = mask_all + (size_t)b * cap;
-  double* out = out_all + H4_OUT * b;
+  const auto [pa, pb, mask, out] = vo_tv_seq_rows<float2>(p, cap, b, mask_all, out_all, H4_OUT);
   const h4_ctrl* cs = ctrl + b;
-  if (cs->best_h < 0) {
-    for (int i = tid; i < n; i += 256) mask[i] = 0;
-    if (tid < H4_OUT) out[tid] = (tid < 19) ? __builtin_nan("") : 0.0;
-    return;
-  }
+  if (cs->best_h < 0) { vo_tv_no_winner(mask, n, out, H4_OUT, 19); return; }
   double H0[9];
   for (int k = 0; k < 9; k++) H0[k] = cs->H[k];
   double acc[H4_NSUM];
-  // ---- the winner's mask (each thread re-reads below what it wrote itself), the inliers' count and centroids
-#pragma unroll
-  for (int k = 0; k < H4_NSUM; k++) acc[k] = 0.0;
-  for (int i = tid; i < n; i += 256) {
-    const float2 a = pa[i], c = pb[i];
-    const bool in = h4_inlier(H0, (double)a.x, (double)a.y, (double)c.x, (double)c.y, thr2);
-    mask[i] = in ? 1 : 0;
-    if (in) { acc[0] += 1.0; acc[1] += (double)a.x; acc[2] += (double)a.y; acc[3] += (double)c.x; acc[4] += (double)c.y; }
-  }
-  vo_block_sum(acc, s_part, s_tot);
-  const double m = s_tot[0];
-  const double c1x = s_tot[1] / m, c1y = s_tot[2] / m, c2x = s_tot[3] / m, c2y = s_tot[4] / m;
+  // ---- the winner's mask, the inliers' count and centroids
+  const vo_tv_centroids g = vo_tv_mask_pass(pa, pb, mask, n, [&](double x, double y, double u, double v) { return h4_inlier(H0, x, y, u, v, thr2); },
+                                            acc, s_part, s_tot);
+  const double m = g.m, c1x = g.c1x, c1y = g.c1y, c2x = g.c2x, c2y = g.c2y;
   if (tid == 0) { for (int k = 0; k < 9; k++) s_H[k] = H0[k]; s_lm = 0; s_flag = 0; }
   if (n > 4) {
-    // ---- Hartley scales of the inliers
-#pragma unroll
-    for (int k = 0; k < H4_NSUM; k++) acc[k] = 0.0;
-    for (int i = tid; i < n; i += 256) {
-      if (!mask[i]) continue;
-      const float2 a = pa[i], c = pb[i];
-      const double dx1 = (double)a.x - c1x, dy1 = (double)a.y - c1y, dx2 = (double)c.x - c2x, dy2 = (double)c.y - c2y;
-      acc[0] += sqrt(dx1 * dx1 + dy1 * dy1); acc[1] += sqrt(dx2 * dx2 + dy2 * dy2);
-    }
-    vo_block_sum(acc, s_part, s_tot);
-    const double s1 = 1.4142135623730951 / (s_tot[0] / m), s2 = 1.4142135623730951 / (s_tot[1] / m);
-    // ---- normal matrix of the DLT rows (-x -y -1 0 0 0 ux uy u), (0 0 0 -x -y -1 vx vy v)
-#pragma unroll
-    for (int k = 0; k < H4_NSUM; k++) acc[k] = 0.0;
-    for (int i = tid; i < n; i += 256) {
-      if (!mask[i]) continue;
-      const float2 a = pa[i], c = pb[i];
-      const double x = ((double)a.x - c1x) * s1, y = ((double)a.y - c1y) * s1, u = ((double)c.x - c2x) * s2, v = ((double)c.y - c2y) * s2;
-      const double r1[9] = {-x, -y, -1.0, 0.0, 0.0, 0.0, u * x, u * y, u}, r2[9] = {0.0, 0.0, 0.0, -x, -y, -1.0, v * x, v * y, v};
-      int k = 0;
-#pragma unroll
-      for (int ia = 0; ia < 9; ia++)
-#pragma unroll
-        for (int ib = ia; ib < 9; ib++, k++) acc[k] += r1[ia] * r1[ib] + r2[ia] * r2[ib];
-    }
-    vo_block_sum(acc, s_part, s_tot);
+    // ---- Hartley scales of the inliers, then the normal matrix of the DLT rows (-x -y -1 0 0 0 ux uy u), (0 0 0 -x -y -1 vx vy v)
+    const auto [s1, s2] = vo_tv_scale_pass(pa, pb, mask, n, g, acc, s_part, s_tot);
+    vo_tv_gram_pass(pa, pb, mask, n, g, s1, s2, [](double x, double y, double u, double v) {
+      return vo_tv_rows<2>{{{-x, -y, -1.0, 0.0, 0.0, 0.0, u * x, u * y, u}, {0.0, 0.0, 0.0, -x, -y, -1.0, v * x, v * y, v}}};
+    }, acc, s_part, s_tot);
     if (tid == 0) {
-      for (int ia = 0, k = 0; ia < 9; ia++)
-        for (int ib = ia; ib < 9; ib++, k++) { s_M[ia][ib] = s_tot[k]; s_M[ib][ia] = s_tot[k]; }
+      vo_tv_unpack_sym9(s_tot, s_M);
       double hn[9];
       vo_smallest_eigenvector9(s_M, s_V, hn);
       bool ok = true;
@@ -453,38 +401,11 @@ __global__ void __launch_bounds__(256) k_h4_finish(const float* __restrict__ p, 
 // ================================================================================================
 // host
 // ================================================================================================
-void vo_hom_destroy(vo_ctx* c) {
-  if (!c->hom) return;
-  vo_hom_ws* w = c->hom;
-  void* bufs[] = {w->d_p, w->d_hyp, w->d_ctrl, w->d_mask, w->d_out};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  if (w->h_ctrl) (void)hipHostFree(w->h_ctrl);
-  if (w->h_out) (void)hipHostFree(w->h_out);
-  delete w;
-  c->hom = nullptr;
-}
+void vo_hom_destroy(vo_ctx* c) { vo_tv_free(c->hom); }
 
 extern "C" int32_t vo_homography_default_params(vo_hom_params* p) {
   if (!p) return VO_E_INVALID;
   p->threshold = 3.0; p->confidence = 0.995; p->max_iters = 2000; p->seed = 0; p->refine_iters = 10; p->_pad = 0;
-  return VO_OK;
-}
-
-static int32_t hom_alloc(vo_ctx* c, int n) {
-  const size_t B = c->batch;
-  if (c->hom && c->hom->cap < n) vo_hom_destroy(c);
-  if (!c->hom) {
-    vo_hom_ws* w = new vo_hom_ws();
-    c->hom = w;
-    w->cap = n > c->max_pts ? n : c->max_pts;
-    VO_HIP(c, hipMalloc((void**)&w->d_p, sizeof(float) * 4 * B * w->cap));
-    VO_HIP(c, hipMalloc((void**)&w->d_hyp, sizeof(h4_hyp) * B * H4_BATCH));
-    VO_HIP(c, hipMalloc((void**)&w->d_ctrl, sizeof(h4_ctrl) * B));
-    VO_HIP(c, hipMalloc((void**)&w->d_mask, B * w->cap));
-    VO_HIP(c, hipMalloc((void**)&w->d_out, sizeof(double) * H4_OUT * B));
-    VO_HIP(c, hipHostMalloc((void**)&w->h_ctrl, sizeof(h4_ctrl) * B, hipHostMallocDefault));
-    VO_HIP(c, hipHostMalloc((void**)&w->h_out, sizeof(double) * H4_OUT * B, hipHostMallocDefault));
-  }
   return VO_OK;
 }
 
@@ -505,15 +426,14 @@ int32_t vo_hom_ransac_tail(vo_ctx* c, const float* pts1, const float* pts2, int3
   VO_CHECK(c, prm->threshold > 0 && prm->confidence > 0 && prm->confidence < 1 && prm->max_iters >= 1 && prm->refine_iters >= 0 && prm->refine_iters <= 100,
            VO_E_INVALID, "bad parameters");
   VO_HIP(c, hipSetDevice(c->device));
-  int32_t r = hom_alloc(c, n);
+  int32_t r = vo_tv_alloc(c, c->hom, vo_hom_destroy, n, H4_OUT);
   if (r != VO_OK) return r;
   vo_hom_ws* w = c->hom;
   const size_t B = c->batch;
   const int cap = w->cap;
   const double thr2 = prm->threshold * prm->threshold;
-  const size_t row = sizeof(float) * 2 * n, pitch = sizeof(float) * 2 * 2 * (size_t)cap;
-  VO_HIP(c, hipMemcpy2DAsync(w->d_p, pitch, pts1, row, row, B, hipMemcpyHostToDevice, c->stream));
-  VO_HIP(c, hipMemcpy2DAsync(w->d_p + (size_t)cap * 2, pitch, pts2, row, row, B, hipMemcpyHostToDevice, c->stream));
+  r = vo_tv_upload(c, c->stream, w, pts1, pts2, n);
+  if (r != VO_OK) return r;
   hipLaunchKernelGGL(k_h4_init, dim3((unsigned)B), dim3(1), 0, c->stream, w->d_ctrl, prm->max_iters);
   r = vo_ransac_rounds(c, c->stream, w->d_ctrl, w->h_ctrl, B, (prm->max_iters + H4_BATCH - 1) / H4_BATCH, [&](int) {
     {
@@ -539,9 +459,8 @@ int32_t vo_hom_ransac_tail(vo_ctx* c, const float* pts1, const float* pts2, int3
     r = tail->enqueue(c, c->stream, w->d_p, cap, n, w->d_out, H4_OUT, w->d_mask, tail->user);
     if (r != VO_OK) return r;
   }
-  VO_HIP(c, hipMemcpyAsync(w->h_out, w->d_out, sizeof(double) * H4_OUT * B, hipMemcpyDeviceToHost, c->stream));
-  if (inlier_mask) VO_HIP(c, hipMemcpy2DAsync(inlier_mask, n, w->d_mask, cap, n, B, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP(c, hipStreamSynchronize(c->stream));
+  r = vo_tv_readback(c, c->stream, w, H4_OUT, inlier_mask, n);
+  if (r != VO_OK) return r;
   for (size_t b = 0; b < B; b++) {
     const double* o = w->h_out + H4_OUT * b;
     const bool none = w->h_ctrl[b].best_h < 0;

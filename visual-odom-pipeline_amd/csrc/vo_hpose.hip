@@ -9,12 +9,15 @@
 //              {(R, t, n), (R, -t, -n)} in closed form, s^2 - 1 entering as (s - 1)(s + 1); s1 - s3 <= 2^-26 is a rotation (one solution,
 //              t = n = 0); det = 0, a zero focal length or an entry that is not finite has no solution
 //   vote       256 threads stride over the points: n_good = mask points with n . m1 > 0 and (R n) . m2 > 0, n_off = points outside the mask
-//              within the Sampson threshold of E = [t / |t|]x R (the expression of e5_sampson), m = ((p - c) / f, 1) in float64
+//              within the Sampson threshold of E = [t / |t|]x R (vo_sampson of vo_epi_dev.h, the essential search's), m = ((p - c) / f, 1)
+//              in float64
 //   reduce     __shfl_xor across the wave, the four waves through LDS in a fixed order: no atomics, no scratch
 //   rank       one lane: viable first, n_off, the hint, n_good, then trace R and the normal's entries; the ambiguity verdict
-// One kernel, grid (batch); vo_homography_pose enqueues it behind k_h4_finish on the search's stream (vo_hom_ransac_tail).
+// One kernel, grid (batch); vo_homography_pose enqueues it behind k_h4_finish on the search's stream (vo_hom_ransac_tail).  The workspace,
+// the upload of the two views and a sequence's pointers are the two-view units' own: vo_twoview.h.
 // This library is built with -ffp-contract=off: each vote expression rounds as the model's does.
-#include "vo_internal.h"
+#include "vo_twoview.h"
+#include "vo_epi_dev.h"
 
 #include <math.h>
 #include <string.h>
@@ -25,13 +28,8 @@
 #define HP_MERGE_TOL 9.5367431640625e-07       // 2^-20
 #define HP_NCNT 9              // n_good (4), n_off (4), n_mask
 
-struct vo_hpose_ws {
-  int cap = 0;
+struct vo_hpose_ws : vo_tv_ws {
   double* d_K = nullptr;       // [B][9] K, then [B][9] H
-  float* d_p = nullptr;        // [B][2][cap][2] pixel coordinates of the two views
-  uint8_t* d_mask = nullptr;   // [B][cap]
-  double* d_out = nullptr;     // [B][HP_OUT]
-  double* h_out = nullptr;     // pinned
 };
 
 // the candidates of one sequence as the one lane leaves them for the vote, in the order of the formulas
@@ -41,13 +39,6 @@ __device__ __forceinline__ bool hp_finite(double x) { return fabs(x) < __builtin
 
 __device__ __forceinline__ void hp_cross(const double* a, const double* b, double* c) {
   c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-__device__ __forceinline__ double hp_sampson(const double* E, double x1, double y1, double x2, double y2) {     // e5_sampson
-  const double a0 = E[0] * x1 + E[1] * y1 + E[2], a1 = E[3] * x1 + E[4] * y1 + E[5], a2 = E[6] * x1 + E[7] * y1 + E[8];
-  const double b0 = E[0] * x2 + E[3] * y2 + E[6], b1 = E[1] * x2 + E[4] * y2 + E[7];
-  const double num = x2 * a0 + y2 * a1 + a2;
-  return num * num / (a0 * a0 + a1 * a1 + b0 * b0 + b1 * b1);
 }
 
 // K (fx, fy, cx, cy of the 3 x 3), H -> the candidates in LDS; c->ns = 0 without a solution.  Every loop has constant bounds and the
@@ -218,8 +209,7 @@ __global__ void __launch_bounds__(256) k_hpose(const double* __restrict__ Kall, 
 #pragma unroll
   for (int k = 0; k < HP_NCNT; k++) cnt[k] = 0;
   if (n > 0) {
-    const float2* pa = (const float2*)(p + ((size_t)b * 2) * cap * 2);
-    const float2* pb = pa + cap;
+    const auto [pa, pb] = vo_tv_seq_views<float2>(p, cap, b);
     const uint8_t* mask = mask_all ? mask_all + (size_t)b * cap : nullptr;
     const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
     const double tn = prm.threshold / ((fx + fy) / 2.0);
@@ -238,7 +228,7 @@ __global__ void __launch_bounds__(256) k_hpose(const double* __restrict__ Kall, 
           const double d2 = (s_c.rn[k][0] * x2 + s_c.rn[k][1] * y2) + s_c.rn[k][2];
           cnt[k] += (d1 > 0 && d2 > 0) ? 1 : 0;
         } else {
-          cnt[4 + k] += (hp_sampson(s_c.E[k], x1, y1, x2, y2) <= thr2) ? 1 : 0;
+          cnt[4 + k] += (vo_sampson(s_c.E[k], x1, y1, x2, y2) <= thr2) ? 1 : 0;
         }
       }
     }
@@ -300,13 +290,8 @@ __global__ void __launch_bounds__(256) k_hpose(const double* __restrict__ Kall, 
 // host
 // ================================================================================================
 void vo_hpose_destroy(vo_ctx* c) {
-  if (!c->hpose) return;
-  vo_hpose_ws* w = c->hpose;
-  void* bufs[] = {w->d_K, w->d_p, w->d_mask, w->d_out};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  if (w->h_out) (void)hipHostFree(w->h_out);
-  delete w;
-  c->hpose = nullptr;
+  if (c->hpose && c->hpose->d_K) (void)hipFree(c->hpose->d_K);
+  vo_tv_free(c->hpose);
 }
 
 extern "C" int32_t vo_homography_pose_default_params(vo_hpose_params* p) {
@@ -330,19 +315,9 @@ static int32_t hpose_check(vo_ctx* c, const vo_hpose_params* prm) {
 }
 
 static int32_t hpose_alloc(vo_ctx* c, int n) {
-  const size_t B = c->batch;
-  if (c->hpose && c->hpose->cap < n) vo_hpose_destroy(c);
-  if (!c->hpose) {
-    vo_hpose_ws* w = new vo_hpose_ws();
-    c->hpose = w;
-    w->cap = n > c->max_pts ? n : c->max_pts;
-    if (w->cap < 1) w->cap = 1;
-    VO_HIP(c, hipMalloc((void**)&w->d_K, sizeof(double) * 18 * B));
-    VO_HIP(c, hipMalloc((void**)&w->d_p, sizeof(float) * 4 * B * w->cap));
-    VO_HIP(c, hipMalloc((void**)&w->d_mask, B * w->cap));
-    VO_HIP(c, hipMalloc((void**)&w->d_out, sizeof(double) * HP_OUT * B));
-    VO_HIP(c, hipHostMalloc((void**)&w->h_out, sizeof(double) * HP_OUT * B, hipHostMallocDefault));
-  }
+  int32_t r = vo_tv_alloc(c, c->hpose, vo_hpose_destroy, n, HP_OUT, 0, 1);
+  if (r != VO_OK) return r;
+  if (!c->hpose->d_K) VO_HIP(c, hipMalloc((void**)&c->hpose->d_K, sizeof(double) * 18 * c->batch));
   return VO_OK;
 }
 
@@ -391,9 +366,8 @@ extern "C" int32_t vo_homography_decompose(vo_ctx* c, const double* K, const dou
   VO_HIP(c, hipMemcpyAsync(w->d_K, K, sizeof(double) * 9 * B, hipMemcpyHostToDevice, c->stream));
   VO_HIP(c, hipMemcpyAsync(w->d_K + 9 * B, H, sizeof(double) * 9 * B, hipMemcpyHostToDevice, c->stream));
   if (n > 0) {
-    const size_t row = sizeof(float) * 2 * n, pitch = sizeof(float) * 2 * 2 * (size_t)cap;
-    VO_HIP(c, hipMemcpy2DAsync(w->d_p, pitch, pts1, row, row, B, hipMemcpyHostToDevice, c->stream));
-    VO_HIP(c, hipMemcpy2DAsync(w->d_p + (size_t)cap * 2, pitch, pts2, row, row, B, hipMemcpyHostToDevice, c->stream));
+    r = vo_tv_upload(c, c->stream, w, pts1, pts2, n);
+    if (r != VO_OK) return r;
     if (mask) VO_HIP(c, hipMemcpy2DAsync(w->d_mask, cap, mask, n, n, B, hipMemcpyHostToDevice, c->stream));
   }
   hpose_launch(c, c->stream, w->d_K + 9 * B, 9, w->d_p, cap, (n > 0 && mask) ? w->d_mask : nullptr, n, prm);

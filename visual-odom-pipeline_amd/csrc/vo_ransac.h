@@ -4,6 +4,8 @@
 //   host    the round loop of the synchronous entry points: enqueue a round, read the control blocks back, stop when every sequence is done
 // The generator and the bound are part of each search's definition: oracle/pnp_oracle.py, oracle/essential_oracle.py,
 // tests/homography_model.py and tests/fundamental_model.py each carry their own copy and are compared with the device hypothesis by hypothesis.
+// What only the two-view units share -- workspace, upload and read-back, the passes of the finish kernels with their 45-sum reduction and
+// the 9 x 9 eigenvector -- is vo_twoview.h, on top of this header; PnP needs none of it.
 #pragma once
 #include "vo_internal.h"
 
@@ -85,47 +87,4 @@ inline int32_t vo_ransac_rounds(vo_ctx* c, hipStream_t q, const Ctrl* d_ctrl, Ct
     if (all) break;
   }
   return VO_OK;
-}
-
-// What the finish kernels of the homography and the fundamental-matrix search share: a 256-thread reduction of VO_NSUM running sums (the 45
-// distinct entries of a 9 x 9 normal matrix) and the eigenvector of its smallest eigenvalue
-#define VO_NSUM 45
-
-// sum of every acc[k] over the 256 threads -> s_tot[k], the same order every time (wave shuffles, then the four waves in order)
-__device__ inline void vo_block_sum(double (&acc)[VO_NSUM], double (*s_part)[VO_NSUM], double* s_tot) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  __syncthreads();                                       // the previous totals have been read
-#pragma unroll
-  for (int k = 0; k < VO_NSUM; k++) {
-    double v = acc[k];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (lane == 0) s_part[wave][k] = v;
-  }
-  __syncthreads();
-  if (tid < VO_NSUM) s_tot[tid] = (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]);
-  __syncthreads();
-}
-
-// eigenvector of the smallest eigenvalue of the symmetric 9 x 9 M (destroyed) by cyclic Jacobi rotations; one thread, arrays in LDS
-__device__ inline void vo_smallest_eigenvector9(double (*M)[9], double (*V)[9], double* out) {
-  for (int i = 0; i < 9; i++) for (int j = 0; j < 9; j++) V[i][j] = (i == j) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 60; sweep++) {
-    bool changed = false;
-    for (int p = 0; p < 8; p++)
-      for (int q = p + 1; q < 9; q++) {
-        const double apq = M[p][q];
-        if (!(apq * apq > 4.930380657631324e-32 * fabs(M[p][p] * M[q][q]))) continue;      // |a_pq| <= 2^-52 sqrt(a_pp a_qq): converged
-        changed = true;
-        const double zeta = (M[q][q] - M[p][p]) / (2.0 * apq);
-        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-        for (int k = 0; k < 9; k++) { const double a = M[k][p], bq = M[k][q]; M[k][p] = c * a - s * bq; M[k][q] = s * a + c * bq; }
-        for (int k = 0; k < 9; k++) { const double a = M[p][k], bq = M[q][k]; M[p][k] = c * a - s * bq; M[q][k] = s * a + c * bq; }
-        for (int k = 0; k < 9; k++) { const double a = V[k][p], bq = V[k][q]; V[k][p] = c * a - s * bq; V[k][q] = s * a + c * bq; }
-      }
-    if (!changed) break;
-  }
-  int j = 0;
-  for (int k = 1; k < 9; k++) if (M[k][k] < M[j][j]) j = k;
-  for (int k = 0; k < 9; k++) out[k] = V[k][j];
 }

@@ -1,0 +1,235 @@
+// What the four two-view units (vo_essential.hip, vo_homography.hip, vo_fundamental.hip, vo_hpose.hip) have in common beyond the sampling
+// side of vo_ransac.h, in one place:
+//   host    the workspace -- the two views [B][2][cap][2] f32, the mask, the result rows and their pinned copy; a search adds its hypotheses
+//           and control blocks -- with its allocate-or-regrow and free, the upload of the two views and the read-back of result and mask
+//   device  a sequence's pointers into those buffers, the no-winner exit of a finish kernel, and what k_h4_finish and k_f7_finish do alike:
+//           the 256-thread reduction of VO_NSUM sums, the winner's mask with count and centroids, the Hartley scales, the Gram matrix of the
+//           normalised inliers' rows, its unpacking, the 9 x 9 eigenvector, and the right factor of the two denormalisations
+// Samplers, minimal solvers, left factors and sign rules are each model's own and stay in its unit.
+#pragma once
+#include "vo_ransac.h"
+
+// ================================================================================================
+// host
+// ================================================================================================
+struct vo_tv_ws {
+  static constexpr bool search = false;
+  int cap = 0;
+  float* d_p = nullptr;        // [B][2][cap][2] pixel coordinates of the two views
+  uint8_t* d_mask = nullptr;   // [B][cap]
+  double* d_out = nullptr;     // [B][n_out]
+  double* h_out = nullptr;     // pinned
+};
+
+template <class Hyp, class Ctrl, int Batch>
+struct vo_tv_search_ws : vo_tv_ws {
+  static constexpr bool search = true;
+  static constexpr int batch = Batch;
+  Hyp* d_hyp = nullptr;        // [B][Batch]
+  Ctrl* d_ctrl = nullptr;      // [B]
+  Ctrl* h_ctrl = nullptr;      // pinned
+};
+
+// the shared buffers of *slot and the workspace itself; a unit's destroy frees its own buffers first.  Copes with null members
+template <class W>
+inline void vo_tv_free(W*& slot) {
+  W* w = slot;
+  if (!w) return;
+  void* bufs[] = {w->d_p, w->d_mask, w->d_out};
+  for (void* p : bufs) if (p) (void)hipFree(p);
+  if constexpr (W::search) {
+    if (w->d_hyp) (void)hipFree(w->d_hyp);
+    if (w->d_ctrl) (void)hipFree(w->d_ctrl);
+    if (w->h_ctrl) (void)hipHostFree(w->h_ctrl);
+  }
+  if (w->h_out) (void)hipHostFree(w->h_out);
+  delete w;
+  slot = nullptr;
+}
+
+// *slot for n correspondences: a workspace of cap < n goes (by the unit's destroy), a new one has cap = max(n, max_pts, min_cap) and
+// n_out (+ h_extra in the pinned copy) doubles per sequence.  It is attached before its buffers are allocated, so a failed allocation
+// leaves it to destroy.  A unit allocates its own buffers behind this call, where they are still null
+template <class W>
+inline int32_t vo_tv_alloc(vo_ctx* c, W*& slot, void (*destroy)(vo_ctx*), int n, int n_out, int h_extra = 0, int min_cap = 0) {
+  const size_t B = c->batch;
+  if (slot && slot->cap < n) destroy(c);
+  if (slot) return VO_OK;
+  W* w = new W();
+  slot = w;
+  w->cap = n > c->max_pts ? n : c->max_pts;
+  if (w->cap < min_cap) w->cap = min_cap;
+  VO_HIP(c, hipMalloc((void**)&w->d_p, sizeof(float) * 4 * B * w->cap));
+  if constexpr (W::search) {
+    VO_HIP(c, hipMalloc((void**)&w->d_hyp, sizeof(*w->d_hyp) * B * W::batch));
+    VO_HIP(c, hipMalloc((void**)&w->d_ctrl, sizeof(*w->d_ctrl) * B));
+  }
+  VO_HIP(c, hipMalloc((void**)&w->d_mask, B * w->cap));
+  VO_HIP(c, hipMalloc((void**)&w->d_out, sizeof(double) * n_out * B));
+  if constexpr (W::search) VO_HIP(c, hipHostMalloc((void**)&w->h_ctrl, sizeof(*w->h_ctrl) * B, hipHostMallocDefault));
+  VO_HIP(c, hipHostMalloc((void**)&w->h_out, sizeof(double) * (n_out + h_extra) * B, hipHostMallocDefault));
+  return VO_OK;
+}
+
+// pts1 / pts2 [B][n][2] f32 of the host -> the two views of every sequence, on q
+inline int32_t vo_tv_upload(vo_ctx* c, hipStream_t q, const vo_tv_ws* w, const float* pts1, const float* pts2, int n) {
+  const size_t row = sizeof(float) * 2 * n, pitch = sizeof(float) * 2 * 2 * (size_t)w->cap;
+  VO_HIP(c, hipMemcpy2DAsync(w->d_p, pitch, pts1, row, row, c->batch, hipMemcpyHostToDevice, q));
+  VO_HIP(c, hipMemcpy2DAsync(w->d_p + (size_t)w->cap * 2, pitch, pts2, row, row, c->batch, hipMemcpyHostToDevice, q));
+  return VO_OK;
+}
+
+// the result rows -> h_out, the mask -> inlier_mask [B][n] (if asked for), and the end of everything enqueued on q
+inline int32_t vo_tv_readback(vo_ctx* c, hipStream_t q, const vo_tv_ws* w, int n_out, uint8_t* inlier_mask, int n) {
+  VO_HIP(c, hipMemcpyAsync(w->h_out, w->d_out, sizeof(double) * n_out * c->batch, hipMemcpyDeviceToHost, q));
+  if (inlier_mask) VO_HIP(c, hipMemcpy2DAsync(inlier_mask, n, w->d_mask, w->cap, n, c->batch, hipMemcpyDeviceToHost, q));
+  VO_HIP(c, hipStreamSynchronize(q));
+  return VO_OK;
+}
+
+// ================================================================================================
+// device
+// ================================================================================================
+// Sequence b's two views in p [B][2][cap][2] of scalars S (float: pixels, double: the essential search's normalised coordinates), as
+// elements T: S itself or a pair of them (float2)
+template <class T> struct vo_tv_views { const T *pa, *pb; };
+template <class T, class S>
+__device__ __forceinline__ vo_tv_views<T> vo_tv_seq_views(const S* p, int cap, int b) {
+  const S* pa = p + ((size_t)b * 2) * cap * 2;
+  return {(const T*)pa, (const T*)(pa + (size_t)cap * 2)};
+}
+
+// ... with the sequence's mask row and result row of n_out doubles: what a finish kernel works on
+template <class T> struct vo_tv_seq { const T *pa, *pb; uint8_t* mask; double* out; };
+template <class T, class S>
+__device__ __forceinline__ vo_tv_seq<T> vo_tv_seq_rows(const S* p, int cap, int b, uint8_t* mask_all, double* out_all, int n_out) {
+  const vo_tv_views<T> v = vo_tv_seq_views<T>(p, cap, b);
+  return {v.pa, v.pb, mask_all + (size_t)b * cap, out_all + n_out * b};
+}
+
+// a finish kernel's exit for a sequence without a winner: an empty mask, the first n_nan of the n_out results NaN, the rest 0
+__device__ __forceinline__ void vo_tv_no_winner(uint8_t* mask, int n, double* out, int n_out, int n_nan) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n; i += 256) mask[i] = 0;
+  if (tid < n_out) out[tid] = (tid < n_nan) ? __builtin_nan("") : 0.0;
+}
+
+// a 256-thread reduction of VO_NSUM running sums (the 45 distinct entries of a 9 x 9 normal matrix)
+#define VO_NSUM 45
+
+// sum of every acc[k] over the 256 threads -> s_tot[k], the same order every time (wave shuffles, then the four waves in order)
+__device__ inline void vo_block_sum(double (&acc)[VO_NSUM], double (*s_part)[VO_NSUM], double* s_tot) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __syncthreads();                                       // the previous totals have been read
+#pragma unroll
+  for (int k = 0; k < VO_NSUM; k++) {
+    double v = acc[k];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (lane == 0) s_part[wave][k] = v;
+  }
+  __syncthreads();
+  if (tid < VO_NSUM) s_tot[tid] = (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]);
+  __syncthreads();
+}
+
+// The passes of a finish kernel over the n points of its sequence, 256 threads; acc, s_part and s_tot are the kernel's reduction buffers.
+// The winner's mask (each thread re-reads in the later passes what it wrote itself) -> the inliers' count m and the centroids of the two
+// views; inlier(x, y, u, v) is the model's consensus test
+struct vo_tv_centroids { double m, c1x, c1y, c2x, c2y; };
+template <class In>
+__device__ __forceinline__ vo_tv_centroids vo_tv_mask_pass(const float2* pa, const float2* pb, uint8_t* mask, int n, In inlier,
+                                                           double (&acc)[VO_NSUM], double (*s_part)[VO_NSUM], double* s_tot) {
+#pragma unroll
+  for (int k = 0; k < VO_NSUM; k++) acc[k] = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float2 a = pa[i], c = pb[i];
+    const bool in = inlier((double)a.x, (double)a.y, (double)c.x, (double)c.y);
+    mask[i] = in ? 1 : 0;
+    if (in) { acc[0] += 1.0; acc[1] += (double)a.x; acc[2] += (double)a.y; acc[3] += (double)c.x; acc[4] += (double)c.y; }
+  }
+  vo_block_sum(acc, s_part, s_tot);
+  const double m = s_tot[0];
+  return {m, s_tot[1] / m, s_tot[2] / m, s_tot[3] / m, s_tot[4] / m};
+}
+
+// Hartley scales of the inliers about their centroids: mean distance sqrt 2
+struct vo_tv_scales { double s1, s2; };
+__device__ __forceinline__ vo_tv_scales vo_tv_scale_pass(const float2* pa, const float2* pb, const uint8_t* mask, int n, const vo_tv_centroids& g,
+                                                         double (&acc)[VO_NSUM], double (*s_part)[VO_NSUM], double* s_tot) {
+#pragma unroll
+  for (int k = 0; k < VO_NSUM; k++) acc[k] = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    if (!mask[i]) continue;
+    const float2 a = pa[i], c = pb[i];
+    const double dx1 = (double)a.x - g.c1x, dy1 = (double)a.y - g.c1y, dx2 = (double)c.x - g.c2x, dy2 = (double)c.y - g.c2y;
+    acc[0] += sqrt(dx1 * dx1 + dy1 * dy1); acc[1] += sqrt(dx2 * dx2 + dy2 * dy2);
+  }
+  vo_block_sum(acc, s_part, s_tot);
+  return {1.4142135623730951 / (s_tot[0] / g.m), 1.4142135623730951 / (s_tot[1] / g.m)};
+}
+
+// Gram matrix (its 45 distinct entries -> s_tot) of the one or two rows that rows(x, y, u, v) gives for each normalised inlier
+template <int NR> struct vo_tv_rows { double r[NR][9]; };
+template <class Rows>
+__device__ __forceinline__ void vo_tv_gram_pass(const float2* pa, const float2* pb, const uint8_t* mask, int n, const vo_tv_centroids& g,
+                                                double s1, double s2, Rows rows, double (&acc)[VO_NSUM], double (*s_part)[VO_NSUM], double* s_tot) {
+#pragma unroll
+  for (int k = 0; k < VO_NSUM; k++) acc[k] = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    if (!mask[i]) continue;
+    const float2 a = pa[i], c = pb[i];
+    const double x = ((double)a.x - g.c1x) * s1, y = ((double)a.y - g.c1y) * s1, u = ((double)c.x - g.c2x) * s2, v = ((double)c.y - g.c2y) * s2;
+    const auto q = rows(x, y, u, v);
+    constexpr int NR = sizeof(q.r) / sizeof(q.r[0]);
+    static_assert(NR == 1 || NR == 2, "one or two rows per point");
+    int k = 0;
+#pragma unroll
+    for (int ia = 0; ia < 9; ia++)
+#pragma unroll
+      for (int ib = ia; ib < 9; ib++, k++) {
+        if constexpr (NR == 2) acc[k] += q.r[0][ia] * q.r[0][ib] + q.r[1][ia] * q.r[1][ib];
+        else acc[k] += q.r[0][ia] * q.r[0][ib];
+      }
+  }
+  vo_block_sum(acc, s_part, s_tot);
+}
+
+// the 45 sums -> the symmetric 9 x 9
+__device__ __forceinline__ void vo_tv_unpack_sym9(const double* s_tot, double (*M)[9]) {
+  for (int ia = 0, k = 0; ia < 9; ia++)
+    for (int ib = ia; ib < 9; ib++, k++) { M[ia][ib] = s_tot[k]; M[ib][ia] = s_tot[k]; }
+}
+
+// eigenvector of the smallest eigenvalue of the symmetric 9 x 9 M (destroyed) by cyclic Jacobi rotations; one thread, arrays in LDS
+__device__ inline void vo_smallest_eigenvector9(double (*M)[9], double (*V)[9], double* out) {
+  for (int i = 0; i < 9; i++) for (int j = 0; j < 9; j++) V[i][j] = (i == j) ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 60; sweep++) {
+    bool changed = false;
+    for (int p = 0; p < 8; p++)
+      for (int q = p + 1; q < 9; q++) {
+        const double apq = M[p][q];
+        if (!(apq * apq > 4.930380657631324e-32 * fabs(M[p][p] * M[q][q]))) continue;      // |a_pq| <= 2^-52 sqrt(a_pp a_qq): converged
+        changed = true;
+        const double zeta = (M[q][q] - M[p][p]) / (2.0 * apq);
+        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+        const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+        for (int k = 0; k < 9; k++) { const double a = M[k][p], bq = M[k][q]; M[k][p] = c * a - s * bq; M[k][q] = s * a + c * bq; }
+        for (int k = 0; k < 9; k++) { const double a = M[p][k], bq = M[q][k]; M[p][k] = c * a - s * bq; M[q][k] = s * a + c * bq; }
+        for (int k = 0; k < 9; k++) { const double a = V[k][p], bq = V[k][q]; V[k][p] = c * a - s * bq; V[k][q] = s * a + c * bq; }
+      }
+    if (!changed) break;
+  }
+  int j = 0;
+  for (int k = 1; k < 9; k++) if (M[k][k] < M[j][j]) j = k;
+  for (int k = 0; k < 9; k++) out[k] = V[k][j];
+}
+
+// The right factor of a denormalisation: M = Xn T1 with T1 = [[s1 0 -s1 c1x] [0 s1 -s1 c1y] [0 0 1]].  The left factor (T2^-1 for a
+// homography, T2^T for a fundamental matrix) and the sign rule are the model's
+__device__ __forceinline__ void vo_tv_right_factor(const double* Xn, double c1x, double c1y, double s1, double* M) {
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    M[3 * r] = Xn[3 * r] * s1; M[3 * r + 1] = Xn[3 * r + 1] * s1;
+    M[3 * r + 2] = Xn[3 * r + 2] - (M[3 * r] * c1x + M[3 * r + 1] * c1y);
+  }
+}

@@ -1028,14 +1028,39 @@ class VoContext:
         return {k: v[0] for k, v in out.items()} if B == 1 else out
 
     # -- 2D-2D bootstrap pose ---------------------------------------------------------------------
+    def _two_views(self, pts1, pts2):
+        """-> (p1, p2, n): the two views as C-contiguous [batch, n, 2] float32"""
+        p1 = np.ascontiguousarray(pts1, np.float32).reshape(self.batch, -1, 2)
+        p2 = np.ascontiguousarray(pts2, np.float32).reshape(self.batch, -1, 2)
+        assert p2.shape[1] == p1.shape[1]
+        return p1, p2, p1.shape[1]
+
+    @staticmethod
+    def _div33(*mats):
+        """each [batch, 3, 3] in place: divided by its 3,3 entry as cv2 returns it, unless that is under 1e-12 of the norm"""
+        for M in mats:
+            for Mb in M:
+                if abs(Mb[2, 2]) >= 1e-12 * np.linalg.norm(Mb):      # (False for NaN: left as it is)
+                    Mb /= Mb[2, 2]
+
+    def _inliers(self, mask):
+        """mask [batch, n] -> the ascending inlier indices (a list of them per sequence if batch > 1)"""
+        return self._out([np.nonzero(m)[0] for m in mask])
+
+    def _hom_params(self, threshold, confidence, max_iters, seed, refine_iters):
+        prm = HomParams()
+        self._L.vo_homography_default_params(C.byref(prm))
+        prm.threshold, prm.confidence, prm.max_iters, prm.seed, prm.refine_iters = threshold, confidence, int(max_iters), int(seed), int(refine_iters)
+        return prm
+
+    def _hom_stats(self, st):
+        return self._out([dict(cost=s.cost, n_inliers=s.n_inliers, hypotheses=s.hypotheses, best=s.best, status=s.status, lm_iters=s.lm_iters) for s in st])
+
     def essential_ransac(self, K, pts1, pts2, threshold=1.0, prob=0.9999, max_iters=1000, seed=0, distance_thresh=50.0):
         """findEssentialMat(RANSAC) + recoverPose.  pts1, pts2 (n,2) pixels [leading batch dim if batch > 1]
         -> E (3,3) unit norm, R (3,3), t (3,) with x2 ~ R x1 + t, inlier indices (ascending), stats dict"""
         B = self.batch
-        p1 = np.ascontiguousarray(pts1, np.float32).reshape(B, -1, 2)
-        p2 = np.ascontiguousarray(pts2, np.float32).reshape(B, -1, 2)
-        n = p1.shape[1]
-        assert p2.shape[1] == n
+        p1, p2, n = self._two_views(pts1, pts2)
         Kc = self._in(K, np.float64, (3, 3))
         prm = EssParams()
         self._L.vo_essential_default_params(C.byref(prm))
@@ -1046,10 +1071,7 @@ class VoContext:
         self._ck(self._L.vo_essential_ransac(self._h, ptr(Kc, C.c_double), ptr(p1, C.c_float), ptr(p2, C.c_float), n, C.byref(prm),
                                              ptr(E, C.c_double), ptr(R, C.c_double), ptr(t, C.c_double), ptr(mask, C.c_uint8), st))
         stats = [dict(n_inliers=s.n_inliers, n_good=s.n_good, hypotheses=s.hypotheses, best=s.best, status=s.status) for s in st]
-        inl = [np.nonzero(mask[b])[0] for b in range(B)]
-        if B == 1:
-            return E[0], R[0], t[0], inl[0], stats[0]
-        return E, R, t, inl, stats
+        return self._out(E), self._out(R), self._out(t), self._inliers(mask), self._out(stats)
 
     def find_homography(self, pts1, pts2, threshold=3.0, confidence=0.995, max_iters=2000, seed=0, refine_iters=10):
         """cv2.findHomography(pts1, pts2, cv2.RANSAC, threshold) (vo_homography_ransac).  pts1, pts2 (n,2) pixels, n >= 4 [leading batch dim
@@ -1057,27 +1079,15 @@ class VoContext:
         stats dict, H0 (3,3) the winning four-point sample's own model.  H and H0 are divided by h33 as cv2 returns them; where |h33| is under
         1e-12 of the norm they stay at unit Frobenius norm.  Without a model: stats['status'] != 0, NaN matrices, no inliers."""
         B = self.batch
-        p1 = np.ascontiguousarray(pts1, np.float32).reshape(B, -1, 2)
-        p2 = np.ascontiguousarray(pts2, np.float32).reshape(B, -1, 2)
-        n = p1.shape[1]
-        assert p2.shape[1] == n
-        prm = HomParams()
-        self._L.vo_homography_default_params(C.byref(prm))
-        prm.threshold, prm.confidence, prm.max_iters, prm.seed, prm.refine_iters = threshold, confidence, int(max_iters), int(seed), int(refine_iters)
+        p1, p2, n = self._two_views(pts1, pts2)
+        prm = self._hom_params(threshold, confidence, max_iters, seed, refine_iters)
         H, H0 = np.zeros((B, 3, 3)), np.zeros((B, 3, 3))
         mask = np.zeros((B, n), np.uint8)
         st = (HomStats * B)()
         self._ck(self._L.vo_homography_ransac(self._h, ptr(p1, C.c_float), ptr(p2, C.c_float), n, C.byref(prm), ptr(H, C.c_double),
                                               ptr(H0, C.c_double), ptr(mask, C.c_uint8), st))
-        for M in (H, H0):
-            for b in range(B):
-                if abs(M[b, 2, 2]) >= 1e-12 * np.linalg.norm(M[b]):      # (False for NaN: left as it is)
-                    M[b] /= M[b, 2, 2]
-        stats = [dict(cost=s.cost, n_inliers=s.n_inliers, hypotheses=s.hypotheses, best=s.best, status=s.status, lm_iters=s.lm_iters) for s in st]
-        inl = [np.nonzero(mask[b])[0] for b in range(B)]
-        if B == 1:
-            return H[0], inl[0], stats[0], H0[0]
-        return H, inl, stats, H0
+        self._div33(H, H0)
+        return self._out(H), self._inliers(mask), self._hom_stats(st), self._out(H0)
 
     def _hpose_params(self, ratio, threshold, min_off, normal_hint):
         prm = HposeParams()
@@ -1091,9 +1101,7 @@ class VoContext:
     def _hpose_out(self, R, t, nrm, st):
         stats = [dict(n_solutions=s.n_solutions, n_distinct=s.n_distinct, ambiguous=s.ambiguous, status=s.status, n_mask=s.n_mask,
                       n_good=list(s.n_good), n_off=list(s.n_off), sigma=np.array(s.sigma), rotation_only=s.n_solutions == 1) for s in st]
-        if self.batch == 1:
-            return R[0], t[0], nrm[0], stats[0]
-        return R, t, nrm, stats
+        return self._out(R), self._out(t), self._out(nrm), self._out(stats)
 
     def decompose_homography(self, K, H, pts1=None, pts2=None, mask=None, ratio=0.75, threshold=1.0, min_off=8, normal_hint=None):
         """cv2.decomposeHomographyMat(H, K) with cv2.filterHomographyDecompByVisibleRefpoints' two visibility tests counted as votes, a ranking
@@ -1110,10 +1118,7 @@ class VoContext:
         p1 = p2 = m = None
         n = 0
         if pts1 is not None:
-            p1 = np.ascontiguousarray(pts1, np.float32).reshape(B, -1, 2)
-            p2 = np.ascontiguousarray(pts2, np.float32).reshape(B, -1, 2)
-            n = p1.shape[1]
-            assert p2.shape[1] == n
+            p1, p2, n = self._two_views(pts1, pts2)
             if mask is not None:
                 m = np.ascontiguousarray(np.asarray(mask).reshape(B, n) != 0, np.uint8)
         prm = self._hpose_params(ratio, threshold, min_off, normal_hint)
@@ -1131,14 +1136,9 @@ class VoContext:
         that of the two calls, bit for bit.  pose_threshold is decompose_homography's threshold.
         -> H (3,3) divided by h33, inlier indices, the search's stats dict, then R, t, n, stats as decompose_homography returns them."""
         B = self.batch
-        p1 = np.ascontiguousarray(pts1, np.float32).reshape(B, -1, 2)
-        p2 = np.ascontiguousarray(pts2, np.float32).reshape(B, -1, 2)
-        n = p1.shape[1]
-        assert p2.shape[1] == n
+        p1, p2, n = self._two_views(pts1, pts2)
         Kc = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (B, 3, 3)))
-        hp = HomParams()
-        self._L.vo_homography_default_params(C.byref(hp))
-        hp.threshold, hp.confidence, hp.max_iters, hp.seed, hp.refine_iters = threshold, confidence, int(max_iters), int(seed), int(refine_iters)
+        hp = self._hom_params(threshold, confidence, max_iters, seed, refine_iters)
         prm = self._hpose_params(ratio, pose_threshold, min_off, normal_hint)
         H = np.zeros((B, 3, 3))
         mask = np.zeros((B, n), np.uint8)
@@ -1147,14 +1147,8 @@ class VoContext:
         self._ck(self._L.vo_homography_pose(self._h, ptr(Kc, C.c_double), ptr(p1, C.c_float), ptr(p2, C.c_float), n, C.byref(hp), C.byref(prm),
                                             ptr(H, C.c_double), ptr(mask, C.c_uint8), ptr(R, C.c_double), ptr(t, C.c_double),
                                             ptr(nrm, C.c_double), hs, st))
-        for b in range(B):
-            if abs(H[b, 2, 2]) >= 1e-12 * np.linalg.norm(H[b]):
-                H[b] /= H[b, 2, 2]
-        hstats = [dict(cost=s.cost, n_inliers=s.n_inliers, hypotheses=s.hypotheses, best=s.best, status=s.status, lm_iters=s.lm_iters) for s in hs]
-        inl = [np.nonzero(mask[b])[0] for b in range(B)]
-        if B == 1:
-            return (H[0], inl[0], hstats[0]) + self._hpose_out(R, t, nrm, st)
-        return (H, inl, hstats) + self._hpose_out(R, t, nrm, st)
+        self._div33(H)
+        return (self._out(H), self._inliers(mask), self._hom_stats(hs)) + self._hpose_out(R, t, nrm, st)
 
     def find_fundamental(self, pts1, pts2, threshold=3.0, confidence=0.99, max_iters=1000, seed=0, refit=0):
         """cv2.findFundamentalMat(pts1, pts2, cv2.FM_RANSAC, threshold, confidence) (vo_fundamental_ransac).  pts1, pts2 (n,2) pixels, n >= 7
@@ -1163,10 +1157,7 @@ class VoContext:
         F0 (3,3) the winning sample's own model.  F and F0 are divided by f33 as cv2 returns them; where |f33| is under 1e-12 of the norm they
         stay at unit Frobenius norm.  Without a model: stats['status'] != 0, NaN matrices, no inliers."""
         B = self.batch
-        p1 = np.ascontiguousarray(pts1, np.float32).reshape(B, -1, 2)
-        p2 = np.ascontiguousarray(pts2, np.float32).reshape(B, -1, 2)
-        n = p1.shape[1]
-        assert p2.shape[1] == n
+        p1, p2, n = self._two_views(pts1, pts2)
         prm = FundParams()
         self._L.vo_fundamental_default_params(C.byref(prm))
         prm.threshold, prm.confidence, prm.max_iters, prm.seed, prm.refit = threshold, confidence, int(max_iters), int(seed), int(refit)
@@ -1175,16 +1166,10 @@ class VoContext:
         st = (FundStats * B)()
         self._ck(self._L.vo_fundamental_ransac(self._h, ptr(p1, C.c_float), ptr(p2, C.c_float), n, C.byref(prm), ptr(F, C.c_double),
                                                ptr(F0, C.c_double), ptr(mask, C.c_uint8), st))
-        for M in (F, F0):
-            for b in range(B):
-                if abs(M[b, 2, 2]) >= 1e-12 * np.linalg.norm(M[b]):      # (False for NaN: left as it is)
-                    M[b] /= M[b, 2, 2]
+        self._div33(F, F0)
         stats = [dict(cost=s.cost, n_inliers=s.n_inliers, hypotheses=s.hypotheses, best=s.best, status=s.status, n_roots=s.n_roots,
                       models=s.models) for s in st]
-        inl = [np.nonzero(mask[b])[0] for b in range(B)]
-        if B == 1:
-            return F[0], inl[0], stats[0], F0[0]
-        return F, inl, stats, F0
+        return self._out(F), self._inliers(mask), self._out(stats), self._out(F0)
 
     def pnp_params(self, reproj_err=2.0, confidence=0.9999, max_iters=1000000, seed=0):
         prm = PnpParams()
