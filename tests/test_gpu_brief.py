@@ -381,3 +381,51 @@ def test_brief_read_states(loop_scene):
         c.set_brief(None)
         rp.step(T1 + 2); assert rp.fetch()["status"] == 0
         assert _code(lambda: c.brief_read(1)) == -4                       # the last detection did not describe
+
+
+# ---- 8. the four per-point side stores at once --------------------------------------------------------------------------------------------------
+def _all_four(sc, state, side, inflight):
+    """the closed loop with the forward-backward check, the predicted start, cornerSubPix and BRIEF all on; afterwards, in the same context, each
+    synchronous corner call takes over its own rows only"""
+    from vo_mi355x import VoContext
+    with VoContext(W, H, max_pts=1024) as c:
+        c.set_side_stream(side)
+        rp = _loop(c, sc, state, fb_max_error=1.0, klt_predict="constant_velocity", subpix={}, descriptor="brief")
+        recs, pending = [], 0
+        for s in range(N_STEPS):
+            rp.step(T1 + 1 + s); pending += 1
+            if pending == inflight or s == N_STEPS - 1:
+                while pending:
+                    recs.append(rp.fetch()); pending -= 1
+        n = recs[-1]["n_tracked"]
+        reads = dict(fb=c.fb_read(n), guess=(c.klt_guess_read(n),), subpix=tuple(c.subpix_read().values()), brief=tuple(c.brief_read().values()))
+        tables = rp.read_tables()
+        pts = np.full((3, 2), 60, np.float32)
+        c.corner_subpix(pts)
+        assert _code(lambda: c.subpix_read(1)) == -4
+        assert len(c.brief_read()["desc"]) == len(reads["brief"][0]) and c.fb_read(n)[0].shape == (n,) and c.klt_guess_read(n).shape == (n, 2)
+        c.brief_compute(pts)
+        assert _code(lambda: c.brief_read(1)) == -4 and _code(lambda: c.subpix_read(1)) == -4
+        assert c.fb_read(n)[0].shape == (n,) and c.klt_guess_read(n).shape == (n, 2)
+        return recs, tables, reads
+
+
+def test_closed_loop_with_all_four_side_stores_is_the_same_on_every_layout(loop_scene):
+    """records, tables and the four side reads (fb_read, klt_guess_read, subpix_read, brief_read) bit-equal with the side stream on, off, and on
+    with the maximum number of steps in flight"""
+    from vo_mi355x.resident import INFLIGHT
+    sc, state = loop_scene
+    recs0, T0, reads0 = _all_four(sc, state, True, 1)
+    assert all(r["status"] == 0 for r in recs0) and recs0[-1]["n_tracked"] > 10 and recs0[-1]["n_detected"] > 10
+    assert all(len(a) > 0 for v in reads0.values() for a in v)
+    for side, inflight in ((False, 1), (True, INFLIGHT)):
+        recs, T, reads = _all_four(sc, state, side, inflight)
+        for s, (x, y) in enumerate(zip(recs0, recs)):
+            for k, v in x.items():
+                assert (np.array_equal(y[k], v, equal_nan=True) if isinstance(v, np.ndarray) else y[k] == v), (side, inflight, s, k)
+        for name in T0:
+            assert np.array_equal(T0[name], T[name], equal_nan=T0[name].dtype.kind == "f"), (side, inflight, name)
+        for name, want in reads0.items():
+            assert len(reads[name]) == len(want)
+            for a, b in zip(want, reads[name]):
+                assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), (side, inflight, name)

@@ -26,8 +26,6 @@
 #include <math.h>
 #include <string.h>
 
-#define BRIEF_CAP 4096                  // corners a Shi-Tomasi launch can put out (ST_OUT_CAP)
-
 struct brief_args {
   const uint8_t* img;          // level 0 of the chosen frame, sequence 0 (padded: interior at (VO_PAD, VO_PAD))
   size_t img_seq;              // pixels per sequence
@@ -83,25 +81,6 @@ __global__ void __launch_bounds__(64) k_brief_describe(brief_args A, const float
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-// c->d_brief, per sequence: desc [cap][32] u8 | in [cap][2] f32 (the synchronous form's corners) | angle [cap] f32 | flags [cap] u8
-static inline int brief_cap(const vo_ctx* c) { return c->max_pts > BRIEF_CAP ? c->max_pts : BRIEF_CAP; }
-static inline size_t brief_off_in(const vo_ctx* c) { return 32 * (size_t)brief_cap(c); }
-static inline size_t brief_off_angle(const vo_ctx* c) { return brief_off_in(c) + sizeof(float) * 2 * (size_t)brief_cap(c); }
-static inline size_t brief_off_flags(const vo_ctx* c) { return brief_off_angle(c) + sizeof(float) * (size_t)brief_cap(c); }
-static inline size_t brief_seq(const vo_ctx* c) { return (brief_off_flags(c) + (size_t)brief_cap(c) + 15) & ~(size_t)15; }
-static inline uint8_t* brief_rows(const vo_ctx* c, size_t off) { return c->d_brief + off; }
-
-static int32_t brief_reserve(vo_ctx* c) {
-  if (c->d_brief) return VO_OK;
-  VO_HIP(c, hipMalloc((void**)&c->d_brief, brief_seq(c) * (size_t)c->batch));
-  return VO_OK;
-}
-
-void vo_brief_destroy(vo_ctx* c) {
-  if (c->d_brief) (void)hipFree(c->d_brief);
-  c->d_brief = nullptr;
-}
-
 extern "C" int32_t vo_brief_default_pattern(int8_t* out) {
   if (!out) return VO_E_INVALID;
   memcpy(out, VO_BRIEF_DEFAULT_PATTERN, 1024);
@@ -133,19 +112,17 @@ int32_t vo_brief_check_pattern(vo_ctx* c, const int8_t* pattern) {
   return VO_OK;
 }
 
+// the kernel over the corner rows `rows`; what it writes goes to c->brief
 static int32_t brief_launch(vo_ctx* c, hipStream_t q, const vo_frame& F, const int8_t* pattern, int cap, const float* rows, size_t rows_seq,
                             const uint32_t* counts, size_t counts_seq) {
+  const vo_side_rows& s = c->brief;
   brief_args A;
   A.img = F.img[0]; A.img_seq = c->lvl_px[0]; A.pitch = c->lv[0].pitch; A.W = c->width; A.H = c->height; A.cap = cap;
   memcpy(A.pat, pattern ? pattern : VO_BRIEF_DEFAULT_PATTERN, 1024);
-  hipLaunchKernelGGL(k_brief_describe, dim3(cap, c->batch), dim3(64), 0, q, A, rows, rows_seq, brief_rows(c, 0),
-                     reinterpret_cast<float*>(brief_rows(c, brief_off_angle(c))), brief_rows(c, brief_off_flags(c)), brief_seq(c), counts, counts_seq);
+  hipLaunchKernelGGL(k_brief_describe, dim3(cap, c->batch), dim3(64), 0, q, A, rows, rows_seq, vo_side_col<uint8_t>(s, VO_BRIEF_DESC),
+                     vo_side_col<float>(s, VO_BRIEF_ANGLE), vo_side_col<uint8_t>(s, VO_BRIEF_FLAGS), s.seq, counts, counts_seq);
   VO_HIP(c, hipGetLastError());
   return VO_OK;
-}
-
-static hipError_t brief_d2h(vo_ctx* c, void* h, size_t off, size_t row_bytes) {
-  return hipMemcpy2DAsync(h, row_bytes, brief_rows(c, off), brief_seq(c), row_bytes, c->batch, hipMemcpyDeviceToHost, c->stream);
 }
 
 extern "C" int32_t vo_brief_compute(vo_ctx* c, int32_t which, const float* corners, int32_t n, const vo_brief_params* prm, const int8_t* pattern,
@@ -153,34 +130,18 @@ extern "C" int32_t vo_brief_compute(vo_ctx* c, int32_t which, const float* corne
   if (!c) return VO_E_INVALID;
   vo_brief_params def;
   if (!prm) { vo_brief_default_params(&def); prm = &def; }
-  VO_CHECK(c, which == 0 || which == 1, VO_E_INVALID, "which must be 0 (previous frame) or 1 (current frame)");
-  VO_CHECK(c, n >= 0 && n <= c->max_pts, VO_E_INVALID, "n exceeds max_pts");
-  { const int32_t r = brief_check(c, prm, pattern); if (r != VO_OK) return r; }
-  VO_CHECK(c, c->n_pushed >= (which == 0 ? 2 : 1), VO_E_STATE, "frame not pushed yet");
-  if (n == 0) return VO_OK;
-  VO_CHECK(c, corners && desc, VO_E_INVALID, "null buffer");
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  { const int32_t rr = brief_reserve(c); if (rr != VO_OK) return rr; }
-  c->brief_n = -1;                        // the rows no longer describe a detection
-  const size_t row = sizeof(float) * 2 * (size_t)n;
-  VO_HIP(c, hipMemcpy2DAsync(brief_rows(c, brief_off_in(c)), brief_seq(c), corners, row, row, c->batch, hipMemcpyHostToDevice, c->stream));
-  { const int32_t r = brief_launch(c, c->stream, c->fr[which == 1 ? c->cur : (c->cur ^ 1)], pattern, n,
-                                   reinterpret_cast<const float*>(brief_rows(c, brief_off_in(c))), brief_seq(c), nullptr, 0);
-    if (r != VO_OK) return r; }
-  VO_HIP(c, brief_d2h(c, desc, 0, 32 * (size_t)n));
-  if (angle) VO_HIP(c, brief_d2h(c, angle, brief_off_angle(c), sizeof(float) * (size_t)n));
-  if (flags) VO_HIP(c, brief_d2h(c, flags, brief_off_flags(c), (size_t)n));
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  return VO_OK;
+  return vo_corner_sync(c, __func__, &c->brief, vo_brief_reserve, VO_BRIEF_IN, which, corners, n, [&] { return brief_check(c, prm, pattern); },
+                        [&](const vo_frame& F) {
+                          return brief_launch(c, c->stream, F, pattern, n, vo_side_col<const float>(c->brief, VO_BRIEF_IN), c->brief.seq, nullptr, 0);
+                        },
+                        {{desc, VO_BRIEF_DESC}, {angle, VO_BRIEF_ANGLE}, {flags, VO_BRIEF_FLAGS}});
 }
 
 extern "C" int32_t vo_set_brief(vo_ctx* c, const vo_brief_params* prm, const int8_t* pattern) {
   if (!c) return VO_E_INVALID;
   if (!prm) { c->brief_on = false; return VO_OK; }
   { const int32_t r = brief_check(c, prm, pattern); if (r != VO_OK) return r; }
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rr = brief_reserve(c); if (rr != VO_OK) return rr; }       // the rows exist before the first enqueue that needs them
+  { const int32_t rr = vo_side_reserve_on_device(c, vo_brief_reserve); if (rr != VO_OK) return rr; }
   vo_brief_default_params(&c->brief_prm);
   c->brief_prm.n_bits = prm->n_bits;
   memcpy(c->brief_pat, pattern ? pattern : VO_BRIEF_DEFAULT_PATTERN, 1024);  // a launch takes the table by value: steps in flight keep theirs
@@ -189,10 +150,7 @@ extern "C" int32_t vo_set_brief(vo_ctx* c, const vo_brief_params* prm, const int
 }
 
 extern "C" int32_t vo_get_brief(vo_ctx* c, int32_t* on, vo_brief_params* prm) {
-  if (!c || !on) return VO_E_INVALID;
-  *on = c->brief_on ? 1 : 0;
-  if (prm) { if (c->brief_on) *prm = c->brief_prm; else vo_brief_default_params(prm); }
-  return VO_OK;
+  return vo_corner_get(c, &vo_ctx::brief_on, &vo_ctx::brief_prm, vo_brief_default_params, on, prm);
 }
 
 extern "C" int32_t vo_brief_pattern_read(vo_ctx* c, int8_t* out) {
@@ -201,31 +159,14 @@ extern "C" int32_t vo_brief_pattern_read(vo_ctx* c, int8_t* out) {
   return VO_OK;
 }
 
-// the resident detections' hook: describe the corners the selection kernel has just left in st_out on q, against the current frame
-int32_t vo_brief_describe_detected(vo_ctx* c, hipStream_t q, int max_corners) {
-  c->brief_n = -1;
-  if (!c->brief_on) return VO_OK;
-  { const int32_t rr = brief_reserve(c); if (rr != VO_OK) return rr; }
-  const int cap = (max_corners > 0 && max_corners < BRIEF_CAP) ? max_corners : BRIEF_CAP;
-  const int32_t r = brief_launch(c, q, c->fr[c->cur], c->brief_pat, cap, vo_slab<const float>(c, c->off_st_out), c->slab_seq,
-                                 vo_slab<const uint32_t>(c, c->off_st_scalars), c->slab_seq);
-  if (r != VO_OK) return r;
-  c->brief_n = cap;
-  return VO_OK;
+// (vo_corners_detected) the corners the selection kernel has just left in st_out on q, described against the current frame
+int32_t vo_brief_launch_detected(vo_ctx* c, hipStream_t q, int cap) {
+  return brief_launch(c, q, c->fr[c->cur], c->brief_pat, cap, vo_slab<const float>(c, c->off_st_out), c->slab_seq,
+                      vo_slab<const uint32_t>(c, c->off_st_scalars), c->slab_seq);
 }
 
 extern "C" int32_t vo_brief_read(vo_ctx* c, uint8_t* desc, float* angle, uint8_t* flags, int32_t n) {
   if (!c) return VO_E_INVALID;
-  VO_CHECK(c, !vo_pipe_busy(c) && c->steps_enq == c->steps_fetched, VO_E_STATE, "steps in flight: fetch them first");
-  VO_CHECK(c, c->brief_n >= 0, VO_E_STATE, "the last detection did not describe");
-  VO_CHECK(c, n >= 0 && n <= c->brief_n, VO_E_INVALID, "n exceeds the corners of the last detection");
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  if (n > 0) {
-    if (desc) VO_HIP(c, brief_d2h(c, desc, 0, 32 * (size_t)n));
-    if (angle) VO_HIP(c, brief_d2h(c, angle, brief_off_angle(c), sizeof(float) * (size_t)n));
-    if (flags) VO_HIP(c, brief_d2h(c, flags, brief_off_flags(c), (size_t)n));
-  }
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  return VO_OK;
+  return vo_side_read(c, __func__, c->brief, "the last detection did not describe", "n exceeds the corners of the last detection", n,
+                      {{desc, VO_BRIEF_DESC}, {angle, VO_BRIEF_ANGLE}, {flags, VO_BRIEF_FLAGS}});
 }

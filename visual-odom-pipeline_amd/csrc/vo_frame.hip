@@ -358,10 +358,7 @@ extern "C" int32_t vo_ctx_destroy(vo_ctx* c) {
   vo_sift_destroy(c);
   vo_st_destroy(c);
   vo_ba_destroy(c);
-  vo_fb_destroy(c);
-  vo_guess_destroy(c);
-  vo_subpix_destroy(c);
-  vo_brief_destroy(c);
+  for (vo_side_rows* s : {&c->fb, &c->guess, &c->subpix, &c->brief}) vo_side_free(s);
   vo_orb_destroy(c);
   vo_ingest_free(&c->und_on, &c->d_und, (void**)&c->d_und_tab);
   vo_ingest_free(&c->cl_on, &c->d_clahe, (void**)&c->d_clahe_lut);

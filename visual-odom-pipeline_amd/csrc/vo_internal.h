@@ -41,6 +41,23 @@ struct vo_dlt_cam {
   double H1z[4];           // third row of H1
 };
 
+// Rows beside the result slab, one store per opt-in per-point feature (the slab goes to the host whole with every fused frame step: it does not
+// grow for a feature that step never runs).  Per sequence up to four typed columns of the same number of rows, in a device allocation of its
+// own that is made when the feature is first asked for (a context that never asks has none), and a note of what the last producer left there
+struct vo_side_rows {
+  uint8_t* d = nullptr;              // [batch][seq]; null until reserved
+  size_t seq = 0;                    // bytes per sequence
+  size_t off[4] = {0, 0, 0, 0};      // column k of sequence 0 starts here
+  size_t elem[4] = {0, 0, 0, 0};     // bytes per row of column k
+  int n = -1;                        // rows per sequence the last producer wrote, else -1
+};
+template <class T> inline T* vo_side_col(const vo_side_rows& s, int k) { return reinterpret_cast<T*>(s.d + s.off[k]); }     // column k of sequence 0
+struct vo_side_copy { void* h; int col; };     // a host array [batch][n rows] (null = not asked for) and the column it mirrors
+enum { VO_FB_P0R, VO_FB_ERR, VO_FB_OK };
+enum { VO_SUBPIX_RAW, VO_SUBPIX_OUT, VO_SUBPIX_ITERS, VO_SUBPIX_FLAGS };
+enum { VO_BRIEF_DESC, VO_BRIEF_IN, VO_BRIEF_ANGLE, VO_BRIEF_FLAGS };
+#define VO_CORNER_CAP 4096          // corners a Shi-Tomasi launch can put out (ST_OUT_CAP)
+
 // A context carries `batch` independent sequences in lockstep: every device buffer has a leading sequence
 // dimension with a uniform stride and every kernel a grid dimension over sequences, so that one launch serves
 // the whole batch (the path is launch / latency bound per sequence; batching is what fills the 256 CUs).
@@ -97,32 +114,20 @@ struct vo_ctx {
   int32_t* d_iters = nullptr;        // [batch][n x (max_level + 1)]
   int n_resident = 0;
   int iters_stride = 0;              // of the last KLT launch
-  // forward-backward check (vo_klt_fb.hip): threshold of vo_set_fb_check (+inf = off), and the check's rows -- p0r [max_pts][2] f32,
-  // fb_err [max_pts] f32, ok [max_pts] u8 per sequence, fb_seq bytes apart -- in an allocation of their own, made when the check is first
-  // asked for (the result slab goes to the host whole with every fused frame step: it does not grow for a check that step never runs)
-  float fb_max_err = __builtin_inff();
-  uint8_t* d_fb = nullptr;
-  size_t fb_seq = 0, fb_off_err = 0, fb_off_ok = 0;
-  int fb_n = -1;                     // points of the last track if it ran the check, else -1
-  // motion-predicted start of the tracker (vo_klt_seed.hip): mode of vo_set_klt_predict, and the guesses [batch][max_pts][2] f32 in the
-  // tracker's point order -- an allocation of its own, made when a guess is first needed (a context that never asks has none)
-  int klt_predict = VO_KLT_PREDICT_OFF;
-  float* d_guess = nullptr;
-  int guess_n = -1;                  // points of the last track if a predictor wrote its start positions, else -1
-  // sub-pixel corner refinement (vo_subpix.hip): the setting of vo_set_subpix, and the kernel's rows per sequence -- the integer corners, the
-  // synchronous form's in / out rows, iters, flags -- in an allocation of their own, made when a refinement is first asked for
-  bool subpix_on = false;
+  // The four side-row stores (vo_side_rows; reserved by vo_fb_reserve ... vo_brief_reserve below), M = max_pts, C = max(max_pts, VO_CORNER_CAP):
+  //   fb      M rows: p0r 8 B | fb_err 4 B | ok 1 B, every column rounded up to 256 B    n = points of the last track if it ran the check
+  //   guess   M rows: the start positions 8 B, in the tracker's point order               n = points of the last track if a predictor wrote them
+  //   subpix  C rows: raw 8 | out 8 | iters 4 | flags 1, the sequence rounded up to 16 B  n = corner slots the last resident detection refined
+  //   brief   C rows: desc 32 | in 8 | angle 4 | flags 1, the sequence rounded up to 16 B n = corner slots the last resident detection described
+  // (subpix out / brief in: the synchronous forms' corner rows; the pipeline's tables never hold a descriptor)
+  vo_side_rows fb, guess, subpix, brief;
+  float fb_max_err = __builtin_inff();              // forward-backward check (vo_klt_fb.hip): threshold of vo_set_fb_check (+inf = off)
+  int klt_predict = VO_KLT_PREDICT_OFF;             // motion-predicted start of the tracker (vo_klt_seed.hip): mode of vo_set_klt_predict
+  bool subpix_on = false;                           // sub-pixel corner refinement (vo_subpix.hip): the setting of vo_set_subpix
   vo_subpix_params subpix_prm = {};
-  uint8_t* d_subpix = nullptr;
-  int subpix_n = -1;                 // corner slots the last resident detection refined, else -1
-  // oriented BRIEF descriptor (vo_brief.hip): the setting of vo_set_brief with its sampling table (a launch takes it by value), and the kernel's
-  // rows per sequence -- descriptors, the synchronous form's corners, angles, flags -- in an allocation of their own: a side buffer, the
-  // pipeline's tables never hold a descriptor
-  bool brief_on = false;
-  vo_brief_params brief_prm = {};
+  bool brief_on = false;                            // oriented BRIEF (vo_brief.hip): the setting of vo_set_brief with its sampling table (a launch
+  vo_brief_params brief_prm = {};                   // takes it by value)
   int8_t brief_pat[1024] = {};
-  uint8_t* d_brief = nullptr;
-  int brief_n = -1;                  // corner slots the last resident detection described, else -1
   // lens undistortion (vo_undistort.hip): the setting of vo_set_undistort, its fixed-point map [h][w] of 8-byte entries (shared by the batch)
   // and the tight [batch][h][w] staging image the level-0 kernels read instead of the raw frame -- allocated when first switched on
   bool und_on = false;
@@ -203,10 +208,12 @@ inline int32_t vo_fail(vo_ctx* c, int32_t code, const std::string& msg) {
     }                                                                                     \
   } while (0)
 
-#define VO_CHECK(c, cond, code, msg)                                                      \
+// (VO_CHECK_AS: in a body several entry points share, under the entry's name `who`)
+#define VO_CHECK_AS(c, who, cond, code, msg)                                              \
   do {                                                                                    \
-    if (!(cond)) return vo_fail((c), (code), std::string(__func__) + ": " + (msg));       \
+    if (!(cond)) return vo_fail((c), (code), std::string(who) + ": " + (msg));            \
   } while (0)
+#define VO_CHECK(c, cond, code, msg) VO_CHECK_AS(c, __func__, cond, code, msg)
 
 // slab accessors (sequence 0; sequence b at + b * slab_seq bytes)
 template <class T> inline T* vo_slab(const vo_ctx* c, size_t off) { return reinterpret_cast<T*>(c->d_slab + off); }
@@ -319,30 +326,21 @@ int vo_fast_n_blockmax(int W, int H);
 void vo_fast_enqueue(vo_ctx* c, hipStream_t q, int t, const uint8_t* d_mask, float* d_R, float* d_blockmax);
 // the resident enqueues with the per-sequence counters named by the caller (device arrays [batch], null = uniform): d_counts = live
 // points of each sequence (KLT input / exclusion discs), d_limit = cap on the corners each sequence's re-detection needs
-// The tracker's form word: KLT_FORM_FB = with the forward-backward check (the ok flags land in vo_fb_ok(c) [batch][fb_seq bytes]),
-// KLT_FORM_SEEDED = started at the guesses a predictor kernel has just written to c->d_guess on q (vo_guess_reserve: those rows exist
+// The tracker's form word: KLT_FORM_FB = with the forward-backward check (the ok flags land in vo_fb_ok(c) [batch][fb.seq bytes]),
+// KLT_FORM_SEEDED = started at the guesses a predictor kernel has just written to c->guess on q (vo_guess_reserve: those rows exist
 // afterwards).  The four values select k_klt_track, k_klt_track_fb, k_klt_seeded, k_klt_seeded_fb (vo_klt_enqueue, vo_klt.hip).
 enum : unsigned { KLT_FORM_FB = 1u, KLT_FORM_SEEDED = 2u };
 int32_t vo_klt_track_resident_enqueue(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts, unsigned form);
 inline bool vo_fb_on(const vo_ctx* c) { return !(c->fb_max_err == __builtin_inff()); }     // +inf = off
-inline const uint8_t* vo_fb_ok(const vo_ctx* c) { return c->d_fb + c->fb_off_ok; }
-void vo_fb_destroy(vo_ctx* c);
+inline const uint8_t* vo_fb_ok(const vo_ctx* c) { return vo_side_col<const uint8_t>(c->fb, VO_FB_OK); }
 inline bool vo_predict_on(const vo_ctx* c) { return c->klt_predict != VO_KLT_PREDICT_OFF; }
 // the form the context's settings ask for (vo_set_fb_check, vo_set_klt_predict): what vo_tracks_track and the closed loop's TRACK stage run
 inline unsigned vo_klt_form(const vo_ctx* c) { return (vo_fb_on(c) ? KLT_FORM_FB : 0u) | (vo_predict_on(c) ? KLT_FORM_SEEDED : 0u); }
-inline size_t vo_guess_seq(const vo_ctx* c) { return sizeof(float) * 2 * (size_t)c->max_pts; }      // bytes per sequence
-int32_t vo_guess_reserve(vo_ctx* c);
-void vo_guess_destroy(vo_ctx* c);
-// sub-pixel refinement (vo_subpix.hip).  vo_subpix_refine_detected: called by the detections that spawn tracks (vo_tracks_detect, the closed
-// loop's DETECT stage) right behind the Shi-Tomasi enqueue on q: with vo_set_subpix on, k_corner_subpix refines the corner rows of st_out in
-// place against the current frame; off, it only notes that the last detection did not refine
-int32_t vo_subpix_refine_detected(vo_ctx* c, hipStream_t q, int max_corners);
-void vo_subpix_destroy(vo_ctx* c);
-// oriented BRIEF (vo_brief.hip).  vo_brief_describe_detected: called by the same detections right behind the Shi-Tomasi enqueue on q and BEFORE
-// vo_subpix_refine_detected, so it always sees the integer corners: with vo_set_brief on, k_brief_describe writes a descriptor, an angle and a
-// flag per corner row of st_out into the side buffer; off, it only notes that the last detection did not describe
-int32_t vo_brief_describe_detected(vo_ctx* c, hipStream_t q, int max_corners);
-void vo_brief_destroy(vo_ctx* c);
+// The corner stages' launches on the corner rows the selection kernel has just left in st_out on q, `cap` slots per sequence against the current
+// frame (vo_corners_detected below is their one caller): k_brief_describe writes a descriptor, an angle and a flag per row into c->brief;
+// k_corner_subpix refines the rows in place and notes the integer corner, the iterations and a flag per row in c->subpix
+int32_t vo_brief_launch_detected(vo_ctx* c, hipStream_t q, int cap);
+int32_t vo_subpix_launch_detected(vo_ctx* c, hipStream_t q, int cap);
 int32_t vo_brief_check_pattern(vo_ctx* c, const int8_t* pattern);    // a caller's sampling table: VO_OK or VO_E_INVALID; null = the default table
 void vo_orb_destroy(vo_ctx* c);                                      // the ORB pyramid and lists (vo_orb.hip)
 // The ingest chain (vo_frame.hip): the optional stages vo_build_pyramid runs in front of level 0, in this order: lens undistortion
@@ -422,3 +420,124 @@ void vo_sift_destroy(vo_ctx* c);
 // sub-workspace lifetime hooks
 void vo_st_destroy(vo_ctx* c);
 void vo_ba_destroy(vo_ctx* c);
+
+// strided copies on the ctx stream between [batch][row_bytes] host arrays and per-sequence device rows d_stride bytes apart
+inline hipError_t rows_h2d(vo_ctx* c, void* d, size_t d_stride, const void* h, size_t row_bytes) {
+  return hipMemcpy2DAsync(d, d_stride, h, row_bytes, row_bytes, c->batch, hipMemcpyHostToDevice, c->stream);
+}
+inline hipError_t rows_d2h(vo_ctx* c, void* h, const void* d, size_t d_stride, size_t row_bytes) {
+  return hipMemcpy2DAsync(h, row_bytes, d, d_stride, row_bytes, c->batch, hipMemcpyDeviceToHost, c->stream);
+}
+
+// ---- the side-row stores (vo_side_rows; the four layouts: at the members of vo_ctx) ----
+// columns of `cap` rows of elem[k] bytes, each column rounded up to col_align bytes and the sequence to seq_align (1 = as it comes)
+inline void vo_side_layout(vo_side_rows* s, int cap, std::initializer_list<size_t> elem, size_t col_align, size_t seq_align) {
+  size_t at = 0;
+  int k = 0;
+  for (size_t e : elem) {
+    s->off[k] = at; s->elem[k++] = e;
+    at += (e * (size_t)cap + col_align - 1) / col_align * col_align;
+  }
+  s->seq = (at + seq_align - 1) / seq_align * seq_align;
+}
+// the allocation, if absent; a refused one leaves the store as it was (not reserved, no layout)
+inline int32_t vo_side_reserve(vo_ctx* c, vo_side_rows* s, int cap, std::initializer_list<size_t> elem, size_t col_align, size_t seq_align) {
+  if (s->d) return VO_OK;
+  vo_side_rows t = *s;
+  vo_side_layout(&t, cap, elem, col_align, seq_align);
+  VO_HIP(c, hipMalloc((void**)&t.d, t.seq * (size_t)c->batch));
+  *s = t;
+  return VO_OK;
+}
+inline void vo_side_free(vo_side_rows* s) {
+  if (s->d) (void)hipFree(s->d);
+  s->d = nullptr;
+}
+inline int vo_corner_cap(const vo_ctx* c) { return c->max_pts > VO_CORNER_CAP ? c->max_pts : VO_CORNER_CAP; }
+inline int32_t vo_fb_reserve(vo_ctx* c) { return vo_side_reserve(c, &c->fb, c->max_pts, {8, 4, 1}, 256, 1); }
+inline int32_t vo_guess_reserve(vo_ctx* c) { return vo_side_reserve(c, &c->guess, c->max_pts, {8}, 1, 1); }
+inline int32_t vo_subpix_reserve(vo_ctx* c) { return vo_side_reserve(c, &c->subpix, vo_corner_cap(c), {8, 8, 4, 1}, 1, 16); }
+inline int32_t vo_brief_reserve(vo_ctx* c) { return vo_side_reserve(c, &c->brief, vo_corner_cap(c), {32, 8, 4, 1}, 1, 16); }
+// a setter that switches its feature on: the rows exist before the first enqueue that needs them
+inline int32_t vo_side_reserve_on_device(vo_ctx* c, int32_t (*reserve)(vo_ctx*)) {
+  VO_HIP(c, hipSetDevice(c->device));
+  return reserve(c);
+}
+// n rows of column k of every sequence <-> a host array [batch][n rows], on the ctx stream
+inline hipError_t vo_side_h2d(vo_ctx* c, const vo_side_rows& s, int k, const void* h, int n) {
+  return rows_h2d(c, vo_side_col<uint8_t>(s, k), s.seq, h, s.elem[k] * (size_t)n);
+}
+inline hipError_t vo_side_d2h(vo_ctx* c, const vo_side_rows& s, int k, void* h, int n) {
+  return rows_d2h(c, h, vo_side_col<const uint8_t>(s, k), s.seq, s.elem[k] * (size_t)n);
+}
+// the read-backs of n rows into the host arrays that were asked for, in the order named, then the one wait for the ctx stream
+inline int32_t vo_side_fetch(vo_ctx* c, const vo_side_rows& s, int32_t n, std::initializer_list<vo_side_copy> cols) {
+  if (n > 0)
+    for (const vo_side_copy& k : cols)
+      if (k.h) VO_HIP(c, vo_side_d2h(c, s, k.col, k.h, n));
+  VO_HIP(c, hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+// The one body of vo_fb_read, vo_klt_guess_read, vo_subpix_read and vo_brief_read, under the export's name `who`: no steps in flight, the last
+// producer wrote (else VO_E_STATE with `not_written`), n within what it wrote (else VO_E_INVALID with `n_exceeds`); then the side streams
+// are waited for and the columns come back.  need_all: with n > 0 a null array is refused (behind the wait, where vo_klt_guess_read refuses it)
+inline int32_t vo_side_read(vo_ctx* c, const char* who, const vo_side_rows& s, const char* not_written, const char* n_exceeds, int32_t n,
+                            std::initializer_list<vo_side_copy> cols, bool need_all = false) {
+  VO_CHECK_AS(c, who, !vo_pipe_busy(c) && c->steps_enq == c->steps_fetched, VO_E_STATE, "steps in flight: fetch them first");
+  VO_CHECK_AS(c, who, s.n >= 0, VO_E_STATE, not_written);
+  VO_CHECK_AS(c, who, n >= 0 && n <= s.n, VO_E_INVALID, n_exceeds);
+  VO_HIP(c, hipSetDevice(c->device));
+  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
+  if (need_all && n > 0)
+    for (const vo_side_copy& k : cols) VO_CHECK_AS(c, who, k.h, VO_E_INVALID, "null buffer");
+  return vo_side_fetch(c, s, n, cols);
+}
+
+// ---- the two corner stages (vo_subpix.hip, vo_brief.hip): both work on corner rows [n][2] f32 and keep a vo_side_rows store ----
+// The synchronous forms (vo_corner_subpix, vo_brief_compute) behind their null-context check and default parameters, under the export's name
+// `who`: `which`, n, the unit's own parameter rules (unit_check), the frame store; n = 0 ends there.  Then `corners` go up into column in_col of
+// the reserved store, launch(frame) enqueues the unit's kernel on the ctx stream over those rows, and `outs` come back (the first is required)
+template <class Check, class Launch>
+int32_t vo_corner_sync(vo_ctx* c, const char* who, vo_side_rows* s, int32_t (*reserve)(vo_ctx*), int in_col, int32_t which, const float* corners,
+                       int32_t n, Check unit_check, Launch launch, std::initializer_list<vo_side_copy> outs) {
+  VO_CHECK_AS(c, who, which == 0 || which == 1, VO_E_INVALID, "which must be 0 (previous frame) or 1 (current frame)");
+  VO_CHECK_AS(c, who, n >= 0 && n <= c->max_pts, VO_E_INVALID, "n exceeds max_pts");
+  { const int32_t r = unit_check(); if (r != VO_OK) return r; }
+  VO_CHECK_AS(c, who, c->n_pushed >= (which == 0 ? 2 : 1), VO_E_STATE, "frame not pushed yet");
+  if (n == 0) return VO_OK;
+  VO_CHECK_AS(c, who, corners && outs.begin()->h, VO_E_INVALID, "null buffer");
+  VO_HIP(c, hipSetDevice(c->device));
+  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
+  { const int32_t rr = reserve(c); if (rr != VO_OK) return rr; }
+  s->n = -1;                              // the rows no longer describe a detection
+  VO_HIP(c, vo_side_h2d(c, *s, in_col, corners, n));
+  { const int32_t r = launch(c->fr[which == 1 ? c->cur : (c->cur ^ 1)]); if (r != VO_OK) return r; }
+  return vo_side_fetch(c, *s, n, outs);
+}
+// vo_get_subpix / vo_get_brief: the switch, and the parameters in force (off: the defaults)
+template <class P>
+int32_t vo_corner_get(vo_ctx* c, bool vo_ctx::*on_m, P vo_ctx::*prm_m, int32_t (*defaults)(P*), int32_t* on, P* prm) {
+  if (!c || !on) return VO_E_INVALID;
+  *on = c->*on_m ? 1 : 0;
+  if (prm) { if (c->*on_m) *prm = c->*prm_m; else defaults(prm); }
+  return VO_OK;
+}
+// one stage behind a resident detection: off, it only notes that the last detection did not run it
+inline int32_t vo_corner_stage_detected(vo_ctx* c, hipStream_t q, int max_corners, bool on, vo_side_rows* s, int32_t (*reserve)(vo_ctx*),
+                                        int32_t (*launch)(vo_ctx*, hipStream_t, int)) {
+  s->n = -1;
+  if (!on) return VO_OK;
+  { const int32_t rr = reserve(c); if (rr != VO_OK) return rr; }
+  const int cap = (max_corners > 0 && max_corners < VO_CORNER_CAP) ? max_corners : VO_CORNER_CAP;
+  const int32_t r = launch(c, q, cap);
+  if (r != VO_OK) return r;
+  s->n = cap;
+  return VO_OK;
+}
+// The hook of every detection that spawns tracks (vo_tracks_detect, the closed loop's DETECT stage), right behind the Shi-Tomasi enqueue on q and
+// in front of the spawn: vo_set_brief's descriptors FIRST, so that they always see the integer corners, then vo_set_subpix's refinement, which
+// moves the rows of st_out in place
+inline int32_t vo_corners_detected(vo_ctx* c, hipStream_t q, int max_corners) {
+  const int32_t r = vo_corner_stage_detected(c, q, max_corners, c->brief_on, &c->brief, vo_brief_reserve, vo_brief_launch_detected);
+  return r != VO_OK ? r : vo_corner_stage_detected(c, q, max_corners, c->subpix_on, &c->subpix, vo_subpix_reserve, vo_subpix_launch_detected);
+}

@@ -378,12 +378,12 @@ static void klt_launch_plain(vo_ctx* c, const klt_launch_rows& L, const klt_args
 // the one launch path of the four forms (vo_klt_lk.h)
 int32_t vo_klt_enqueue(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* d_counts, unsigned form) {
   const bool fb = form & KLT_FORM_FB, seeded = form & KLT_FORM_SEEDED;
-  c->fb_n = -1;                         // until this launch is enqueued, the last track ran without the forward-backward check (vo_fb_read)
-  c->guess_n = -1;                      // ... and without a predicted start (vo_klt_guess_read; set by the resident seeded form)
+  c->fb.n = -1;                         // until this launch is enqueued, the last track ran without the forward-backward check (vo_fb_read)
+  c->guess.n = -1;                      // ... and without a predicted start (vo_klt_guess_read; set by the resident seeded form)
   klt_args A;
   { const int32_t r = vo_klt_make_args(c, n, prm, A); if (r != VO_OK) return r; }
-  if (n == 0) { if (fb) c->fb_n = 0; return VO_OK; }
-  if (seeded) VO_CHECK(c, c->d_guess, VO_E_STATE, "no guesses");
+  if (n == 0) { if (fb) c->fb.n = 0; return VO_OK; }
+  if (seeded) VO_CHECK(c, c->guess.d, VO_E_STATE, "no guesses");
   klt_fb_args F;
   if (fb) {
     { const int32_t r = vo_fb_reserve(c); if (r != VO_OK) return r; }
@@ -398,7 +398,7 @@ int32_t vo_klt_enqueue(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* prm
     else klt_launch_plain(c, L, A);
   }
   VO_HIP(c, hipGetLastError());
-  if (fb) c->fb_n = n;
+  if (fb) c->fb.n = n;
   return VO_OK;
 }
 
@@ -417,14 +417,14 @@ static int32_t klt_track_sync(vo_ctx* c, unsigned form, const float* p0, const f
   if (seeded) { const int32_t rg = vo_guess_reserve(c); if (rg != VO_OK) return rg; }
   const size_t off_in = vo_off_p(c), off_out = vo_off_p_next(c);
   VO_HIP(c, rows_h2d(c, c->d_slab + off_in, c->slab_seq, p0, sizeof(float) * 2 * n));
-  if (seeded) VO_HIP(c, rows_h2d(c, c->d_guess, vo_guess_seq(c), guess, sizeof(float) * 2 * n));
+  if (seeded) VO_HIP(c, vo_side_h2d(c, c->guess, 0, guess, n));
   { const int32_t r = vo_klt_enqueue(c, c->stream, n, prm, off_in, off_out, nullptr, form); if (r != VO_OK) return r; }
   VO_HIP(c, rows_d2h(c, p1, c->d_slab + off_out, c->slab_seq, sizeof(float) * 2 * n));
   VO_HIP(c, rows_d2h(c, status, c->d_slab + c->off_status, c->slab_seq, n));
   VO_HIP(c, rows_d2h(c, err, c->d_slab + c->off_err, c->slab_seq, sizeof(float) * n));
   if (fb) {
-    VO_HIP(c, rows_d2h(c, p0r, c->d_fb, c->fb_seq, sizeof(float) * 2 * n));
-    VO_HIP(c, rows_d2h(c, fb_err, c->d_fb + c->fb_off_err, c->fb_seq, sizeof(float) * n));
+    VO_HIP(c, vo_side_d2h(c, c->fb, VO_FB_P0R, p0r, n));
+    VO_HIP(c, vo_side_d2h(c, c->fb, VO_FB_ERR, fb_err, n));
   }
   if (iters) VO_HIP(c, iters_d2h(c, iters, n, prm->max_level + 1));
   VO_HIP(c, hipStreamSynchronize(c->stream));
@@ -488,14 +488,14 @@ extern "C" int32_t vo_klt_track_resident(vo_ctx* c, int32_t n, const vo_klt_para
 }
 
 // the resident form of every track (vo_frame_step_*, vo_tracks_track, the closed loop's TRACK stage): the resident point set in, the other half
-// of the ping-pong out.  A seeded form runs behind a predictor kernel on q, whose guesses stay in c->d_guess (vo_klt_guess_read)
+// of the ping-pong out.  A seeded form runs behind a predictor kernel on q, whose guesses stay in c->guess (vo_klt_guess_read)
 int32_t vo_klt_track_resident_enqueue(vo_ctx* c, hipStream_t q, int32_t n, const vo_klt_params* prm, const int32_t* d_counts, unsigned form) {
   vo_klt_params def;
   if (!prm) { vo_klt_default_params(&def); prm = &def; }
   VO_CHECK(c, n >= 0 && n <= c->n_resident, VO_E_INVALID, "n exceeds the resident point set");
   const int32_t r = vo_klt_enqueue(c, q, n, prm, vo_off_p(c), vo_off_p_next(c), d_counts, form);
   if (r != VO_OK) return r;
-  if (form & KLT_FORM_SEEDED) c->guess_n = n;
+  if (form & KLT_FORM_SEEDED) c->guess.n = n;
   c->p_parity ^= 1;   // tracked positions become the resident set
   return VO_OK;
 }

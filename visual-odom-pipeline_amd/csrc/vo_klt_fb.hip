@@ -67,20 +67,6 @@ __global__ void __launch_bounds__(64, WAVES) k_klt_track_fb(klt_args A, klt_fb_a
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-int32_t vo_fb_reserve(vo_ctx* c) {
-  if (c->d_fb) return VO_OK;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t M = (size_t)c->max_pts;
-  c->fb_off_err = al(8 * M); c->fb_off_ok = c->fb_off_err + al(4 * M); c->fb_seq = c->fb_off_ok + al(M);
-  VO_HIP(c, hipMalloc((void**)&c->d_fb, c->fb_seq * (size_t)c->batch));
-  return VO_OK;
-}
-
-void vo_fb_destroy(vo_ctx* c) {
-  if (c->d_fb) (void)hipFree(c->d_fb);
-  c->d_fb = nullptr;
-}
-
 // the backward pass's argument block for the forward block A (the check's rows must exist: vo_fb_reserve)
 void vo_klt_fb_make_args(const vo_ctx* c, const klt_args& A, klt_fb_args& F) {
   const vo_frame& P = c->fr[c->cur ^ 1];
@@ -89,20 +75,19 @@ void vo_klt_fb_make_args(const vo_ctx* c, const klt_args& A, klt_fb_args& F) {
     F.bw[l] = A.lv[l];
     F.bw[l].imgI = C.img[l]; F.bw[l].derI = reinterpret_cast<const uint32_t*>(C.der[l]); F.bw[l].imgJ = P.img[l];
   }
-  F.fb_seq = c->fb_seq; F.off_err = c->fb_off_err; F.off_ok = c->fb_off_ok;
+  F.fb_seq = c->fb.seq; F.off_err = c->fb.off[VO_FB_ERR]; F.off_ok = c->fb.off[VO_FB_OK];
   F.max_err = c->fb_max_err;
 }
 
 void vo_klt_launch_fb(vo_ctx* c, const klt_launch_rows& L, const klt_args& A, const klt_fb_args& F) {
-  hipLaunchKernelGGL(k_klt_track_fb<6>, dim3(L.n, c->batch), dim3(64), 0, L.q, A, F, L.p0, L.p1, L.status, L.err, c->d_iters, L.counts, c->d_fb);
+  hipLaunchKernelGGL(k_klt_track_fb<6>, dim3(L.n, c->batch), dim3(64), 0, L.q, A, F, L.p0, L.p1, L.status, L.err, c->d_iters, L.counts, c->fb.d);
 }
 
 extern "C" int32_t vo_set_fb_check(vo_ctx* c, float max_err) {
   if (!c) return VO_E_INVALID;
   VO_CHECK(c, max_err == max_err, VO_E_INVALID, "NaN threshold (+inf turns the check off)");
   if (!(max_err == __builtin_inff())) {       // the rows of the check exist before the first enqueue that needs them
-    VO_HIP(c, hipSetDevice(c->device));
-    const int32_t r = vo_fb_reserve(c);
+    const int32_t r = vo_side_reserve_on_device(c, vo_fb_reserve);
     if (r != VO_OK) return r;
   }
   c->fb_max_err = max_err;
@@ -117,15 +102,6 @@ extern "C" int32_t vo_get_fb_check(vo_ctx* c, float* max_err) {
 
 extern "C" int32_t vo_fb_read(vo_ctx* c, uint8_t* ok, float* fb_err, int32_t n) {
   if (!c) return VO_E_INVALID;
-  VO_CHECK(c, !vo_pipe_busy(c) && c->steps_enq == c->steps_fetched, VO_E_STATE, "steps in flight: fetch them first");
-  VO_CHECK(c, c->fb_n >= 0, VO_E_STATE, "the last track ran without the forward-backward check");
-  VO_CHECK(c, n >= 0 && n <= c->fb_n, VO_E_INVALID, "n exceeds the points of the last track");
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  if (n > 0) {
-    if (ok) VO_HIP(c, rows_d2h(c, ok, c->d_fb + c->fb_off_ok, c->fb_seq, n));
-    if (fb_err) VO_HIP(c, rows_d2h(c, fb_err, c->d_fb + c->fb_off_err, c->fb_seq, sizeof(float) * n));
-  }
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  return VO_OK;
+  return vo_side_read(c, __func__, c->fb, "the last track ran without the forward-backward check", "n exceeds the points of the last track", n,
+                      {{ok, VO_FB_OK}, {fb_err, VO_FB_ERR}});
 }

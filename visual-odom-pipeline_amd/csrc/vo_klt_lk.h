@@ -425,14 +425,13 @@ __device__ __forceinline__ void klt_lk_point(const klt_args& A, const klt_level_
 // ------------------------------------------------------------------------------------------------
 // host side: one launch path for the four forms (vo_internal.h: KLT_FORM_FB, KLT_FORM_SEEDED)
 // ------------------------------------------------------------------------------------------------
-// One tracker launch on q from the slab rows at off_in to those at off_out (vo_klt.hip): resets fb_n / guess_n, checks and fills the argument
-// block (vo_klt_make_args; n == 0 ends there, fb_n = 0 for a form with the check), reserves the check's rows or asks for the guesses in
-// c->d_guess as the form needs them, launches the form's kernel inside ONE VO_PROF_KLT bracket, and sets fb_n.  d_counts: see vo_internal.h
+// One tracker launch on q from the slab rows at off_in to those at off_out (vo_klt.hip): resets fb.n / guess.n, checks and fills the argument
+// block (vo_klt_make_args; n == 0 ends there, fb.n = 0 for a form with the check), reserves the check's rows or asks for the guesses in
+// c->guess as the form needs them, launches the form's kernel inside ONE VO_PROF_KLT bracket, and sets fb.n.  d_counts: see vo_internal.h
 int32_t vo_klt_enqueue(vo_ctx* c, hipStream_t q, int n, const vo_klt_params* prm, size_t off_in, size_t off_out, const int32_t* d_counts, unsigned form);
 // the argument checks and block of a tracker launch (vo_klt.hip); nothing is filled for n = 0
 int32_t vo_klt_make_args(vo_ctx* c, int n, const vo_klt_params* prm, klt_args& A);
-// the forward-backward check's rows (allocated on first use) and the backward pass's argument block (vo_klt_fb.hip)
-int32_t vo_fb_reserve(vo_ctx* c);
+// the backward pass's argument block (vo_klt_fb.hip)
 void vo_klt_fb_make_args(const vo_ctx* c, const klt_args& A, klt_fb_args& F);
 
 // what vo_klt_enqueue hands a unit's launcher: the stream and the resolved rows (sequence 0).  A launcher is the hipLaunchKernelGGL of the
@@ -446,13 +445,6 @@ struct klt_launch_rows {
 void vo_klt_launch_fb(vo_ctx* c, const klt_launch_rows& L, const klt_args& A, const klt_fb_args& F);            // vo_klt_fb.hip: k_klt_track_fb
 void vo_klt_launch_seeded(vo_ctx* c, const klt_launch_rows& L, const klt_args& A, const klt_fb_args* F);        // vo_klt_seed.hip: F null = k_klt_seeded, else k_klt_seeded_fb
 
-// strided copies on the ctx stream between [batch][row_bytes] host arrays and per-sequence device rows d_stride bytes apart
-inline hipError_t rows_h2d(vo_ctx* c, void* d, size_t d_stride, const void* h, size_t row_bytes) {
-  return hipMemcpy2DAsync(d, d_stride, h, row_bytes, row_bytes, c->batch, hipMemcpyHostToDevice, c->stream);
-}
-inline hipError_t rows_d2h(vo_ctx* c, void* h, const void* d, size_t d_stride, size_t row_bytes) {
-  return hipMemcpy2DAsync(h, row_bytes, d, d_stride, row_bytes, c->batch, hipMemcpyDeviceToHost, c->stream);
-}
 // the iteration table of the last launch: n points x `levels` entries per sequence
 inline hipError_t iters_d2h(vo_ctx* c, int32_t* h, int n, int levels) {
   return rows_d2h(c, h, c->d_iters, sizeof(int32_t) * (size_t)c->max_pts * VO_MAX_LEVELS, sizeof(int32_t) * (size_t)n * levels);

@@ -10,7 +10,7 @@
 // unit of their own: co-compiled kernels perturb each other's register allocation, and k_klt_track / k_klt_track_fb are pinned.
 //
 // The guesses of the resident paths come from two small predictor kernels (vo_tracks.hip: k_trk_predict, vo_pipeline.hip: k_pipe_predict),
-// constant velocity from the track's own history: g = uv + (uv - prev), or uv without a finite prev.  They write c->d_guess
+// constant velocity from the track's own history: g = uv + (uv - prev), or uv without a finite prev.  They write c->guess
 // [batch][max_pts][2] f32 in the tracker's point order on the tracker's stream, right before the launch here.
 #include "vo_klt_lk.h"
 
@@ -112,31 +112,19 @@ __global__ void __launch_bounds__(64, WAVES) k_klt_seeded_fb(klt_args A, klt_fb_
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-int32_t vo_guess_reserve(vo_ctx* c) {
-  if (c->d_guess) return VO_OK;
-  VO_HIP(c, hipMalloc((void**)&c->d_guess, vo_guess_seq(c) * (size_t)c->batch));
-  return VO_OK;
-}
-
-void vo_guess_destroy(vo_ctx* c) {
-  if (c->d_guess) (void)hipFree(c->d_guess);
-  c->d_guess = nullptr;
-}
-
-// the guesses are the rows of c->d_guess
+// the guesses are the rows of c->guess
 void vo_klt_launch_seeded(vo_ctx* c, const klt_launch_rows& L, const klt_args& A, const klt_fb_args* F) {
-  if (F) hipLaunchKernelGGL(k_klt_seeded_fb<5>, dim3(L.n, c->batch), dim3(64), 0, L.q, A, *F, L.p0, c->d_guess, vo_guess_seq(c), L.p1, L.status, L.err,
-                            c->d_iters, L.counts, c->d_fb);
-  else hipLaunchKernelGGL(k_klt_seeded<5>, dim3(L.n, c->batch), dim3(64), 0, L.q, A, L.p0, c->d_guess, vo_guess_seq(c), L.p1, L.status, L.err,
-                          c->d_iters, L.counts);
+  const float* const g = vo_side_col<const float>(c->guess, 0);
+  if (F) hipLaunchKernelGGL(k_klt_seeded_fb<5>, dim3(L.n, c->batch), dim3(64), 0, L.q, A, *F, L.p0, g, c->guess.seq, L.p1, L.status, L.err,
+                            c->d_iters, L.counts, c->fb.d);
+  else hipLaunchKernelGGL(k_klt_seeded<5>, dim3(L.n, c->batch), dim3(64), 0, L.q, A, L.p0, g, c->guess.seq, L.p1, L.status, L.err, c->d_iters, L.counts);
 }
 
 extern "C" int32_t vo_set_klt_predict(vo_ctx* c, int32_t mode) {
   if (!c) return VO_E_INVALID;
   VO_CHECK(c, mode == VO_KLT_PREDICT_OFF || mode == VO_KLT_PREDICT_CONST_VELOCITY, VO_E_INVALID, "unknown prediction mode");
   if (mode != VO_KLT_PREDICT_OFF) {           // the guess rows exist before the first enqueue that needs them
-    VO_HIP(c, hipSetDevice(c->device));
-    const int32_t r = vo_guess_reserve(c);
+    const int32_t r = vo_side_reserve_on_device(c, vo_guess_reserve);
     if (r != VO_OK) return r;
   }
   c->klt_predict = mode;
@@ -151,15 +139,5 @@ extern "C" int32_t vo_get_klt_predict(vo_ctx* c, int32_t* mode) {
 
 extern "C" int32_t vo_klt_guess_read(vo_ctx* c, float* guess, int32_t n) {
   if (!c) return VO_E_INVALID;
-  VO_CHECK(c, !vo_pipe_busy(c) && c->steps_enq == c->steps_fetched, VO_E_STATE, "steps in flight: fetch them first");
-  VO_CHECK(c, c->guess_n >= 0, VO_E_STATE, "the last track did not predict");
-  VO_CHECK(c, n >= 0 && n <= c->guess_n, VO_E_INVALID, "n exceeds the points of the last track");
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  if (n > 0) {
-    VO_CHECK(c, guess, VO_E_INVALID, "null buffer");
-    VO_HIP(c, rows_d2h(c, guess, c->d_guess, vo_guess_seq(c), sizeof(float) * 2 * n));
-  }
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  return VO_OK;
+  return vo_side_read(c, __func__, c->guess, "the last track did not predict", "n exceeds the points of the last track", n, {{guess, 0}}, true);
 }

@@ -1523,7 +1523,7 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
       r = vo_guess_reserve(c);
       if (r == VO_OK && w->N > 0) {
         hipLaunchKernelGGL(k_pipe_predict, dim3(vo_div_up(w->N, 256), B), dim3(256), 0, tq, P, vo_slab<const float>(c, vo_off_p(c)), c->slab_seq,
-                           c->d_guess, vo_guess_seq(c));
+                           vo_side_col<float>(c->guess, 0), c->guess.seq);
         if (hipGetLastError() != hipSuccess) r = vo_fail(c, VO_E_HIP, "pipe_step: k_pipe_predict launch");
       }
     }
@@ -1536,7 +1536,7 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
   if ((stages & VO_PIPE_TRACK) || (stages & (VO_PIPE_TRACK_CANDIDATES | VO_PIPE_TRACK_LANDMARKS))) {
     const size_t lds = sizeof(int32_t) * ((w->N > 4 * PIPE_TPB ? 0 : (size_t)w->R) + 3 * (size_t)w->N);     // (above 4 096 slots the row words are global)
     PIPE_DISPATCH_LDS(k_pipe_extend, lds, c->stream, P, vo_slab<const float>(c, vo_off_p(c)), c->slab_seq, c->width, c->height, pv.X, pv.uv, pv.cap,
-                      halves, const_cast<uint8_t*>(pv.mask), (w->fb_active && w->N > 0) ? vo_fb_ok(c) : nullptr, c->fb_seq);
+                      halves, const_cast<uint8_t*>(pv.mask), (w->fb_active && w->N > 0) ? vo_fb_ok(c) : nullptr, c->fb.seq);
   }
   if (stages & VO_PIPE_POSE) {
     r = vo_pnp_enqueue_counts(c, c->stream, &prm.pnp, prm.pnp_blind_batches, w->d_dn + DN_PNP * B);
@@ -1569,12 +1569,16 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
   // on the shared BA workspace (vo_ba_solve_resident on a problem written through vo_ba_obs_device) sees every slot
   vo_ba_enqueue_opts ba_live = {};
   ba_live.d_live = (const int32_t*)w->tab[VO_PIPE_COUNTS] + C_NLM; ba_live.live_stride = PIPE_NCNT;
+  // the DETECT stage's enqueues on q in front of the spawn: the re-detection, then the corner stages on what it found
+  auto detect = [&](hipStream_t q) -> int32_t {
+    if (!(stages & VO_PIPE_DETECT)) return VO_OK;
+    const int32_t rd = vo_shi_tomasi_resident_counts(c, q, w->N, prm.mask_radius, &prm.st, w->d_dn + DN_PTS * B, w->d_dn + DN_ROOM * B);
+    return rd != VO_OK ? rd : vo_corners_detected(c, q, prm.st.max_corners);
+  };
   if (side) {
     // re-detection + spawn on the side stream behind promote / dense; adjustment + write-back on the main stream
     VO_HIP(c, vo_stream_fork(c->ev_fork, c->stream, c->stream2));
-    r = (stages & VO_PIPE_DETECT) ? vo_shi_tomasi_resident_counts(c, c->stream2, w->N, prm.mask_radius, &prm.st, w->d_dn + DN_PTS * B, w->d_dn + DN_ROOM * B) : VO_OK;
-    if (r == VO_OK && (stages & VO_PIPE_DETECT)) r = vo_brief_describe_detected(c, c->stream2, prm.st.max_corners);    // vo_set_brief: the integer corners
-    if (r == VO_OK && (stages & VO_PIPE_DETECT)) r = vo_subpix_refine_detected(c, c->stream2, prm.st.max_corners);     // vo_set_subpix: before the spawn
+    r = detect(c->stream2);
     if (r == VO_OK) pipe_launch_spawn(c, c->stream2, (stages & VO_PIPE_DETECT) ? 1 : 0, (stages & VO_PIPE_KEEP_FREE_LISTS) ? 0 : 1);
     if (r == VO_OK && (stages & VO_PIPE_ADJUST)) r = vo_ba_enqueue_budget(c, c->stream, &prm.ba, 0, prm.ba_budget, ba_live);
     if (r == VO_OK) PIPE_DISPATCH_LDS(k_pipe_writeback, 0, c->stream, P, (stages & VO_PIPE_ADJUST) ? 1 : 0, bv.pub, bv.pub_bytes, bv.x0, bv.x_stride, bv.W, w->d_rec);
@@ -1586,14 +1590,8 @@ static int32_t pipe_step(vo_ctx* c, int32_t frame_idx, int32_t stages, bool main
       r = vo_ba_enqueue_budget(c, c->stream, &prm.ba, 0, prm.ba_budget, ba_live);
       if (r != VO_OK) return r;
     }
-    if (stages & VO_PIPE_DETECT) {
-      r = vo_shi_tomasi_resident_counts(c, c->stream, w->N, prm.mask_radius, &prm.st, w->d_dn + DN_PTS * B, w->d_dn + DN_ROOM * B);
-      if (r != VO_OK) return r;
-      r = vo_brief_describe_detected(c, c->stream, prm.st.max_corners);    // vo_set_brief: the integer corners
-      if (r != VO_OK) return r;
-      r = vo_subpix_refine_detected(c, c->stream, prm.st.max_corners);     // vo_set_subpix: before the spawn
-      if (r != VO_OK) return r;
-    }
+    r = detect(c->stream);
+    if (r != VO_OK) return r;
     PIPE_DISPATCH_LDS(k_pipe_writeback, 0, c->stream, P, (stages & VO_PIPE_ADJUST) ? 1 : 0, bv.pub, bv.pub_bytes, bv.x0, bv.x_stride, bv.W, w->d_rec);
     pipe_launch_spawn(c, c->stream, (stages & VO_PIPE_DETECT) ? 1 : 0, (stages & VO_PIPE_KEEP_FREE_LISTS) ? 0 : 1);
   }

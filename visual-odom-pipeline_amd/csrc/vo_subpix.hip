@@ -23,7 +23,6 @@
 #define SUBPIX_MAX_WIN 7
 #define SUBPIX_PW (2 * SUBPIX_MAX_WIN + 3)                    // patch pitch = its largest width
 #define SUBPIX_MAX_PIX ((2 * SUBPIX_MAX_WIN + 1) * (2 * SUBPIX_MAX_WIN + 1))
-#define SUBPIX_CAP 4096                                       // corners a Shi-Tomasi launch can put out (ST_OUT_CAP)
 
 struct subpix_args {
   const uint8_t* img;          // level 0 of the chosen frame, sequence 0 (padded: interior at (VO_PAD, VO_PAD))
@@ -161,24 +160,6 @@ __global__ void __launch_bounds__(256) k_corner_subpix(subpix_args A, const floa
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-// c->d_subpix, per sequence: raw [cap][2] f32 | out [cap][2] f32 (the synchronous form's rows) | iters [cap] i32 | flags [cap] u8
-static inline int subpix_cap(const vo_ctx* c) { return c->max_pts > SUBPIX_CAP ? c->max_pts : SUBPIX_CAP; }
-static inline size_t subpix_off_out(const vo_ctx* c) { return sizeof(float) * 2 * (size_t)subpix_cap(c); }
-static inline size_t subpix_off_iters(const vo_ctx* c) { return 2 * subpix_off_out(c); }
-static inline size_t subpix_off_flags(const vo_ctx* c) { return subpix_off_iters(c) + sizeof(int32_t) * (size_t)subpix_cap(c); }
-static inline size_t subpix_seq(const vo_ctx* c) { return (subpix_off_flags(c) + (size_t)subpix_cap(c) + 15) & ~(size_t)15; }
-
-static int32_t subpix_reserve(vo_ctx* c) {
-  if (c->d_subpix) return VO_OK;
-  VO_HIP(c, hipMalloc((void**)&c->d_subpix, subpix_seq(c) * (size_t)c->batch));
-  return VO_OK;
-}
-
-void vo_subpix_destroy(vo_ctx* c) {
-  if (c->d_subpix) (void)hipFree(c->d_subpix);
-  c->d_subpix = nullptr;
-}
-
 extern "C" int32_t vo_subpix_default_params(vo_subpix_params* p) {
   if (!p) return VO_E_INVALID;
   p->win_x = p->win_y = 5; p->zero_x = p->zero_y = -1; p->max_count = 40; p->_pad = 0; p->epsilon = 0.001;
@@ -218,18 +199,13 @@ static void subpix_make_args(const vo_ctx* c, const vo_frame& F, const vo_subpix
       for (int j = A.wx - zx; j <= A.wx + zx; j++) A.mask[i * ww + j] = 0.f;
 }
 
-static inline uint8_t* subpix_info(const vo_ctx* c, size_t off) { return reinterpret_cast<uint8_t*>(c->d_subpix) + off; }
-
+// the kernel over the corner rows `rows` (refined in place); its notes go to c->subpix
 static int32_t subpix_launch(vo_ctx* c, hipStream_t q, const subpix_args& A, float* rows, size_t rows_seq, const uint32_t* counts, size_t counts_seq) {
-  hipLaunchKernelGGL(k_corner_subpix, dim3(vo_div_up(A.cap, 4), c->batch), dim3(256), 0, q, A, rows, rows, rows_seq,
-                     reinterpret_cast<float*>(subpix_info(c, 0)), reinterpret_cast<int32_t*>(subpix_info(c, subpix_off_iters(c))),
-                     subpix_info(c, subpix_off_flags(c)), subpix_seq(c), counts, counts_seq);
+  const vo_side_rows& s = c->subpix;
+  hipLaunchKernelGGL(k_corner_subpix, dim3(vo_div_up(A.cap, 4), c->batch), dim3(256), 0, q, A, rows, rows, rows_seq, vo_side_col<float>(s, VO_SUBPIX_RAW),
+                     vo_side_col<int32_t>(s, VO_SUBPIX_ITERS), vo_side_col<uint8_t>(s, VO_SUBPIX_FLAGS), s.seq, counts, counts_seq);
   VO_HIP(c, hipGetLastError());
   return VO_OK;
-}
-
-static hipError_t subpix_d2h(vo_ctx* c, void* h, size_t off, size_t row_bytes) {
-  return hipMemcpy2DAsync(h, row_bytes, subpix_info(c, off), subpix_seq(c), row_bytes, c->batch, hipMemcpyDeviceToHost, c->stream);
 }
 
 extern "C" int32_t vo_corner_subpix(vo_ctx* c, int32_t which, const float* corners, int32_t n, const vo_subpix_params* prm, float* out,
@@ -237,73 +213,38 @@ extern "C" int32_t vo_corner_subpix(vo_ctx* c, int32_t which, const float* corne
   if (!c) return VO_E_INVALID;
   vo_subpix_params def;
   if (!prm) { vo_subpix_default_params(&def); prm = &def; }
-  VO_CHECK(c, which == 0 || which == 1, VO_E_INVALID, "which must be 0 (previous frame) or 1 (current frame)");
-  VO_CHECK(c, n >= 0 && n <= c->max_pts, VO_E_INVALID, "n exceeds max_pts");
-  { const int32_t r = subpix_check(c, prm); if (r != VO_OK) return r; }
-  VO_CHECK(c, c->n_pushed >= (which == 0 ? 2 : 1), VO_E_STATE, "frame not pushed yet");
-  if (n == 0) return VO_OK;
-  VO_CHECK(c, corners && out, VO_E_INVALID, "null buffer");
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  { const int32_t rr = subpix_reserve(c); if (rr != VO_OK) return rr; }
-  c->subpix_n = -1;                       // the info rows no longer describe a detection
-  subpix_args A;
-  subpix_make_args(c, c->fr[which == 1 ? c->cur : (c->cur ^ 1)], prm, n, A);
-  const size_t row = sizeof(float) * 2 * (size_t)n;
-  VO_HIP(c, hipMemcpy2DAsync(subpix_info(c, subpix_off_out(c)), subpix_seq(c), corners, row, row, c->batch, hipMemcpyHostToDevice, c->stream));
-  { const int32_t r = subpix_launch(c, c->stream, A, reinterpret_cast<float*>(subpix_info(c, subpix_off_out(c))), subpix_seq(c), nullptr, 0);
-    if (r != VO_OK) return r; }
-  VO_HIP(c, subpix_d2h(c, out, subpix_off_out(c), row));
-  if (iters) VO_HIP(c, subpix_d2h(c, iters, subpix_off_iters(c), sizeof(int32_t) * (size_t)n));
-  if (flags) VO_HIP(c, subpix_d2h(c, flags, subpix_off_flags(c), (size_t)n));
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  return VO_OK;
+  return vo_corner_sync(c, __func__, &c->subpix, vo_subpix_reserve, VO_SUBPIX_OUT, which, corners, n, [&] { return subpix_check(c, prm); },
+                        [&](const vo_frame& F) {
+                          subpix_args A;
+                          subpix_make_args(c, F, prm, n, A);
+                          return subpix_launch(c, c->stream, A, vo_side_col<float>(c->subpix, VO_SUBPIX_OUT), c->subpix.seq, nullptr, 0);
+                        },
+                        {{out, VO_SUBPIX_OUT}, {iters, VO_SUBPIX_ITERS}, {flags, VO_SUBPIX_FLAGS}});
 }
 
 extern "C" int32_t vo_set_subpix(vo_ctx* c, const vo_subpix_params* prm) {
   if (!c) return VO_E_INVALID;
   if (!prm) { c->subpix_on = false; return VO_OK; }
   { const int32_t r = subpix_check(c, prm); if (r != VO_OK) return r; }
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rr = subpix_reserve(c); if (rr != VO_OK) return rr; }      // the rows exist before the first enqueue that needs them
+  { const int32_t rr = vo_side_reserve_on_device(c, vo_subpix_reserve); if (rr != VO_OK) return rr; }
   c->subpix_prm = *prm; c->subpix_prm._pad = 0;
   c->subpix_on = true;
   return VO_OK;
 }
 
 extern "C" int32_t vo_get_subpix(vo_ctx* c, int32_t* on, vo_subpix_params* prm) {
-  if (!c || !on) return VO_E_INVALID;
-  *on = c->subpix_on ? 1 : 0;
-  if (prm) { if (c->subpix_on) *prm = c->subpix_prm; else vo_subpix_default_params(prm); }
-  return VO_OK;
+  return vo_corner_get(c, &vo_ctx::subpix_on, &vo_ctx::subpix_prm, vo_subpix_default_params, on, prm);
 }
 
-// the resident detections' hook: refine the corners the selection kernel has just left in st_out on q, in place, against the current frame
-int32_t vo_subpix_refine_detected(vo_ctx* c, hipStream_t q, int max_corners) {
-  c->subpix_n = -1;
-  if (!c->subpix_on) return VO_OK;
-  { const int32_t rr = subpix_reserve(c); if (rr != VO_OK) return rr; }
-  const int cap = (max_corners > 0 && max_corners < SUBPIX_CAP) ? max_corners : SUBPIX_CAP;
+// (vo_corners_detected) the corners the selection kernel has just left in st_out on q, refined in place against the current frame
+int32_t vo_subpix_launch_detected(vo_ctx* c, hipStream_t q, int cap) {
   subpix_args A;
   subpix_make_args(c, c->fr[c->cur], &c->subpix_prm, cap, A);
-  const int32_t r = subpix_launch(c, q, A, vo_slab<float>(c, c->off_st_out), c->slab_seq, vo_slab<const uint32_t>(c, c->off_st_scalars), c->slab_seq);
-  if (r != VO_OK) return r;
-  c->subpix_n = cap;
-  return VO_OK;
+  return subpix_launch(c, q, A, vo_slab<float>(c, c->off_st_out), c->slab_seq, vo_slab<const uint32_t>(c, c->off_st_scalars), c->slab_seq);
 }
 
 extern "C" int32_t vo_subpix_read(vo_ctx* c, float* raw, int32_t* iters, uint8_t* flags, int32_t n) {
   if (!c) return VO_E_INVALID;
-  VO_CHECK(c, !vo_pipe_busy(c) && c->steps_enq == c->steps_fetched, VO_E_STATE, "steps in flight: fetch them first");
-  VO_CHECK(c, c->subpix_n >= 0, VO_E_STATE, "the last detection did not refine");
-  VO_CHECK(c, n >= 0 && n <= c->subpix_n, VO_E_INVALID, "n exceeds the corners of the last detection");
-  VO_HIP(c, hipSetDevice(c->device));
-  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  if (n > 0) {
-    if (raw) VO_HIP(c, subpix_d2h(c, raw, 0, sizeof(float) * 2 * (size_t)n));
-    if (iters) VO_HIP(c, subpix_d2h(c, iters, subpix_off_iters(c), sizeof(int32_t) * (size_t)n));
-    if (flags) VO_HIP(c, subpix_d2h(c, flags, subpix_off_flags(c), (size_t)n));
-  }
-  VO_HIP(c, hipStreamSynchronize(c->stream));
-  return VO_OK;
+  return vo_side_read(c, __func__, c->subpix, "the last detection did not refine", "n exceeds the corners of the last detection", n,
+                      {{raw, VO_SUBPIX_RAW}, {iters, VO_SUBPIX_ITERS}, {flags, VO_SUBPIX_FLAGS}});
 }

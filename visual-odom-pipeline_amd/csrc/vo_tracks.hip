@@ -258,7 +258,7 @@ extern "C" int32_t vo_tracks_track(vo_ctx* c, int32_t t, const vo_klt_params* pr
     { const int32_t rg = vo_guess_reserve(c); if (rg != VO_OK) return rg; }
     if (tw->n_hi > 0) {
       hipLaunchKernelGGL(k_trk_predict, dim3(vo_div_up(tw->n_hi, 256), c->batch), dim3(256), 0, c->stream, trk_make(tw),
-                         vo_slab<const float>(c, vo_off_p(c)), c->slab_seq, t, tw->n_hi, c->d_guess, vo_guess_seq(c));
+                         vo_slab<const float>(c, vo_off_p(c)), c->slab_seq, t, tw->n_hi, vo_side_col<float>(c->guess, 0), c->guess.seq);
       VO_HIP(c, hipGetLastError());
     }
   }
@@ -267,7 +267,7 @@ extern "C" int32_t vo_tracks_track(vo_ctx* c, int32_t t, const vo_klt_params* pr
     if (r != VO_OK) return r;
   }
   hipLaunchKernelGGL(k_trk_extend, dim3(c->batch), dim3(1024), 0, c->stream, trk_make(tw), vo_slab<float>(c, vo_off_p(c)),
-                     c->slab_seq, t, c->width, c->height, (fb && tw->n_hi > 0) ? vo_fb_ok(c) : nullptr, c->fb_seq);
+                     c->slab_seq, t, c->width, c->height, (fb && tw->n_hi > 0) ? vo_fb_ok(c) : nullptr, c->fb.seq);
   VO_HIP(c, hipGetLastError());
   return VO_OK;
 }
@@ -283,8 +283,7 @@ extern "C" int32_t vo_tracks_detect(vo_ctx* c, int32_t t, int32_t mask_radius, c
   if (!st) { vo_st_default_params(&def); st = &def; }
   const int32_t r = vo_shi_tomasi_resident(c, tw->n_hi, mask_radius, st);
   if (r != VO_OK) return r;
-  { const int32_t rb = vo_brief_describe_detected(c, c->stream, st->max_corners); if (rb != VO_OK) return rb; }    // vo_set_brief: the integer corners
-  { const int32_t rs = vo_subpix_refine_detected(c, c->stream, st->max_corners); if (rs != VO_OK) return rs; }     // vo_set_subpix: before the spawn
+  { const int32_t rc = vo_corners_detected(c, c->stream, st->max_corners); if (rc != VO_OK) return rc; }
   if (max_new < 0) max_new = 0;
   hipLaunchKernelGGL(k_trk_spawn, dim3(c->batch), dim3(256), 0, c->stream, trk_make(tw), vo_slab<float>(c, vo_off_p(c)), c->slab_seq,
                      vo_slab<const uint32_t>(c, c->off_st_scalars), vo_slab<const float>(c, c->off_st_out), t, max_new);

@@ -33,7 +33,7 @@ class VoContext:
         self.width, self.height, self.max_pts = width, height, max_pts
         self.max_level, self.win, self.device, self.batch = max_level, win, device, batch
         self._st_max_corners = 1000
-        self._subpix_slots = 1000       # corner slots of the last detection that may have refined (subpix_read)
+        self._corner_slots = 1000       # corner slots the last detection could fill (subpix_read, brief_read)
         self._klt_levels = max_level + 1
         self.comm_ranks, self.comm_rank = 1, 0
         if self.default_tuning:
@@ -389,6 +389,17 @@ class VoContext:
         p.max_count, p.epsilon = int(max_count), float(epsilon)
         return p
 
+    @staticmethod
+    def _which(which):
+        """the frame a corner stage works on: "prev" / "cur" or the library's 0 / 1"""
+        return int({"prev": 0, "cur": 1}.get(which, which))
+
+    def _cut_corner_rows(self, n, dead, **cols):
+        """per sequence the rows in front of the first slot the detection did not fill (dead [B, n]) -> dict of copies [list of B dicts if batch > 1]"""
+        ms = [int(np.argmax(d)) if d.any() else n for d in dead]
+        out = [{k: v[b, :m].copy() for k, v in cols.items()} for b, m in enumerate(ms)]
+        return out[0] if self.batch == 1 else out
+
     def corner_subpix(self, corners, which="cur", params=None, return_info=False):
         """cv2.cornerSubPix on a frame of the frame store (vo_corner_subpix): corners (n,2) f32 -> refined (n,2) f32, with return_info also
         iters (n,) i32 and flags (n,) u8 (0 stopped, 1 singular, 2 left the image, 3 reverted, 4 input not usable)  [leading batch dim if
@@ -396,11 +407,10 @@ class VoContext:
         p, n = self._npts(corners)
         B = self.batch
         prm = params if params is not None else self.subpix_params()
-        w = {"prev": 0, "cur": 1}.get(which, which)
         out = p.copy()
         it = np.zeros((B, n), np.int32)
         fl = np.zeros((B, n), np.uint8)
-        self._ck(self._L.vo_corner_subpix(self._h, int(w), ptr(p, C.c_float), n, C.byref(prm), ptr(out, C.c_float), ptr(it, C.c_int32),
+        self._ck(self._L.vo_corner_subpix(self._h, self._which(which), ptr(p, C.c_float), n, C.byref(prm), ptr(out, C.c_float), ptr(it, C.c_int32),
                                           ptr(fl, C.c_uint8)))
         if return_info:
             return self._out(out), self._out(it), self._out(fl)
@@ -425,17 +435,12 @@ class VoContext:
         (default: all the detection could fill); slots the detection did not fill hold NaN and are cut off."""
         B = self.batch
         if n is None:
-            n = self._subpix_slots
+            n = self._corner_slots
         raw = np.zeros((B, n, 2), np.float32)
         it = np.zeros((B, n), np.int32)
         fl = np.zeros((B, n), np.uint8)
         self._ck(self._L.vo_subpix_read(self._h, ptr(raw, C.c_float), ptr(it, C.c_int32), ptr(fl, C.c_uint8), n))
-        out = []
-        for b in range(B):
-            dead = np.isnan(raw[b]).any(axis=1)
-            m = int(np.argmax(dead)) if dead.any() else n
-            out.append(dict(raw=raw[b, :m].copy(), iters=it[b, :m].copy(), flags=fl[b, :m].copy()))
-        return out[0] if B == 1 else out
+        return self._cut_corner_rows(n, np.isnan(raw).any(axis=2), raw=raw, iters=it, flags=fl)
 
     # -- oriented BRIEF descriptor -------------------------------------------------------------------
     @staticmethod
@@ -473,11 +478,10 @@ class VoContext:
         B = self.batch
         prm = params if params is not None else self.brief_params()
         pat = self._brief_pattern(pattern)
-        w = {"prev": 0, "cur": 1}.get(which, which)
         desc = np.zeros((B, n, 32), np.uint8)
         ang = np.zeros((B, n), np.float32)
         fl = np.zeros((B, n), np.uint8)
-        self._ck(self._L.vo_brief_compute(self._h, int(w), ptr(p, C.c_float), n, C.byref(prm), ptr(pat, C.c_int8), ptr(desc, C.c_uint8),
+        self._ck(self._L.vo_brief_compute(self._h, self._which(which), ptr(p, C.c_float), n, C.byref(prm), ptr(pat, C.c_int8), ptr(desc, C.c_uint8),
                                           ptr(ang, C.c_float), ptr(fl, C.c_uint8)))
         return self._out(desc), self._out(ang), self._out(fl)
 
@@ -509,17 +513,12 @@ class VoContext:
         the detection did not fill carry flags = 2 and are cut off."""
         B = self.batch
         if n is None:
-            n = self._subpix_slots
+            n = self._corner_slots
         desc = np.zeros((B, n, 32), np.uint8)
         ang = np.zeros((B, n), np.float32)
         fl = np.zeros((B, n), np.uint8)
         self._ck(self._L.vo_brief_read(self._h, ptr(desc, C.c_uint8), ptr(ang, C.c_float), ptr(fl, C.c_uint8), n))
-        out = []
-        for b in range(B):
-            dead = fl[b] == 2
-            m = int(np.argmax(dead)) if dead.any() else n
-            out.append(dict(desc=desc[b, :m].copy(), angle=ang[b, :m].copy(), flags=fl[b, :m].copy()))
-        return out[0] if B == 1 else out
+        return self._cut_corner_rows(n, fl == 2, desc=desc, angle=ang, flags=fl)
 
     def points_upload(self, p):
         p, n = self._npts(p)
@@ -1213,7 +1212,7 @@ class VoContext:
     def tracks_detect(self, t, mask_radius=7, params=None, max_new=1000):
         """Shi-Tomasi re-detection around the live tracks; corners become tracks born at t (async)."""
         prm = params if params is not None else self.st_params()
-        self._subpix_slots = prm.max_corners if 0 < prm.max_corners < 4096 else 4096
+        self._corner_slots = prm.max_corners if 0 < prm.max_corners < 4096 else 4096
         self._ck(self._L.vo_tracks_detect(self._h, int(t), int(mask_radius), C.byref(prm), int(max_new)))
 
     def tracks_read(self):

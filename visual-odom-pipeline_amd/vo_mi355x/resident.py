@@ -107,7 +107,7 @@ class ResidentPipeline:
         if not (descriptor is None and ctx.get_brief() is None):
             ctx.set_brief(descriptor == 'brief' or None, brief_pattern)
         ctx.apply_ingest(undistort, clahe, clear_missing=True)
-        ctx._subpix_slots = p.st.max_corners if 0 < p.st.max_corners < 4096 else 4096
+        ctx._corner_slots = p.st.max_corners if 0 < p.st.max_corners < 4096 else 4096
         self.N, self.R, self.B = ctx.max_pts, 4 * ctx.max_pts, B
         self.ba_window = ba_window
         self._inflight = 0
