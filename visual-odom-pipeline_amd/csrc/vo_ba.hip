@@ -959,18 +959,7 @@ __global__ void __launch_bounds__(256) k_ba_cost_r(ba_ptrs Pall, ba_params_dev p
 // host side
 // ------------------------------------------------------------------------------------------------
 void vo_ba_destroy(vo_ctx* c) {
-  if (!c->ba) return;
-  vo_ba_ws* b = c->ba;
-  if (b->d_x0_own) { b->d_x0 = b->d_x0_own; b->d_obs = b->d_obs_own; }
-  if (b->d_bank_x0) (void)hipFree(b->d_bank_x0);
-  if (b->d_bank_obs) (void)hipFree(b->d_bank_obs);
-  void* bufs[] = {b->d_K, b->d_obs, b->d_x0, b->d_x[0], b->d_x[1], b->d_aux, b->d_posepart, b->d_gmax,
-                  b->d_tiles, b->d_dp, b->d_evalpart, b->d_tilesum, b->d_xstat, b->d_gather, b->d_cams, b->d_S, b->d_Hpp, b->d_res, b->d_dl, b->d_pub, b->d_state, b->d_info, b->d_gdyn};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  if (b->h_gather) (void)hipHostFree(b->h_gather);
-  if (b->h_state) (void)hipHostFree(b->h_state);
-  if (b->h_pub) (void)hipHostFree(b->h_pub);
-  delete b;
+  delete c->ba;
   c->ba = nullptr;
 }
 
@@ -1039,7 +1028,57 @@ template <int LOSS> static hipError_t ba_set_lds_limits() {
   return e;
 }
 
-// every buffer: [batch] x per-problem size
+// the buffers of a new workspace for W slots x N landmark slots.  Every buffer: [batch] x per-problem size
+static int32_t ba_build(vo_ctx* c, vo_ba_ws* b, int W, int N) {
+  const size_t B = (size_t)c->batch;
+  b->cap_W = W; b->cap_N = N;
+  ba_geometry(b, W, N, c->tune);
+  // any N' <= N runs with 256-lane workgroups when that gives <= 160 sets, else with the 1024-lane ones of N at most
+  {
+    const int small = vo_div_up(N, 256 / b->LPP);
+    b->cap_nblk = b->nblk > (small < 160 ? small : 160) ? b->nblk : (small < 160 ? small : 160);
+  }
+  const int nblk_alloc = b->cap_nblk;
+  const size_t nx = (size_t)6 * W + 3 * N;
+  VO_HIP(c, b->d_K.reserve(9 * B));
+  VO_HIP(c, b->d_obs_own.reserve((size_t)2 * W * N * B));
+  VO_HIP(c, b->d_x0_own.reserve(nx * B));
+  b->d_obs = b->d_obs_own; b->d_x0 = b->d_x0_own;
+  VO_HIP(c, b->d_x[0].reserve(nx * B));
+  VO_HIP(c, b->d_x[1].reserve(nx * B));
+  VO_HIP(c, b->d_aux.reserve((size_t)N * BA_AUX * B));
+  VO_HIP(c, b->d_posepart.reserve((size_t)nblk_alloc * W * BA_POSE_VALS * B));
+  VO_HIP(c, b->d_gmax.reserve(nblk_alloc * B));
+  VO_HIP(c, b->d_tiles.reserve((size_t)nblk_alloc * b->n_tiles * 256 * B));
+  VO_HIP(c, b->d_dp.reserve((size_t)6 * W * B));
+  VO_HIP(c, b->d_evalpart.reserve((size_t)nblk_alloc * BA_EVAL_VALS * B));
+  b->red_stride = (size_t)b->n_tiles * 256 + (size_t)W * BA_POSE_VALS + 1 + VO_COMM_MAX_RANKS;
+  VO_HIP(c, b->d_tilesum.reserve(b->red_stride * B));
+  VO_HIP(c, hipMemsetAsync(b->d_tilesum, 0, sizeof(double) * b->red_stride * B, c->stream));
+  b->d_posesum = b->d_tilesum + (size_t)b->n_tiles * 256;
+  VO_HIP(c, b->d_xstat.reserve(BA_EVAL_VALS * B));
+  VO_HIP(c, b->d_cams.reserve((size_t)2 * W * BA_CAM * B));
+  VO_HIP(c, b->d_S.reserve((size_t)36 * W * W + 6 * W));          // probes: problem 0 only
+  VO_HIP(c, b->d_Hpp.reserve((size_t)W * BA_POSE_VALS));
+  VO_HIP(c, b->d_res.reserve((size_t)W * N * B));
+  VO_HIP(c, b->d_dl.reserve((size_t)3 * N));
+  b->pub_bytes = VO_BA_PUB_HEADER + sizeof(double) * nx;                                                        // per problem
+  VO_HIP(c, b->d_pub.reserve(b->pub_bytes * B));
+  VO_HIP(c, b->h_pub.reserve(3 * b->pub_bytes * B));   // two halves (pipelined frame steps) + one for vo_ba_fetch
+  b->d_xout = reinterpret_cast<double*>(b->d_pub.get() + VO_BA_PUB_HEADER);
+  VO_HIP(c, b->d_state.reserve(2 * B));
+  VO_HIP(c, b->d_info.reserve(B));
+  VO_HIP(c, b->d_gdyn.reserve(2 * B));
+  VO_HIP(c, hipMemsetAsync(b->d_gdyn, 0, sizeof(int) * 2 * B, c->stream));
+  VO_HIP(c, b->h_state.reserve(B));
+  VO_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_solve), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  for (auto set : {ba_set_lds_limits<VO_LOSS_HUBER>, ba_set_lds_limits<VO_LOSS_SOFT_L1>, ba_set_lds_limits<VO_LOSS_CAUCHY>, ba_set_lds_limits<VO_LOSS_ARCTAN>})
+    VO_HIP(c, set());
+  VO_HIP(c, vo_ba_f_set_lds_limits());
+  return VO_OK;
+}
+
+// the workspace for (W, N): kept, or destroyed and built afresh (vo_ws_replace: attached only when every buffer exists)
 static int32_t ba_alloc(vo_ctx* c, int W, int N) {
   VO_CHECK(c, W >= 1 && W <= BA_MAX_SLOTS, VO_E_CAPACITY, "window size must be 1..20");
   VO_CHECK(c, N >= 1, VO_E_INVALID, "no landmarks");
@@ -1051,53 +1090,9 @@ static int32_t ba_alloc(vo_ctx* c, int W, int N) {
     ba_geometry(&probe, W, N, c->tune);
     if (probe.nblk > c->ba->cap_nblk) vo_ba_destroy(c);
   }
-  const size_t B = (size_t)c->batch;
   if (!c->ba) {
-    vo_ba_ws* b = new vo_ba_ws();
-    c->ba = b;
-    b->cap_W = W; b->cap_N = N;
-    ba_geometry(b, W, N, c->tune);
-    // any N' <= N runs with 256-lane workgroups when that gives <= 160 sets, else with the 1024-lane ones of N at most
-    {
-      const int small = vo_div_up(N, 256 / b->LPP);
-      b->cap_nblk = b->nblk > (small < 160 ? small : 160) ? b->nblk : (small < 160 ? small : 160);
-    }
-    const int nblk_alloc = b->cap_nblk;
-    const size_t nx = (size_t)6 * W + 3 * N;
-    VO_HIP(c, hipMalloc((void**)&b->d_K, 9 * sizeof(double) * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_obs, sizeof(double) * 2 * W * N * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_x0, sizeof(double) * nx * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_x[0], sizeof(double) * nx * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_x[1], sizeof(double) * nx * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_aux, sizeof(double) * (size_t)N * BA_AUX * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_posepart, sizeof(double) * (size_t)nblk_alloc * W * BA_POSE_VALS * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_gmax, sizeof(double) * nblk_alloc * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_tiles, sizeof(double) * (size_t)nblk_alloc * b->n_tiles * 256 * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_dp, sizeof(double) * 6 * W * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_evalpart, sizeof(double) * nblk_alloc * BA_EVAL_VALS * B));
-    b->red_stride = (size_t)b->n_tiles * 256 + (size_t)W * BA_POSE_VALS + 1 + VO_COMM_MAX_RANKS;
-    VO_HIP(c, hipMalloc((void**)&b->d_tilesum, sizeof(double) * b->red_stride * B));
-    VO_HIP(c, hipMemsetAsync(b->d_tilesum, 0, sizeof(double) * b->red_stride * B, c->stream));
-    b->d_posesum = b->d_tilesum + (size_t)b->n_tiles * 256;
-    VO_HIP(c, hipMalloc((void**)&b->d_xstat, sizeof(double) * BA_EVAL_VALS * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_cams, sizeof(double) * 2 * W * BA_CAM * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_S, sizeof(double) * ((size_t)36 * W * W + 6 * W)));          // probes: problem 0 only
-    VO_HIP(c, hipMalloc((void**)&b->d_Hpp, sizeof(double) * (size_t)W * BA_POSE_VALS));
-    VO_HIP(c, hipMalloc((void**)&b->d_res, sizeof(double) * (size_t)W * N * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_dl, sizeof(double) * (size_t)3 * N));
-    b->pub_bytes = VO_BA_PUB_HEADER + sizeof(double) * nx;                                                        // per problem
-    VO_HIP(c, hipMalloc((void**)&b->d_pub, b->pub_bytes * B));
-    VO_HIP(c, hipHostMalloc((void**)&b->h_pub, 3 * b->pub_bytes * B, hipHostMallocDefault));   // two halves (pipelined frame steps) + one for vo_ba_fetch
-    b->d_xout = reinterpret_cast<double*>(b->d_pub + VO_BA_PUB_HEADER);
-    VO_HIP(c, hipMalloc((void**)&b->d_state, sizeof(ba_state) * 2 * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_info, sizeof(ba_info) * B));
-    VO_HIP(c, hipMalloc((void**)&b->d_gdyn, sizeof(int) * 2 * B));
-    VO_HIP(c, hipMemsetAsync(b->d_gdyn, 0, sizeof(int) * 2 * B, c->stream));
-    VO_HIP(c, hipHostMalloc((void**)&b->h_state, sizeof(ba_state) * B, hipHostMallocDefault));
-    VO_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_solve), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    for (auto set : {ba_set_lds_limits<VO_LOSS_HUBER>, ba_set_lds_limits<VO_LOSS_SOFT_L1>, ba_set_lds_limits<VO_LOSS_CAUCHY>, ba_set_lds_limits<VO_LOSS_ARCTAN>})
-      VO_HIP(c, set());
-    VO_HIP(c, vo_ba_f_set_lds_limits());
+    const int32_t r = vo_ws_replace(c->ba, [&](vo_ba_ws& b) { return ba_build(c, &b, W, N); });
+    if (r != VO_OK) return r;
   }
   ba_geometry(c->ba, W, N, c->tune);
   if (c->batch > 1024) c->ba->v2 = 0;             // (ba2_select_work keeps the running-problem flags of <= 1 024 problems in LDS)
@@ -1126,14 +1121,13 @@ extern "C" int32_t vo_ba_upload_bank(vo_ctx* c, const double* K, const double* p
   if (r != VO_OK) return r;
   vo_ba_ws* b = c->ba;
   const size_t W = b->W, N = b->N, B = c->batch, nx = 6 * W + 3 * N, no = 2 * W * N;
-  VO_HIP(c, hipMalloc((void**)&b->d_bank_x0, sizeof(double) * nx * B * n_problems));
-  VO_HIP(c, hipMalloc((void**)&b->d_bank_obs, sizeof(double) * no * B * n_problems));
+  VO_HIP(c, b->d_bank_x0.reserve(nx * B * n_problems));
+  VO_HIP(c, b->d_bank_obs.reserve(no * B * n_problems));
   VO_HIP(c, hipMemcpyAsync(b->d_K, K, 9 * sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
   VO_HIP(c, hipMemcpyAsync(b->d_bank_obs, obs, sizeof(double) * no * B * n_problems, hipMemcpyHostToDevice, c->stream));
   VO_HIP(c, hipMemcpy2DAsync(b->d_bank_x0, sizeof(double) * nx, poses, sizeof(double) * 6 * W, sizeof(double) * 6 * W, B * n_problems, hipMemcpyHostToDevice, c->stream));
   VO_HIP(c, hipMemcpy2DAsync(b->d_bank_x0 + 6 * W, sizeof(double) * nx, points, sizeof(double) * 3 * N, sizeof(double) * 3 * N, B * n_problems, hipMemcpyHostToDevice, c->stream));
   VO_HIP(c, hipStreamSynchronize(c->stream));
-  b->d_x0_own = b->d_x0; b->d_obs_own = b->d_obs;
   b->d_x0 = b->d_bank_x0; b->d_obs = b->d_bank_obs;
   b->bank_n = n_problems; b->bank_sel = 0;
   b->uploaded = true;
@@ -1470,14 +1464,8 @@ extern "C" int32_t vo_ba_gather_points(vo_ctx* c, double* points_all) {
   VO_HIP(c, hipSetDevice(c->device));
   vo_ba_ws* b = c->ba;
   const size_t B = c->batch, R = c->comm_ranks, cnt = B * 3 * (size_t)b->N;
-  if (b->gather_cap < cnt * (1 + R)) {
-    if (b->d_gather) (void)hipFree(b->d_gather);
-    if (b->h_gather) (void)hipHostFree(b->h_gather);
-    b->d_gather = nullptr; b->h_gather = nullptr; b->gather_cap = 0;
-    VO_HIP(c, hipMalloc((void**)&b->d_gather, sizeof(double) * cnt * (1 + R)));
-    VO_HIP(c, hipHostMalloc((void**)&b->h_gather, sizeof(double) * cnt * R, hipHostMallocDefault));
-    b->gather_cap = cnt * (1 + R);
-  }
+  VO_HIP(c, b->d_gather.reserve(cnt * (1 + R)));
+  VO_HIP(c, b->h_gather.reserve(cnt * R));
   double* send = b->d_gather; double* recv = b->d_gather + cnt;
   // points part of the published x of every problem -> packed send buffer
   VO_HIP(c, hipMemcpy2DAsync(send, sizeof(double) * 3 * b->N, b->d_pub + VO_BA_PUB_HEADER + sizeof(double) * 6 * b->W, b->pub_bytes,

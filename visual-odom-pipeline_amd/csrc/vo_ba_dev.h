@@ -80,45 +80,44 @@ struct vo_ba_ws {
   int cap_nblk = 0;             // partial sets the nblk-sized buffers (posepart, gmax, tiles, evalpart) were allocated for
   size_t build_lds = 0, solve_lds = 0;
   int cam_off = 0;
-  double* d_K = nullptr;        // 9
-  double* d_obs = nullptr;      // W*N*2
-  double* d_x0 = nullptr;       // W*6 + N*3
-  double* d_x[2] = {nullptr, nullptr};
-  double* d_aux = nullptr;      // N * BA_AUX
-  double* d_posepart = nullptr; // nblk * W * 28
-  double* d_gmax = nullptr;     // nblk
-  double* d_tiles = nullptr;    // nblk * n_tiles * 256
-  double* d_dp = nullptr;       // 6W
-  double* d_evalpart = nullptr; // nblk * 4
-  double* d_tilesum = nullptr;  // n_tiles * 256                  } one allocation, red_stride doubles per problem:
+  vo_dev<double> d_K;           // 9
+  double* d_obs = nullptr;      // W*N*2   } the problem a solve reads: d_obs_own / d_x0_own, or the selected problem of the bank
+  double* d_x0 = nullptr;       // W*6 + N*3 } (d_bank_obs / d_bank_x0)
+  vo_dev<double> d_obs_own, d_x0_own;
+  vo_dev<double> d_x[2];
+  vo_dev<double> d_aux;         // N * BA_AUX
+  vo_dev<double> d_posepart;    // nblk * W * 28
+  vo_dev<double> d_gmax;        // nblk
+  vo_dev<double> d_tiles;       // nblk * n_tiles * 256
+  vo_dev<double> d_dp;          // 6W
+  vo_dev<double> d_evalpart;    // nblk * 4
+  vo_dev<double> d_tilesum;     // n_tiles * 256                  } one allocation, red_stride doubles per problem:
   double* d_posesum = nullptr;  // W * 28 + 1 (+ 16 rank slots)    } d_posesum = d_tilesum + n_tiles * 256
   size_t red_stride = 0;
-  double* d_xstat = nullptr;    // [batch][4] sharded solve: summed step statistics
-  double* d_gather = nullptr;   // vo_ba_gather_points: send [batch][N][3] | recv [n_ranks][batch][N][3]
-  double* h_gather = nullptr;   // pinned mirror of recv
-  size_t gather_cap = 0;
-  double* d_cams = nullptr;     // 2 * W * 21
-  double* d_S = nullptr;        // probe: (6W)^2 + 6W
-  double* d_Hpp = nullptr;      // W*28 reduced pose values (probe)
-  double* d_res = nullptr;      // probe residual W*N
-  double* d_dl = nullptr;       // probe d_points 3N
+  vo_dev<double> d_xstat;       // [batch][4] sharded solve: summed step statistics
+  vo_dev<double> d_gather;      // vo_ba_gather_points: send [batch][N][3] | recv [n_ranks][batch][N][3]; made and grown there
+  vo_pinned<double> h_gather;   // pinned mirror of recv
+  vo_dev<double> d_cams;        // 2 * W * 21
+  vo_dev<double> d_S;           // probe: (6W)^2 + 6W
+  vo_dev<double> d_Hpp;         // W*28 reduced pose values (probe)
+  vo_dev<double> d_res;         // probe residual W*N
+  vo_dev<double> d_dl;          // probe d_points 3N
   double* d_xout = nullptr;     // published solution 6W + 3N (points into d_pub)
-  uint8_t* d_pub = nullptr;     // [ba_state (64 B) | x]: what a fetch copies back in one go
-  uint8_t* h_pub = nullptr;     // pinned mirror
+  vo_dev<uint8_t> d_pub;        // [ba_state (64 B) | x]: what a fetch copies back in one go
+  vo_pinned<uint8_t> h_pub;     // pinned mirror
   size_t pub_bytes = 0;
-  ba_state* d_state = nullptr;  // [2]
-  ba_info* d_info = nullptr;
-  ba_state* h_state = nullptr;  // pinned
+  vo_dev<ba_state> d_state;     // [2]
+  vo_dev<ba_info> d_info;
+  vo_pinned<ba_state> h_state;
   bool uploaded = false;
-  // bank of resident problems (vo_ba_upload_bank): d_x0 / d_obs point at the selected one; the workspace's own buffers are kept for the free
-  double* d_x0_own = nullptr; double* d_obs_own = nullptr;
-  double* d_bank_x0 = nullptr; double* d_bank_obs = nullptr;
+  // bank of resident problems (vo_ba_upload_bank): d_x0 / d_obs point at the selected one
+  vo_dev<double> d_bank_x0, d_bank_obs;
   int bank_n = 0, bank_sel = 0;
   // wave-private kernels (vo_ba_wave.h): windows of <= 10 slots; v2 = 2: their factored form (vo_ba_factored.hip) where the loss allows it
   int v2 = 0, v2_rt = 0, v2_spl = 0, v2_lpp = 8;
   size_t v2_lds = 0;
   int v2_g0 = 1, v2_gcap = 1;       // workgroups per problem of a launch; the most a running problem is given once others have finished
-  int* d_gdyn = nullptr;            // [2][batch]
+  vo_dev<int> d_gdyn;               // [2][batch]
 };
 
 // ------------------------------------------------------------------------------------------------

@@ -215,7 +215,7 @@ extern "C" int32_t vo_set_clahe(vo_ctx* c, double clip_limit, int32_t tiles_x, i
   const size_t lut_bytes = (size_t)c->batch * CL_MAX_TILES * CL_MAX_TILES * 256;      // room for every accepted grid
   int32_t r = vo_ingest_reserve(c, &c->d_clahe);
   if (r != VO_OK) return r;
-  if (!c->d_clahe_lut) VO_HIP(c, hipMalloc((void**)&c->d_clahe_lut, lut_bytes));
+  VO_HIP(c, c->d_clahe_lut.reserve(lut_bytes));
   r = vo_sync_streams(c);                                                // no build in flight runs with the setting that is replaced
   if (r != VO_OK) return r;
   VO_HIP(c, hipMemsetAsync(c->d_clahe_lut, 0, lut_bytes, c->stream));    // vo_clahe_lut_read before the first launch of a setting: zeros

@@ -137,7 +137,7 @@ static int32_t dlt_set_cams(vo_ctx* c, const float* P0, const float* P1, const d
       for (int k = 0; k < 4; k++) a.H1z[k] = H1b[8 + k];
     }
   }
-  if (!c->d_dlt_cam) VO_HIP(c, hipMalloc((void**)&c->d_dlt_cam, sizeof(vo_dlt_cam) * B));
+  VO_HIP(c, c->d_dlt_cam.reserve(B));
   VO_HIP(c, hipMemcpy(c->d_dlt_cam, cams.data(), sizeof(vo_dlt_cam) * B, hipMemcpyHostToDevice));   // synchronous: `cams` is a local
   c->dlt_stats = K ? 1 : 0;
   return VO_OK;

@@ -34,8 +34,8 @@ static_assert(sizeof(e5_ctrl) == 96 && offsetof(e5_ctrl, best_h) == 12 && offset
               offsetof(e5_ctrl, E) == 24, "e5_ctrl layout");
 
 struct vo_ess_ws : vo_tv_search_ws<e5_hyp, e5_ctrl, E5_BATCH> {      // h_out: [B][E5_OUT], then 10 staging doubles per sequence
-  double* d_K = nullptr;       // [B][9] K, then [B] squared thresholds
-  double* d_q = nullptr;       // [B][2][cap][2] normalised
+  vo_dev<double> d_K;          // [B][9] K, then [B] squared thresholds
+  vo_dev<double> d_q;          // [B][2][cap][2] normalised
 };
 
 __constant__ int c_mul11[4][4] = {{0, 3, 4, 6}, {3, 1, 5, 7}, {4, 5, 2, 8}, {6, 7, 8, 9}};
@@ -625,11 +625,7 @@ __global__ void __launch_bounds__(256) k_e5_finish(const double* __restrict__ q,
 // ================================================================================================
 // host
 // ================================================================================================
-void vo_ess_destroy(vo_ctx* c) {
-  if (c->ess && c->ess->d_K) (void)hipFree(c->ess->d_K);
-  if (c->ess && c->ess->d_q) (void)hipFree(c->ess->d_q);
-  vo_tv_free(c->ess);
-}
+void vo_ess_destroy(vo_ctx* c) { vo_tv_free(c->ess); }
 
 extern "C" int32_t vo_essential_default_params(vo_ess_params* p) {
   if (!p) return VO_E_INVALID;
@@ -638,12 +634,11 @@ extern "C" int32_t vo_essential_default_params(vo_ess_params* p) {
 }
 
 static int32_t ess_alloc(vo_ctx* c, int n) {
-  int32_t r = vo_tv_alloc(c, c->ess, vo_ess_destroy, n, E5_OUT, 10);
-  if (r != VO_OK) return r;
-  vo_ess_ws* w = c->ess;
-  if (!w->d_K) VO_HIP(c, hipMalloc((void**)&w->d_K, sizeof(double) * (9 + 1) * c->batch));
-  if (!w->d_q) VO_HIP(c, hipMalloc((void**)&w->d_q, sizeof(double) * 4 * c->batch * w->cap));
-  return VO_OK;
+  return vo_tv_alloc(c, c->ess, vo_ess_destroy, n, E5_OUT, 10, 0, [c](vo_ess_ws& w) -> int32_t {
+    VO_HIP(c, w.d_K.reserve((size_t)(9 + 1) * c->batch));
+    VO_HIP(c, w.d_q.reserve((size_t)4 * c->batch * w.cap));
+    return VO_OK;
+  });
 }
 
 // K [batch][9], pts1 / pts2 [batch][n][2] f32 (pixels, view 1 / view 2) -> E [batch][9] (unit Frobenius norm),
@@ -677,7 +672,7 @@ extern "C" int32_t vo_essential_ransac(vo_ctx* c, const double* K, const float* 
   if (r != VO_OK) return r;
   hipLaunchKernelGGL(k_e5_prep, dim3(vo_div_up(n, 256), (unsigned)B), dim3(256), 0, c->stream, w->d_K, w->d_p, w->d_q, cap, n);
   hipLaunchKernelGGL(k_e5_init, dim3((unsigned)B), dim3(1), 0, c->stream, w->d_ctrl, prm->max_iters);
-  r = vo_ransac_rounds(c, c->stream, w->d_ctrl, w->h_ctrl, B, (prm->max_iters + E5_BATCH - 1) / E5_BATCH, [&](int) {
+  r = vo_ransac_rounds(c, c->stream, w->d_ctrl.get(), w->h_ctrl.get(), B, (prm->max_iters + E5_BATCH - 1) / E5_BATCH, [&](int) {
     hipLaunchKernelGGL(k_e5_solve, dim3(E5_BATCH / 64, (unsigned)B), dim3(64), 0, c->stream, w->d_q, cap, n, (unsigned)prm->seed, w->d_hyp, w->d_ctrl);
     hipLaunchKernelGGL(k_e5_score, dim3(E5_BATCH, (unsigned)B), dim3(64 * E5_MAXSOL), 0, c->stream, w->d_q, cap, n, d_thr2, w->d_hyp);
     hipLaunchKernelGGL(k_e5_select, dim3((unsigned)B), dim3(E5_BATCH), 0, c->stream, w->d_hyp, w->d_ctrl, n, prm->prob, prm->max_iters);

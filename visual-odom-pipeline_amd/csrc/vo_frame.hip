@@ -360,19 +360,18 @@ extern "C" int32_t vo_ctx_destroy(vo_ctx* c) {
   vo_ba_destroy(c);
   for (vo_side_rows* s : {&c->fb, &c->guess, &c->subpix, &c->brief}) vo_side_free(s);
   vo_orb_destroy(c);
-  vo_ingest_free(&c->und_on, &c->d_und, (void**)&c->d_und_tab);
-  vo_ingest_free(&c->cl_on, &c->d_clahe, (void**)&c->d_clahe_lut);
-  for (int f = 0; f < 2; f++)
-    for (int l = 0; l < VO_MAX_LEVELS; l++) {
-      if (c->fr[f].img[l]) (void)hipFree(c->fr[f].img[l]);
-      if (c->fr[f].der[l]) (void)hipFree(c->fr[f].der[l]);
-    }
+  vo_ingest_free(&c->und_on);
+  vo_ingest_free(&c->cl_on);
   for (auto& g : c->step_graphs) if (g.second) (void)hipGraphExecDestroy(g.second);
-  void* bufs[] = {c->d_bil_cw, c->d_dbg, c->d_raw, c->d_seq, c->d_iters, c->d_uv0, c->d_uv1, c->d_slab, c->d_frame_idx, c->d_dlt_cam};
-  for (void* b : bufs) if (b) (void)hipFree(b);
-  if (c->h_slab) (void)hipHostFree(c->h_slab);
-  if (c->h_frame_idx) (void)hipHostFree(c->h_frame_idx);
-  if (c->h_raw) (void)hipHostFree(c->h_raw);
+  // the context's own memory goes here, in front of its events and streams, not with `delete c` behind them
+  c->d_und.reset(); c->d_und_tab.reset(); c->d_clahe.reset(); c->d_clahe_lut.reset();
+  for (int f = 0; f < 2; f++)
+    for (int l = 0; l < VO_MAX_LEVELS; l++) { c->fr_img[f][l].reset(); c->fr_der[f][l].reset(); }
+  c->d_bil_cw.reset(); c->d_dbg.reset(); c->d_raw.reset(); c->d_seq.reset(); c->d_iters.reset(); c->d_uv0.reset(); c->d_uv1.reset();
+  c->d_slab.reset(); c->d_frame_idx.reset(); c->d_dlt_cam.reset();
+  c->h_slab.reset(); c->h_frame_idx.reset(); c->h_raw.reset();
+  for (int k = 0; k < 2; k++) c->d_host_raw[k].reset();
+  c->h_ptr_tab.reset();
   if (c->ev_raw) (void)hipEventDestroy(c->ev_raw);
   for (hipEvent_t e : c->prof.pool) (void)hipEventDestroy(e);
   for (int k = 0; k < 2; k++) if (c->ev_step[k]) (void)hipEventDestroy(c->ev_step[k]);
@@ -381,12 +380,10 @@ extern "C" int32_t vo_ctx_destroy(vo_ctx* c) {
   if (c->stream2) (void)hipStreamDestroy(c->stream2);
   if (c->stream3) (void)hipStreamDestroy(c->stream3);
   for (int k = 0; k < 2; k++) {
-    if (c->d_host_raw[k]) (void)hipFree(c->d_host_raw[k]);
     if (c->ev_h2d[k]) (void)hipEventDestroy(c->ev_h2d[k]);
     if (c->ev_raw_free[k]) (void)hipEventDestroy(c->ev_raw_free[k]);
   }
   if (c->stream_h2d) (void)hipStreamDestroy(c->stream_h2d);
-  if (c->h_ptr_tab) (void)hipHostFree(c->h_ptr_tab);
   for (int k = 0; k < 2; k++) if (c->ev_ba_wide[k]) (void)hipEventDestroy(c->ev_ba_wide[k]);
   for (int k = 0; k < 2; k++) { if (c->ev_ba[k]) (void)hipEventDestroy(c->ev_ba[k]); if (c->ev_pub[k]) (void)hipEventDestroy(c->ev_pub[k]); if (c->ev_copy1[k]) (void)hipEventDestroy(c->ev_copy1[k]); }
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -428,8 +425,6 @@ extern "C" int32_t vo_ctx_create_batched(int32_t device, int32_t width, int32_t 
   if (device < 0 || device >= ndev) { g_create_err = "vo_ctx_create: bad device index"; return VO_E_INVALID; }
   vo_ctx* c = new (std::nothrow) vo_ctx();
   if (!c) return VO_E_NOMEM;
-  for (int f = 0; f < 2; f++)
-    for (int l = 0; l < VO_MAX_LEVELS; l++) { c->fr[f].img[l] = nullptr; c->fr[f].der[l] = nullptr; }
   c->device = device; c->width = width; c->height = height; c->max_pts = max_pts; c->batch = batch;
   c->max_level = max_level; c->win = win;
   auto fail = [&](int32_t code) { g_create_err = c->err; vo_ctx_destroy(c); return code; };
@@ -464,13 +459,14 @@ extern "C" int32_t vo_ctx_create_batched(int32_t device, int32_t width, int32_t 
   for (int f = 0; f < 2; f++)
     for (int l = 0; l <= top; l++) {
       const size_t px = c->lvl_px[l] * (size_t)batch;
-      CR(hipMalloc((void**)&c->fr[f].img[l], px));
-      CR(hipMalloc((void**)&c->fr[f].der[l], px * 4));
+      CR(c->fr_img[f][l].reserve(px));
+      CR(c->fr_der[f][l].reserve(px * 2));
+      c->fr[f].img[l] = c->fr_img[f][l]; c->fr[f].der[l] = c->fr_der[f][l];
       CR(hipMemsetAsync(c->fr[f].img[l], 0, px, c->stream));
       CR(hipMemsetAsync(c->fr[f].der[l], 0, px * 4, c->stream));   // border stays 0 forever
     }
-  CR(hipMalloc((void**)&c->d_raw, (size_t)width * height * batch));
-  CR(hipMalloc((void**)&c->d_dbg, sizeof(unsigned long long) * 32));
+  CR(c->d_raw.reserve((size_t)width * height * batch));
+  CR(c->d_dbg.reserve(32));
   CR(hipMemsetAsync(c->d_dbg, 0, sizeof(unsigned long long) * 32, c->stream));
   {
     // result slab layout (all offsets 256-byte aligned)
@@ -482,15 +478,15 @@ extern "C" int32_t vo_ctx_create_batched(int32_t device, int32_t width, int32_t 
     c->off_st_scalars = take(64); c->off_st_out = take(8 * 4096);
     c->slab_seq = off;
     c->slab_bytes = off * (size_t)batch;
-    CR(hipMalloc((void**)&c->d_slab, c->slab_bytes));
+    CR(c->d_slab.reserve(c->slab_bytes));
     CR(hipMemsetAsync(c->d_slab, 0, c->slab_bytes, c->stream));
-    CR(hipHostMalloc((void**)&c->h_slab, 2 * c->slab_bytes, hipHostMallocDefault));
+    CR(c->h_slab.reserve(2 * c->slab_bytes));
   }
-  CR(hipMalloc((void**)&c->d_iters, sizeof(int32_t) * (size_t)max_pts * VO_MAX_LEVELS * batch));
-  CR(hipMalloc((void**)&c->d_uv0, sizeof(float) * 2 * (size_t)max_pts * batch));
-  CR(hipMalloc((void**)&c->d_uv1, sizeof(float) * 2 * (size_t)max_pts * batch));
-  CR(hipMalloc((void**)&c->d_frame_idx, sizeof(int32_t)));
-  CR(hipHostMalloc((void**)&c->h_frame_idx, sizeof(int32_t) * 64, hipHostMallocDefault));
+  CR(c->d_iters.reserve((size_t)max_pts * VO_MAX_LEVELS * batch));
+  CR(c->d_uv0.reserve(2 * (size_t)max_pts * batch));
+  CR(c->d_uv1.reserve(2 * (size_t)max_pts * batch));
+  CR(c->d_frame_idx.reserve(1));
+  CR(c->h_frame_idx.reserve(64));
   CR(hipStreamSynchronize(c->stream));
 #undef CR
   *out = c;
@@ -509,8 +505,8 @@ extern "C" int32_t vo_sync(vo_ctx* c) {
 // frames
 // ------------------------------------------------------------------------------------------------
 // ---- what the ingest stages' entry points share (vo_internal.h) ----
-int32_t vo_ingest_reserve(vo_ctx* c, uint8_t** staging) {
-  if (!*staging) VO_HIP(c, hipMalloc((void**)staging, (size_t)c->width * c->height * c->batch));
+int32_t vo_ingest_reserve(vo_ctx* c, vo_dev<uint8_t>* staging) {
+  VO_HIP(c, staging->reserve((size_t)c->width * c->height * c->batch));
   return VO_OK;
 }
 
@@ -521,11 +517,7 @@ int32_t vo_ingest_commit(vo_ctx* c, bool* on) {
   return VO_OK;
 }
 
-void vo_ingest_free(bool* on, uint8_t** staging, void** table) {
-  if (*staging) (void)hipFree(*staging);
-  if (*table) (void)hipFree(*table);
-  *staging = nullptr; *table = nullptr; *on = false;
-}
+void vo_ingest_free(bool* on) { *on = false; }
 
 int32_t vo_ingest_run(vo_ctx* c, const vo_ingest_stage& s, const char* off_msg, const uint8_t* img, int32_t stride, uint8_t* out) {
   VO_CHECK(c, img != nullptr && out != nullptr && stride >= c->width, VO_E_INVALID, "bad image / stride");
@@ -600,7 +592,7 @@ extern "C" int32_t vo_frame_push(vo_ctx* c, const uint8_t* img, int32_t stride) 
   // longer waits for the pyramid (the caller's buffer is free as soon as the memcpy is done)
   const size_t rows = (size_t)c->height * c->batch, bytes = rows * c->width;
   if (!c->h_raw) {
-    VO_HIP(c, hipHostMalloc((void**)&c->h_raw, bytes, hipHostMallocDefault));
+    VO_HIP(c, c->h_raw.reserve(bytes));
     VO_HIP(c, hipEventCreateWithFlags(&c->ev_raw, hipEventDisableTiming));
   } else {
     VO_HIP(c, hipEventSynchronize(c->ev_raw));    // the previous frame has left the staging buffer
@@ -618,9 +610,10 @@ extern "C" int32_t vo_seq_upload(vo_ctx* c, const uint8_t* frames, int32_t n_fra
   VO_CHECK(c, frames != nullptr && n_frames > 0, VO_E_INVALID, "bad sequence");
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rs = vo_sync_streams(c); if (rs != VO_OK) return rs; }
-  if (c->d_seq) { VO_HIP(c, hipFree(c->d_seq)); c->d_seq = nullptr; c->seq_n = 0; }
+  c->d_seq.reset();             // every upload has a block of its own size
+  c->seq_n = 0;
   const size_t bytes = (size_t)c->width * c->height * n_frames * c->batch;
-  VO_HIP(c, hipMalloc((void**)&c->d_seq, bytes));
+  VO_HIP(c, c->d_seq.reserve(bytes));
   VO_HIP(c, hipMemcpy(c->d_seq, frames, bytes, hipMemcpyHostToDevice));
   c->seq_n = n_frames;
   return VO_OK;
@@ -689,7 +682,7 @@ extern "C" int32_t vo_set_prefilter(vo_ctx* c, int32_t d, double sigma_color, do
       c->bil_dx[maxk] = (signed char)j; c->bil_dy[maxk] = (signed char)i;
       maxk++;
     }
-  if (!c->d_bil_cw) VO_HIP(c, hipMalloc((void**)&c->d_bil_cw, sizeof(cw)));
+  VO_HIP(c, c->d_bil_cw.reserve(256));
   VO_HIP(c, hipMemcpyAsync(c->d_bil_cw, cw, sizeof(cw), hipMemcpyHostToDevice, c->stream));
   VO_HIP(c, hipStreamSynchronize(c->stream));
   c->bil_maxk = maxk;

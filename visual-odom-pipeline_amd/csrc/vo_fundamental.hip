@@ -482,7 +482,7 @@ static int32_t fund_search(vo_ctx* c, hipStream_t q, const float* pts1, const fl
   int32_t r = vo_tv_upload(c, q, w, pts1, pts2, n);
   if (r != VO_OK) return r;
   hipLaunchKernelGGL(k_f7_init, dim3((unsigned)B), dim3(1), 0, q, w->d_ctrl, prm->max_iters);
-  r = vo_ransac_rounds(c, q, w->d_ctrl, w->h_ctrl, B, (prm->max_iters + F7_BATCH - 1) / F7_BATCH, [&](int) {
+  r = vo_ransac_rounds(c, q, w->d_ctrl.get(), w->h_ctrl.get(), B, (prm->max_iters + F7_BATCH - 1) / F7_BATCH, [&](int) {
     {
       vo_prof_scope prof(c, q, VO_PROF_FUND_SOLVE);
       hipLaunchKernelGGL(k_f7_solve, dim3(F7_BATCH / 64, (unsigned)B), dim3(64), 0, q, w->d_p, cap, n, (unsigned)prm->seed, w->d_hyp, w->d_ctrl);

@@ -435,7 +435,7 @@ int32_t vo_hom_ransac_tail(vo_ctx* c, const float* pts1, const float* pts2, int3
   r = vo_tv_upload(c, c->stream, w, pts1, pts2, n);
   if (r != VO_OK) return r;
   hipLaunchKernelGGL(k_h4_init, dim3((unsigned)B), dim3(1), 0, c->stream, w->d_ctrl, prm->max_iters);
-  r = vo_ransac_rounds(c, c->stream, w->d_ctrl, w->h_ctrl, B, (prm->max_iters + H4_BATCH - 1) / H4_BATCH, [&](int) {
+  r = vo_ransac_rounds(c, c->stream, w->d_ctrl.get(), w->h_ctrl.get(), B, (prm->max_iters + H4_BATCH - 1) / H4_BATCH, [&](int) {
     {
       vo_prof_scope prof(c, c->stream, VO_PROF_HOM_SOLVE);
       hipLaunchKernelGGL(k_h4_solve, dim3(H4_BATCH / 64, (unsigned)B), dim3(64), 0, c->stream, w->d_p, cap, n, (unsigned)prm->seed, w->d_hyp, w->d_ctrl);

@@ -29,7 +29,7 @@
 #define HP_NCNT 9              // n_good (4), n_off (4), n_mask
 
 struct vo_hpose_ws : vo_tv_ws {
-  double* d_K = nullptr;       // [B][9] K, then [B][9] H
+  vo_dev<double> d_K;          // [B][9] K, then [B][9] H
 };
 
 // the candidates of one sequence as the one lane leaves them for the vote, in the order of the formulas
@@ -289,10 +289,7 @@ __global__ void __launch_bounds__(256) k_hpose(const double* __restrict__ Kall, 
 // ================================================================================================
 // host
 // ================================================================================================
-void vo_hpose_destroy(vo_ctx* c) {
-  if (c->hpose && c->hpose->d_K) (void)hipFree(c->hpose->d_K);
-  vo_tv_free(c->hpose);
-}
+void vo_hpose_destroy(vo_ctx* c) { vo_tv_free(c->hpose); }
 
 extern "C" int32_t vo_homography_pose_default_params(vo_hpose_params* p) {
   if (!p) return VO_E_INVALID;
@@ -315,10 +312,10 @@ static int32_t hpose_check(vo_ctx* c, const vo_hpose_params* prm) {
 }
 
 static int32_t hpose_alloc(vo_ctx* c, int n) {
-  int32_t r = vo_tv_alloc(c, c->hpose, vo_hpose_destroy, n, HP_OUT, 0, 1);
-  if (r != VO_OK) return r;
-  if (!c->hpose->d_K) VO_HIP(c, hipMalloc((void**)&c->hpose->d_K, sizeof(double) * 18 * c->batch));
-  return VO_OK;
+  return vo_tv_alloc(c, c->hpose, vo_hpose_destroy, n, HP_OUT, 0, 1, [c](vo_hpose_ws& w) -> int32_t {
+    VO_HIP(c, w.d_K.reserve((size_t)18 * c->batch));
+    return VO_OK;
+  });
 }
 
 // the pinned read-back -> the caller's arrays

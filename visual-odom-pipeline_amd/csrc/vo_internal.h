@@ -6,6 +6,7 @@
 #include <string>
 #include <type_traits>
 
+#include "vo_buf.h"
 #include "vo_mi355x.h"
 
 #define VO_PAD 32          // border (pixels) around every pyramid level, >= win + 1
@@ -18,7 +19,7 @@ struct vo_level {
   int ph;          // padded rows = h + 2*VO_PAD
 };
 
-struct vo_frame {
+struct vo_frame {                // the levels of one frame-store half: plain pointers, owned by vo_ctx::fr_img / fr_der
   uint8_t* img[VO_MAX_LEVELS];   // padded, origin of the interior at (VO_PAD, VO_PAD)
   int16_t* der[VO_MAX_LEVELS];   // padded, interleaved (Ix, Iy), same pixel pitch; border = 0
 };
@@ -45,13 +46,13 @@ struct vo_dlt_cam {
 // grow for a feature that step never runs).  Per sequence up to four typed columns of the same number of rows, in a device allocation of its
 // own that is made when the feature is first asked for (a context that never asks has none), and a note of what the last producer left there
 struct vo_side_rows {
-  uint8_t* d = nullptr;              // [batch][seq]; null until reserved
+  vo_dev<uint8_t> d;                 // [batch][seq]; null until reserved
   size_t seq = 0;                    // bytes per sequence
   size_t off[4] = {0, 0, 0, 0};      // column k of sequence 0 starts here
   size_t elem[4] = {0, 0, 0, 0};     // bytes per row of column k
   int n = -1;                        // rows per sequence the last producer wrote, else -1
 };
-template <class T> inline T* vo_side_col(const vo_side_rows& s, int k) { return reinterpret_cast<T*>(s.d + s.off[k]); }     // column k of sequence 0
+template <class T> inline T* vo_side_col(const vo_side_rows& s, int k) { return reinterpret_cast<T*>(s.d.get() + s.off[k]); }     // column k of sequence 0
 struct vo_side_copy { void* h; int col; };     // a host array [batch][n rows] (null = not asked for) and the column it mirrors
 enum { VO_FB_P0R, VO_FB_ERR, VO_FB_OK };
 enum { VO_SUBPIX_RAW, VO_SUBPIX_OUT, VO_SUBPIX_ITERS, VO_SUBPIX_FLAGS };
@@ -81,7 +82,7 @@ struct vo_ctx {
   int bil_maxk = 0;                  // 0 = off
   signed char bil_dx[49], bil_dy[49];
   float bil_sw[49];
-  float* d_bil_cw = nullptr;         // [256] colour weights
+  vo_dev<float> d_bil_cw;            // [256] colour weights
   int side_stream = 1;               // vo_set_side_stream
   vo_tuning tune = {};               // forced forms (vo_set_tuning); all zero = the library's rules
   bool main_dirty = true;            // an entry point other than vo_pipe_step may have enqueued work on `stream` since the last pipe step (set by
@@ -91,27 +92,29 @@ struct vo_ctx {
   int top = 0;                       // highest pyramid level index built
   vo_level lv[VO_MAX_LEVELS];
   size_t lvl_px[VO_MAX_LEVELS];      // pixels per sequence per level (= pitch * ph): the per-sequence stride
-  vo_frame fr[2];                    // sequence 0 of each buffer; sequence b at + b * lvl_px[l] pixels
+  vo_frame fr[2] = {};               // sequence 0 of each buffer; sequence b at + b * lvl_px[l] pixels
+  vo_dev<uint8_t> fr_img[2][VO_MAX_LEVELS];     // the owners of fr[f].img[l] / der[l]
+  vo_dev<int16_t> fr_der[2][VO_MAX_LEVELS];
   int cur = 0;                       // index of the current frame in fr[]
   int n_pushed = 0;
-  uint8_t* d_raw = nullptr;          // staging of one raw frame per sequence
-  uint8_t* h_raw = nullptr;          // pinned host staging of vo_frame_push (allocated on first use)
+  vo_dev<uint8_t> d_raw;             // staging of one raw frame per sequence
+  vo_pinned<uint8_t> h_raw;          // pinned host staging of vo_frame_push (allocated on first use)
   hipEvent_t ev_raw = nullptr;       // the upload out of h_raw is done
   // vo_frame_step_host: the frames of a step arrive from the host on a copy stream of their own, double-buffered like the steps in flight
   hipStream_t stream_h2d = nullptr;
-  uint8_t* d_host_raw[2] = {nullptr, nullptr};      // [batch][h][w], by step parity
+  vo_dev<uint8_t> d_host_raw[2];                    // [batch][h][w], by step parity
   hipEvent_t ev_h2d[2] = {nullptr, nullptr};        // the upload into d_host_raw[k] is complete (recorded on stream_h2d, awaited by the ctx stream)
   hipEvent_t ev_raw_free[2] = {nullptr, nullptr};   // the pyramid has read d_host_raw[k] (recorded on the ctx stream, awaited by stream_h2d)
   bool raw_free_recorded[2] = {false, false};
   int pipe_host_slot = 0;                           // vo_pipe_step_host alternates the two buffers on its own count
   // page-locked [VO_HOST_TAB_SLOTS][batch]: device-visible addresses of a step's images, read by k_gather_frames WHILE it runs -- so one slot per
   // step that can be in flight (vo_host_tab_slot), never one per d_host_raw half
-  const uint8_t** h_ptr_tab = nullptr;
-  uint8_t* d_seq = nullptr;          // preloaded sequences [batch][seq_n][h][w] (vo_seq_upload)
+  vo_pinned<const uint8_t*> h_ptr_tab;
+  vo_dev<uint8_t> d_seq;             // preloaded sequences [batch][seq_n][h][w] (vo_seq_upload)
   int seq_n = 0;
   // tracked point sets live in the result slab (off_pa / off_pb, ping-pong selected by p_parity)
   int p_parity = 0;                  // 0: current points at off_pa
-  int32_t* d_iters = nullptr;        // [batch][n x (max_level + 1)]
+  vo_dev<int32_t> d_iters;           // [batch][n x (max_level + 1)]
   int n_resident = 0;
   int iters_stride = 0;              // of the last KLT launch
   // The four side-row stores (vo_side_rows; reserved by vo_fb_reserve ... vo_brief_reserve below), M = max_pts, C = max(max_pts, VO_CORNER_CAP):
@@ -132,21 +135,21 @@ struct vo_ctx {
   // and the tight [batch][h][w] staging image the level-0 kernels read instead of the raw frame -- allocated when first switched on
   bool und_on = false;
   double und_K[4] = {0, 0, 0, 0}, und_dist[8] = {0, 0, 0, 0, 0, 0, 0, 0}, und_newK[4] = {0, 0, 0, 0};
-  uint64_t* d_und_tab = nullptr;
-  uint8_t* d_und = nullptr;
+  vo_dev<uint64_t> d_und_tab;
+  vo_dev<uint8_t> d_und;
   // CLAHE (vo_clahe.hip): the setting of vo_set_clahe, the tables [batch][tiles_y][tiles_x][256] u8 the last launch wrote (room for 16 x 16
   // tiles) and the tight [batch][h][w] staging image the level-0 kernels read instead of the raw frame -- allocated when first switched on
   bool cl_on = false;
   double cl_clip = 0.0;
   int cl_tx = 0, cl_ty = 0;
-  uint8_t* d_clahe_lut = nullptr;
-  uint8_t* d_clahe = nullptr;
+  vo_dev<uint8_t> d_clahe_lut;
+  vo_dev<uint8_t> d_clahe;
   // bumped by every accepted change of an ingest setting (vo_set_prefilter, vo_set / vo_clear_undistort, vo_set / vo_clear_clahe): all that a
   // captured step's key holds of the ingest chain
   unsigned ingest_gen = 0;
   // DLT inputs
-  float* d_uv0 = nullptr; float* d_uv1 = nullptr;    // [batch][max_pts][2]
-  vo_dlt_cam* d_dlt_cam = nullptr;   // [batch]
+  vo_dev<float> d_uv0, d_uv1;        // [batch][max_pts][2]
+  vo_dev<vo_dlt_cam> d_dlt_cam;      // [batch]
   int dlt_n = 0, dlt_stats = 0;
   vo_st_ws* st = nullptr;
   struct vo_pnp_ws* pnp = nullptr;   // PnP-RANSAC workspace (vo_pnp.hip)
@@ -164,11 +167,11 @@ struct vo_ctx {
                                           // The closed-loop pipeline passes its own counters explicitly (the resident enqueues) and never touches this.
   vo_ba_ws* ba = nullptr;
   vo_prof prof;
-  unsigned long long* d_dbg = nullptr;   // 4 x 8 phase stamps (vo_debug_cycles)
+  vo_dev<unsigned long long> d_dbg;      // 4 x 8 phase stamps (vo_debug_cycles)
   // result slab: every per-frame output of the front end lives in ONE device allocation (mirrored in pinned host
   // memory) so that a frame's results come back with a single D2H copy instead of ten.
-  uint8_t* d_slab = nullptr;             // [batch][slab_seq]
-  uint8_t* h_slab = nullptr;             // pinned, 2 x slab_bytes: steps alternate between the halves so that step t + 1 can
+  vo_dev<uint8_t> d_slab;                // [batch][slab_seq]
+  vo_pinned<uint8_t> h_slab;             // pinned, 2 x slab_bytes: steps alternate between the halves so that step t + 1 can
                                          // be enqueued while the host still reads step t (vo_frame_step_resident / vo_frame_fetch)
   hipEvent_t ev_step[2] = {nullptr, nullptr};   // recorded after the result copies of the step using half k
   size_t step_off_p[2] = {0, 0};         // slab offset of the tracked points of that step
@@ -181,8 +184,8 @@ struct vo_ctx {
   // captured steps, keyed by the hash of everything a capture bakes in: parameters by value, device pointers (the selected problem of a
   // BA bank among them), problem shapes, frame-store parity and the pinned mirror half the results go to
   std::vector<std::pair<uint64_t, hipGraphExec_t>> step_graphs;
-  int32_t* d_frame_idx = nullptr;        // frame index consumed by the captured k_pad_level0
-  int32_t* h_frame_idx = nullptr;        // pinned ring of frame indices (H2D source must outlive the copy)
+  vo_dev<int32_t> d_frame_idx;           // frame index consumed by the captured k_pad_level0
+  vo_pinned<int32_t> h_frame_idx;        // pinned ring of frame indices (H2D source must outlive the copy)
   int frame_ring = 0;
   int use_graph = 0;                     // hipGraph replay is opt-in (vo_set_graph_mode): on ROCm 7.2 it is slower than plain launches
   // landmark-sharded bundle adjustment (vo_comm.hip): RCCL communicator of this context, one process per GPU
@@ -216,7 +219,7 @@ inline int32_t vo_fail(vo_ctx* c, int32_t code, const std::string& msg) {
 #define VO_CHECK(c, cond, code, msg) VO_CHECK_AS(c, __func__, cond, code, msg)
 
 // slab accessors (sequence 0; sequence b at + b * slab_seq bytes)
-template <class T> inline T* vo_slab(const vo_ctx* c, size_t off) { return reinterpret_cast<T*>(c->d_slab + off); }
+template <class T> inline T* vo_slab(const vo_ctx* c, size_t off) { return reinterpret_cast<T*>(c->d_slab.get() + off); }
 inline size_t vo_off_p(const vo_ctx* c) { return c->p_parity ? c->off_pb : c->off_pa; }       // current points
 inline size_t vo_off_p_next(const vo_ctx* c) { return c->p_parity ? c->off_pa : c->off_pb; }  // KLT output
 // device side: pointer of sequence b given the sequence-0 pointer and the byte stride
@@ -353,11 +356,11 @@ void vo_clahe_enqueue(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t
 // what the stages' entry points share.  A setting change: vo_ingest_reserve (the staging image, if absent), vo_sync_streams (no build in flight
 // runs with the setting that is replaced), the caller's upload or reset on the ctx stream, vo_ingest_commit (waits for it, switches the stage
 // on, bumps ingest_gen), then the caller's fields.  vo_ingest_run: a stage alone on `batch` host images, [batch][height] rows of `stride` (in) /
-// width (out) bytes; VO_E_STATE with `off_msg` when the stage is off.  vo_ingest_free: a stage's two device buffers (vo_ctx_destroy)
-int32_t vo_ingest_reserve(vo_ctx* c, uint8_t** staging);
+// width (out) bytes; VO_E_STATE with `off_msg` when the stage is off.  vo_ingest_free: the stage is off (vo_ctx_destroy, which releases its buffers)
+int32_t vo_ingest_reserve(vo_ctx* c, vo_dev<uint8_t>* staging);
 int32_t vo_ingest_commit(vo_ctx* c, bool* on);
 int32_t vo_ingest_run(vo_ctx* c, const vo_ingest_stage& s, const char* off_msg, const uint8_t* img, int32_t stride, uint8_t* out);
-void vo_ingest_free(bool* on, uint8_t** staging, void** table);
+void vo_ingest_free(bool* on);
 int32_t vo_shi_tomasi_resident_counts(vo_ctx* c, hipStream_t q, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm, const int32_t* d_counts,
                                       const int32_t* d_limit);
 
@@ -443,16 +446,14 @@ inline void vo_side_layout(vo_side_rows* s, int cap, std::initializer_list<size_
 // the allocation, if absent; a refused one leaves the store as it was (not reserved, no layout)
 inline int32_t vo_side_reserve(vo_ctx* c, vo_side_rows* s, int cap, std::initializer_list<size_t> elem, size_t col_align, size_t seq_align) {
   if (s->d) return VO_OK;
-  vo_side_rows t = *s;
+  vo_side_rows t;
+  t.n = s->n;
   vo_side_layout(&t, cap, elem, col_align, seq_align);
-  VO_HIP(c, hipMalloc((void**)&t.d, t.seq * (size_t)c->batch));
-  *s = t;
+  VO_HIP(c, t.d.reserve(t.seq * (size_t)c->batch));
+  *s = std::move(t);
   return VO_OK;
 }
-inline void vo_side_free(vo_side_rows* s) {
-  if (s->d) (void)hipFree(s->d);
-  s->d = nullptr;
-}
+inline void vo_side_free(vo_side_rows* s) { s->d.reset(); }
 inline int vo_corner_cap(const vo_ctx* c) { return c->max_pts > VO_CORNER_CAP ? c->max_pts : VO_CORNER_CAP; }
 inline int32_t vo_fb_reserve(vo_ctx* c) { return vo_side_reserve(c, &c->fb, c->max_pts, {8, 4, 1}, 256, 1); }
 inline int32_t vo_guess_reserve(vo_ctx* c) { return vo_side_reserve(c, &c->guess, c->max_pts, {8}, 1, 1); }

@@ -44,10 +44,10 @@
 // them.  Beside the two descriptor sets a guided call moves two slabs: every gate input in one upload from a pinned mirror, every output in
 // one read-back into a pinned mirror (a copy per array from and to the caller's pageable memory costs more than the kernels at these sizes).
 struct vo_match_ws {
-  struct buf { void* p = nullptr; size_t cap = 0; };
-  buf a, b;                               // descriptors
-  buf in, out, rev;                       // gate inputs; match | idx | dist | n_admitted | rbest; the reverse pass's idx | dist
-  buf h_in, h_out;                        // pinned mirrors of in and out
+  // every buffer counts bytes and only grows; the calls are synchronous, so nothing is in flight when one is replaced
+  vo_dev<char> a, b;                      // descriptors
+  vo_dev<char> in, out, rev;              // gate inputs; match | idx | dist | n_admitted | rbest; the reverse pass's idx | dist
+  vo_pinned<char> h_in, h_out;            // pinned mirrors of in and out
 };
 
 struct gm_gate {
@@ -273,25 +273,9 @@ __global__ void __launch_bounds__(256) k_match_accept(const int32_t* __restrict_
 }
 
 void vo_match_destroy(vo_ctx* c) {
-  if (!c->match) return;
-  vo_match_ws* w = c->match;
-  for (vo_match_ws::buf* p : {&w->a, &w->b, &w->in, &w->out, &w->rev}) if (p->p) (void)hipFree(p->p);
-  for (vo_match_ws::buf* p : {&w->h_in, &w->h_out}) if (p->p) (void)hipHostFree(p->p);
-  delete w;
+  delete c->match;
   c->match = nullptr;
 }
-
-// grow-only; the calls are synchronous, so nothing is in flight
-static int32_t gm_reserve(vo_ctx* c, vo_match_ws::buf& b, size_t need, bool pinned = false) {
-  if (b.cap >= need) return VO_OK;
-  if (b.p) { (void)(pinned ? hipHostFree(b.p) : hipFree(b.p)); b.p = nullptr; b.cap = 0; }
-  if (pinned) VO_HIP(c, hipHostMalloc(&b.p, need, hipHostMallocDefault));
-  else VO_HIP(c, hipMalloc(&b.p, need));
-  b.cap = need;
-  return VO_OK;
-}
-
-#define GM_RESERVE(buf, bytes, pinned) do { const int32_t _rc = gm_reserve(c, (buf), (bytes), (pinned)); if (_rc != VO_OK) return _rc; } while (0)
 
 extern "C" int32_t vo_gmatch_default_params(vo_gmatch_params* p) {
   if (!p) return VO_E_INVALID;
@@ -346,19 +330,19 @@ static int32_t gm_run(vo_ctx* c, const void* desc1, int32_t n1, const void* desc
   // the output slab: match | idx | dist | n_admitted | rbest
   const size_t o_idx = N1 * sizeof(int32_t), o_dist = o_idx + N1 * 2 * sizeof(int32_t), o_nadm = o_dist + N1 * 2 * sizeof(DT),
                o_rbest = o_nadm + N1 * sizeof(int32_t), out_bytes = o_rbest + N2 * sizeof(int32_t);
-  GM_RESERVE(w->a, N1 * row, false);
-  GM_RESERVE(w->b, N2 * row, false);
-  GM_RESERVE(w->in, in_bytes, false);
-  GM_RESERVE(w->out, out_bytes, false);
-  if (cross) GM_RESERVE(w->rev, N2 * 2 * (sizeof(int32_t) + sizeof(DT)), false);
+  VO_HIP(c, w->a.reserve(N1 * row));
+  VO_HIP(c, w->b.reserve(N2 * row));
+  VO_HIP(c, w->in.reserve(in_bytes));
+  VO_HIP(c, w->out.reserve(out_bytes));
+  if (cross) VO_HIP(c, w->rev.reserve(N2 * 2 * (sizeof(int32_t) + sizeof(DT))));
   // the 2-D form: the runtime stages the rows and copies them on the device; after the 1-D form (a host-to-device transfer from the caller's
   // pageable memory) the Hamming scan took 0.3 - 0.5 us longer in a kernel trace and the call 3 - 20 us longer (EXPERIMENTS.md)
-  VO_HIP(c, hipMemcpy2DAsync(w->a.p, n1 * row, desc1, n1 * row, n1 * row, B, hipMemcpyHostToDevice, c->stream));
-  VO_HIP(c, hipMemcpy2DAsync(w->b.p, n2 * row, desc2, n2 * row, n2 * row, B, hipMemcpyHostToDevice, c->stream));
+  VO_HIP(c, hipMemcpy2DAsync(w->a.get(), n1 * row, desc1, n1 * row, n1 * row, B, hipMemcpyHostToDevice, c->stream));
+  VO_HIP(c, hipMemcpy2DAsync(w->b.get(), n2 * row, desc2, n2 * row, n2 * row, B, hipMemcpyHostToDevice, c->stream));
   const bool use_ce = (P.gate & 1) && centers;
   if (P.gate || counts1 || counts2) {
-    GM_RESERVE(w->h_in, in_bytes, true);
-    char* const h = (char*)w->h_in.p;
+    VO_HIP(c, w->h_in.reserve(in_bytes));
+    char* const h = (char*)w->h_in.get();
     if (P.gate & 2) {
       double* hF = (double*)h;
       for (size_t b = 0; b < B; b++)
@@ -372,21 +356,21 @@ static int32_t gm_run(vo_ctx* c, const void* desc1, int32_t n1, const void* desc
     if (use_ce) memcpy(h + o_ce, centers, N1 * sizeof(float2));
     if (counts1) memcpy(h + o_c1, counts1, B * sizeof(int32_t));
     if (counts2) memcpy(h + o_c2, counts2, B * sizeof(int32_t));
-    VO_HIP(c, hipMemcpyAsync(w->in.p, h, in_bytes, hipMemcpyHostToDevice, c->stream));
+    VO_HIP(c, hipMemcpyAsync(w->in.get(), h, in_bytes, hipMemcpyHostToDevice, c->stream));
   }
-  char* const din = (char*)w->in.p; char* const dout = (char*)w->out.p;
+  char* const din = (char*)w->in.get(); char* const dout = (char*)w->out.get();
   const float2* const dp1 = (const float2*)(din + o_p1); const float2* const dp2 = (const float2*)(din + o_p2);
   const float2* const dc = use_ce ? (const float2*)(din + o_ce) : dp1;
   const int32_t* const dc1 = counts1 ? (const int32_t*)(din + o_c1) : nullptr; const int32_t* const dc2 = counts2 ? (const int32_t*)(din + o_c2) : nullptr;
   int32_t* const d_match = (int32_t*)dout; int32_t* const d_idx = (int32_t*)(dout + o_idx); DT* const d_dist = (DT*)(dout + o_dist);
   int32_t* const d_nadm = (int32_t*)(dout + o_nadm); int32_t* const d_rbest = (int32_t*)(dout + o_rbest);
-  int32_t* const d_ridx = (int32_t*)w->rev.p; DT* const d_rdist = (DT*)((char*)w->rev.p + N2 * 2 * sizeof(int32_t));
+  int32_t* const d_ridx = (int32_t*)w->rev.get(); DT* const d_rdist = (DT*)((char*)w->rev.get() + N2 * 2 * sizeof(int32_t));
   gm_gate g;
   g.gate = P.gate; g.r2 = P.radius * P.radius; g.e2 = P.epi_dist * P.epi_dist; g.F = (const double*)din;
   g.f_off = 0; g.qw = dc; g.qe = dp1; g.tw = dp2; g.te = dp2;
   if (!match) {                                    // a plain call: the scan, and idx and dist straight into the caller's arrays (no pinned mirror:
                                                    // through it the call is 14 us shorter, the Hamming scan 0.4 - 0.9 us longer in a kernel trace)
-    gm_scan<HAM>(c, w->a.p, w->b.p, n1, n2, width, dc1, dc2, g, d_idx, d_dist, (int32_t*)nullptr);
+    gm_scan<HAM>(c, w->a.get(), w->b.get(), n1, n2, width, dc1, dc2, g, d_idx, d_dist, (int32_t*)nullptr);
     VO_HIP(c, hipGetLastError());
     const size_t ri = (size_t)n1 * 2 * sizeof(int32_t), rd = (size_t)n1 * 2 * sizeof(DT);
     VO_HIP(c, hipMemcpy2DAsync(idx, ri, d_idx, ri, ri, B, hipMemcpyDeviceToHost, c->stream));
@@ -396,14 +380,14 @@ static int32_t gm_run(vo_ctx* c, const void* desc1, int32_t n1, const void* desc
   }
   {
     vo_prof_scope prof(c, c->stream, VO_PROF_GMATCH_FORWARD);
-    gm_scan<HAM>(c, w->a.p, w->b.p, n1, n2, width, dc1, dc2, g, d_idx, d_dist, d_nadm);
+    gm_scan<HAM>(c, w->a.get(), w->b.get(), n1, n2, width, dc1, dc2, g, d_idx, d_dist, d_nadm);
   }
   VO_HIP(c, hipGetLastError());
   if (cross) {                                     // the reverse pass: the train rows ask, the queries answer
     gm_gate gr = g;
     gr.f_off = 9; gr.qw = dp2; gr.qe = dp2; gr.tw = dc; gr.te = dp1;
     vo_prof_scope prof(c, c->stream, VO_PROF_GMATCH_REVERSE);
-    gm_scan<HAM>(c, w->b.p, w->a.p, n2, n1, width, dc2, dc1, gr, d_ridx, d_rdist, (int32_t*)nullptr);
+    gm_scan<HAM>(c, w->b.get(), w->a.get(), n2, n1, width, dc2, dc1, gr, d_ridx, d_rdist, (int32_t*)nullptr);
   }
   VO_HIP(c, hipGetLastError());
   {
@@ -412,9 +396,9 @@ static int32_t gm_run(vo_ctx* c, const void* desc1, int32_t n1, const void* desc
                        (const DT*)d_dist, (const int32_t*)d_ridx, n1, n2, cross, P.ratio, P.max_dist, d_match, d_rbest);
   }
   VO_HIP(c, hipGetLastError());
-  GM_RESERVE(w->h_out, out_bytes, true);
-  const char* const ho = (const char*)w->h_out.p;
-  VO_HIP(c, hipMemcpyAsync(w->h_out.p, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP(c, w->h_out.reserve(out_bytes));
+  const char* const ho = (const char*)w->h_out.get();
+  VO_HIP(c, hipMemcpyAsync(w->h_out.get(), dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
   VO_HIP(c, hipStreamSynchronize(c->stream));
   memcpy(match, ho, N1 * sizeof(int32_t));
   if (idx) memcpy(idx, ho + o_idx, N1 * 2 * sizeof(int32_t));

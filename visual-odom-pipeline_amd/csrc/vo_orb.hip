@@ -299,15 +299,16 @@ __global__ void __launch_bounds__(64) k_orb_describe(orb_desc_args A, const uint
 // host side
 // ------------------------------------------------------------------------------------------------
 struct vo_orb_ws {
-  uint8_t* d_pyr = nullptr;    size_t pyr_bytes = 0;      // [batch][pyr_seq]: the padded levels
-  uint8_t* d_score = nullptr;  size_t score_bytes = 0;    // [batch][score_seq]
-  uint2* d_cand = nullptr;     size_t cand_slots = 0;     // [batch][cand_seq]
-  uint2* d_tab = nullptr;      size_t tab_n = 0;          // the resize tables of the levels above 0: x then y
-  uint8_t* d_in = nullptr;                                // [batch][H][W]: the frames as uploaded
-  uint8_t* d_mask = nullptr;                                // [batch][H][W]
-  int32_t* d_meta = nullptr;                              // [batch][ORB_LEVELS][ORB_META] i32, then the histograms [batch][ORB_LEVELS][256] u32
-  float* d_resp = nullptr; uint32_t* d_xy = nullptr; int32_t* d_pos = nullptr;   // rows [batch][ORB_LEVELS][ORB_KEEP_CAP]
-  vo_orb_kp* d_kps = nullptr; uint8_t* d_desc = nullptr; int out_cap = 0;       // [batch][out_cap]
+  // every buffer only grows, each on its own: after a refused allocation it is empty and the next call reserves it again
+  vo_dev<uint8_t> d_pyr;                                  // [batch][pyr_seq]: the padded levels
+  vo_dev<uint8_t> d_score;                                // [batch][score_seq]
+  vo_dev<uint2> d_cand;                                   // [batch][cand_seq]
+  vo_dev<uint2> d_tab;                                    // the resize tables of the levels above 0: x then y
+  vo_dev<uint8_t> d_in;                                   // [batch][H][W]: the frames as uploaded
+  vo_dev<uint8_t> d_mask;                                 // [batch][H][W]
+  vo_dev<int32_t> d_meta;                                 // [batch][ORB_LEVELS][ORB_META] i32, then the histograms [batch][ORB_LEVELS][256] u32
+  vo_dev<float> d_resp; vo_dev<uint32_t> d_xy; vo_dev<int32_t> d_pos;            // rows [batch][ORB_LEVELS][ORB_KEEP_CAP]
+  vo_dev<vo_orb_kp> d_kps; vo_dev<uint8_t> d_desc;        // [batch][max_out] of the largest max_out asked for
   orb_geom G = {};
   bool have = false;                                      // G and n_l describe a call that succeeded
   std::vector<int32_t> n_l;                               // [batch][ORB_LEVELS]
@@ -316,11 +317,7 @@ struct vo_orb_ws {
 };
 
 void vo_orb_destroy(vo_ctx* c) {
-  if (!c->orb) return;
-  vo_orb_ws* w = c->orb;
-  void* bufs[] = {w->d_pyr, w->d_score, w->d_cand, w->d_tab, w->d_in, w->d_mask, w->d_meta, w->d_resp, w->d_xy, w->d_pos, w->d_kps, w->d_desc};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  delete w;
+  delete c->orb;
   c->orb = nullptr;
 }
 
@@ -328,16 +325,6 @@ extern "C" int32_t vo_orb_default_params(vo_orb_params* p) {
   if (!p) return VO_E_INVALID;
   memset(p, 0, sizeof(*p));
   p->nfeatures = 500; p->nlevels = 8; p->scale_factor = 1.2; p->fast_threshold = 20; p->edge_threshold = ORB_EDGE; p->harris_k = 0.04f;
-  return VO_OK;
-}
-
-// a buffer that only grows: *have elements of `elem` bytes -> at least `need`
-static int32_t orb_grow(vo_ctx* c, void** p, size_t* have, size_t need, size_t elem) {
-  if (*p && *have >= need) return VO_OK;
-  if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
-  if (need == 0) return VO_OK;
-  VO_HIP(c, hipMalloc(p, need * elem));
-  *have = need;
   return VO_OK;
 }
 
@@ -400,31 +387,22 @@ static int32_t orb_reserve(vo_ctx* c, const orb_geom& G, bool with_mask, int max
   if (!c->orb) c->orb = new vo_orb_ws();
   vo_orb_ws* w = c->orb;
   const size_t B = c->batch;
-  const bool fresh = !w->d_pyr || w->pyr_bytes < B * G.pyr_seq;
-  { const int32_t r = orb_grow(c, (void**)&w->d_pyr, &w->pyr_bytes, B * G.pyr_seq, 1); if (r != VO_OK) return r; }
-  if (fresh) VO_HIP(c, hipMemsetAsync(w->d_pyr, 0, w->pyr_bytes, c->stream));        // the borders: read by tile loads, never part of a result
-  { const int32_t r = orb_grow(c, (void**)&w->d_score, &w->score_bytes, B * G.score_seq, 1); if (r != VO_OK) return r; }
-  { const int32_t r = orb_grow(c, (void**)&w->d_cand, &w->cand_slots, B * G.cand_seq, sizeof(uint2)); if (r != VO_OK) return r; }
+  VO_HIP(c, w->d_pyr.reserve(B * G.pyr_seq));
+  if (w->d_pyr.grew()) VO_HIP(c, hipMemsetAsync(w->d_pyr, 0, w->d_pyr.bytes(), c->stream));   // the borders: read by tile loads, never part of a result
+  VO_HIP(c, w->d_score.reserve(B * G.score_seq));
+  VO_HIP(c, w->d_cand.reserve(B * G.cand_seq));
   size_t tab = 0;
   for (int l = 1; l < G.nlevels; l++) tab += (size_t)G.w[l] + G.h[l];
-  { const int32_t r = orb_grow(c, (void**)&w->d_tab, &w->tab_n, tab, sizeof(uint2)); if (r != VO_OK) return r; }
-  if (!w->d_in) VO_HIP(c, hipMalloc((void**)&w->d_in, B * (size_t)c->width * c->height));
-  if (with_mask && !w->d_mask) VO_HIP(c, hipMalloc((void**)&w->d_mask, B * (size_t)c->width * c->height));
-  if (!w->d_meta) {
-    const size_t rows = B * ORB_LEVELS * ORB_KEEP_CAP;
-    VO_HIP(c, hipMalloc((void**)&w->d_meta, sizeof(int32_t) * B * ORB_LEVELS * (ORB_META + 256)));
-    VO_HIP(c, hipMalloc((void**)&w->d_resp, sizeof(float) * rows));
-    VO_HIP(c, hipMalloc((void**)&w->d_xy, sizeof(uint32_t) * rows));
-    VO_HIP(c, hipMalloc((void**)&w->d_pos, sizeof(int32_t) * rows));
-  }
-  if (w->out_cap < max_out) {
-    if (w->d_kps) (void)hipFree(w->d_kps);
-    if (w->d_desc) (void)hipFree(w->d_desc);
-    w->d_kps = nullptr; w->d_desc = nullptr; w->out_cap = 0;
-    VO_HIP(c, hipMalloc((void**)&w->d_kps, sizeof(vo_orb_kp) * B * max_out));
-    VO_HIP(c, hipMalloc((void**)&w->d_desc, (size_t)32 * B * max_out));
-    w->out_cap = max_out;
-  }
+  VO_HIP(c, w->d_tab.reserve(tab));
+  VO_HIP(c, w->d_in.reserve(B * (size_t)c->width * c->height));
+  if (with_mask) VO_HIP(c, w->d_mask.reserve(B * (size_t)c->width * c->height));
+  const size_t rows = B * ORB_LEVELS * ORB_KEEP_CAP;
+  VO_HIP(c, w->d_meta.reserve(B * ORB_LEVELS * (ORB_META + 256)));
+  VO_HIP(c, w->d_resp.reserve(rows));
+  VO_HIP(c, w->d_xy.reserve(rows));
+  VO_HIP(c, w->d_pos.reserve(rows));
+  VO_HIP(c, w->d_kps.reserve(B * (size_t)max_out));
+  VO_HIP(c, w->d_desc.reserve((size_t)32 * B * max_out));
   return VO_OK;
 }
 

@@ -56,17 +56,17 @@ enum { DN_PTS = 0, DN_PNP = 1, DN_RIPE = 2, DN_ROOM = 3 };   // DN_ROOM: free sl
 struct vo_pipe_ws {
   int N = 0, R = 0;
   vo_pipe_params prm;
-  void* tab[VO_PIPE_N_TABLES] = {};              // all inside ONE allocation (tab_slab), in table order: the lists, the counters and the
+  void* tab[VO_PIPE_N_TABLES] = {};              // pointers into tab_slab, in table order: the lists, the counters and the
   size_t tab_bytes[VO_PIPE_N_TABLES] = {};       // trajectory ring (tables VO_PIPE_CAND ...) are contiguous -> vo_pipe_lists_read is one copy.  (per sequence)
-  uint8_t* tab_slab = nullptr;
+  vo_dev<uint8_t> tab_slab;                      // ONE allocation for every table
   size_t lists_bytes = 0;                        // from tab[VO_PIPE_CAND] to the end of the slab
-  uint8_t* d_gather = nullptr;                   // vo_pipe_rows_read: packed rows [N][288 B]
-  int32_t* d_gather_rows = nullptr;
-  int32_t *d_ripe = nullptr, *d_freeK = nullptr, *d_freeL = nullptr, *d_scr = nullptr, *d_dn = nullptr, *d_cam_sel = nullptr;
-  vo_dlt_cam* d_cams = nullptr;                  // [B][HIST]: one camera pair per birth frame of the ripe candidates
-  double* d_K = nullptr;
-  vo_pipe_record* d_rec = nullptr;               // [B]
-  vo_pipe_record* h_rec = nullptr;               // pinned [VO_PIPE_INFLIGHT][B]
+  vo_dev<uint8_t> d_gather;                      // vo_pipe_rows_read: packed rows [N][288 B]
+  vo_dev<int32_t> d_gather_rows;
+  vo_dev<int32_t> d_ripe, d_freeK, d_freeL, d_scr, d_dn, d_cam_sel;
+  vo_dev<vo_dlt_cam> d_cams;                     // [B][HIST]: one camera pair per birth frame of the ripe candidates
+  vo_dev<double> d_K;
+  vo_dev<vo_pipe_record> d_rec;                  // [B]
+  vo_pinned<vo_pipe_record> h_rec;               // [VO_PIPE_INFLIGHT][B]
   hipEvent_t ev[VO_PIPE_INFLIGHT] = {};
   hipEvent_t ev_track = nullptr;                 // the side stream's pyramid + KLT of a step are done
   long enq = 0, fetched = 0;
@@ -1152,15 +1152,15 @@ __global__ void __launch_bounds__(256) k_pipe_predict(pipe_ptrs Pall, const floa
 // ================================================================================================
 bool vo_pipe_busy(const vo_ctx* c) { return c->pipe && c->pipe->enq != c->pipe->fetched; }
 
-void vo_pipe_destroy(vo_ctx* c) {
-  if (!c->pipe) return;
-  vo_pipe_ws* w = c->pipe;
-  void* bufs[] = {w->tab_slab, w->d_gather, w->d_gather_rows, w->d_ripe, w->d_freeK, w->d_freeL, w->d_scr, w->d_dn, w->d_cam_sel, w->d_cams, w->d_K, w->d_rec};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  if (w->h_rec) (void)hipHostFree(w->h_rec);
+static void pipe_destroy_events(vo_pipe_ws* w) {
   for (hipEvent_t e : w->ev) if (e) (void)hipEventDestroy(e);
   if (w->ev_track) (void)hipEventDestroy(w->ev_track);
-  delete w;
+}
+
+void vo_pipe_destroy(vo_ctx* c) {
+  if (!c->pipe) return;
+  pipe_destroy_events(c->pipe);
+  delete c->pipe;
   c->pipe = nullptr;
 }
 
@@ -1175,17 +1175,10 @@ extern "C" int32_t vo_pipe_default_params(vo_pipe_params* p) {
   return VO_OK;
 }
 
-static int32_t pipe_create(vo_ctx* c, const double* K, const vo_pipe_params* prm, bool* replaced);
+static int32_t pipe_build(vo_ctx* c, vo_pipe_ws* w, const double* K, const vo_pipe_params* prm);
 
-extern "C" int32_t vo_pipe_create(vo_ctx* c, const double* K, const vo_pipe_params* prm) {
-  if (!c) return VO_E_INVALID;
-  bool replaced = false;                          // rejected arguments leave an existing pipeline alone
-  const int32_t r = pipe_create(c, K, prm, &replaced);
-  if (r != VO_OK && replaced) vo_pipe_destroy(c); // never leave a half-built workspace behind (vo_last_error keeps the reason)
-  return r;
-}
-
-static int32_t pipe_create(vo_ctx* c, const double* K, const vo_pipe_params* prm, bool* replaced) {
+// rejected arguments leave an existing pipeline alone; a failure behind them leaves none (vo_last_error keeps the reason)
+static int32_t pipe_create(vo_ctx* c, const double* K, const vo_pipe_params* prm) {
   VO_CHECK(c, K, VO_E_INVALID, "null K");
   vo_pipe_params def;
   if (!prm) { vo_pipe_default_params(&def); prm = &def; }
@@ -1199,9 +1192,35 @@ static int32_t pipe_create(vo_ctx* c, const double* K, const vo_pipe_params* prm
   VO_HIP(c, hipSetDevice(c->device));
   VO_HIP(c, hipStreamSynchronize(c->stream));
   vo_pipe_destroy(c);
-  *replaced = true;
-  vo_pipe_ws* w = new vo_pipe_ws();
-  c->pipe = w;
+  int32_t r = vo_ws_replace(c->pipe, [&](vo_pipe_ws& w) -> int32_t {
+    const int32_t rb = pipe_build(c, &w, K, prm);
+    if (rb != VO_OK) pipe_destroy_events(&w);
+    return rb;
+  });
+  if (r != VO_OK) return r;
+  // the stage units' workspaces, then the seeded state; the pipeline goes again if one of them fails
+  r = vo_ba_reserve(c, K, prm->ba_window, c->pipe->N);
+  // (the adjustment walks the landmark slots in use, not the table: pipe_step names the counters before every enqueue -- an uploaded
+  //  problem, vo_ba_upload*, forgets them)
+  if (r == VO_OK) r = vo_pnp_reserve(c, K);
+  if (r == VO_OK) r = vo_st_prepare(c, &c->pipe->prm.st);
+  if (r == VO_OK) {
+    c->n_resident = c->max_pts;
+    // (the per-sequence counters -- live points DN_PTS, free slots + 1 DN_ROOM -- are handed to the KLT / re-detection launches by pipe_step
+    //  itself: the context's other resident entry points never see them)
+    r = vo_pipe_commit(c);
+  }
+  if (r != VO_OK) vo_pipe_destroy(c);
+  return r;
+}
+
+extern "C" int32_t vo_pipe_create(vo_ctx* c, const double* K, const vo_pipe_params* prm) {
+  if (!c) return VO_E_INVALID;
+  return pipe_create(c, K, prm);
+}
+
+// the tables, lists and events of a new workspace, with K on the device when it returns
+static int32_t pipe_build(vo_ctx* c, vo_pipe_ws* w, const double* K, const vo_pipe_params* prm) {
   w->prm = *prm;
   w->N = c->max_pts; w->R = 4 * c->max_pts;
   const size_t B = c->batch, N = w->N, R = w->R;
@@ -1210,27 +1229,27 @@ static int32_t pipe_create(vo_ctx* c, const double* K, const vo_pipe_params* prm
   {
     size_t off[VO_PIPE_N_TABLES + 1] = {};
     for (int i = 0; i < VO_PIPE_N_TABLES; i++) { w->tab_bytes[i] = sz[i]; off[i + 1] = off[i] + ((sz[i] * B + 255) & ~(size_t)255); }
-    VO_HIP(c, hipMalloc((void**)&w->tab_slab, off[VO_PIPE_N_TABLES]));
+    VO_HIP(c, w->tab_slab.reserve(off[VO_PIPE_N_TABLES]));
     VO_HIP(c, hipMemsetAsync(w->tab_slab, 0, off[VO_PIPE_N_TABLES], c->stream));
     for (int i = 0; i < VO_PIPE_N_TABLES; i++) w->tab[i] = w->tab_slab + off[i];
     w->lists_bytes = off[VO_PIPE_N_TABLES] - off[VO_PIPE_CAND];
   }
-  VO_HIP(c, hipMalloc((void**)&w->d_gather, 288 * N * B));
-  VO_HIP(c, hipMalloc((void**)&w->d_gather_rows, 4 * N * B));
-  VO_HIP(c, hipMalloc((void**)&w->d_ripe, 4 * N * B));
-  VO_HIP(c, hipMalloc((void**)&w->d_freeK, 4 * R * B));
-  VO_HIP(c, hipMalloc((void**)&w->d_freeL, 4 * R * B));
-  VO_HIP(c, hipMalloc((void**)&w->d_scr, 4 * R * B));
-  VO_HIP(c, hipMalloc((void**)&w->d_cam_sel, 4 * N * B));
+  VO_HIP(c, w->d_gather.reserve(288 * N * B));
+  VO_HIP(c, w->d_gather_rows.reserve(N * B));
+  VO_HIP(c, w->d_ripe.reserve(N * B));
+  VO_HIP(c, w->d_freeK.reserve(R * B));
+  VO_HIP(c, w->d_freeL.reserve(R * B));
+  VO_HIP(c, w->d_scr.reserve(R * B));
+  VO_HIP(c, w->d_cam_sel.reserve(N * B));
   VO_HIP(c, hipMemsetAsync(w->d_cam_sel, 0, 4 * N * B, c->stream));
-  VO_HIP(c, hipMalloc((void**)&w->d_cams, sizeof(vo_dlt_cam) * PIPE_HIST * B));
+  VO_HIP(c, w->d_cams.reserve(PIPE_HIST * B));
   VO_HIP(c, hipMemsetAsync(w->d_cams, 0, sizeof(vo_dlt_cam) * PIPE_HIST * B, c->stream));
-  VO_HIP(c, hipMalloc((void**)&w->d_dn, 4 * 4 * B));
+  VO_HIP(c, w->d_dn.reserve(4 * B));
   VO_HIP(c, hipMemsetAsync(w->d_dn, 0, 4 * 4 * B, c->stream));
-  VO_HIP(c, hipMalloc((void**)&w->d_K, 72 * B));
-  VO_HIP(c, hipMalloc((void**)&w->d_rec, sizeof(vo_pipe_record) * B));
+  VO_HIP(c, w->d_K.reserve(9 * B));
+  VO_HIP(c, w->d_rec.reserve(B));
   VO_HIP(c, hipMemsetAsync(w->d_rec, 0, sizeof(vo_pipe_record) * B, c->stream));
-  VO_HIP(c, hipHostMalloc((void**)&w->h_rec, sizeof(vo_pipe_record) * B * VO_PIPE_INFLIGHT, hipHostMallocDefault));
+  VO_HIP(c, w->h_rec.reserve(B * VO_PIPE_INFLIGHT));
   const unsigned fl = hipEventDisableTiming | (vo_blocking_sync() ? hipEventBlockingSync : 0u);
   for (int i = 0; i < VO_PIPE_INFLIGHT; i++) VO_HIP(c, hipEventCreateWithFlags(&w->ev[i], fl));
   VO_HIP(c, hipEventCreateWithFlags(&w->ev_track, hipEventDisableTiming));
@@ -1245,18 +1264,7 @@ static int32_t pipe_create(vo_ctx* c, const double* K, const vo_pipe_params* prm
   VO_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pipe_spawn<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * PIPE_TPB * 8));
   VO_HIP(c, hipMemcpyAsync(w->d_K, K, 72 * B, hipMemcpyHostToDevice, c->stream));
   VO_HIP(c, hipStreamSynchronize(c->stream));
-  int32_t r = vo_ba_reserve(c, K, prm->ba_window, w->N);
-  if (r != VO_OK) return r;
-  // (the adjustment walks the landmark slots in use, not the table: pipe_step names the counters before every enqueue -- an uploaded
-  //  problem, vo_ba_upload*, forgets them)
-  r = vo_pnp_reserve(c, K);
-  if (r != VO_OK) return r;
-  r = vo_st_prepare(c, &w->prm.st);
-  if (r != VO_OK) return r;
-  c->n_resident = c->max_pts;
-  // (the per-sequence counters -- live points DN_PTS, free slots + 1 DN_ROOM -- are handed to the KLT / re-detection launches by pipe_step
-  //  itself: the context's other resident entry points never see them)
-  return vo_pipe_commit(c);
+  return VO_OK;
 }
 
 extern "C" int32_t vo_pipe_table_bytes(vo_ctx* c, int32_t which, uint64_t* bytes) {

@@ -36,15 +36,15 @@ static_assert(sizeof(pnp_hyp) == 104 && sizeof(pnp_ctrl) == 120 && offsetof(pnp_
 
 struct vo_pnp_ws {
   int cap = 0;
-  double* d_K = nullptr;        // [B][9]
-  float* d_X = nullptr;         // [B][cap][3]
-  float* d_uv = nullptr;        // [B][cap][2]
-  pnp_hyp* d_hyp = nullptr;     // [B][PNP_BATCH]
-  pnp_ctrl* d_ctrl = nullptr;   // [B]
-  uint8_t* d_mask = nullptr;    // [B][cap]
-  double* d_out = nullptr;      // [B][8]: rvec, t, cost, n_inliers
-  pnp_ctrl* h_ctrl = nullptr;   // pinned
-  double* h_out = nullptr;      // pinned
+  vo_dev<double> d_K;           // [B][9]
+  vo_dev<float> d_X;            // [B][cap][3]
+  vo_dev<float> d_uv;           // [B][cap][2]
+  vo_dev<pnp_hyp> d_hyp;        // [B][PNP_BATCH]
+  vo_dev<pnp_ctrl> d_ctrl;      // [B]
+  vo_dev<uint8_t> d_mask;       // [B][cap]
+  vo_dev<double> d_out;         // [B][8]: rvec, t, cost, n_inliers
+  vo_pinned<pnp_ctrl> h_ctrl;
+  vo_pinned<double> h_out;
   int n = 0;                    // resident correspondences per sequence
 };
 
@@ -756,13 +756,7 @@ __global__ void k_pnp_init(pnp_ctrl* ctrl, int max_iters) { pnp_ctrl_reset(ctrl 
 // host
 // ================================================================================================
 void vo_pnp_destroy(vo_ctx* c) {
-  if (!c->pnp) return;
-  vo_pnp_ws* w = c->pnp;
-  void* bufs[] = {w->d_K, w->d_X, w->d_uv, w->d_hyp, w->d_ctrl, w->d_mask, w->d_out};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  if (w->h_ctrl) (void)hipHostFree(w->h_ctrl);
-  if (w->h_out) (void)hipHostFree(w->h_out);
-  delete w;
+  delete c->pnp;
   c->pnp = nullptr;
 }
 
@@ -775,23 +769,22 @@ extern "C" int32_t vo_pnp_default_params(vo_pnp_params* p) {
 static int32_t pnp_alloc(vo_ctx* c, int n) {
   const size_t B = c->batch;
   if (c->pnp && c->pnp->cap < n) vo_pnp_destroy(c);
-  if (!c->pnp) {
-    vo_pnp_ws* w = new vo_pnp_ws();
-    c->pnp = w;
-    w->cap = n > c->max_pts ? n : c->max_pts;
-    VO_HIP(c, hipMalloc((void**)&w->d_K, sizeof(double) * 9 * B));
-    VO_HIP(c, hipMalloc((void**)&w->d_X, sizeof(float) * 3 * B * w->cap));
-    VO_HIP(c, hipMalloc((void**)&w->d_uv, sizeof(float) * 2 * B * w->cap));
-    VO_HIP(c, hipMalloc((void**)&w->d_hyp, sizeof(pnp_hyp) * B * PNP_BATCH));
-    VO_HIP(c, hipMalloc((void**)&w->d_ctrl, sizeof(pnp_ctrl) * B));
-    VO_HIP(c, hipMalloc((void**)&w->d_mask, B * w->cap));
-    VO_HIP(c, hipMalloc((void**)&w->d_out, sizeof(double) * 8 * B));
-    VO_HIP(c, hipMemsetAsync(w->d_out, 0, sizeof(double) * 8 * B, c->stream));
-    VO_HIP(c, hipMemsetAsync(w->d_ctrl, 0, sizeof(pnp_ctrl) * B, c->stream));
-    VO_HIP(c, hipHostMalloc((void**)&w->h_ctrl, sizeof(pnp_ctrl) * B, hipHostMallocDefault));
-    VO_HIP(c, hipHostMalloc((void**)&w->h_out, sizeof(double) * 8 * B, hipHostMallocDefault));
-  }
-  return VO_OK;
+  if (c->pnp) return VO_OK;
+  return vo_ws_replace(c->pnp, [&](vo_pnp_ws& w) -> int32_t {
+    w.cap = n > c->max_pts ? n : c->max_pts;
+    VO_HIP(c, w.d_K.reserve(9 * B));
+    VO_HIP(c, w.d_X.reserve(3 * B * w.cap));
+    VO_HIP(c, w.d_uv.reserve(2 * B * w.cap));
+    VO_HIP(c, w.d_hyp.reserve(B * PNP_BATCH));
+    VO_HIP(c, w.d_ctrl.reserve(B));
+    VO_HIP(c, w.d_mask.reserve(B * w.cap));
+    VO_HIP(c, w.d_out.reserve(8 * B));
+    VO_HIP(c, hipMemsetAsync(w.d_out, 0, sizeof(double) * 8 * B, c->stream));
+    VO_HIP(c, hipMemsetAsync(w.d_ctrl, 0, sizeof(pnp_ctrl) * B, c->stream));
+    VO_HIP(c, w.h_ctrl.reserve(B));
+    VO_HIP(c, w.h_out.reserve(8 * B));
+    return VO_OK;
+  });
 }
 
 // k: index of the batch within its search (0: the small first batch); first: the control block is reset by this batch's own kernels
@@ -836,7 +829,7 @@ int32_t vo_pnp_reserve(vo_ctx* c, const double* K_host) {
 int32_t vo_pnp_get_view(vo_ctx* c, vo_pnp_view* v) {
   VO_CHECK(c, c->pnp, VO_E_STATE, "vo_pnp_reserve first");
   vo_pnp_ws* w = c->pnp;
-  v->X = w->d_X; v->uv = w->d_uv; v->mask = w->d_mask; v->out = w->d_out; v->ctrl = reinterpret_cast<const int32_t*>(w->d_ctrl);
+  v->X = w->d_X; v->uv = w->d_uv; v->mask = w->d_mask; v->out = w->d_out; v->ctrl = reinterpret_cast<const int32_t*>(w->d_ctrl.get());
   v->ctrl_stride = sizeof(pnp_ctrl) / sizeof(int32_t); v->cap = w->cap;
   return VO_OK;
 }
@@ -923,7 +916,7 @@ extern "C" int32_t vo_pnp_ransac(vo_ctx* c, const double* K, const float* pts3d,
   hipLaunchKernelGGL(k_pnp_init, dim3((unsigned)B), dim3(1), 0, c->stream, w->d_ctrl, prm->max_iters);
   // batches of 32, then 256 hypotheses per sequence until every sequence has reached its iteration bound (typically one or
   // two batches: the bound is 33 iterations at 70 % inliers, 145 at 50 %)
-  r = vo_ransac_rounds(c, c->stream, w->d_ctrl, w->h_ctrl, B, (prm->max_iters + PNP_BATCH - 1) / PNP_BATCH + 1,
+  r = vo_ransac_rounds(c, c->stream, w->d_ctrl.get(), w->h_ctrl.get(), B, (prm->max_iters + PNP_BATCH - 1) / PNP_BATCH + 1,
                        [&](int round) { pnp_enqueue_batch(c, c->stream, prm, round); });
   if (r != VO_OK) return r;
   r = pnp_enqueue_refine(c, c->stream, prm);

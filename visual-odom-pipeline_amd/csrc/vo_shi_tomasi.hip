@@ -30,18 +30,18 @@
 #define ST_MAX_RADIUS 31
 
 struct vo_st_ws {
-  uint8_t* d_mask = nullptr;
-  uint8_t* d_user_mask = nullptr;
-  int32_t* d_h = nullptr;          // 3 planes W*H: hxx, hxy, hyy
-  float* d_eig = nullptr;
-  uint32_t* d_scalars = nullptr;   // [0] max eig bits, [1] n candidates, [2] n out (int), [3] rounds
-  unsigned long long* d_cand = nullptr;
-  uint32_t* d_nraw = nullptr;      // [batch] raw candidate counters (appended to by the NMS stage, re-armed by k_st_select)
+  vo_dev<uint8_t> d_mask;
+  vo_dev<uint8_t> d_user_mask;
+  vo_dev<int32_t> d_h;             // 3 planes W*H: hxx, hxy, hyy; made by the first launch of the two-kernel eigenvalue path
+  vo_dev<float> d_eig;
+  uint32_t* d_scalars = nullptr;   // [0] max eig bits, [1] n candidates, [2] n out (int), [3] rounds; in the ctx slab (d_slab)
+  vo_dev<unsigned long long> d_cand;
+  vo_dev<uint32_t> d_nraw;         // [batch] raw candidate counters (appended to by the NMS stage, re-armed by k_st_select)
   bool mask_clean = false;         // the mask is all 255 (k_st_eig_fused restored it): the next resident launch needs no k_st_mask_init
   bool eig_valid = false;          // the last launch stored the eigenvalue map (vo_shi_tomasi_read)
-  float* d_blockmax = nullptr;     // per-workgroup masked maxima of the eigenvalue pass
-  float* d_out = nullptr;          // ST_OUT_CAP x 2
-  float* d_pts = nullptr;          // uploaded cur_pts (non-resident call)
+  vo_dev<float> d_blockmax;        // per-workgroup masked maxima of the eigenvalue pass
+  float* d_out = nullptr;          // ST_OUT_CAP x 2; in the ctx slab (d_slab)
+  vo_dev<float> d_pts;             // uploaded cur_pts (non-resident call)
   int n_blockmax = 0;
   int last_max_corners = 0;
 };
@@ -1049,35 +1049,31 @@ __global__ void __launch_bounds__(1024) k_st_select(unsigned long long* __restri
 // host side
 // ------------------------------------------------------------------------------------------------
 void vo_st_destroy(vo_ctx* c) {
-  if (!c->st) return;
-  vo_st_ws* s = c->st;
-  void* bufs[] = {s->d_mask, s->d_user_mask, s->d_h, s->d_eig, s->d_cand, s->d_nraw, s->d_blockmax, s->d_pts};   // scalars / out live in the ctx slab
-  for (void* b : bufs) if (b) (void)hipFree(b);
-  delete s;
+  delete c->st;
   c->st = nullptr;
 }
 
 static int32_t st_init(vo_ctx* c, hipStream_t q) {
   if (c->st) return VO_OK;
-  vo_st_ws* s = new vo_st_ws();
-  c->st = s;
-  const size_t np = (size_t)c->width * c->height, B = (size_t)c->batch;
-  VO_HIP(c, hipMalloc((void**)&s->d_mask, np * B));
-  VO_HIP(c, hipMalloc((void**)&s->d_user_mask, np * B));
-  VO_HIP(c, hipMalloc((void**)&s->d_eig, np * sizeof(float) * B));
-  s->d_scalars = vo_slab<uint32_t>(c, c->off_st_scalars);
-  VO_HIP(c, hipMalloc((void**)&s->d_cand, sizeof(unsigned long long) * ST_CAND_STRIDE * B));
-  VO_HIP(c, hipMalloc((void**)&s->d_nraw, sizeof(uint32_t) * B));
-  VO_HIP(c, hipMemsetAsync(s->d_nraw, 0, sizeof(uint32_t) * B, q));
-  s->n_blockmax = vo_div_up(c->width, 256 - 32) * c->height;                     // upper bound over both eigenvalue paths (1-row bands)
-  VO_HIP(c, hipMalloc((void**)&s->d_blockmax, sizeof(float) * (size_t)s->n_blockmax * B));
-  s->d_out = vo_slab<float>(c, c->off_st_out);
-  VO_HIP(c, hipMalloc((void**)&s->d_pts, sizeof(float) * 2 * (size_t)c->max_pts * B));
-  VO_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_st_select<ST_CAP_CLOSED_LOOP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)st_sel_lds(ST_CAP_CLOSED_LOOP)));
-  VO_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_st_select<ST_CAND_CAP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)ST_SEL_LDS));
-  return VO_OK;
+  return vo_ws_replace(c->st, [c, q](vo_st_ws& s) -> int32_t {
+    const size_t np = (size_t)c->width * c->height, B = (size_t)c->batch;
+    VO_HIP(c, s.d_mask.reserve(np * B));
+    VO_HIP(c, s.d_user_mask.reserve(np * B));
+    VO_HIP(c, s.d_eig.reserve(np * B));
+    s.d_scalars = vo_slab<uint32_t>(c, c->off_st_scalars);
+    VO_HIP(c, s.d_cand.reserve(ST_CAND_STRIDE * B));
+    VO_HIP(c, s.d_nraw.reserve(B));
+    VO_HIP(c, hipMemsetAsync(s.d_nraw, 0, sizeof(uint32_t) * B, q));
+    s.n_blockmax = vo_div_up(c->width, 256 - 32) * c->height;                     // upper bound over both eigenvalue paths (1-row bands)
+    VO_HIP(c, s.d_blockmax.reserve((size_t)s.n_blockmax * B));
+    s.d_out = vo_slab<float>(c, c->off_st_out);
+    VO_HIP(c, s.d_pts.reserve(2 * (size_t)c->max_pts * B));
+    VO_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_st_select<ST_CAP_CLOSED_LOOP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)st_sel_lds(ST_CAP_CLOSED_LOOP)));
+    VO_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_st_select<ST_CAND_CAP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)ST_SEL_LDS));
+    return VO_OK;
+  });
 }
 
 // filled-circle row table: the integer midpoint loop of imgproc/drawing.cpp Circle()
@@ -1110,7 +1106,7 @@ int32_t vo_st_prepare(vo_ctx* c, const vo_st_params* prm) {
   if (r != VO_OK) return r;
   vo_st_ws* s = c->st;
   const bool fused = !c->tune.st_two_kernels && prm && prm->block_size == 31 && c->height > 31 && c->width > 31;
-  if (!fused && !(prm && prm->fast_threshold > 0) && !s->d_h) VO_HIP(c, hipMalloc((void**)&s->d_h, (size_t)c->width * c->height * 3 * sizeof(int32_t) * c->batch));
+  if (!fused && !(prm && prm->fast_threshold > 0)) VO_HIP(c, s->d_h.reserve((size_t)c->width * c->height * 3 * c->batch));
   return VO_OK;
 }
 
@@ -1174,7 +1170,7 @@ static int32_t st_launch(vo_ctx* c, hipStream_t q, const float* d_pts, size_t pt
       hipLaunchKernelGGL(k_st_mask_init, dim3(vo_div_up((int)(((size_t)W * H + 15) / 16), 256), B), dim3(256), 0, q, s->d_mask, d_user_mask,
                          (size_t)W * H, s->d_scalars, c->slab_seq);
   } else {
-    if (!s->d_h) VO_HIP(c, hipMalloc((void**)&s->d_h, (size_t)W * H * 3 * sizeof(int32_t) * B));
+    VO_HIP(c, s->d_h.reserve((size_t)W * H * 3 * B));
     hipLaunchKernelGGL(k_st_sobel_hsum, dim3(vo_div_up(W, ST_HS_COLS), H, B), dim3(256), 0, q, F.img[0], c->lvl_px[0],
                        c->lv[0].pitch, W, H, r, s->d_h, s->d_mask, d_user_mask, s->d_scalars, c->slab_seq);
   }

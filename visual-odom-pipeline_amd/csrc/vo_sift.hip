@@ -39,16 +39,17 @@ struct sift_geom {
 
 struct vo_sift_ws {
   sift_geom G;
-  uint8_t* d_img = nullptr;      // [B][H][W]
-  float* d_a = nullptr;          // [B][2H][2W] scratch (upsampled image / row pass)
-  float* d_b = nullptr;
-  float* d_gauss = nullptr; float* d_dog = nullptr;
-  float* d_taps = nullptr;       // [6][SIFT_MAX_TAPS]
+  vo_dev<uint8_t> d_img;         // [B][H][W]
+  vo_dev<float> d_a, d_b;        // [B][2H][2W] scratch (upsampled image / row pass)
+  vo_dev<float> d_gauss, d_dog;
+  vo_dev<float> d_taps;          // [6][SIFT_MAX_TAPS]
   int taps_r[6];
-  int4* d_cand = nullptr;        // [B][SIFT_CAND_CAP]
-  vo_sift_kp* d_raw = nullptr;   // [B][SIFT_RAW_CAP]
-  int* d_cnt = nullptr;          // [B][2]: candidates, raw keypoints
-  vo_sift_kp* d_fin = nullptr; float* d_desc = nullptr; int fin_cap = 0;
+  vo_dev<int4> d_cand;           // [B][SIFT_CAND_CAP]
+  vo_dev<vo_sift_kp> d_raw;      // [B][SIFT_RAW_CAP]
+  vo_dev<int> d_cnt;             // [B][2]: candidates, raw keypoints
+  vo_dev<vo_sift_kp> d_fin;      // [B][fin_cap] the output rows, grown by the largest max_out asked for
+  vo_dev<float> d_desc;          // [B][fin_cap][128]
+  int fin_cap = 0;               // the row stride of both: 0 unless both hold that many rows per sequence
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -401,11 +402,7 @@ __global__ void __launch_bounds__(64) k_sift_desc(sift_geom G, const float* __re
 // host
 // ================================================================================================
 void vo_sift_destroy(vo_ctx* c) {
-  if (!c->sift) return;
-  vo_sift_ws* w = c->sift;
-  void* bufs[] = {w->d_img, w->d_a, w->d_b, w->d_gauss, w->d_dog, w->d_taps, w->d_cand, w->d_raw, w->d_cnt, w->d_fin, w->d_desc};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  delete w;
+  delete c->sift;
   c->sift = nullptr;
 }
 
@@ -418,10 +415,8 @@ static int sift_taps(double sigma, float* out) {       // cv::getGaussianKernel 
   return n / 2;
 }
 
-static int32_t sift_alloc(vo_ctx* c) {
-  if (c->sift) return VO_OK;
-  vo_sift_ws* w = new vo_sift_ws();
-  c->sift = w;
+// the scale space, taps and lists of a new workspace
+static int32_t sift_build(vo_ctx* c, vo_sift_ws* w) {
   const size_t B = c->batch;
   const int W = c->width, H = c->height;
   sift_geom& G = w->G;
@@ -437,15 +432,15 @@ static int32_t sift_alloc(vo_ctx* c) {
   }
   G.n_oct = n; G.g_seq = go; G.d_seq = dof;
   const size_t base_px = (size_t)4 * W * H;
-  VO_HIP(c, hipMalloc((void**)&w->d_img, B * W * H));
-  VO_HIP(c, hipMalloc((void**)&w->d_a, sizeof(float) * B * base_px));
-  VO_HIP(c, hipMalloc((void**)&w->d_b, sizeof(float) * B * base_px));
-  VO_HIP(c, hipMalloc((void**)&w->d_gauss, sizeof(float) * B * G.g_seq));
-  VO_HIP(c, hipMalloc((void**)&w->d_dog, sizeof(float) * B * G.d_seq));
-  VO_HIP(c, hipMalloc((void**)&w->d_taps, sizeof(float) * 6 * SIFT_MAX_TAPS));
-  VO_HIP(c, hipMalloc((void**)&w->d_cand, sizeof(int4) * B * SIFT_CAND_CAP));
-  VO_HIP(c, hipMalloc((void**)&w->d_raw, sizeof(vo_sift_kp) * B * SIFT_RAW_CAP));
-  VO_HIP(c, hipMalloc((void**)&w->d_cnt, sizeof(int) * 3 * B));
+  VO_HIP(c, w->d_img.reserve(B * W * H));
+  VO_HIP(c, w->d_a.reserve(B * base_px));
+  VO_HIP(c, w->d_b.reserve(B * base_px));
+  VO_HIP(c, w->d_gauss.reserve(B * G.g_seq));
+  VO_HIP(c, w->d_dog.reserve(B * G.d_seq));
+  VO_HIP(c, w->d_taps.reserve(6 * SIFT_MAX_TAPS));
+  VO_HIP(c, w->d_cand.reserve(B * SIFT_CAND_CAP));
+  VO_HIP(c, w->d_raw.reserve(B * SIFT_RAW_CAP));
+  VO_HIP(c, w->d_cnt.reserve(3 * B));
   // taps: [0] the initial blur sqrt(max(1.6^2 - 4 * 0.5^2, 0.01)), [1..5] the layer increments
   float taps[6][SIFT_MAX_TAPS];
   memset(taps, 0, sizeof(taps));
@@ -457,6 +452,11 @@ static int32_t sift_alloc(vo_ctx* c) {
   }
   VO_HIP(c, hipMemcpy(w->d_taps, taps, sizeof(taps), hipMemcpyHostToDevice));
   return VO_OK;
+}
+
+static int32_t sift_alloc(vo_ctx* c) {
+  if (c->sift) return VO_OK;
+  return vo_ws_replace(c->sift, [c](vo_sift_ws& w) { return sift_build(c, &w); });
 }
 
 static void sift_blur(vo_ctx* c, const float* src, size_t src_seq, float* dst, size_t dst_seq, int w, int h, int which) {
@@ -568,11 +568,9 @@ extern "C" int32_t vo_sift_detect_compute(vo_ctx* c, const uint8_t* img, int32_t
   }
   if (max_fin == 0) return VO_OK;
   if (w->fin_cap < max_out) {
-    if (w->d_fin) (void)hipFree(w->d_fin);
-    if (w->d_desc) (void)hipFree(w->d_desc);
-    w->d_fin = nullptr; w->d_desc = nullptr;
-    VO_HIP(c, hipMalloc((void**)&w->d_fin, sizeof(vo_sift_kp) * B * max_out));
-    VO_HIP(c, hipMalloc((void**)&w->d_desc, sizeof(float) * 128 * B * max_out));
+    w->fin_cap = 0;
+    VO_HIP(c, w->d_fin.reserve(B * max_out));
+    VO_HIP(c, w->d_desc.reserve(128 * B * max_out));
     w->fin_cap = max_out;
   }
   int* d_nfin = w->d_cnt + 2 * B;

@@ -175,8 +175,8 @@ static uint64_t step_signature(vo_ctx* c, const step_cfg& s) {
   auto mix_i = [&](long long v) { mix(&v, sizeof(v)); };
   mix(&s, sizeof(s));                       // the caller zero-fills the struct, so padding bytes are defined
   mix_i(c->p_parity); mix_i(c->dlt_n); mix_i(c->dlt_stats); mix_i(c->ingest_gen); mix_i(c->ba_sharded); mix_i(c->side_stream);
-  mix_i((long long)(uintptr_t)c->d_seq); mix_i(c->seq_n);
-  mix_i((long long)(uintptr_t)c->d_uv0); mix_i((long long)(uintptr_t)c->d_dlt_cam);
+  mix_i((long long)(uintptr_t)c->d_seq.get()); mix_i(c->seq_n);
+  mix_i((long long)(uintptr_t)c->d_uv0.get()); mix_i((long long)(uintptr_t)c->d_dlt_cam.get());
   mix_i((long long)(uintptr_t)c->st); mix_i((long long)(uintptr_t)c->ba); mix_i((long long)(uintptr_t)c->d_pt_counts);
   int W = 0, N = 0;
   mix_i((long long)(uintptr_t)vo_ba_obs_device(c, &W, &N)); mix_i(W); mix_i(N);
@@ -227,31 +227,29 @@ __global__ __launch_bounds__(256) void k_gather_frames(const uint8_t* const* __r
 static int32_t host_frames_setup(vo_ctx* c) {
   const size_t fr = (size_t)c->width * c->height;
   hipStream_t st = nullptr;
-  const uint8_t** tab = nullptr;
-  uint8_t* raw[2] = {nullptr, nullptr};
+  vo_pinned<const uint8_t*> tab;
+  vo_dev<uint8_t> raw[2];
   hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
   // One row of pointers per step that can be in flight (VO_HOST_TAB_SLOTS, vo_internal.h): k_gather_frames reads its row while it runs, and a row
   // is written again only after the step that used it has been fetched -- whose pyramid waited for ev_h2d, i.e. for the gather to end.  So the
   // enqueue path never waits on the host for a row
   hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&tab, VO_HOST_TAB_SLOTS * sizeof(void*) * (size_t)c->batch, hipHostMallocDefault);
+  if (e == hipSuccess) e = tab.reserve(VO_HOST_TAB_SLOTS * (size_t)c->batch);
   for (int k = 0; k < 2 && e == hipSuccess; k++) {
-    e = hipMalloc((void**)&raw[k], fr * c->batch);
+    e = raw[k].reserve(fr * c->batch);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_h2d[k], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_free[k], hipEventDisableTiming);
   }
   if (e != hipSuccess) {
     for (int k = 0; k < 2; k++) {
-      if (raw[k]) (void)hipFree(raw[k]);
       if (ev_h2d[k]) (void)hipEventDestroy(ev_h2d[k]);
       if (ev_free[k]) (void)hipEventDestroy(ev_free[k]);
     }
-    if (tab) (void)hipHostFree(tab);
     if (st) (void)hipStreamDestroy(st);
-    VO_HIP(c, e);
+    VO_HIP(c, e);               // the three local buffers go with the scope
   }
-  c->h_ptr_tab = tab;
-  for (int k = 0; k < 2; k++) { c->d_host_raw[k] = raw[k]; c->ev_h2d[k] = ev_h2d[k]; c->ev_raw_free[k] = ev_free[k]; c->raw_free_recorded[k] = false; }
+  c->h_ptr_tab.swap(tab);
+  for (int k = 0; k < 2; k++) { c->d_host_raw[k].swap(raw[k]); c->ev_h2d[k] = ev_h2d[k]; c->ev_raw_free[k] = ev_free[k]; c->raw_free_recorded[k] = false; }
   c->stream_h2d = st;                         // last: the key of the first-use test
   return VO_OK;
 }

@@ -28,48 +28,43 @@
 struct vo_trk_ws {
   int cap = 0;                  // = max_pts
   int n_hi = 0;                 // host-side upper bound of the per-sequence counts
-  int32_t* d_n = nullptr;       // [B] live tracks
-  int32_t* d_next_tag = nullptr;// [B]
-  int32_t* d_ndead = nullptr;   // [B] tracks that died in the last vo_tracks_track
-  int32_t* d_dead_tag = nullptr;// [B][cap]
-  float* d_first = nullptr;     // [B][cap][2]
-  int32_t* d_tf = nullptr;      // [B][cap]
-  int32_t* d_tt = nullptr;      // [B][cap]
-  int32_t* d_tag = nullptr;     // [B][cap]
-  float* d_hist = nullptr;      // [B][VO_TRK_HIST][cap][2]
-  double* d_obs = nullptr;      // staging of vo_tracks_obs [B][window][cap][2]
-  size_t obs_cap = 0;
+  vo_dev<int32_t> d_n;          // [B] live tracks
+  vo_dev<int32_t> d_next_tag;   // [B]
+  vo_dev<int32_t> d_ndead;      // [B] tracks that died in the last vo_tracks_track
+  vo_dev<int32_t> d_dead_tag;   // [B][cap]
+  vo_dev<float> d_first;        // [B][cap][2]
+  vo_dev<int32_t> d_tf;         // [B][cap]
+  vo_dev<int32_t> d_tt;         // [B][cap]
+  vo_dev<int32_t> d_tag;        // [B][cap]
+  vo_dev<float> d_hist;         // [B][VO_TRK_HIST][cap][2]
+  vo_dev<double> d_obs;         // staging of vo_tracks_obs [B][window][cap][2], grown by the widest window asked for
 };
 
 void vo_trk_destroy(vo_ctx* c) {
-  if (!c->trk) return;
-  vo_trk_ws* t = c->trk;
-  void* bufs[] = {t->d_n, t->d_next_tag, t->d_ndead, t->d_dead_tag, t->d_first, t->d_tf, t->d_tt, t->d_tag, t->d_hist, t->d_obs};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  delete t;
+  delete c->trk;
   c->trk = nullptr;
   c->d_pt_counts = nullptr;
 }
 
 static int32_t trk_init(vo_ctx* c) {
   if (c->trk) return VO_OK;
-  vo_trk_ws* t = new vo_trk_ws();
-  c->trk = t;
-  t->cap = c->max_pts;
-  const size_t B = c->batch, cap = t->cap;
-  VO_HIP(c, hipMalloc((void**)&t->d_n, sizeof(int32_t) * B));
-  VO_HIP(c, hipMalloc((void**)&t->d_next_tag, sizeof(int32_t) * B));
-  VO_HIP(c, hipMalloc((void**)&t->d_ndead, sizeof(int32_t) * B));
-  VO_HIP(c, hipMalloc((void**)&t->d_dead_tag, sizeof(int32_t) * B * cap));
-  VO_HIP(c, hipMalloc((void**)&t->d_first, sizeof(float) * 2 * B * cap));
-  VO_HIP(c, hipMalloc((void**)&t->d_tf, sizeof(int32_t) * B * cap));
-  VO_HIP(c, hipMalloc((void**)&t->d_tt, sizeof(int32_t) * B * cap));
-  VO_HIP(c, hipMalloc((void**)&t->d_tag, sizeof(int32_t) * B * cap));
-  VO_HIP(c, hipMalloc((void**)&t->d_hist, sizeof(float) * 2 * B * cap * VO_TRK_HIST));
-  VO_HIP(c, hipMemsetAsync(t->d_n, 0, sizeof(int32_t) * B, c->stream));
-  VO_HIP(c, hipMemsetAsync(t->d_next_tag, 0, sizeof(int32_t) * B, c->stream));
-  VO_HIP(c, hipMemsetAsync(t->d_ndead, 0, sizeof(int32_t) * B, c->stream));
-  return VO_OK;
+  return vo_ws_replace(c->trk, [c](vo_trk_ws& t) -> int32_t {
+    t.cap = c->max_pts;
+    const size_t B = c->batch, cap = t.cap;
+    VO_HIP(c, t.d_n.reserve(B));
+    VO_HIP(c, t.d_next_tag.reserve(B));
+    VO_HIP(c, t.d_ndead.reserve(B));
+    VO_HIP(c, t.d_dead_tag.reserve(B * cap));
+    VO_HIP(c, t.d_first.reserve(2 * B * cap));
+    VO_HIP(c, t.d_tf.reserve(B * cap));
+    VO_HIP(c, t.d_tt.reserve(B * cap));
+    VO_HIP(c, t.d_tag.reserve(B * cap));
+    VO_HIP(c, t.d_hist.reserve(2 * B * cap * VO_TRK_HIST));
+    VO_HIP(c, hipMemsetAsync(t.d_n, 0, sizeof(int32_t) * B, c->stream));
+    VO_HIP(c, hipMemsetAsync(t.d_next_tag, 0, sizeof(int32_t) * B, c->stream));
+    VO_HIP(c, hipMemsetAsync(t.d_ndead, 0, sizeof(int32_t) * B, c->stream));
+    return VO_OK;
+  });
 }
 
 struct trk_ptrs {
@@ -333,12 +328,7 @@ extern "C" int32_t vo_tracks_obs(vo_ctx* c, int32_t t_now, int32_t window, doubl
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   vo_trk_ws* tw = c->trk;
   const size_t total = (size_t)c->batch * window * tw->cap * 2;
-  if (tw->obs_cap < total) {
-    if (tw->d_obs) (void)hipFree(tw->d_obs);
-    tw->d_obs = nullptr; tw->obs_cap = 0;
-    VO_HIP(c, hipMalloc((void**)&tw->d_obs, sizeof(double) * total));
-    tw->obs_cap = total;
-  }
+  VO_HIP(c, tw->d_obs.reserve(total));
   hipLaunchKernelGGL(k_trk_obs, dim3(vo_div_up(tw->cap, 256), window, c->batch), dim3(256), 0, c->stream, trk_make(tw), t_now, window, tw->d_obs);
   VO_HIP(c, hipGetLastError());
   VO_HIP(c, hipMemcpyAsync(obs, tw->d_obs, sizeof(double) * total, hipMemcpyDeviceToHost, c->stream));

@@ -7,6 +7,7 @@
 //           normalised inliers' rows, its unpacking, the 9 x 9 eigenvector, and the right factor of the two denormalisations
 // Samplers, minimal solvers, left factors and sign rules are each model's own and stay in its unit.
 #pragma once
+#include "vo_buf.h"
 #include "vo_ransac.h"
 
 // ================================================================================================
@@ -15,60 +16,52 @@
 struct vo_tv_ws {
   static constexpr bool search = false;
   int cap = 0;
-  float* d_p = nullptr;        // [B][2][cap][2] pixel coordinates of the two views
-  uint8_t* d_mask = nullptr;   // [B][cap]
-  double* d_out = nullptr;     // [B][n_out]
-  double* h_out = nullptr;     // pinned
+  vo_dev<float> d_p;           // [B][2][cap][2] pixel coordinates of the two views
+  vo_dev<uint8_t> d_mask;      // [B][cap]
+  vo_dev<double> d_out;        // [B][n_out]
+  vo_pinned<double> h_out;
 };
 
 template <class Hyp, class Ctrl, int Batch>
 struct vo_tv_search_ws : vo_tv_ws {
   static constexpr bool search = true;
   static constexpr int batch = Batch;
-  Hyp* d_hyp = nullptr;        // [B][Batch]
-  Ctrl* d_ctrl = nullptr;      // [B]
-  Ctrl* h_ctrl = nullptr;      // pinned
+  vo_dev<Hyp> d_hyp;           // [B][Batch]
+  vo_dev<Ctrl> d_ctrl;         // [B]
+  vo_pinned<Ctrl> h_ctrl;
 };
 
-// the shared buffers of *slot and the workspace itself; a unit's destroy frees its own buffers first.  Copes with null members
+// a unit's destroy hook: the workspace goes with every buffer it owns
 template <class W>
 inline void vo_tv_free(W*& slot) {
-  W* w = slot;
-  if (!w) return;
-  void* bufs[] = {w->d_p, w->d_mask, w->d_out};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  if constexpr (W::search) {
-    if (w->d_hyp) (void)hipFree(w->d_hyp);
-    if (w->d_ctrl) (void)hipFree(w->d_ctrl);
-    if (w->h_ctrl) (void)hipHostFree(w->h_ctrl);
-  }
-  if (w->h_out) (void)hipHostFree(w->h_out);
-  delete w;
+  delete slot;
   slot = nullptr;
 }
 
 // *slot for n correspondences: a workspace of cap < n goes (by the unit's destroy), a new one has cap = max(n, max_pts, min_cap) and
-// n_out (+ h_extra in the pinned copy) doubles per sequence.  It is attached before its buffers are allocated, so a failed allocation
-// leaves it to destroy.  A unit allocates its own buffers behind this call, where they are still null
-template <class W>
-inline int32_t vo_tv_alloc(vo_ctx* c, W*& slot, void (*destroy)(vo_ctx*), int n, int n_out, int h_extra = 0, int min_cap = 0) {
+// n_out (+ h_extra in the pinned copy) doubles per sequence.  `extra` allocates the unit's own buffers behind the shared ones.  The
+// workspace is attached once all of it is built (vo_ws_replace): a failed allocation leaves the slot null and the next call builds afresh
+inline int32_t vo_tv_no_extra(vo_tv_ws&) { return VO_OK; }
+template <class W, class Extra = int32_t (*)(vo_tv_ws&)>
+inline int32_t vo_tv_alloc(vo_ctx* c, W*& slot, void (*destroy)(vo_ctx*), int n, int n_out, int h_extra = 0, int min_cap = 0,
+                           Extra extra = vo_tv_no_extra) {
   const size_t B = c->batch;
   if (slot && slot->cap < n) destroy(c);
   if (slot) return VO_OK;
-  W* w = new W();
-  slot = w;
-  w->cap = n > c->max_pts ? n : c->max_pts;
-  if (w->cap < min_cap) w->cap = min_cap;
-  VO_HIP(c, hipMalloc((void**)&w->d_p, sizeof(float) * 4 * B * w->cap));
-  if constexpr (W::search) {
-    VO_HIP(c, hipMalloc((void**)&w->d_hyp, sizeof(*w->d_hyp) * B * W::batch));
-    VO_HIP(c, hipMalloc((void**)&w->d_ctrl, sizeof(*w->d_ctrl) * B));
-  }
-  VO_HIP(c, hipMalloc((void**)&w->d_mask, B * w->cap));
-  VO_HIP(c, hipMalloc((void**)&w->d_out, sizeof(double) * n_out * B));
-  if constexpr (W::search) VO_HIP(c, hipHostMalloc((void**)&w->h_ctrl, sizeof(*w->h_ctrl) * B, hipHostMallocDefault));
-  VO_HIP(c, hipHostMalloc((void**)&w->h_out, sizeof(double) * (n_out + h_extra) * B, hipHostMallocDefault));
-  return VO_OK;
+  return vo_ws_replace(slot, [&](W& w) -> int32_t {
+    w.cap = n > c->max_pts ? n : c->max_pts;
+    if (w.cap < min_cap) w.cap = min_cap;
+    VO_HIP(c, w.d_p.reserve(4 * B * w.cap));
+    if constexpr (W::search) {
+      VO_HIP(c, w.d_hyp.reserve(B * W::batch));
+      VO_HIP(c, w.d_ctrl.reserve(B));
+    }
+    VO_HIP(c, w.d_mask.reserve(B * w.cap));
+    VO_HIP(c, w.d_out.reserve(n_out * B));
+    if constexpr (W::search) VO_HIP(c, w.h_ctrl.reserve(B));
+    VO_HIP(c, w.h_out.reserve((n_out + h_extra) * B));
+    return extra(w);
+  });
 }
 
 // pts1 / pts2 [B][n][2] f32 of the host -> the two views of every sequence, on q

@@ -98,7 +98,7 @@ static void und_build_table(int w, int h, const double* K, const double* d, cons
 void vo_undistort_enqueue(vo_ctx* c, hipStream_t q, const uint8_t* d_raw_img, size_t raw_seq_stride, const int32_t* d_frame_idx, int remap) {
   const int w = c->width, h = c->height;
   hipLaunchKernelGGL(k_undistort, dim3(vo_div_up(vo_div_up(w, 4) * h, 256), 1, c->batch), dim3(256), 0, q, d_raw_img, raw_seq_stride, d_frame_idx,
-                     w, h, reinterpret_cast<const uint2*>(c->d_und_tab), c->d_und, remap);
+                     w, h, reinterpret_cast<const uint2*>(c->d_und_tab.get()), c->d_und, remap);
 }
 
 extern "C" int32_t vo_set_undistort(vo_ctx* c, const double* K, const double* dist, int32_t n_dist, const double* newK) {
@@ -117,7 +117,7 @@ extern "C" int32_t vo_set_undistort(vo_ctx* c, const double* K, const double* di
   std::vector<uint64_t> tab;
   und_build_table(c->width, c->height, K, d, nK, tab);
   const size_t px = (size_t)c->width * c->height;
-  if (!c->d_und_tab) VO_HIP(c, hipMalloc((void**)&c->d_und_tab, px * sizeof(uint64_t)));
+  VO_HIP(c, c->d_und_tab.reserve(px));
   int32_t r = vo_ingest_reserve(c, &c->d_und);
   if (r == VO_OK) r = vo_sync_streams(c);                               // no build in flight reads the table that is replaced
   if (r != VO_OK) return r;
