@@ -206,6 +206,27 @@ typedef struct {
   int32_t models;            /* models scored over the whole search */
 } vo_fund_stats;
 
+/* Sim(3) / rigid alignment of two 3-D point sets, dst ~ s R src + t (vo_sim3_ransac, vo_sim3_fit): Umeyama's closed form inside the RANSAC
+ * of cv2.estimateAffine3D(src, dst, ransacThreshold = 3.0, confidence = 0.99).  The six fields fill the 32 bytes: there is no padding */
+typedef struct {
+  double  threshold;         /* 3.0, in dst's units: consensus threshold on |dst - (s R src + t)| */
+  double  confidence;        /* 0.99 */
+  int32_t max_iters;         /* 1000 */
+  int32_t seed;              /* of the counter-based sample generator */
+  int32_t with_scale;        /* 1: a similarity (7 parameters); 0: s = 1, a rigid motion (Kabsch) */
+  int32_t refit;             /* 1: Umeyama over the consensus set; 0: the winning sample's model is returned */
+} vo_sim3_params;
+
+typedef struct {
+  double  cost;              /* sum of squared errors |dst - (s R src + t)|^2 over the mask at the returned model */
+  int32_t n_inliers;         /* consensus set of the winning sample's model (vo_sim3_fit: rows fitted) */
+  int32_t hypotheses;        /* three-point samples evaluated */
+  int32_t best;              /* index of the winning sample (vo_sim3_fit: -1) */
+  int32_t status;            /* 0, or VO_E_NUMERIC when no model with >= 3 inliers was found (vo_sim3_fit: fewer than 3 rows, or a degenerate set) */
+  int32_t degenerate;        /* samples without a model: a coordinate that is not finite, collinear or coincident points, s <= 0 */
+  int32_t refit;             /* 1: the returned model is Umeyama over the consensus set; 0: it is the winning sample's own */
+} vo_sim3_stats;
+
 /* cv2.decomposeHomographyMat(H, K) with cv2.filterHomographyDecompByVisibleRefpoints' two tests counted as votes, a ranking and an
  * ambiguity verdict (vo_homography_decompose, vo_homography_pose) */
 typedef struct {
@@ -759,6 +780,43 @@ int32_t vo_fundamental_default_params(vo_fund_params* p);
 int32_t vo_fundamental_ransac(vo_ctx* ctx, const float* pts1, const float* pts2, int32_t n, const vo_fund_params* prm,
                               double* F, double* F0, uint8_t* inlier_mask, vo_fund_stats* stats);
 
+/* ---- Sim(3) / rigid alignment of two 3-D point sets ------------------------------------------------
+ * dst ~ s R src + t between two sets of corresponding 3-D points with outliers: two maps of the same landmarks after a re-bootstrap, an
+ * estimated trajectory against its ground truth, a loop closure.  Umeyama 1991 / Horn 1987 inside the RANSAC of
+ * cv2.estimateAffine3D(src, dst, ransacThreshold = 3.0, confidence = 0.99) and of ORB-SLAM's ComputeSim3, next to the 2D-2D searches
+ * above.  Rounds of 256 three-point samples: hypothesis h draws sample3(seed, h, n), the generator of the other searches; a lane per
+ * sample forms the centroids and Sigma = 1/3 sum (y_i - yc)(x_i - xc)^T, takes its singular values and vectors by one-sided Jacobi
+ * rotations, R = U diag(1, 1, det U det V) V^T (a three-point Sigma has rank 2, so the determinant rule decides every sample and R is a
+ * proper rotation also where dst mirrors src), s = tr(D S) / var_x (with_scale = 0: s = 1, Kabsch) and t = yc - s R xc.  A sample with
+ * a coordinate that is not finite, with collinear or coincident points in either set
+ * (|(b - a) x (c - a)|^2 <= 1e-10 |b - a|^2 |c - a|^2) or, with scale, with s <= 0 or not finite has no model and still counts
+ * (stats.degenerate).  A wave per sample counts |y - (s R x + t)|^2 <= threshold^2 in dst's units; most inliers win, ties to the
+ * smallest h, at least 3; the bound is RANSACUpdateNumIters with 3 model points.  The mask is the winner's and is not recomputed.
+ * refit = 1: Umeyama over the consensus set in two passes (centroids, then central moments about them, a fixed reduction order), unless
+ * the set is degenerate -- the second eigenvalue of either set's scatter matrix <= 1e-10 of the first -- or the re-fit is not finite;
+ * then, and with refit = 0, the winning sample's model is returned; stats.refit says which.  cost is the sum of squared errors of the
+ * consensus set under the returned model.  The algorithm is defined by tests/sim3_model.py.
+ * Stated deviations from cv2.estimateAffine3D: the sample draws are this library's, so parity is statistical; the model is a similarity
+ * (or a rigid motion), not a 12-parameter affine map; the error is evaluated in float64.
+ * Measured on the model against a 40-digit truth (tests/test_sim3_model.py), with kappa = s1 / (s2 + d3) of Sigma's signed singular
+ * values: a three-point model lies within SOLVE_FACTOR x 2^-52 x kappa and a re-fit within REFIT_FACTOR x 2^-52 x kappa of the truth
+ * (SOLVE_FACTOR = 13, REFIT_FACTOR = 32: 4 x the measured 3.00 and 7.93); the kernels are held to the same bounds against the model
+ * (measured on the MI355X: at most 1.84 and 5.7), and results are bitwise reproducible across calls and batch positions.
+ * vo_sim3_ransac: src, dst [batch][n][3] f32 (a row with a coordinate that is not finite in either set is never an inlier); prm NULL:
+ * the defaults; scale [batch], R [batch][9] row-major, t [batch][3]; model0 [batch][13] = (s, R, t) of the winning sample as found;
+ * inlier_mask [batch][n] u8 (of model0); stats [batch]; every output may be NULL.  A sequence without a model: status VO_E_NUMERIC,
+ * NaN outputs, an empty mask; the call returns VO_OK.
+ * vo_sim3_fit: the finish pass alone, without a search: Umeyama over the rows of mask [batch][n] u8 (NULL: every row) whose
+ * coordinates are finite -- the plain least-squares alignment.  vo_sim3_ransac returns, bit for bit, what vo_sim3_fit returns on the
+ * mask it reports (stats.refit = 1).  Fewer than 3 rows or a degenerate set: status VO_E_NUMERIC, NaN outputs.
+ * VO_E_INVALID with nothing enqueued: n < 3, threshold <= 0 or not finite, confidence outside (0, 1), max_iters < 1, with_scale or
+ * refit outside 0..1, a NULL src or dst. */
+int32_t vo_sim3_default_params(vo_sim3_params* p);
+int32_t vo_sim3_ransac(vo_ctx* ctx, const float* src, const float* dst, int32_t n, const vo_sim3_params* prm, double* scale,
+                       double* R, double* t, double* model0, uint8_t* inlier_mask, vo_sim3_stats* stats);
+int32_t vo_sim3_fit(vo_ctx* ctx, const float* src, const float* dst, const uint8_t* mask, int32_t n, int32_t with_scale,
+                    double* scale, double* R, double* t, vo_sim3_stats* stats);
+
 /* ---- SIFT features (SURVEY.md 8f "next" row 4, feature part) -----------------------------------
  * Replaces cv2.SIFT_create(nfeatures=1000).detect(img, mask) + .compute(img, kps) in
  * Extractor.extract(detector='custom', describe=True) (src/extractor/extractor.py:26-28, 114-122; the two bootstrap
@@ -1145,13 +1203,16 @@ int32_t vo_step_layout(vo_ctx* ctx, int32_t* layout, int32_t* gate_groups, int32
  * vo_fundamental_ransac and its k_f7_finish launch (tools/fundamental_timing.py).
  * VO_PROF_GMATCH_FORWARD / _REVERSE / _ACCEPT bracket the forward pass, the cross-check's reverse pass and the k_match_accept launch of
  * vo_match_guided_hamming / vo_match_guided_l2 (tools/guided_match_timing.py).
- * VO_PROF_HPOSE brackets the k_hpose launch of vo_homography_decompose and vo_homography_pose (tools/hpose_timing.py). */
+ * VO_PROF_HPOSE brackets the k_hpose launch of vo_homography_decompose and vo_homography_pose (tools/hpose_timing.py).
+ * VO_PROF_SIM3_SOLVE / _SCORE / _SELECT / _FINISH bracket the k_s3_solve / k_s3_score / k_s3_select launch of every round of
+ * vo_sim3_ransac and the k_s3_finish launch of vo_sim3_ransac and vo_sim3_fit (tools/sim3_timing.py). */
 enum { VO_PROF_FRAME = 0, VO_PROF_KLT = 1, VO_PROF_ST = 2, VO_PROF_DLT = 3, VO_PROF_BA = 4, VO_PROF_CLAHE_LUT = 5, VO_PROF_CLAHE_APPLY = 6,
        VO_PROF_HOM_SOLVE = 7, VO_PROF_HOM_SCORE = 8, VO_PROF_HOM_SELECT = 9, VO_PROF_HOM_FINISH = 10, VO_PROF_ORB_PYRAMID = 11,
        VO_PROF_ORB_CANDIDATES = 12, VO_PROF_ORB_RETAIN = 13, VO_PROF_ORB_DESCRIBE = 14,
        VO_PROF_FUND_SOLVE = 15, VO_PROF_FUND_SCORE = 16, VO_PROF_FUND_SELECT = 17, VO_PROF_FUND_FINISH = 18,
        VO_PROF_GMATCH_FORWARD = 19, VO_PROF_GMATCH_REVERSE = 20, VO_PROF_GMATCH_ACCEPT = 21, VO_PROF_HPOSE = 22,
-       VO_PROF_COUNT = 23 };
+       VO_PROF_SIM3_SOLVE = 23, VO_PROF_SIM3_SCORE = 24, VO_PROF_SIM3_SELECT = 25, VO_PROF_SIM3_FINISH = 26,
+       VO_PROF_COUNT = 27 };
 int32_t vo_profile_enable(vo_ctx* ctx, int32_t region_mask);
 int32_t vo_profile_read(vo_ctx* ctx, int32_t region, double* total_ms, int32_t* count);
 /* diagnostic: shader-clock stamps (s_memtime deltas, cycles) of the phases of the last launch of a

@@ -28,6 +28,7 @@
 #include "vo_internal.h"
 #include "vo_twoview.h"
 #include "vo_epi_dev.h"
+#include "vo_svd3.h"
 
 #include <math.h>
 #include <string.h>
@@ -370,29 +371,8 @@ __global__ void __launch_bounds__(F7_BATCH) k_f7_select(const f7_hyp* __restrict
 // ------------------------------------------------------------------------------------------------
 // unit eigenvector of the smallest eigenvalue of the symmetric 3 x 3 (a00 a01 a02 a11 a12 a22) by cyclic Jacobi rotations, in registers
 __device__ inline void f7_smallest_eigenvector3(double a00, double a01, double a02, double a11, double a12, double a22, double* out) {
-  double M[3][3] = {{a00, a01, a02}, {a01, a11, a12}, {a02, a12, a22}}, V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-  for (int sweep = 0; sweep < 30; sweep++) {
-    bool changed = false;
-#pragma unroll
-    for (int p = 0; p < 2; p++)
-#pragma unroll
-      for (int q = p + 1; q < 3; q++) {
-        const double apq = M[p][q];
-        if (apq * apq > 4.930380657631324e-32 * fabs(M[p][p] * M[q][q])) {       // as vo_smallest_eigenvector9
-          changed = true;
-          const double zeta = (M[q][q] - M[p][p]) / (2.0 * apq);
-          const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-          const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-          for (int k = 0; k < 3; k++) { const double a = M[k][p], bq = M[k][q]; M[k][p] = c * a - s * bq; M[k][q] = s * a + c * bq; }
-#pragma unroll
-          for (int k = 0; k < 3; k++) { const double a = M[p][k], bq = M[q][k]; M[p][k] = c * a - s * bq; M[q][k] = s * a + c * bq; }
-#pragma unroll
-          for (int k = 0; k < 3; k++) { const double a = V[k][p], bq = V[k][q]; V[k][p] = c * a - s * bq; V[k][q] = s * a + c * bq; }
-        }
-      }
-    if (!changed) break;
-  }
+  double M[3][3] = {{a00, a01, a02}, {a01, a11, a12}, {a02, a12, a22}}, V[3][3];
+  vo_jacobi3_sym(M, V);
   const bool m1 = M[1][1] < M[0][0];
   const double e01 = m1 ? M[1][1] : M[0][0];
   const bool m2 = M[2][2] < e01;

@@ -5,7 +5,7 @@
 // candidate instead of all-or-nothing, so that an outlier does not veto a candidate (ORB-SLAM's ReconstructH and COLMAP rank the same way).
 // The algorithm is defined by tests/hpose_model.py and compared with it candidate by candidate and count by count:
 //   decompose  one lane, float64: G = K^-1 H K of the H scaled by its largest entry, negated if det G < 0; one-sided Jacobi on the columns
-//              of G (the sweeps of e5_decompose: the condition of G is never squared), singular values over the middle one; the two pairs
+//              of G (vo_jacobi3_cols of vo_svd3.h, the sweeps of e5_decompose: the condition of G is never squared), singular values over the middle one; the two pairs
 //              {(R, t, n), (R, -t, -n)} in closed form, s^2 - 1 entering as (s - 1)(s + 1); s1 - s3 <= 2^-26 is a rotation (one solution,
 //              t = n = 0); det = 0, a zero focal length or an entry that is not finite has no solution
 //   vote       256 threads stride over the points: n_good = mask points with n . m1 > 0 and (R n) . m2 > 0, n_off = points outside the mask
@@ -18,6 +18,7 @@
 // This library is built with -ffp-contract=off: each vote expression rounds as the model's does.
 #include "vo_twoview.h"
 #include "vo_epi_dev.h"
+#include "vo_svd3.h"
 
 #include <math.h>
 #include <string.h>
@@ -66,47 +67,9 @@ __device__ inline void hp_decompose(const double* K, const double* Hin, hp_cand*
 #pragma unroll
   for (int i = 0; i < 3; i++)
 #pragma unroll
-    for (int j = 0; j < 3; j++) { U[i][j] = sg * U[i][j]; V[i][j] = (i == j) ? 1.0 : 0.0; }
-  for (int sweep = 0; sweep < 60; sweep++) {
-    bool changed = false;
-#pragma unroll
-    for (int p = 0; p < 2; p++)
-#pragma unroll
-      for (int q = p + 1; q < 3; q++) {
-        double al = 0, be = 0, ga = 0;
-#pragma unroll
-        for (int k = 0; k < 3; k++) { al += U[k][p] * U[k][p]; be += U[k][q] * U[k][q]; ga += U[k][p] * U[k][q]; }
-        if (ga * ga > 4.930380657631324e-32 * (al * be)) {
-          changed = true;
-          const double zeta = (be - al) / (2.0 * ga);
-          const double tt = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-          const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = cs * tt;
-#pragma unroll
-          for (int k = 0; k < 3; k++) {
-            const double up = U[k][p], uq = U[k][q];
-            U[k][p] = cs * up - sn * uq; U[k][q] = sn * up + cs * uq;
-            const double vp = V[k][p], vq = V[k][q];
-            V[k][p] = cs * vp - sn * vq; V[k][q] = sn * vp + cs * vq;
-          }
-        }
-      }
-    if (!changed) break;
-  }
+    for (int j = 0; j < 3; j++) U[i][j] = sg * U[i][j];
   double nn[3];
-#pragma unroll
-  for (int j = 0; j < 3; j++) nn[j] = (U[0][j] * U[0][j] + U[1][j] * U[1][j]) + U[2][j] * U[2][j];
-  // descending, a tie keeps the column order: (0,1), (1,2), (0,1)
-#pragma unroll
-  for (int pass = 0; pass < 3; pass++) {
-    const int j = (pass == 1) ? 1 : 0;
-    const bool sw = nn[j] < nn[j + 1];
-    { const double a = nn[j], b = nn[j + 1]; nn[j] = sw ? b : a; nn[j + 1] = sw ? a : b; }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      const double a = U[k][j], b = U[k][j + 1]; U[k][j] = sw ? b : a; U[k][j + 1] = sw ? a : b;
-      const double e = V[k][j], f = V[k][j + 1]; V[k][j] = sw ? f : e; V[k][j + 1] = sw ? e : f;
-    }
-  }
+  vo_jacobi3_cols(U, V, nn);
   const double s1 = sqrt(nn[0]), s2 = sqrt(nn[1]), s3 = sqrt(nn[2]);
   double u1[3], u2[3], u3[3], v1[3], v2[3], v3[3];
 #pragma unroll

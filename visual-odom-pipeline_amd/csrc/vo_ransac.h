@@ -1,9 +1,10 @@
-// What the four RANSAC searches (vo_pnp.hip, vo_essential.hip, vo_homography.hip, vo_fundamental.hip) have in common, in one place:
+// What the five RANSAC searches (vo_pnp.hip, vo_essential.hip, vo_homography.hip, vo_fundamental.hip, vo_sim3.hip) have in common, in one place:
 //   device  the counter-based splitmix64 sample generator, OpenCV's iteration bound, the head of a sequence's control block (bound,
 //           hypotheses done, done flag) with its reset, and the tail of a select kernel: the winner of a batch and the advance of the head
 //   host    the round loop of the synchronous entry points: enqueue a round, read the control blocks back, stop when every sequence is done
 // The generator and the bound are part of each search's definition: oracle/pnp_oracle.py, oracle/essential_oracle.py,
-// tests/homography_model.py and tests/fundamental_model.py each carry their own copy and are compared with the device hypothesis by hypothesis.
+// tests/homography_model.py, tests/fundamental_model.py and tests/sim3_model.py each carry their own copy and are compared with the device
+// hypothesis by hypothesis.
 // What only the two-view units share -- workspace, upload and read-back, the passes of the finish kernels with their 45-sum reduction and
 // the 9 x 9 eigenvector -- is vo_twoview.h, on top of this header; PnP needs none of it.
 #pragma once
@@ -20,7 +21,8 @@ __device__ __forceinline__ unsigned long long vo_splitmix64(unsigned long long x
 }
 
 // M distinct indices in [0, n), n >= M, of hypothesis h: draw k is splitmix64(seed, h, k) mod n, a draw that repeats an index is skipped
-// (M = 4: sample4(seed, h, n) of oracle/pnp_oracle.py and tests/homography_model.py, M = 5: sample5 of oracle/essential_oracle.py, M = 7: sample7 of tests/fundamental_model.py)
+// (M = 4: sample4(seed, h, n) of oracle/pnp_oracle.py and tests/homography_model.py, M = 5: sample5 of oracle/essential_oracle.py, M = 7: sample7 of tests/fundamental_model.py,
+// M = 3: sample3 of tests/sim3_model.py)
 template <int M>
 __device__ inline void vo_ransac_sample(unsigned seed, unsigned h, int n, int* idx) {
   int cnt = 0;

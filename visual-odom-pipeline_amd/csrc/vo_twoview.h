@@ -1,6 +1,6 @@
 // What the four two-view units (vo_essential.hip, vo_homography.hip, vo_fundamental.hip, vo_hpose.hip) have in common beyond the sampling
-// side of vo_ransac.h, in one place:
-//   host    the workspace -- the two views [B][2][cap][2] f32, the mask, the result rows and their pinned copy; a search adds its hypotheses
+// side of vo_ransac.h, in one place; the 3D-3D unit (vo_sim3.hip) takes the host side and the reduction with points of three coordinates:
+//   host    the workspace -- the two views [B][2][cap][dim] f32 (dim = 2), the mask, the result rows and their pinned copy; a search adds its hypotheses
 //           and control blocks -- with its allocate-or-regrow and free, the upload of the two views and the read-back of result and mask
 //   device  a sequence's pointers into those buffers, the no-winner exit of a finish kernel, and what k_h4_finish and k_f7_finish do alike:
 //           the 256-thread reduction of VO_NSUM sums, the winner's mask with count and centroids, the Hartley scales, the Gram matrix of the
@@ -15,8 +15,9 @@
 // ================================================================================================
 struct vo_tv_ws {
   static constexpr bool search = false;
+  static constexpr int dim = 2;        // coordinates per point; a workspace of 3-D point sets (vo_sim3.hip) says 3
   int cap = 0;
-  vo_dev<float> d_p;           // [B][2][cap][2] pixel coordinates of the two views
+  vo_dev<float> d_p;           // [B][2][cap][dim] pixel coordinates of the two views
   vo_dev<uint8_t> d_mask;      // [B][cap]
   vo_dev<double> d_out;        // [B][n_out]
   vo_pinned<double> h_out;
@@ -51,7 +52,7 @@ inline int32_t vo_tv_alloc(vo_ctx* c, W*& slot, void (*destroy)(vo_ctx*), int n,
   return vo_ws_replace(slot, [&](W& w) -> int32_t {
     w.cap = n > c->max_pts ? n : c->max_pts;
     if (w.cap < min_cap) w.cap = min_cap;
-    VO_HIP(c, w.d_p.reserve(4 * B * w.cap));
+    VO_HIP(c, w.d_p.reserve(2 * W::dim * B * w.cap));
     if constexpr (W::search) {
       VO_HIP(c, w.d_hyp.reserve(B * W::batch));
       VO_HIP(c, w.d_ctrl.reserve(B));
@@ -64,11 +65,11 @@ inline int32_t vo_tv_alloc(vo_ctx* c, W*& slot, void (*destroy)(vo_ctx*), int n,
   });
 }
 
-// pts1 / pts2 [B][n][2] f32 of the host -> the two views of every sequence, on q
-inline int32_t vo_tv_upload(vo_ctx* c, hipStream_t q, const vo_tv_ws* w, const float* pts1, const float* pts2, int n) {
-  const size_t row = sizeof(float) * 2 * n, pitch = sizeof(float) * 2 * 2 * (size_t)w->cap;
+// pts1 / pts2 [B][n][dim] f32 of the host -> the two views of every sequence, on q
+inline int32_t vo_tv_upload(vo_ctx* c, hipStream_t q, const vo_tv_ws* w, const float* pts1, const float* pts2, int n, int dim = 2) {
+  const size_t row = sizeof(float) * dim * n, pitch = sizeof(float) * 2 * dim * (size_t)w->cap;
   VO_HIP(c, hipMemcpy2DAsync(w->d_p, pitch, pts1, row, row, c->batch, hipMemcpyHostToDevice, q));
-  VO_HIP(c, hipMemcpy2DAsync(w->d_p + (size_t)w->cap * 2, pitch, pts2, row, row, c->batch, hipMemcpyHostToDevice, q));
+  VO_HIP(c, hipMemcpy2DAsync(w->d_p + (size_t)w->cap * dim, pitch, pts2, row, row, c->batch, hipMemcpyHostToDevice, q));
   return VO_OK;
 }
 

@@ -113,6 +113,18 @@ class FundStats(C.Structure):
                 ("status", C.c_int32), ("n_roots", C.c_int32), ("models", C.c_int32)]
 
 
+class Sim3Params(C.Structure):
+    """vo_sim3_params (32 bytes)"""
+    _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("max_iters", C.c_int32), ("seed", C.c_int32),
+                ("with_scale", C.c_int32), ("refit", C.c_int32)]
+
+
+class Sim3Stats(C.Structure):
+    """vo_sim3_stats (32 bytes)"""
+    _fields_ = [("cost", C.c_double), ("n_inliers", C.c_int32), ("hypotheses", C.c_int32), ("best", C.c_int32),
+                ("status", C.c_int32), ("degenerate", C.c_int32), ("refit", C.c_int32)]
+
+
 class HposeParams(C.Structure):
     _fields_ = [("ratio", C.c_double), ("threshold", C.c_double), ("hint", C.c_double * 3), ("min_off", C.c_int32), ("use_hint", C.c_int32)]
 
@@ -279,6 +291,9 @@ SIGNATURES = {
                                        _f64p, _f64p, _f64p, C.POINTER(HomStats), C.POINTER(HposeStats)]),
     "vo_fundamental_default_params": (C.c_int32, [C.POINTER(FundParams)]),
     "vo_fundamental_ransac": (C.c_int32, [_ctx, _f32p, _f32p, C.c_int32, C.POINTER(FundParams), _f64p, _f64p, _u8p, C.POINTER(FundStats)]),
+    "vo_sim3_default_params": (C.c_int32, [C.POINTER(Sim3Params)]),
+    "vo_sim3_ransac": (C.c_int32, [_ctx, _f32p, _f32p, C.c_int32, C.POINTER(Sim3Params), _f64p, _f64p, _f64p, _f64p, _u8p, C.POINTER(Sim3Stats)]),
+    "vo_sim3_fit": (C.c_int32, [_ctx, _f32p, _f32p, _u8p, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, C.POINTER(Sim3Stats)]),
     "vo_sift_detect_compute": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32, C.POINTER(SiftKp), _f32p, _i32p]),
     "vo_orb_default_params": (C.c_int32, [C.POINTER(OrbParams)]),
     "vo_orb_detect_compute": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.POINTER(OrbParams), _i8p, C.c_int32, C.POINTER(OrbKp), _u8p, _i32p]),

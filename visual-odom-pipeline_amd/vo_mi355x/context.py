@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, FundParams, FundStats, GMatchParams, HomParams, HomStats, HposeParams, HposeStats, KltParams, OrbKp, OrbParams, SiftKp, PnpParams, PnpStats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
+from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, FundParams, FundStats, GMatchParams, HomParams, HomStats, HposeParams, HposeStats, KltParams, OrbKp, OrbParams, SiftKp, PnpParams, PnpStats, Sim3Params, Sim3Stats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
 
 # vo_set_klt_predict modes (include/vo_mi355x.h)
 KLT_PREDICT_MODES = {"off": 0, "constant_velocity": 1}
@@ -767,6 +767,7 @@ class VoContext:
     PROF_FUND_SOLVE, PROF_FUND_SCORE, PROF_FUND_SELECT, PROF_FUND_FINISH = range(15, 19)
     PROF_GMATCH_FORWARD, PROF_GMATCH_REVERSE, PROF_GMATCH_ACCEPT = range(19, 22)
     PROF_HPOSE = 22
+    PROF_SIM3_SOLVE, PROF_SIM3_SCORE, PROF_SIM3_SELECT, PROF_SIM3_FINISH = range(23, 27)
 
     def profile_enable(self, regions=(0, 1, 2, 3, 4)):
         """regions: iterable of PROF_* ids to time with hipEvent pairs on the ctx stream; () switches timing off"""
@@ -1169,6 +1170,51 @@ class VoContext:
         stats = [dict(cost=s.cost, n_inliers=s.n_inliers, hypotheses=s.hypotheses, best=s.best, status=s.status, n_roots=s.n_roots,
                       models=s.models) for s in st]
         return self._out(F), self._inliers(mask), self._out(stats), self._out(F0)
+
+    def _two_sets(self, src, dst):
+        """-> (src, dst, n): two sets of 3-D points as C-contiguous [batch, n, 3] float32"""
+        a = np.ascontiguousarray(src, np.float32).reshape(self.batch, -1, 3)
+        b = np.ascontiguousarray(dst, np.float32).reshape(self.batch, -1, 3)
+        assert a.shape[1] == b.shape[1]
+        return a, b, a.shape[1]
+
+    def _sim3_stats(self, st):
+        return self._out([dict(cost=s.cost, n_inliers=s.n_inliers, hypotheses=s.hypotheses, best=s.best, status=s.status,
+                               degenerate=s.degenerate, refit=s.refit) for s in st])
+
+    def estimate_sim3(self, src, dst, threshold=3.0, confidence=0.99, max_iters=1000, seed=0, with_scale=True, refit=1):
+        """The similarity (with_scale=False: rigid motion) dst ~ s R src + t between two sets of corresponding 3-D points with outliers
+        (vo_sim3_ransac; the algorithm: tests/sim3_model.py): three-point RANSAC with Umeyama's closed form, cv2.estimateAffine3D's
+        threshold (in dst's units) and confidence.  src, dst (n,3), n >= 3 [leading batch dim if batch > 1]
+        -> s (float; (batch,) if batch > 1), R (3,3), t (3,) -- refit=1: Umeyama over the consensus set, refit=0 or a degenerate set: the
+        winning sample's model; stats['refit'] says which -- inlier indices (ascending, the consensus set of model0), stats dict, model0
+        (13,) = (s, R row-major, t) of the winning sample.  Without a model: stats['status'] != 0, NaN outputs, no inliers."""
+        B = self.batch
+        a, b, n = self._two_sets(src, dst)
+        prm = Sim3Params()
+        self._L.vo_sim3_default_params(C.byref(prm))
+        prm.threshold, prm.confidence, prm.max_iters, prm.seed = threshold, confidence, int(max_iters), int(seed)
+        prm.with_scale, prm.refit = int(with_scale), int(refit)
+        s, R, t, m0 = np.zeros(B), np.zeros((B, 3, 3)), np.zeros((B, 3)), np.zeros((B, 13))
+        mask = np.zeros((B, n), np.uint8)
+        st = (Sim3Stats * B)()
+        self._ck(self._L.vo_sim3_ransac(self._h, ptr(a, C.c_float), ptr(b, C.c_float), n, C.byref(prm), ptr(s, C.c_double), ptr(R, C.c_double),
+                                        ptr(t, C.c_double), ptr(m0, C.c_double), ptr(mask, C.c_uint8), st))
+        return self._out(s), self._out(R), self._out(t), self._inliers(mask), self._sim3_stats(st), self._out(m0)
+
+    def fit_sim3(self, src, dst, mask=None, with_scale=True):
+        """Umeyama's least-squares alignment dst ~ s R src + t over the rows of `mask` ((n,), nonzero = use; None: every row) whose
+        coordinates are finite, without a search (vo_sim3_fit).  On the inliers estimate_sim3 returned it gives that call's (s, R, t) bit
+        for bit.  -> s, R (3,3), t (3,), stats dict [leading batch dim if batch > 1]; fewer than 3 rows or a collinear set:
+        stats['status'] != 0 and NaN outputs."""
+        B = self.batch
+        a, b, n = self._two_sets(src, dst)
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask).reshape(B, n) != 0, np.uint8)
+        s, R, t = np.zeros(B), np.zeros((B, 3, 3)), np.zeros((B, 3))
+        st = (Sim3Stats * B)()
+        self._ck(self._L.vo_sim3_fit(self._h, ptr(a, C.c_float), ptr(b, C.c_float), ptr(m, C.c_uint8), n, int(with_scale), ptr(s, C.c_double),
+                                     ptr(R, C.c_double), ptr(t, C.c_double), st))
+        return self._out(s), self._out(R), self._out(t), self._sim3_stats(st)
 
     def pnp_params(self, reproj_err=2.0, confidence=0.9999, max_iters=1000000, seed=0):
         prm = PnpParams()

@@ -577,6 +577,25 @@ class Extractor:
         F, inliers, st, F0 = self._ctx.find_fundamental(*self._uv_pairs(list_1, list_2), **kw)
         return F, inliers.reshape((-1,)).tolist(), st, F0
 
+    def align_landmarks(self, list_1, list_2, matches=None, **kw):
+        """The similarity between two maps through the landmarks both hold -- what joins a map that bootstrap_pose has started anew, with
+        its own scale and origin, to the old one.  list_1, list_2: lists of Landmark; matches: DMatch es as match_lists returns them
+        (m.queryIdx indexes list_1, m.trainIdx list_2), wrong ones among them allowed; None: the lists are index-aligned.
+        -> (S 4x4 with p_2 ~ S p_1 in homogeneous coordinates, S[:3, :3] = s R; the indices of the inlier pairs -- into `matches`, or into
+        the lists -- as a list; stats dict); keywords as VoContext.estimate_sim3"""
+        if self._ctx is None:
+            raise RuntimeError("align_landmarks needs the device context: track a frame first (or pass ctx=)")
+        if matches is None:
+            pairs = [(i, i) for i in range(min(len(list_1), len(list_2)))]
+        else:
+            pairs = [(m.queryIdx, m.trainIdx) for m in matches]
+        src = np.array([np.asarray(list_1[i].p, np.float64).reshape(3) for i, _ in pairs], np.float32).reshape(-1, 3)
+        dst = np.array([np.asarray(list_2[j].p, np.float64).reshape(3) for _, j in pairs], np.float32).reshape(-1, 3)
+        s, R, t, inliers, st, _ = self._ctx.estimate_sim3(src, dst, **kw)
+        S = np.eye(4)
+        S[:3, :3], S[:3, 3] = s * R, t
+        return S, inliers.reshape((-1,)).tolist(), st
+
     def bootstrap_check(self, K, list_1, list_2, threshold=1.0, max_h_ratio=0.8, seed=0):
         """Is this frame pair fit for the 2D-2D bootstrap?  One essential_ransac and one find_homography call at the same pixel threshold;
         -> dict e_inliers, h_inliers, h_ratio = h_inliers / max(e_inliers, 1), degenerate = h_ratio > max_h_ratio (COLMAP's
