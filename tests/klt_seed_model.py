@@ -36,9 +36,38 @@ def predict(uv, prev):
     return g
 
 
-def klt_np(im0, im1, p0, init=None, win=31, max_level=3, max_count=30, eps=0.03, min_eig_thr=1e-4):
-    """-> p1 (n, 2) f32, status (n,) u8, err (n,) f32, iters (n, max_level + 1) i32 (-1 = level skipped)"""
+MUTANTS = ("int32_sums", "int32_combine", "thr_le", "half_up", "unclamped")
+
+
+def _wrap32(v):
+    return ((int(v) + (1 << 31)) & 0xFFFFFFFF) - (1 << 31)
+
+
+def klt_np(im0, im1, p0, init=None, win=31, max_level=3, max_count=30, eps=0.03, min_eig_thr=1e-4, trace=None, mutant=None):
+    """-> p1 (n, 2) f32, status (n,) u8, err (n,) f32, iters (n, max_level + 1) i32 (-1 = level skipped)
+    The criteria are clamped as calcOpticalFlowPyrLK clamps them: max_count to [0, 100], eps to [0, 10].
+    trace: a list that receives one dict per (point, level) whose template was formed: pt, level, min_eig (float32), Iw (the interpolated
+    template, 5 fractional bits), gx, gy (the interpolated derivatives) and diffs (the difference window of every LK iteration), all int64
+    win x win arrays -- what tests/range_cases.py sums lane by lane.  It changes no result.
+    mutant: one of MUTANTS, a deliberately WRONG variant for tests/test_range_cases.py to catch:
+      int32_sums     the window sums are accumulated in wrapping int32
+      int32_combine  the sums are exact as 16-bit halves, but hi * 65536 + lo is formed in wrapping int32 (no float64 branch)
+      thr_le         minEig <= threshold rejects
+      half_up        the bilinear weights round half up instead of half to even
+      unclamped      max_count and eps are used as given"""
     F = np.float32
+    assert mutant is None or mutant in MUTANTS
+    if mutant != "unclamped":
+        max_count = min(max(int(max_count), 0), 100)
+        eps = min(max(float(eps), 0.0), 10.0)
+
+    def isum(x):                                   # the window sum that becomes a float
+        v = int(x.sum())
+        if mutant == "int32_sums":
+            return _wrap32(v)
+        if mutant == "int32_combine":
+            return _wrap32((v >> 16) * 65536 + (v & 0xFFFF))
+        return v
     p0 = np.asarray(p0, np.float32).reshape(-1, 2)
     lv0, lv1 = [im0], [im1]
     while len(lv0) <= max_level:
@@ -64,10 +93,12 @@ def klt_np(im0, im1, p0, init=None, win=31, max_level=3, max_count=30, eps=0.03,
     iters = np.full((n, max_level + 1), -1, np.int32)
     half, scale20, eps2 = F((win - 1) * 0.5), F(1.0 / (1 << 20)), float(eps) * float(eps)
 
+    rnd = (lambda x: np.floor(x + F(0.5))) if mutant == "half_up" else np.rint
+
     def weights(a, b):
-        w00 = int(np.rint((F(1) - a) * (F(1) - b) * F(1 << 14)))
-        w01 = int(np.rint(a * (F(1) - b) * F(1 << 14)))
-        w10 = int(np.rint((F(1) - a) * b * F(1 << 14)))
+        w00 = int(rnd((F(1) - a) * (F(1) - b) * F(1 << 14)))
+        w01 = int(rnd(a * (F(1) - b) * F(1 << 14)))
+        w10 = int(rnd((F(1) - a) * b * F(1 << 14)))
         return w00, w01, w10, (1 << 14) - w00 - w01 - w10
 
     def sample(P, wts, shift):                     # P: (win + 1, win + 1[, c]) int64
@@ -100,10 +131,15 @@ def klt_np(im0, im1, p0, init=None, win=31, max_level=3, max_count=30, eps=0.03,
             Iw = sample(window(I[level], ipx, ipy), wts, 14 - 5)
             dI = sample(window(D[level], ipx, ipy), wts, 14)
             gx, gy = dI[..., 0], dI[..., 1]
-            A11, A12, A22 = F(int((gx * gx).sum())) * scale20, F(int((gx * gy).sum())) * scale20, F(int((gy * gy).sum())) * scale20
+            A11, A12, A22 = F(isum(gx * gx)) * scale20, F(isum(gx * gy)) * scale20, F(isum(gy * gy)) * scale20
             det = A11 * A22 - A12 * A12
             min_eig = (A22 + A11 - np.sqrt((A11 - A22) * (A11 - A22) + F(4) * A12 * A12)) / F(2 * win * win)
-            if min_eig < F(min_eig_thr) or det < F(1.1920929e-07):
+            rec = None
+            if trace is not None:
+                rec = dict(pt=pt, level=level, min_eig=min_eig, Iw=Iw, gx=gx, gy=gy, diffs=[])
+                trace.append(rec)
+            low = (min_eig <= F(min_eig_thr)) if mutant == "thr_le" else (min_eig < F(min_eig_thr))
+            if low or det < F(1.1920929e-07):
                 if level == 0:
                     status[pt] = 0
                 continue
@@ -118,7 +154,9 @@ def klt_np(im0, im1, p0, init=None, win=31, max_level=3, max_count=30, eps=0.03,
                         status[pt] = 0
                     break
                 diff = sample(window(J[level], inx, iny), weights(nextx - F(inx), nexty - F(iny)), 14 - 5) - Iw
-                b1, b2 = F(int((diff * gx).sum())) * scale20, F(int((diff * gy).sum())) * scale20
+                if rec is not None:
+                    rec["diffs"].append(diff)
+                b1, b2 = F(isum(diff * gx)) * scale20, F(isum(diff * gy)) * scale20
                 dx = (A12 * b2 - A22 * b1) * det
                 dy = (A12 * b1 - A11 * b2) * det
                 nextx, nexty = nextx + dx, nexty + dy
@@ -140,5 +178,5 @@ def klt_np(im0, im1, p0, init=None, win=31, max_level=3, max_count=30, eps=0.03,
                     status[pt] = 0
                     continue
                 diff = sample(window(J[level], inx, iny), weights(nx - F(inx), ny - F(iny)), 14 - 5) - Iw
-                err[pt] = F(int(np.abs(diff).sum())) * F(1) / F(32 * win * win)
+                err[pt] = F(isum(np.abs(diff))) * F(1) / F(32 * win * win)
     return p1, status, err, iters
