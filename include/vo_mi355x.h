@@ -1138,7 +1138,8 @@ typedef struct {
   int32_t gate_groups;         /* stream layout 2: LM launch groups of frame t ahead of the tracker launch of frame t + 1; -1: none */
   int32_t reserve_cus;         /* stream layout 2: compute units the front-end stream leaves free; -1: none */
   int32_t gather_workgroups;   /* frames from the host: workgroups of k_gather_frames (rule: 2 per image in the gated layout of a batch, else 32) */
-  int32_t reserved[13];
+  int32_t klt_reuse;           /* plain tracker, read per launch: 1 = k_klt_track_r (keeps the target window while LK stays in one pixel cell; same bits), -1 = k_klt_track; 0: the rule (k_klt_track_r, unless klt_waves or klt_pair name k_klt_track) */
+  int32_t reserved[12];
 } vo_tuning;
 int32_t vo_get_tuning(vo_ctx* ctx, vo_tuning* out);
 int32_t vo_set_tuning(vo_ctx* ctx, const vo_tuning* t);

@@ -1,13 +1,15 @@
 #!/bin/bash
 # Per-kernel time of the default batch (256 sequences, one context) without cross-stream overlap (rocprofv3 --kernel-trace --stats):
 #   tools/kstats256.sh [tag]      -> gpurun_out/<tag>_kstats256.txt
+# a second argument holds more bench arguments, e.g. tools/kstats256.sh reuse "--tune klt_reuse=1"
 TAG=${1:-k}
+MORE=${2:-}
 OUT=$PWD/gpurun_out
 export TMPDIR=/tmp
 BENCH="$PWD/bench.py"
 cd /tmp
 rm -rf $OUT/${TAG}_ks256
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_ks256 -o ks -- python3 $BENCH --full --steps 20 --warmup 5 --regions 1 --no-extras --seqs 256 --ctxs 1 --host-threads 1 --side-stream off --no-cpu-baseline > $OUT/${TAG}_ks256.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_ks256 -o ks -- python3 $BENCH --full --steps 20 --warmup 5 --regions 1 --no-extras --seqs 256 --ctxs 1 --host-threads 1 --side-stream off --no-cpu-baseline $MORE > $OUT/${TAG}_ks256.log 2>&1
 cd - > /dev/null
 python3 - <<PY > $OUT/${TAG}_kstats256.txt
 import csv, glob

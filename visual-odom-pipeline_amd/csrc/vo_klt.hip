@@ -357,8 +357,13 @@ int32_t vo_klt_make_args(vo_ctx* c, int n, const vo_klt_params* prm, klt_args& A
   return VO_OK;
 }
 
-// k_klt_track on L.q; the only form with a choice of instantiation (vo_tuning.klt_waves), the experiment's pair kernel and the diagnostic stamps
+// The plain form on L.q; the only form with a choice of kernel -- k_klt_track_r (vo_klt_reuse.hip; vo_tuning.klt_reuse, read per launch: 1 forces it,
+// -1 forces k_klt_track, 0 is the rule KLT_REUSE_RULE) -- and, for k_klt_track, of instantiation (vo_tuning.klt_waves), the experiment's pair kernel
+// and the diagnostic stamps.  A forced klt_waves or klt_pair names k_klt_track and is not overruled by the rule
+#define KLT_REUSE_RULE 1      // +3.0 % frames/s in the interleaved A/B, tracker launch 3042 -> 2830 us (profiles/klt_reuse_ab.txt, klt_reuse_kstats.txt)
 static void klt_launch_plain(vo_ctx* c, const klt_launch_rows& L, const klt_args& A) {
+  const bool rule = KLT_REUSE_RULE && c->tune.klt_waves == 0 && c->tune.klt_pair == 0;
+  if (c->tune.klt_reuse > 0 || (c->tune.klt_reuse == 0 && rule)) { vo_klt_launch_reuse(c, L, A); return; }
   const int waves = c->tune.klt_waves > 0 ? c->tune.klt_waves : 6;
 #define VO_KLT_LAUNCH(WV) hipLaunchKernelGGL(k_klt_track<WV>, dim3(L.n, c->batch), dim3(64), 0, L.q, A, L.p0, L.p1, L.status, L.err, c->d_iters, c->d_dbg, L.counts)
 #ifdef VO_EXPERIMENTS

@@ -1,9 +1,11 @@
 // Lucas-Kanade pieces shared by the tracker kernels: the argument blocks, the cross-lane sums and the packed bilinear / derivative taps
-// (vo_klt.hip: k_klt_track; vo_klt_fb.hip: k_klt_track_fb; vo_klt_seed.hip: their seeded forms) and, built from them, the per-point LK body
+// (vo_klt.hip: k_klt_track; vo_klt_fb.hip: k_klt_track_fb; vo_klt_seed.hip: their seeded forms; vo_klt_reuse.hip: k_klt_track_r) and, built from them, the per-point LK body
 // klt_lk_point that all of them call.
 // All of it is inlined into the kernels.  At the end, the host side the three units share: the one launch path and the row copies.
 #pragma once
 #include "vo_internal.h"
+
+#include <limits.h>
 
 #define W_BITS 14
 
@@ -199,6 +201,49 @@ __device__ __forceinline__ uint32_t sample2(uint32_t T, uint32_t B, uint32_t wt,
   const u16x2 h = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm((uint32_t)s1, (uint32_t)s0, 0x06050201u));
   return __builtin_bit_cast(uint32_t, h >> (unsigned short)(W_BITS - 5 - 8));
 }
+// sample2 in two parts, sample2(T, B, ..) == sample2_combine(sample2_gather(T), sample2_gather(B), ..): the gather widens a row dword to its two
+// byte pairs (it depends on the row alone), the combine weighs the pairs of the top and the bottom row.  klt_lk_point<.., REUSE = true> keeps the
+// gathered rows while the window stays in one pixel cell.  sample2 itself is not written as that call: the order of the four gathers in the
+// source decides the instruction order of the pinned kernels (tests/test_klt_fb_build.py), and their device code is to stay what it is.
+__device__ __forceinline__ uint2 sample2_gather(uint32_t T) { return make_uint2(bytes01(T), bytes12(T)); }
+__device__ __forceinline__ uint32_t sample2_combine(uint2 t, uint2 b, uint32_t wt, uint32_t wb) {
+  const int s0 = dot2(b.x, wb, dot2k(t.x, wt, 1 << (W_BITS - 5 - 1)));
+  const int s1 = dot2(b.y, wb, dot2k(t.y, wt, 1 << (W_BITS - 5 - 1)));
+  typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+  const u16x2 h = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm((uint32_t)s1, (uint32_t)s0, 0x06050201u));
+  return __builtin_bit_cast(uint32_t, h >> (unsigned short)(W_BITS - 5 - 8));
+}
+
+// ---- REUSE: the gathered rows of the target window, parked in LDS for as long as the window origin stays in one pixel cell ----
+// Row k (0..8: the eight rows a lane loads and the one it takes from the lane 16 further up) of lane l is the pair (bytes01, bytes12) at
+// rows[k * 64 + l]: one ds_write_b64 / ds_read_b64 per row at an immediate offset from ONE per-lane address, consecutive lanes on consecutive
+// bank pairs.  4608 bytes per one-wave workgroup; a lane reads only what it wrote itself, so there is no barrier.
+__device__ __forceinline__ char* klt_rows_lds() {
+  __shared__ uint2 rows[9 * 64];
+  return reinterpret_cast<char*>(rows);
+}
+__device__ __forceinline__ uint2 klt_row_read(const char* rows, uint32_t ab, int k) {
+  return *reinterpret_cast<const uint2*>(rows + ab + (uint32_t)k * 512u);
+}
+// what every sampling of klt_lk_point did: eight dword loads, the ninth row from the neighbour lane, the byte gathers -- here into LDS.
+// uo: the window origin's pixel offset (wave-uniform)
+__device__ __forceinline__ void klt_rows_fetch(char* rows, uint32_t ab, __amdgpu_buffer_rsrc_t rJ, uint32_t lane_off, uint32_t uo, uint32_t pitch, int lane) {
+  uint32_t Tj[8];
+#pragma unroll
+  for (int s = 0; s < 8; s++) Tj[s] = __builtin_amdgcn_raw_buffer_load_b32(rJ, (int)lane_off, (int)(uo + (uint32_t)s * pitch), 0);
+  const uint32_t Tj8 = row_next(Tj[0], lane);
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+    *reinterpret_cast<uint2*>(rows + ab + (uint32_t)k * 512u) = sample2_gather(k < 8 ? Tj[k & 7] : Tj8);
+  }
+}
+// The step loops of a REUSE sampling walk the parked rows two reads ahead of the step that needs them: rows s and s + 1 in registers, row s + 2
+// in flight.  Left to itself the compiler issues all nine reads at the head of the loop and the 18 registers they occupy push the 6-wave
+// instance into scratch; the empty asm ties the address of the next read to a sum of the step before it (vo_ba_wave.h pins an order the same way).
+#define KLT_ROWS_PIN(ab, acc) asm volatile("" : "+v"(ab), "+v"(acc))
+// after a fetch the reads go through an address the compiler cannot match with the writes: forwarding the fetched registers past the branch
+// splits the 64-bit reads and adds a branch and copies to every sampling
+#define KLT_ROWS_OPAQUE(v) asm volatile("" : "+v"(v))
 
 // interpolated derivative of one pixel, times 2^16: top pair / bottom pair already gathered as (left | right << 16).  The
 // derivative image holds 4 x Scharr (vo_frame.hip), so the sum is 4 (s + 2^13) and the value OpenCV keeps, (s + 2^13) >> 14, is its
@@ -230,8 +275,12 @@ __device__ __forceinline__ uint32_t deriv1(uint32_t top, uint32_t bot, uint32_t 
 // SEEDED (OpenCV's OPTFLOW_USE_INITIAL_FLOW; vo_klt_seed.hip): the top level starts at the guess (gx, gy) (wave-uniform, finite: the callers
 // replace a non-finite guess by p0) scaled like p0 instead of at p0 itself; nothing else changes, so (gx, gy) = (p0x, p0y) gives the unseeded
 // bits.  The unseeded instantiation does not see the two values.
+// REUSE (vo_klt_reuse.hip): inside one level -- its LK loop and, on level 0, the error pass behind it -- the gathered rows of the target window
+// stay in LDS together with the integer cell (inx, iny) they were fetched for.  The first sampling of a level fetches; a later one fetches only
+// if its cell differs (wave-uniform, compared on the scalar unit), else only the four weights are new.  Nothing carries over to the next level.
+// The same bytes go through the same integer sums: the bits of REUSE = false, whose code is textually what it was.
 // ------------------------------------------------------------------------------------------------
-template <bool SEEDED = false>
+template <bool SEEDED = false, bool REUSE = false>
 __device__ __forceinline__ void klt_lk_point(const klt_args& A, const klt_level_args (&lv)[VO_MAX_LEVELS], int bseq, int pt, int lane,
                                              float p0x, float p0y, int32_t* iters, unsigned long long* dbgk,
                                              float& outx, float& outy, int& st, float& errv, float gx = 0.f, float gy = 0.f) {
@@ -250,6 +299,9 @@ __device__ __forceinline__ void klt_lk_point(const klt_args& A, const klt_level_
   const uint32_t colones = colmask & 0x00010001u;
   // v_perm selector "upper halves of (a, b)" with the constant-zero code 0x0c for the columns outside the window
   const uint32_t colsel = (0x07060302u & colmask) | (0x0c0c0c0cu & ~colmask);
+  char* rows = nullptr;             // REUSE: the parked rows and the lane's byte address in them
+  uint32_t rows_ab = 0;
+  if constexpr (REUSE) { rows = klt_rows_lds(); rows_ab = (uint32_t)lane * 8u; }
 
   for (int level = A.top; level >= 0; level--) {
     klt_level_args L = lv[level];
@@ -337,6 +389,9 @@ __device__ __forceinline__ void klt_lk_point(const klt_args& A, const klt_level_
       nextx -= half; nexty -= half;
       const __amdgpu_buffer_rsrc_t rJ = klt_rsrc(L.imgJ);
       float pdx = 0.f, pdy = 0.f;
+      // REUSE: the cell the parked rows were fetched for.  Nothing is parked when a level starts (no window origin is INT_MIN), so the first
+      // sampling of a level always fetches: cell numbers can coincide across levels while the images differ
+      int cellx = INT_MIN, celly = INT_MIN;
       int j = 0;
       for (; j < A.max_count; j++) {
         const float fnx = floorf(nextx), fny = floorf(nexty);
@@ -347,18 +402,39 @@ __device__ __forceinline__ void klt_lk_point(const klt_args& A, const klt_level_
         }
         uint32_t jt, jb;
         lk_weights(nextx - fnx, nexty - fny, jt, jb);
-        uint32_t Tj[8];
-        const uint32_t uj = (uint32_t)(iny + VO_PAD) * (uint32_t)L.pitch + (uint32_t)(inx + VO_PAD);
-#pragma unroll
-        for (int s = 0; s < 8; s++) Tj[s] = __builtin_amdgcn_raw_buffer_load_b32(rJ, (int)lane_off, (int)(uj + (uint32_t)s * (uint32_t)L.pitch), 0);
-        const uint32_t Tj8 = row_next(Tj[0], lane);
         int b1 = 0, b2 = 0;
+        if constexpr (REUSE) {
+          // the cell is wave-uniform: compared on the scalar unit, a branch without exec masking
+          const int ux = __builtin_amdgcn_readfirstlane(inx), uy = __builtin_amdgcn_readfirstlane(iny);
+          if (ux != cellx || uy != celly) {
+            klt_rows_fetch(rows, rows_ab, rJ, lane_off, (uint32_t)(uy + VO_PAD) * (uint32_t)L.pitch + (uint32_t)(ux + VO_PAD), (uint32_t)L.pitch, lane);
+            cellx = ux; celly = uy;
+          }
+          KLT_ROWS_OPAQUE(rows_ab);
+          uint2 r0 = klt_row_read(rows, rows_ab, 0), r1 = klt_row_read(rows, rows_ab, 1);
 #pragma unroll
-        for (int s = 0; s < 8; s++) {
-          const uint32_t B = (s < 7) ? Tj[(s + 1) & 7] : Tj8;
-          const uint32_t d = pk_sub(sample2(Tj[s], B, jt, jb), tI[s]);   // (diff0 | diff1 << 16), |diff| <= 8160
-          b1 = s ? dot2(d, tX[s], b1) : dot2k(d, tX[0], 0);
-          b2 = s ? dot2(d, tY[s], b2) : dot2k(d, tY[0], 0);
+          for (int s = 0; s < 8; s++) {
+            uint2 r2 = r1;
+            if (s < 7) r2 = klt_row_read(rows, rows_ab, s + 2);
+            const uint32_t d = pk_sub(sample2_combine(r0, r1, jt, jb), tI[s]);
+            b1 = s ? dot2(d, tX[s], b1) : dot2k(d, tX[0], 0);
+            b2 = s ? dot2(d, tY[s], b2) : dot2k(d, tY[0], 0);
+            if (s < 6) KLT_ROWS_PIN(rows_ab, b1);
+            r0 = r1; r1 = r2;
+          }
+        } else {
+          uint32_t Tj[8];
+          const uint32_t uj = (uint32_t)(iny + VO_PAD) * (uint32_t)L.pitch + (uint32_t)(inx + VO_PAD);
+#pragma unroll
+          for (int s = 0; s < 8; s++) Tj[s] = __builtin_amdgcn_raw_buffer_load_b32(rJ, (int)lane_off, (int)(uj + (uint32_t)s * (uint32_t)L.pitch), 0);
+          const uint32_t Tj8 = row_next(Tj[0], lane);
+#pragma unroll
+          for (int s = 0; s < 8; s++) {
+            const uint32_t B = (s < 7) ? Tj[(s + 1) & 7] : Tj8;
+            const uint32_t d = pk_sub(sample2(Tj[s], B, jt, jb), tI[s]);   // (diff0 | diff1 << 16), |diff| <= 8160
+            b1 = s ? dot2(d, tX[s], b1) : dot2k(d, tX[0], 0);
+            b2 = s ? dot2(d, tY[s], b2) : dot2k(d, tY[0], 0);
+          }
         }
         // per lane 16 products |diff| <= 8160 (255 << 5) times |derivative| <= 4080: < 2^28.99, a quad's sum < 2^30.99
         int l1, h1, l2, h2;
@@ -400,18 +476,41 @@ __device__ __forceinline__ void klt_lk_point(const klt_args& A, const klt_level_
         } else {
           uint32_t jt, jb;
           lk_weights(nx - fnx, ny - fny, jt, jb);
-          uint32_t Tj[8];
-          const uint32_t uj = (uint32_t)(iny + VO_PAD) * (uint32_t)L.pitch + (uint32_t)(inx + VO_PAD);
-#pragma unroll
-          for (int s = 0; s < 8; s++) Tj[s] = __builtin_amdgcn_raw_buffer_load_b32(rJ, (int)lane_off, (int)(uj + (uint32_t)s * (uint32_t)L.pitch), 0);
-          const uint32_t Tj8 = row_next(Tj[0], lane);
           int e = 0;
+          if constexpr (REUSE) {
+            // the rows of the last iteration serve when the result lies in its cell; with max_count == 0 nothing is parked and this fetches
+            const int ux = __builtin_amdgcn_readfirstlane(inx), uy = __builtin_amdgcn_readfirstlane(iny);
+            if (ux != cellx || uy != celly)
+              klt_rows_fetch(rows, rows_ab, rJ, lane_off, (uint32_t)(uy + VO_PAD) * (uint32_t)L.pitch + (uint32_t)(ux + VO_PAD), (uint32_t)L.pitch, lane);
+            KLT_ROWS_OPAQUE(rows_ab);
+            // the row masks are made here, once per keypoint: as eight loop invariants of the level loop they cost the 6-wave instance three
+            // registers it does not have
+            uint32_t cones = colones;
+            KLT_ROWS_OPAQUE(cones);
+            uint2 r0 = klt_row_read(rows, rows_ab, 0), r1 = klt_row_read(rows, rows_ab, 1);
 #pragma unroll
-          for (int s = 0; s < 8; s++) {
-            const uint32_t B = (s < 7) ? Tj[(s + 1) & 7] : Tj8;
-            const uint32_t d = pk_abs(pk_sub(sample2(Tj[s], B, jt, jb), tI[s]));
-            const uint32_t ones = (8 * r + s < win) ? colones : 0u;
-            e = s ? dot2(d, ones, e) : dot2k(d, ones, 0);
+            for (int s = 0; s < 8; s++) {
+              uint2 r2 = r1;
+              if (s < 7) r2 = klt_row_read(rows, rows_ab, s + 2);
+              const uint32_t d = pk_abs(pk_sub(sample2_combine(r0, r1, jt, jb), tI[s]));
+              const uint32_t ones = (8 * r + s < win) ? cones : 0u;
+              e = s ? dot2(d, ones, e) : dot2k(d, ones, 0);
+              if (s < 6) KLT_ROWS_PIN(rows_ab, e);
+              r0 = r1; r1 = r2;
+            }
+          } else {
+            uint32_t Tj[8];
+            const uint32_t uj = (uint32_t)(iny + VO_PAD) * (uint32_t)L.pitch + (uint32_t)(inx + VO_PAD);
+#pragma unroll
+            for (int s = 0; s < 8; s++) Tj[s] = __builtin_amdgcn_raw_buffer_load_b32(rJ, (int)lane_off, (int)(uj + (uint32_t)s * (uint32_t)L.pitch), 0);
+            const uint32_t Tj8 = row_next(Tj[0], lane);
+#pragma unroll
+            for (int s = 0; s < 8; s++) {
+              const uint32_t B = (s < 7) ? Tj[(s + 1) & 7] : Tj8;
+              const uint32_t d = pk_abs(pk_sub(sample2(Tj[s], B, jt, jb), tI[s]));
+              const uint32_t ones = (8 * r + s < win) ? colones : 0u;
+              e = s ? dot2(d, ones, e) : dot2k(d, ones, 0);
+            }
           }
           const int ierr = wave_sum_i32(e);
           errv = (float)ierr * 1.f / (float)(32 * win * win);
@@ -444,6 +543,7 @@ struct klt_launch_rows {
 };
 void vo_klt_launch_fb(vo_ctx* c, const klt_launch_rows& L, const klt_args& A, const klt_fb_args& F);            // vo_klt_fb.hip: k_klt_track_fb
 void vo_klt_launch_seeded(vo_ctx* c, const klt_launch_rows& L, const klt_args& A, const klt_fb_args* F);        // vo_klt_seed.hip: F null = k_klt_seeded, else k_klt_seeded_fb
+void vo_klt_launch_reuse(vo_ctx* c, const klt_launch_rows& L, const klt_args& A);                               // vo_klt_reuse.hip: k_klt_track_r
 
 // the iteration table of the last launch: n points x `levels` entries per sequence
 inline hipError_t iters_d2h(vo_ctx* c, int32_t* h, int n, int levels) {

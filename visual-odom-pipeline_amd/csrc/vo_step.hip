@@ -550,7 +550,8 @@ extern "C" int32_t vo_set_tuning(vo_ctx* c, const vo_tuning* t) {
   VO_CHECK(c, t->klt_pair == 0 || (t->klt_pair >= 3 && t->klt_pair <= 5), VO_E_INVALID, "klt_pair: 3, 4 or 5");
 #endif
   VO_CHECK(c, t->gather_workgroups >= 0 && t->gather_workgroups <= 65536, VO_E_INVALID, "gather_workgroups out of range");
-  for (int k = 0; k < 13; k++) VO_CHECK(c, t->reserved[k] == 0, VO_E_INVALID, "reserved fields must be 0");
+  VO_CHECK(c, t->klt_reuse >= -1 && t->klt_reuse <= 1, VO_E_INVALID, "klt_reuse: -1, 0 or 1");
+  for (int k = 0; k < 12; k++) VO_CHECK(c, t->reserved[k] == 0, VO_E_INVALID, "reserved fields must be 0");
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   c->tune = *t;

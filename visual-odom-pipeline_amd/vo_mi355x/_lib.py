@@ -66,12 +66,12 @@ class BaParams(C.Structure):
 
 TUNING_FIELDS = ("ba_kernels", "ba_lanes", "ba_threads", "ba_pitch_pad", "ba_chunks", "ba_workgroups", "ba_workgroup_cap", "ba_fold", "klt_waves", "klt_pair",
                  "st_two_kernels", "st_band_rows", "st_separate_nms", "st_keep_eig", "st_host_limit", "xcd_remap_off", "gate_groups", "reserve_cus",
-                 "gather_workgroups")
+                 "gather_workgroups", "klt_reuse")
 
 
 class Tuning(C.Structure):
     """vo_tuning: forced forms for parity tests and A/B measurements; 0 = the library's rule"""
-    _fields_ = [(k, C.c_int32) for k in TUNING_FIELDS] + [("reserved", C.c_int32 * 13)]
+    _fields_ = [(k, C.c_int32) for k in TUNING_FIELDS] + [("reserved", C.c_int32 * 12)]
 
 
 class PnpParams(C.Structure):
