@@ -817,6 +817,62 @@ int32_t vo_sim3_ransac(vo_ctx* ctx, const float* src, const float* dst, int32_t 
 int32_t vo_sim3_fit(vo_ctx* ctx, const float* src, const float* dst, const uint8_t* mask, int32_t n, int32_t with_scale,
                     double* scale, double* R, double* t, vo_sim3_stats* stats);
 
+/* ---- sparse direct image alignment: the frame's pose BEFORE any feature is tracked ---------------
+ * The reference has a pose for a new frame only after KLT and cv2.solvePnPRansac (extractor.py:182-186), so its tracker starts every
+ * point where it was.  vo_sparse_align gives the 6-DoF pose of the CURRENT frame of the store against the PREVIOUS one directly from the
+ * two pyramids and n 3-D points given in the previous camera's coordinates -- the first stage of semi-direct VO (Forster et al., SVO,
+ * ICRA 2014, IV-A): 4 x 4 patches around the projected points, photometric error, inverse-compositional Gauss-Newton with Huber
+ * weights, coarse to fine.  Projecting the points with it yields start positions for vo_klt_track_init, also for tracks born one frame
+ * earlier, and a pose when tracking collapses.  The algorithm is defined by tests/align_model.py, in short:
+ *   level l (max_level down to min_level)   f_l = f / 2^l, c_l = c / 2^l (the tracker's p_l = p / (1 << l)); bilinear samples
+ *             top = I00 + a (I01 - I00), bot likewise, I = top + b (bot - top) in float32; interior: 4 <= x < w_l - 5, 4 <= y < h_l - 5
+ *   reference u = pi_l(X); usable: X finite, X.z > 0, u in the interior; patch offsets {-2, -1, 0, 1}^2; gradient by central
+ *             differences of the same bilinear samples; J_p = dpi_l/dX [I | -[X]x] of the patch centre; xi = (translation, rotation)
+ *   iteration Y = R X + t, v = pi_l(Y); used: usable, Y.z > 0, v in the interior; r = I_cur(v + o) - I_prev(u + o); weight 1 where
+ *             |r| <= huber, else huber / |r| (huber = 0: off); H = sum w J J^T, b = sum w J r, chi = sum w r^2 / (16 n_used) with
+ *             J = gx J_p[0] + gy J_p[1]; fewer than min_points used in a level's first iteration: the level is skipped (iters -1);
+ *             later, or chi > chi_prev: the previous pose is restored and the level ends; H xi = b by Cholesky (a pivot that is not
+ *             positive ends the level, pose kept); T <- T E(xi)^-1 with E = (Rodrigues(omega), v); max(|omega_i|, |v_i| / zbar) < eps
+ *             ends the level (zbar: mean depth of the points used in the level's first iteration -- free of the monocular scale)
+ * The per-pixel arithmetic is float32, the 16-pixel sums of a point are float32 in a fixed order, everything from there on float64 in
+ * a fixed order: a result does not depend on the batch position or on the call.  Against the model the kernel is held to 4 x what
+ * the model's own float32 switch moves the pose (tests/test_gpu_align.py).  The basin is about the patch half-width times 2^max_level
+ * pixels of image motion: with two levels a 10-pixel motion is outside it.
+ * One workgroup per sequence runs a level in one launch on the front-end stream; the call is synchronous like vo_klt_track.
+ * K [batch][9] row-major (fx, fy, cx, cy are read); pts3d [batch][n][3] f32 (a NaN row or a row with z <= 0 is never used);
+ * rvec0 / tvec0 [batch][3] the initial pose, both NULL = identity; rvec / tvec [batch][3] with x_cur = R(rvec) x_prev + tvec, as
+ * vo_pnp_ransac; used_mask [batch][n] u8: the points used in the last kept linearisation of the finest level that ran; stats [batch];
+ * rvec, tvec, used_mask and stats may be NULL.  No level ran: stats.status = VO_E_NUMERIC, the pose is the initial one, an empty mask;
+ * the call returns VO_OK.
+ * Errors, nothing enqueued: fewer than two frames pushed or a step in flight: VO_E_STATE; n > max_pts: VO_E_CAPACITY; VO_E_INVALID for
+ * n < 0, a NULL K or pts3d, a level outside the store (max_level = -1: its top level), min_level > max_level, max_iters < 1,
+ * min_points < 1, a NaN or negative huber or eps, form outside 0..2, and exactly one of rvec0 / tvec0 NULL.
+ * The two structures have no hidden padding: 32 and 56 bytes. */
+typedef struct {
+  int32_t max_level;         /* -1: the store's top level */
+  int32_t min_level;         /* 0 */
+  int32_t max_iters;         /* 10, per level */
+  int32_t min_points;        /* 10 */
+  float   huber;             /* 10 grey levels; 0: no weighting */
+  float   eps;               /* 1e-5 */
+  int32_t form;              /* 0: the rule; 1: reference patches and gradients kept in a workspace; 2: recomputed every iteration.  Same bits */
+  int32_t reserved;          /* 0 */
+} vo_align_params;
+
+enum { VO_ALIGN_END_EPS = 1, VO_ALIGN_END_MAX_ITERS = 2, VO_ALIGN_END_CHI = 3, VO_ALIGN_END_PIVOT = 4, VO_ALIGN_END_POINTS = 5 };
+typedef struct {
+  int32_t status;            /* 0, or VO_E_NUMERIC when no level ran */
+  int32_t n_used;            /* points used in the last kept linearisation of the finest level that ran */
+  int32_t levels_run;
+  int32_t flags;             /* how the finest level that ran ended: VO_ALIGN_END_* */
+  int32_t iters[8];          /* linearisations per level; -1: skipped; 0: not asked for */
+  float   chi2;              /* chi of that linearisation: mean weighted squared residual, grey levels squared */
+  float   zbar;              /* mean depth of the points used in that level's first iteration */
+} vo_align_stats;
+int32_t vo_align_default_params(vo_align_params* p);
+int32_t vo_sparse_align(vo_ctx* ctx, const double* K, const float* pts3d, int32_t n, const double* rvec0, const double* tvec0,
+                        const vo_align_params* prm, double* rvec, double* tvec, uint8_t* used_mask, vo_align_stats* stats);
+
 /* ---- SIFT features (SURVEY.md 8f "next" row 4, feature part) -----------------------------------
  * Replaces cv2.SIFT_create(nfeatures=1000).detect(img, mask) + .compute(img, kps) in
  * Extractor.extract(detector='custom', describe=True) (src/extractor/extractor.py:26-28, 114-122; the two bootstrap
@@ -1206,14 +1262,15 @@ int32_t vo_step_layout(vo_ctx* ctx, int32_t* layout, int32_t* gate_groups, int32
  * vo_match_guided_hamming / vo_match_guided_l2 (tools/guided_match_timing.py).
  * VO_PROF_HPOSE brackets the k_hpose launch of vo_homography_decompose and vo_homography_pose (tools/hpose_timing.py).
  * VO_PROF_SIM3_SOLVE / _SCORE / _SELECT / _FINISH bracket the k_s3_solve / k_s3_score / k_s3_select launch of every round of
- * vo_sim3_ransac and the k_s3_finish launch of vo_sim3_ransac and vo_sim3_fit (tools/sim3_timing.py). */
+ * vo_sim3_ransac and the k_s3_finish launch of vo_sim3_ransac and vo_sim3_fit (tools/sim3_timing.py).
+ * VO_PROF_ALIGN brackets each k_align_level launch of vo_sparse_align, one per level (tools/align_timing.py). */
 enum { VO_PROF_FRAME = 0, VO_PROF_KLT = 1, VO_PROF_ST = 2, VO_PROF_DLT = 3, VO_PROF_BA = 4, VO_PROF_CLAHE_LUT = 5, VO_PROF_CLAHE_APPLY = 6,
        VO_PROF_HOM_SOLVE = 7, VO_PROF_HOM_SCORE = 8, VO_PROF_HOM_SELECT = 9, VO_PROF_HOM_FINISH = 10, VO_PROF_ORB_PYRAMID = 11,
        VO_PROF_ORB_CANDIDATES = 12, VO_PROF_ORB_RETAIN = 13, VO_PROF_ORB_DESCRIBE = 14,
        VO_PROF_FUND_SOLVE = 15, VO_PROF_FUND_SCORE = 16, VO_PROF_FUND_SELECT = 17, VO_PROF_FUND_FINISH = 18,
        VO_PROF_GMATCH_FORWARD = 19, VO_PROF_GMATCH_REVERSE = 20, VO_PROF_GMATCH_ACCEPT = 21, VO_PROF_HPOSE = 22,
        VO_PROF_SIM3_SOLVE = 23, VO_PROF_SIM3_SCORE = 24, VO_PROF_SIM3_SELECT = 25, VO_PROF_SIM3_FINISH = 26,
-       VO_PROF_COUNT = 27 };
+       VO_PROF_ALIGN = 27, VO_PROF_COUNT = 28 };
 int32_t vo_profile_enable(vo_ctx* ctx, int32_t region_mask);
 int32_t vo_profile_read(vo_ctx* ctx, int32_t region, double* total_ms, int32_t* count);
 /* diagnostic: shader-clock stamps (s_memtime deltas, cycles) of the phases of the last launch of a

@@ -18,6 +18,7 @@
 // iteration bound on the device, another one refines.
 #include "vo_internal.h"
 #include "vo_ransac.h"
+#include "vo_chol6.h"
 
 #include <math.h>
 #include <string.h>
@@ -136,14 +137,6 @@ __device__ __forceinline__ double pnp_rcp(double x) {
   double y = __builtin_amdgcn_rcp(x);
   y = fma(fma(-x, y, 1.0), y, y);
   return fma(fma(-x, y, 1.0), y, y);
-}
-
-__device__ __forceinline__ double pnp_rsqrt(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-  double e = fma(-x * y, y, 1.0);
-  y = fma(0.5 * y, e, y);
-  e = fma(-x * y, y, 1.0);
-  return fma(0.5 * y, e, y);
 }
 
 // wave-wide sum in every lane: DPP row rotations + permlane swaps (no LDS traffic, unlike __shfl_xor on f64)
@@ -653,50 +646,11 @@ __global__ void __launch_bounds__(PNP_REFINE_THREADS) k_pnp_refine(const double*
   }
   for (int iter = 0; iter < 20; iter++) {
     if (tid == 0) {
-      // Cholesky of the 6x6 normal matrix, solve H d = -g.  Every loop is unrolled over compile-time bounds (no early exit: a bad pivot
-      // only clears the flag), so the factor lives in registers -- indexed by run-time loop counters it sat in scratch memory
-      // (480 bytes per thread) and every access of this one-lane chain was a memory round trip
-      double Hm[6][6], g[6], d[6];
-      {
-        int q = 0;
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-          for (int c = a; c < 6; c++) { Hm[a][c] = s_sum[q]; Hm[c][a] = s_sum[q]; q++; }
-      }
+      // Cholesky of the 6x6 normal matrix, solve H d = -g (vo_chol6.h)
+      double g[6], d[6];
 #pragma unroll
       for (int a = 0; a < 6; a++) g[a] = -s_sum[21 + a];
-      bool okc = true;
-#pragma unroll
-      for (int j = 0; j < 6; j++) {
-        double sdiag = Hm[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) sdiag -= Hm[j][k] * Hm[j][k];
-        if (!(sdiag > 0)) { okc = false; sdiag = 1.0; }
-        const double rs = pnp_rsqrt(sdiag);           // 1 / L_jj
-        Hm[j][j] = rs;                                // the diagonal holds the INVERSE pivot
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-          double sv = Hm[i][j];
-#pragma unroll
-          for (int k = 0; k < j; k++) sv -= Hm[i][k] * Hm[j][k];
-          Hm[i][j] = sv * rs;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 6; i++) {
-        double sv = g[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) sv -= Hm[i][k] * d[k];
-        d[i] = sv * Hm[i][i];
-      }
-#pragma unroll
-      for (int i = 5; i >= 0; i--) {
-        double sv = d[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++) sv -= Hm[k][i] * d[k];
-        d[i] = sv * Hm[i][i];
-      }
+      const bool okc = vo_chol6_solve(s_sum, g, d);
       if (okc) {
 #pragma unroll
         for (int i = 0; i < 6; i++) s_d[i] = d[i];

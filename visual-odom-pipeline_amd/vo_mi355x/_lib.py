@@ -125,6 +125,18 @@ class Sim3Stats(C.Structure):
                 ("status", C.c_int32), ("degenerate", C.c_int32), ("refit", C.c_int32)]
 
 
+class AlignParams(C.Structure):
+    """vo_align_params (32 bytes)"""
+    _fields_ = [("max_level", C.c_int32), ("min_level", C.c_int32), ("max_iters", C.c_int32), ("min_points", C.c_int32),
+                ("huber", C.c_float), ("eps", C.c_float), ("form", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AlignStats(C.Structure):
+    """vo_align_stats (56 bytes)"""
+    _fields_ = [("status", C.c_int32), ("n_used", C.c_int32), ("levels_run", C.c_int32), ("flags", C.c_int32), ("iters", C.c_int32 * 8),
+                ("chi2", C.c_float), ("zbar", C.c_float)]
+
+
 class HposeParams(C.Structure):
     _fields_ = [("ratio", C.c_double), ("threshold", C.c_double), ("hint", C.c_double * 3), ("min_off", C.c_int32), ("use_hint", C.c_int32)]
 
@@ -294,6 +306,8 @@ SIGNATURES = {
     "vo_sim3_default_params": (C.c_int32, [C.POINTER(Sim3Params)]),
     "vo_sim3_ransac": (C.c_int32, [_ctx, _f32p, _f32p, C.c_int32, C.POINTER(Sim3Params), _f64p, _f64p, _f64p, _f64p, _u8p, C.POINTER(Sim3Stats)]),
     "vo_sim3_fit": (C.c_int32, [_ctx, _f32p, _f32p, _u8p, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, C.POINTER(Sim3Stats)]),
+    "vo_align_default_params": (C.c_int32, [C.POINTER(AlignParams)]),
+    "vo_sparse_align": (C.c_int32, [_ctx, _f64p, _f32p, C.c_int32, _f64p, _f64p, C.POINTER(AlignParams), _f64p, _f64p, _u8p, C.POINTER(AlignStats)]),
     "vo_sift_detect_compute": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32, C.POINTER(SiftKp), _f32p, _i32p]),
     "vo_orb_default_params": (C.c_int32, [C.POINTER(OrbParams)]),
     "vo_orb_detect_compute": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.POINTER(OrbParams), _i8p, C.c_int32, C.POINTER(OrbKp), _u8p, _i32p]),

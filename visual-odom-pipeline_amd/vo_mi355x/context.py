@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BaParams, BaStats, BriefParams, EssParams, EssStats, FundParams, FundStats, GMatchParams, HomParams, HomStats, HposeParams, HposeStats, KltParams, OrbKp, OrbParams, SiftKp, PnpParams, PnpStats, Sim3Params, Sim3Stats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
+from ._lib import AlignParams, AlignStats, BaParams, BaStats, BriefParams, EssParams, EssStats, FundParams, FundStats, GMatchParams, HomParams, HomStats, HposeParams, HposeStats, KltParams, OrbKp, OrbParams, SiftKp, PnpParams, PnpStats, Sim3Params, Sim3Stats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
 
 # vo_set_klt_predict modes (include/vo_mi355x.h)
 KLT_PREDICT_MODES = {"off": 0, "constant_velocity": 1}
@@ -768,6 +768,7 @@ class VoContext:
     PROF_GMATCH_FORWARD, PROF_GMATCH_REVERSE, PROF_GMATCH_ACCEPT = range(19, 22)
     PROF_HPOSE = 22
     PROF_SIM3_SOLVE, PROF_SIM3_SCORE, PROF_SIM3_SELECT, PROF_SIM3_FINISH = range(23, 27)
+    PROF_ALIGN = 27
 
     def profile_enable(self, regions=(0, 1, 2, 3, 4)):
         """regions: iterable of PROF_* ids to time with hipEvent pairs on the ctx stream; () switches timing off"""
@@ -1215,6 +1216,39 @@ class VoContext:
         self._ck(self._L.vo_sim3_fit(self._h, ptr(a, C.c_float), ptr(b, C.c_float), ptr(m, C.c_uint8), n, int(with_scale), ptr(s, C.c_double),
                                      ptr(R, C.c_double), ptr(t, C.c_double), st))
         return self._out(s), self._out(R), self._out(t), self._sim3_stats(st)
+
+    def align_params(self, max_level=-1, min_level=0, max_iters=10, min_points=10, huber=10.0, eps=1e-5, form=0):
+        """vo_align_params: max_level -1 = the store's top level; huber in grey levels (0: no weighting); form 0 = the library's rule,
+        1 = reference patches kept in a workspace, 2 = recomputed every iteration (the same bits)"""
+        p = AlignParams()
+        self._L.vo_align_default_params(C.byref(p))
+        p.max_level, p.min_level, p.max_iters, p.min_points = int(max_level), int(min_level), int(max_iters), int(min_points)
+        p.huber, p.eps, p.form = huber, eps, int(form)
+        return p
+
+    def sparse_align(self, K, pts3d, rvec0=None, tvec0=None, params=None):
+        """Sparse direct image alignment (vo_sparse_align; the algorithm: tests/align_model.py): the pose of the store's current frame against
+        its previous one from the two pyramids and pts3d (n,3), points in the PREVIOUS camera's coordinates (a NaN row or z <= 0 is never
+        used) -- available before any feature is tracked.  K (3,3); rvec0 / tvec0 (3,): the initial pose, both None = identity [leading
+        batch dim if batch > 1] -> rvec (3,), tvec (3,) with x_cur = R(rvec) x_prev + tvec, used (n,) bool (the points of the last kept
+        linearisation of the finest level that ran), stats dict.  No level ran: stats['status'] != 0 and the initial pose comes back."""
+        B = self.batch
+        X = np.ascontiguousarray(pts3d, np.float32).reshape(B, -1, 3)
+        n = X.shape[1]
+        Kc = self._in(K, np.float64, (3, 3))
+        if (rvec0 is None) != (tvec0 is None):
+            raise ValueError("rvec0 and tvec0 go together")
+        r0 = None if rvec0 is None else self._in(rvec0, np.float64, (3,))
+        t0 = None if tvec0 is None else self._in(tvec0, np.float64, (3,))
+        prm = params if params is not None else self.align_params()
+        rv, tv = np.zeros((B, 3)), np.zeros((B, 3))
+        mask = np.zeros((B, n), np.uint8)
+        st = (AlignStats * B)()
+        self._ck(self._L.vo_sparse_align(self._h, ptr(Kc, C.c_double), ptr(X, C.c_float), n, ptr(r0, C.c_double), ptr(t0, C.c_double), C.byref(prm),
+                                         ptr(rv, C.c_double), ptr(tv, C.c_double), ptr(mask, C.c_uint8), st))
+        stats = [dict(status=s.status, n_used=s.n_used, levels_run=s.levels_run, flags=s.flags, iters=list(s.iters), chi2=s.chi2, zbar=s.zbar)
+                 for s in st]
+        return self._out(rv), self._out(tv), self._out(mask != 0), self._out(stats)
 
     def pnp_params(self, reproj_err=2.0, confidence=0.9999, max_iters=1000000, seed=0):
         prm = PnpParams()

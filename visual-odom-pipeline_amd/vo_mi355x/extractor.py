@@ -229,8 +229,19 @@ class Extractor:
         uv = p1.reshape(-1, 2, 1).copy()
         return keep, uv, uv.copy()
 
-    def extend_tracks(self, im_curr, kp, max_bidir_error=30):
-        s = self._session()
+    def _start(self, init, kps, p0):
+        """where the tracker starts: `init` (n, 2), e.g. project_landmarks under align_frame's pose, in place of this class's own guess"""
+        if init is None:
+            return self._guess(kps, p0)
+        g = np.ascontiguousarray(init, np.float32).reshape(-1, 2)
+        if g.shape != p0.shape:
+            raise ValueError("init must hold one start position per keypoint")
+        return g
+
+    def extend_tracks(self, im_curr, kp, max_bidir_error=30, init=None):
+        """init (None: as the reference): start positions (len(kp), 2) for the tracker in place of predict='s guess; a call with it takes
+        the plain path, like every call a lazy session does not serve"""
+        s = self._session() if init is None else None
         if s is not None:
             r = s.extend_tracks(self._im_prev, im_curr, kp, max_bidir_error)
             if r is not NotImplemented:
@@ -240,7 +251,7 @@ class Extractor:
         new_tracks = []
         if len(kp):
             p0 = self._uv_block(kp)
-            p1, good = self._track(im_curr, p0, max_bidir_error, self._guess(kp, p0))
+            p1, good = self._track(im_curr, p0, max_bidir_error, self._start(init, kp, p0))
             keep, uv, hist = self._survivors(im_curr, p1, good)
             for i in np.nonzero(keep)[0]:
                 k = kp[i]
@@ -250,8 +261,9 @@ class Extractor:
                 new_tracks.append(k)
         return new_tracks
 
-    def extend_landmarks(self, im_curr, landmarks, landmarks_kp, max_bidir_error=30):
-        s = self._session()
+    def extend_landmarks(self, im_curr, landmarks, landmarks_kp, max_bidir_error=30, init=None):
+        """init: as extend_tracks, one start position per landmark keypoint"""
+        s = self._session() if init is None else None
         if s is not None:
             r = s.extend_landmarks(self._im_prev, im_curr, landmarks, landmarks_kp, max_bidir_error)
             if r is not NotImplemented:
@@ -262,7 +274,7 @@ class Extractor:
         if not len(landmarks_kp):
             return landmarks_new, kp_new, landmarks_dead, kp_dead
         p0 = self._uv_block(landmarks_kp)
-        p1, good = self._track(im_curr, p0, max_bidir_error, self._guess(landmarks_kp, p0))
+        p1, good = self._track(im_curr, p0, max_bidir_error, self._start(init, landmarks_kp, p0))
         keep, uv, hist = self._survivors(im_curr, p1, good)
         # the reference converts p1 with .tolist() here (python floats): uv / history entries are float64 in this method
         uv, hist = uv.astype(np.float64), hist.astype(np.float64)
@@ -595,6 +607,50 @@ class Extractor:
         S = np.eye(4)
         S[:3, :3], S[:3, 3] = s * R, t
         return S, inliers.reshape((-1,)).tolist(), st
+
+    @staticmethod
+    def _points_in_camera(H, landmarks):
+        """the landmarks' world points in the camera of pose H (x_cam = H x_world) -> (n, 3) float64"""
+        P = np.array([np.asarray(l.p, np.float64).reshape(3) for l in landmarks], np.float64).reshape(-1, 3)
+        H = np.asarray(H, np.float64)
+        return P @ H[:3, :3].T + H[:3, 3]
+
+    def align_frame(self, K, im_curr, landmarks, H_prev, H_init=None, **params):
+        """The pose of im_curr BEFORE anything is tracked: sparse direct image alignment (VoContext.sparse_align) of the pair
+        (_im_prev, im_curr) on the landmarks, which are moved into the previous camera's frame on the host (x = H_prev p).  The pair goes
+        into the frame store as extend_tracks would put it, so the extend_* calls that follow on the same image push nothing again.
+        H_prev: the previous frame's pose (4x4, x_cam = H x_world); H_init: a guess for the new pose (None: H_prev, no motion); params:
+        VoContext.align_params' keywords.  -> (H_cur 4x4, info dict: the context's stats plus 'used', the indices of the landmarks of the
+        last linearisation).  No level ran (too few landmarks in view): info['status'] != 0 and H_cur is the guess.
+        project_landmarks(K, H_cur, landmarks) then gives extend_landmarks(init=) its start positions.  A live lazy session ends here: the
+        call takes the plain path, like every call outside the reference's order."""
+        from .so3 import rodrigues_mat_to_vec, rodrigues_vec_to_mat
+        if self._im_prev is None:
+            raise RuntimeError("align_frame needs _im_prev, the frame the landmarks were last seen in")
+        self._plain("align_frame", im_curr)
+        self._ensure_pair(self._im_prev, im_curr)
+        H_prev = np.asarray(H_prev, np.float64)
+        X = self._points_in_camera(H_prev, landmarks).astype(np.float32)
+        r0 = t0 = None
+        if H_init is not None:
+            T0 = np.asarray(H_init, np.float64) @ np.linalg.inv(H_prev)
+            r0, t0 = rodrigues_mat_to_vec(T0[:3, :3]), T0[:3, 3].copy()
+        rv, tv, used, st = self._ctx.sparse_align(K, X, r0, t0, self._ctx.align_params(**params))
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = rodrigues_vec_to_mat(rv), tv
+        info = dict(st)
+        info["used"] = np.nonzero(used)[0].tolist()
+        return T @ H_prev, info
+
+    def project_landmarks(self, K, H, landmarks):
+        """the landmarks' pixels under the pose H (4x4, x_cam = H x_world) -> (n, 2) float32; a point at or behind the camera gives NaN,
+        which the seeded tracker reads as `start where the keypoint was`"""
+        K = np.asarray(K, np.float64).reshape(3, 3)
+        Y = self._points_in_camera(H, landmarks)
+        with np.errstate(all="ignore"):
+            z = np.where(Y[:, 2] > 0, Y[:, 2], np.nan)
+            uv = np.stack([K[0, 0] * Y[:, 0] / z + K[0, 2], K[1, 1] * Y[:, 1] / z + K[1, 2]], 1)
+        return uv.astype(np.float32)
 
     def bootstrap_check(self, K, list_1, list_2, threshold=1.0, max_h_ratio=0.8, seed=0):
         """Is this frame pair fit for the 2D-2D bootstrap?  One essential_ransac and one find_homography call at the same pixel threshold;
