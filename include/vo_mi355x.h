@@ -834,6 +834,10 @@ int32_t vo_sim3_fit(vo_ctx* ctx, const float* src, const float* dst, const uint8
  *             later, or chi > chi_prev: the previous pose is restored and the level ends; H xi = b by Cholesky (a pivot that is not
  *             positive ends the level, pose kept); T <- T E(xi)^-1 with E = (Rodrigues(omega), v); max(|omega_i|, |v_i| / zbar) < eps
  *             ends the level (zbar: mean depth of the points used in the level's first iteration -- free of the monocular scale)
+ *   order     the tests of a linearisation, which is what stats.flags names: too few points (VO_ALIGN_END_POINTS) before chi > chi_prev
+ *             (CHI; chi == chi_prev continues), then the pivot (PIVOT), then the step below eps (EPS); the level's last linearisation
+ *             ends it by MAX_ITERS.  A point that is not used samples at (8, 8), on a level below 12 pixels in the store's border: its
+ *             values reach no sum (tests/test_gpu_align_edges.py runs every exit, levels down to 9 x 6 and the interior's edges)
  * The per-pixel arithmetic is float32, the 16-pixel sums of a point are float32 in a fixed order, everything from there on float64 in
  * a fixed order: a result does not depend on the batch position or on the call.  Against the model the kernel is held to 4 x what
  * the model's own float32 switch moves the pose (tests/test_gpu_align.py).  The basin is about the patch half-width times 2^max_level

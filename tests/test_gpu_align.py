@@ -1,5 +1,6 @@
 """GPU: sparse direct image alignment (vo_sparse_align, csrc/vo_align.hip) through the C ABI against tests/align_model.py, on the problems
-tests/test_align_model.py shows the model to decide on its own.  Frames 208 x 120: the store holds two levels.
+tests/test_align_model.py shows the model to decide on its own.  Frames 208 x 120: the store holds two levels.  check_case() also serves
+tests/test_gpu_align_edges.py, whose cases run on stores of four levels, odd sizes and levels smaller than a patch.
 
 Tolerance: the largest displacement, in level-0 pixels, of a case's points between the kernel's pose and the float64 model's, against
 4 x the displacement between the model's float32 switch and its float64 run on that case (the factor covers FMA contraction and a summation
@@ -63,48 +64,125 @@ def test_the_store_holds_the_levels_the_model_is_given(ctx):
 RATIOS = {}
 
 
-@pytest.mark.parametrize("case", am.gpu_cases(), ids=lambda c: c["name"])
-def test_kernel_against_model(ctx, case):
+class Stores:
+    """the contexts the cases of align_model run on, one per (frame size, window, batch), opened when first asked for"""
+
+    def __init__(self):
+        self.open = {}
+
+    def get(self, case, batch=1):
+        from vo_mi355x import VoContext
+        (w, h), win, levels = am.case_store(case)
+        key = (w, h, win, batch)
+        if key not in self.open:
+            c = VoContext(w, h, max_pts=256, win=win, batch=batch)
+            self.open[key] = c
+            assert [c.level_size(l) for l in range(levels)] == am.level_sizes(w, h, levels)
+            with pytest.raises(Exception):
+                c.level_size(levels)
+        return self.open[key]
+
+    def close(self):
+        for c in self.open.values():
+            c.close()
+        self.open = {}
+
+
+@pytest.fixture(scope="module")
+def stores():
+    s = Stores()
+    yield s
+    s.close()
+
+
+def check_case(c, case, form=0, record=True):
+    """one case of align_model.gpu_cases() / edge_cases() on the context c against the float64 model -> (rvec, tvec, mask, stats bytes).
+    The pose by displacement against FACTOR x the float32 switch (a log_exp case: rvec against the model's, see below); where the model
+    alone decides the case: iters, levels_run, n_used, the mask, chi2 and flags"""
     m64, m32 = am.case_runs(case)
-    _push_pair(ctx, case["t"])
-    rc, rv, tv, mask, st = raw_align(ctx, case["K"], case["X"], case["rvec0"], case["tvec0"], **case["params"])
+    prev, cur = am.case_frames(case)
+    levels = am.case_store(case)[2]
+    c.push_frame(prev); c.push_frame(cur)
+    rc, rv, tv, mask, st = raw_align(c, case["K"], case["X"], case["rvec0"], case["tvec0"], form=form, **case["params"])
     assert rc == 0
     s = st[0]
+    out = (rv[0].copy(), tv[0].copy(), mask[0].copy(), bytes(s))
     R = am.rodrigues(rv[0])
     d = am.displacement(case["K"], case["X"], R, tv[0], m64["R"], m64["t"])
     d32 = am.displacement(case["K"], case["X"], m32["R"], m32["t"], m64["R"], m64["t"])
-    dec = am.decided(m64, m32)
+    dec = am.case_decided(case)
     ratio = d / d32 if d32 > 0 else (0.0 if d == 0 else np.inf)
-    RATIOS[case["name"]] = ratio
-    print("%s: kernel - model %.3g px, float32 switch - model %.3g px, ratio %.3g (bound %g); decided %s; iters %s (model %s), levels_run %d, "
-          "n_used %d (model %d), chi2 %.4f (model %.4f), end %d, zbar %.3f" % (case["name"], d, d32, ratio, FACTOR, dec, list(s.iters)[:2], list(m64["iters"][:2]),
-                                                                             s.levels_run, s.n_used, m64["n_used"], s.chi2, m64["chi2"], s.flags, s.zbar))
+    print("%s form %d: kernel - model %.3g px, float32 switch - model %.3g px, ratio %.3g (bound %g); decided %s; iters %s (model %s), levels_run %d, "
+          "n_used %d (model %d), chi2 %.4f (model %.4f), end %d (model %d), zbar %.3f"
+          % (case["name"], form, d, d32, ratio, FACTOR, dec, list(s.iters)[:levels], list(m64["iters"][:levels]), s.levels_run, s.n_used, m64["n_used"],
+             s.chi2, m64["chi2"], s.flags, m64["flags"], s.zbar))
+    given_r = np.zeros(3) if case["rvec0"] is None else case["rvec0"]
+    given_t = np.zeros(3) if case["tvec0"] is None else case["tvec0"]
     assert s.status == m64["status"]
     if m64["status"] != 0:
         # no level ran: VO_E_NUMERIC in the stats, the pose is the initial one as it was given, nobody was used
-        assert s.status == am.VO_E_NUMERIC and s.levels_run == 0 and list(s.iters)[:2] == [-1, -1] and not mask.any()
-        assert np.array_equal(rv[0], case["rvec0"]) and np.array_equal(tv[0], case["tvec0"])
-        return
-    assert d <= FACTOR * d32
+        assert s.status == am.VO_E_NUMERIC and s.levels_run == 0 and list(s.iters) == list(m64["iters"]) and not mask.any()
+        assert s.n_used == 0 and s.flags == m64["flags"] == 0
+        assert np.array_equal(rv[0], given_r) and np.array_equal(tv[0], given_t)
+        if record:
+            RATIOS[case["name"]] = 0.0
+        return out
+    if "log_exp" in case:
+        # the level's first linearisation ends by PIVOT with the pose kept: rvec is the host's log(Rodrigues(r0)).  Against the model's
+        # rvec on the same input, bound 8 x max(the model's own round-trip error at this angle, 2^-52 x angle)
+        own = np.abs(m64["rvec"] - case["rvec0"]).max()
+        bound = 8.0 * max(own, 2.0 ** -52 * case["log_exp"])
+        dr = np.abs(rv[0] - m64["rvec"]).max()
+        print("   angle %g: |rvec - model's rvec| %.3g, the model's own round trip %.3g, bound %.3g" % (case["log_exp"], dr, own, bound))
+        assert dr <= bound and np.array_equal(tv[0], given_t)
+    else:
+        if record:
+            RATIOS[case["name"]] = ratio
+        assert d <= FACTOR * d32
+    if case.get("pose_exact"):
+        assert np.array_equal(rv[0], given_r) and np.array_equal(tv[0], given_t)         # (-0.0 equals 0.0 here)
     if dec:
         assert list(s.iters) == list(m64["iters"]) and s.levels_run == m64["levels_run"] and s.n_used == m64["n_used"]
         assert np.array_equal(mask[0] != 0, m64["used"])
-        assert abs(s.chi2 - m64["chi2"]) <= 1e-4 * m64["chi2"]
+        # chi2: 1e-4 relative, which presumes a chi far above the float32 rounding of a residual.  Where chi is that rounding itself (an
+        # exact one-pixel shift: chi = 6e-8, an rms residual of 2.5e-4 grey levels of samples rounded to 1.5e-5) the model's own float32
+        # switch moves it by more (1.6e-3 relative), and the yardstick is the pose's: FACTOR x what the switch moves it.  On every
+        # other case that is below 1e-4 chi by a factor of 40 and more; chi = 0 stays an equality.  chi2 is a float: one rounding of it
+        dchi, dchi32 = abs(s.chi2 - m64["chi2"]), abs(m32["chi2"] - m64["chi2"])
+        print("   chi2: kernel - model %.3g, float32 switch - model %.3g, 1e-4 chi %.3g" % (dchi, dchi32, 1e-4 * m64["chi2"]))
+        assert dchi <= max(1e-4 * m64["chi2"], FACTOR * dchi32 + 2.0 ** -24 * m64["chi2"])
+        assert s.flags == m64["flags"]
     if case["truth"]:
         sc = am.scene(am.W, am.H)
         motion, err = am.prediction_error(case["K"], case["X"], R, tv[0], *am.true_pose(sc, case["t"]))
         print("   ground truth: median image motion %.3f px, median prediction error %.4f px (1/%.0f)" % (motion, err, motion / err))
         assert err <= motion / 10.0
+    return out
 
 
-def test_largest_ratio_over_the_cases(ctx):
-    """the figure EXPERIMENTS.md records (the cases above have left their ratios; one that did not run is run here)"""
-    for case in am.gpu_cases():
+@pytest.mark.parametrize("case", am.gpu_cases(), ids=lambda c: c["name"])
+def test_kernel_against_model(ctx, case):
+    check_case(ctx, case)
+
+
+def ratio_cases():
+    """the cases held to the displacement rule (a log_exp case is held to its own bound on rvec)"""
+    return [c for c in am.all_cases() if "log_exp" not in c]
+
+
+def test_largest_ratio_over_the_cases(ctx, stores):
+    """the figure EXPERIMENTS.md records, over gpu_cases() and edge_cases() (the tests of the two files have left their ratios; a case that
+    did not run is run here)"""
+    for case in ratio_cases():
         if case["name"] not in RATIOS:
-            test_kernel_against_model(ctx, case)
-    k = max(RATIOS, key=RATIOS.get)
-    print("largest (kernel - model) / (float32 switch - model) over %d cases: %.3g (%s); bound %g" % (len(RATIOS), RATIOS[k], k, FACTOR))
-    assert len(RATIOS) == len(am.gpu_cases()) and RATIOS[k] <= FACTOR
+            check_case(ctx if "size" not in case else stores.get(case), case)
+    r = {c["name"]: RATIOS[c["name"]] for c in ratio_cases()}
+    k = max(r, key=r.get)
+    old = {c["name"] for c in am.gpu_cases()}
+    ko = max(old, key=r.get)
+    print("largest (kernel - model) / (float32 switch - model) over %d cases: %.3g (%s); over the %d of gpu_cases(): %.3g (%s); bound %g"
+          % (len(r), r[k], k, len(old), r[ko], ko, FACTOR))
+    assert len(r) == len(ratio_cases()) and r[k] <= FACTOR
 
 
 def test_both_forms_give_the_same_bits(ctx):
