@@ -368,7 +368,17 @@ int32_t vo_pyramid_read_seq(vo_ctx* ctx, int32_t seq, int32_t which, int32_t lev
  * Replaces cv2.calcOpticalFlowPyrLK(prev, cur, p0, None, **lk_params) at extractor.py:44,65
  * (and, being deterministic, the redundant second call at :45,:66).
  * p0: n x 2 f32.  Outputs: p1 n x 2 f32, status n u8, err n f32, iters n x (max_level+1) i32
- * (iterations run per pyramid level, -1 = level skipped; may be NULL). */
+ * (iterations run per pyramid level, -1 = level skipped; may be NULL).
+ * KEYPOINTS THAT ARE NOT HONEST NUMBERS (every tracker form: vo_klt_track*, vo_klt_track_resident, vo_tracks_track, vo_frame_step_*, vo_pipe_step*):
+ *   OpenCV's cvFloor makes INT_MIN of a NaN and of every value outside [-2^31, 2^31), so such a p0 is outside the image on every level:
+ *   status 0, err 0, every iters entry -1, and p1 is p0 passed through.  Here:
+ *   - a p0 row with a component that is infinite or beyond int32 gives exactly that, p1 = p0 bit for bit (the scalings by 2^-l and 2 are exact);
+ *   - a p0 row with a NaN component gives that status, err and iters, and a p1 row that is NOT FINITE.  Every entry that copies caller points
+ *     to the device -- vo_klt_track, _fb, _init, _fb_init, vo_points_upload, vo_tracks_seed, vo_pipe_table_write(VO_PIPE_K_UV) -- stores such a
+ *     row as (+inf, +inf); the synchronous calls hand the caller's own row back in p1 (and in p0r), the resident forms keep (+inf, +inf);
+ *   - forward-backward: such a row has ok = 0 and an fb_err that is NaN or +inf, below no threshold;
+ *   - the row draws no exclusion disc (vo_shi_tomasi below) and fails the keep rule of a track table or of the closed loop.
+ *   Nothing on the device turns a finite point into a NaN one (front-end contract).  Guesses keep their own rule (below). */
 int32_t vo_klt_default_params(vo_klt_params* p);
 int32_t vo_klt_track(vo_ctx* ctx, const float* p0, int32_t n, const vo_klt_params* prm,
                      float* p1, uint8_t* status, float* err, int32_t* iters);
@@ -439,6 +449,9 @@ int32_t vo_klt_guess_read(vo_ctx* ctx, float* guess, int32_t n);
  * tracked keypoints; discs of `mask_radius` at int32-truncated coordinates are excluded
  * (cv2.circle fill semantics).  `mask` (h x w u8, may be NULL) is an optional explicit mask that
  * is AND-ed with the discs.  out_pts: max_corners x 2 f32 (integer-valued x, y); *n_out set.
+ * A centre with a component that is NaN or outside [-2^31, 2^31) draws nothing, on every path that draws discs (vo_shi_tomasi*,
+ * vo_tracks_detect, vo_frame_step_*, the closed loop): np.int32() makes INT_MIN of it and cv2.circle clips that away.  Any other centre,
+ * however far outside the image, is clipped row by row.
  * The detector is a choice of RESPONSE MAP (vo_st_params): the minimum eigenvalue (default), the Harris response (use_harris), or the
  * FAST-9/16 corner score of cv2.FastFeatureDetector (fast_threshold = 1..254; k_fast_score, csrc/vo_fast.hip -- the detector ORB builds
  * on; orientation and descriptor: vo_brief_* below).  What follows the map is the same for all three on every path that takes a vo_st_params

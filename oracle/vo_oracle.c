@@ -119,6 +119,14 @@ static inline int deriv0(const int16_t* d, int w, int h, int x, int y, int c) {
   return d[((size_t)y * w + x) * 2 + c];
 }
 
+/* cvFloor as OpenCV's SSE build computes it (cvtss2si, then the correction of the truncation): NaN and every value outside [-2^31, 2^31)
+ * give the "integer indefinite" INT_MIN.  Written out, because (int)floorf(x) is undefined in C for exactly those values; inside the range
+ * it IS (int)floorf(x).  INT_MIN is outside every image for the window tests below (ipx < -win). */
+static inline int cv_floor(float x) {
+  if (!(x >= -2147483648.f && x < 2147483648.f)) return INT32_MIN;
+  return (int)floorf(x);
+}
+
 #define W_BITS 14
 #define DESCALE(x, n) (((x) + (1 << ((n)-1))) >> (n))
 
@@ -136,9 +144,20 @@ static inline void lk_weights(float a, float b, int* iw00, int* iw01, int* iw10,
  * acc_mode: 1 exact int64 accumulation, 0 float accumulators in raster order
  * returns the highest pyramid level used.
  */
+int vo_oracle_klt_init(const uint8_t* im0, const uint8_t* im1, int w, int h, const float* p0, const float* init, int n,
+                       int win, int max_level, int max_count, double eps, float min_eig_thr,
+                       int acc_mode, float* p1, uint8_t* status, float* err, int32_t* iters);
 int vo_oracle_klt(const uint8_t* im0, const uint8_t* im1, int w, int h, const float* p0, int n,
                   int win, int max_level, int max_count, double eps, float min_eig_thr,
                   int acc_mode, float* p1, uint8_t* status, float* err, int32_t* iters) {
+  return vo_oracle_klt_init(im0, im1, w, h, p0, NULL, n, win, max_level, max_count, eps, min_eig_thr, acc_mode, p1, status, err, iters);
+}
+
+/* init (n x 2, or NULL): OPTFLOW_USE_INITIAL_FLOW -- the top level starts at the guess scaled like p0; a guess with a component that is
+ * not finite starts from p0 (the project's rule for what OpenCV leaves undefined).  Nothing else changes. */
+int vo_oracle_klt_init(const uint8_t* im0, const uint8_t* im1, int w, int h, const float* p0, const float* init, int n,
+                       int win, int max_level, int max_count, double eps, float min_eig_thr,
+                       int acc_mode, float* p1, uint8_t* status, float* err, int32_t* iters) {
   level_t L0[VO_MAX_LEVELS], L1[VO_MAX_LEVELS];
   if (max_level >= VO_MAX_LEVELS) max_level = VO_MAX_LEVELS - 1;
   if (max_count < 0) max_count = 0;
@@ -177,12 +196,17 @@ int vo_oracle_klt(const uint8_t* im0, const uint8_t* im1, int w, int h, const fl
       float prevx = p0[2 * pt] * (float)(1. / (1 << level));
       float prevy = p0[2 * pt + 1] * (float)(1. / (1 << level));
       float nextx, nexty;
-      if (level == top) { nextx = prevx; nexty = prevy; }
+      if (level == top) {
+        nextx = prevx; nexty = prevy;
+        if (init && isfinite(init[2 * pt]) && isfinite(init[2 * pt + 1])) {
+          nextx = init[2 * pt] * (float)(1. / (1 << level)); nexty = init[2 * pt + 1] * (float)(1. / (1 << level));
+        }
+      }
       else { nextx = p1[2 * pt] * 2.f; nexty = p1[2 * pt + 1] * 2.f; }
       p1[2 * pt] = nextx; p1[2 * pt + 1] = nexty;
 
       prevx -= half; prevy -= half;
-      int ipx = (int)floorf(prevx), ipy = (int)floorf(prevy);
+      int ipx = cv_floor(prevx), ipy = cv_floor(prevy);
       if (ipx < -win || ipx >= cols || ipy < -win || ipy >= rows) {
         if (level == 0) { status[pt] = 0; err[pt] = 0.f; }
         continue;
@@ -227,7 +251,7 @@ int vo_oracle_klt(const uint8_t* im0, const uint8_t* im1, int w, int h, const fl
       float pdx = 0, pdy = 0;
       int j;
       for (j = 0; j < max_count; j++) {
-        int inx = (int)floorf(nextx), iny = (int)floorf(nexty);
+        int inx = cv_floor(nextx), iny = cv_floor(nexty);
         if (inx < -win || inx >= cols || iny < -win || iny >= rows) {
           if (level == 0) status[pt] = 0;
           break;
@@ -265,7 +289,7 @@ int vo_oracle_klt(const uint8_t* im0, const uint8_t* im1, int w, int h, const fl
 
       if (status[pt] && level == 0) {
         float nx = p1[2 * pt] - half, ny = p1[2 * pt + 1] - half;
-        int inx = (int)floorf(nx), iny = (int)floorf(ny);
+        int inx = cv_floor(nx), iny = cv_floor(ny);
         if (inx < -win || inx >= cols || iny < -win || iny >= rows) { status[pt] = 0; continue; }
         float aa = nx - inx, bb = ny - iny;
         lk_weights(aa, bb, &iw00, &iw01, &iw10, &iw11);
@@ -300,6 +324,10 @@ static void hline(uint8_t* img, int w, int h, int y, int x0, int x1, uint8_t col
 }
 
 void vo_oracle_circle(uint8_t* img, int w, int h, int cx, int cy, int radius, int color) {
+  /* a centre more than the radius outside the image touches no pixel (cv2.circle clips the same way); compared in 64 bits, so that the span
+   * arithmetic below never sees a centre at which cx +- dx could overflow an int */
+  if (radius < 0 || (int64_t)cx < -(int64_t)radius || (int64_t)cx > (int64_t)w - 1 + radius ||
+      (int64_t)cy < -(int64_t)radius || (int64_t)cy > (int64_t)h - 1 + radius) return;
   int err = 0, dx = radius, dy = 0, plus = 1, minus = (radius << 1) - 1;
   while (dx >= dy) {
     int mask;

@@ -42,6 +42,9 @@ def lib():
         L.vo_oracle_klt.argtypes = [u8p, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_double, C.c_float, C.c_int, f32p, u8p, f32p, i32p]
         L.vo_oracle_klt.restype = C.c_int
+        L.vo_oracle_klt_init.argtypes = [u8p, u8p, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_double, C.c_float, C.c_int, f32p, u8p, f32p, i32p]
+        L.vo_oracle_klt_init.restype = C.c_int
         L.vo_oracle_circle.argtypes = [u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         L.vo_oracle_circle.restype = None
         L.vo_oracle_circle_rows.argtypes = [C.c_int, i32p]
@@ -102,9 +105,10 @@ def build_pyramid(img, win=31, max_level=3):
 
 
 def klt(im0, im1, p0, winSize=(31, 31), maxLevel=3, criteria=(3, 30, 0.03), minEigThreshold=1e-4,
-        acc_mode=1, return_iters=False):
+        acc_mode=1, return_iters=False, init=None):
     """Restatement of cv2.calcOpticalFlowPyrLK(im0, im1, p0, None, winSize, maxLevel, criteria).
-    criteria = (type, maxCount, eps) with type = COUNT|EPS (both always active here)."""
+    criteria = (type, maxCount, eps) with type = COUNT|EPS (both always active here).
+    init (n, 2): OPTFLOW_USE_INITIAL_FLOW with these guesses; a guess that is not finite starts from p0."""
     im0, im1 = _img(im0), _img(im1)
     assert im0.shape == im1.shape and winSize[0] == winSize[1]
     h, w = im0.shape
@@ -114,10 +118,14 @@ def klt(im0, im1, p0, winSize=(31, 31), maxLevel=3, criteria=(3, 30, 0.03), minE
     st = np.zeros(n, np.uint8)
     err = np.zeros(n, np.float32)
     iters = np.zeros((n, maxLevel + 1), np.int32)
-    lib().vo_oracle_klt(_p(im0, C.c_uint8), _p(im1, C.c_uint8), w, h, _p(p0, C.c_float), n, int(winSize[0]),
-                        int(maxLevel), int(criteria[1]), float(criteria[2]), float(minEigThreshold),
-                        int(acc_mode), _p(p1, C.c_float), _p(st, C.c_uint8), _p(err, C.c_float),
-                        _p(iters, C.c_int32))
+    if init is not None:
+        init = np.ascontiguousarray(np.asarray(init, np.float32).reshape(-1, 2))
+        assert init.shape == p0.shape
+    lib().vo_oracle_klt_init(_p(im0, C.c_uint8), _p(im1, C.c_uint8), w, h, _p(p0, C.c_float),
+                             None if init is None else _p(init, C.c_float), n, int(winSize[0]),
+                             int(maxLevel), int(criteria[1]), float(criteria[2]), float(minEigThreshold),
+                             int(acc_mode), _p(p1, C.c_float), _p(st, C.c_uint8), _p(err, C.c_float),
+                             _p(iters, C.c_int32))
     if return_iters:
         return p1, st, err, iters
     return p1, st, err

@@ -7,6 +7,9 @@ and the project's own rule for what OpenCV leaves undefined: a guess with a comp
 position, the propagation to the lower levels, the skips, the exits, status, err and the iteration counts are those of the unseeded tracker;
 a skipped top level passes the scaled guess down as it passes prevPt down.  init=None is the unseeded tracker.
 
+`cv_floor` and `to_int32` are OpenCV's float -> int conversions with x86's answer for NaN and values beyond int32 (INT_MIN) written out, so that
+rows with such components run through the model (outside on every level) instead of raising; tests/nonfinite_cases.py holds those rows.
+
 `predict(uv, prev)` is the constant-velocity rule of the resident predictors: g = uv + (uv - prev) in float32, g = uv where prev is missing
 (NaN) or not finite."""
 import numpy as np
@@ -37,6 +40,32 @@ def predict(uv, prev):
 
 
 MUTANTS = ("int32_sums", "int32_combine", "thr_le", "half_up", "unclamped")
+
+
+INT_MIN = -(1 << 31)
+
+
+def cv_floor(x):
+    """OpenCV's cvFloor (SSE cvtss2si): floor as a Python int; INT_MIN for NaN and for every value outside [-2^31, 2^31)"""
+    x = float(x)
+    if not (-2147483648.0 <= x < 2147483648.0):          # NaN fails both comparisons
+        return INT_MIN
+    return int(np.floor(x))
+
+
+def to_int32(p):
+    """np.int32(p) as x86 computes it (cvttss2si), written out: truncation toward zero; INT_MIN for NaN and for every value outside
+    [-2^31, 2^31).  What the reference's disc centres np.int32(kp.uv) become.  p: any shape; -> int32 array of that shape."""
+    p = np.asarray(p, np.float32)
+    out = np.empty(p.shape, np.int32)
+    flat, o = p.reshape(-1), out.reshape(-1)
+    for i, v in enumerate(flat):
+        v = float(v)
+        if not (-2147483648.0 <= v < 2147483648.0):
+            o[i] = INT_MIN
+        else:
+            o[i] = int(v)                                   # Python's int(): toward zero
+    return out
 
 
 def _wrap32(v):
@@ -108,7 +137,7 @@ def klt_np(im0, im1, p0, init=None, win=31, max_level=3, max_count=30, eps=0.03,
     def window(A, ix, iy):
         return A[iy + pad: iy + pad + win + 1, ix + pad: ix + pad + win + 1]
 
-    def outside(ix, iy, cols, rows):               # (floats beyond the int range are outside too: floor() keeps them exact in Python)
+    def outside(ix, iy, cols, rows):               # (NaN and floats beyond the int range are INT_MIN through cv_floor: outside)
         return ix < -win or ix >= cols or iy < -win or iy >= rows
 
     for level in range(top, -1, -1):
@@ -122,7 +151,7 @@ def klt_np(im0, im1, p0, init=None, win=31, max_level=3, max_count=30, eps=0.03,
                 nextx, nexty = p1[pt, 0] * F(2), p1[pt, 1] * F(2)
             p1[pt] = (nextx, nexty)
             prevx, prevy = prevx - half, prevy - half
-            ipx, ipy = int(np.floor(prevx)), int(np.floor(prevy))
+            ipx, ipy = cv_floor(prevx), cv_floor(prevy)
             if outside(ipx, ipy, cols, rows):
                 if level == 0:
                     status[pt], err[pt] = 0, 0
@@ -148,7 +177,7 @@ def klt_np(im0, im1, p0, init=None, win=31, max_level=3, max_count=30, eps=0.03,
             pdx = pdy = F(0)
             j = 0
             while j < max_count:
-                inx, iny = int(np.floor(nextx)), int(np.floor(nexty))
+                inx, iny = cv_floor(nextx), cv_floor(nexty)
                 if outside(inx, iny, cols, rows):
                     if level == 0:
                         status[pt] = 0
@@ -173,7 +202,7 @@ def klt_np(im0, im1, p0, init=None, win=31, max_level=3, max_count=30, eps=0.03,
             iters[pt, level] = j
             if status[pt] and level == 0:
                 nx, ny = p1[pt, 0] - half, p1[pt, 1] - half
-                inx, iny = int(np.floor(nx)), int(np.floor(ny))
+                inx, iny = cv_floor(nx), cv_floor(ny)
                 if outside(inx, iny, cols, rows):
                     status[pt] = 0
                     continue

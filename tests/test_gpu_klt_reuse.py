@@ -180,6 +180,11 @@ def test_batch_of_three_with_dead_slots_and_nan_rows():
     for b in range(B):
         want = o.klt(frames[b, 1], frames[b, 2], holes[b][finite[b]], return_iters=True)
         assert _same([sync1[k][b][finite[b]] for k in range(4)], list(want)), b
+        # the NaN rows too: outside at every level (cvFloor(NaN) = INT_MIN), so status 0, err 0 and no level entered -- on both kernels
+        full = o.klt(frames[b, 1], frames[b, 2], holes[b], return_iters=True)
+        for got in (sync1, sync0):
+            assert _same([got[k][b] for k in (1, 2, 3)], [full[k] for k in (1, 2, 3)]), b
+        assert (full[1][~finite[b]] == 0).all() and (full[3][~finite[b]] == -1).all(), b
 
 
 def test_fused_step_two_in_flight_is_identical_with_either_kernel():

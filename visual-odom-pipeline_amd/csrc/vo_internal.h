@@ -116,6 +116,7 @@ struct vo_ctx {
   int p_parity = 0;                  // 0: current points at off_pa
   vo_dev<int32_t> d_iters;           // [batch][n x (max_level + 1)]
   int n_resident = 0;
+  std::vector<float> pts_stage;      // vo_points_in: the caller's point rows with the NaN rows replaced (kept until the upload out of it is done)
   int iters_stride = 0;              // of the last KLT launch
   // The four side-row stores (vo_side_rows; reserved by vo_fb_reserve ... vo_brief_reserve below), M = max_pts, C = max(max_pts, VO_CORNER_CAP):
   //   fb      M rows: p0r 8 B | fb_err 4 B | ok 1 B, every column rounded up to 256 B    n = points of the last track if it ran the check
@@ -434,6 +435,21 @@ inline hipError_t rows_h2d(vo_ctx* c, void* d, size_t d_stride, const void* h, s
 }
 inline hipError_t rows_d2h(vo_ctx* c, void* h, const void* d, size_t d_stride, size_t row_bytes) {
   return hipMemcpy2DAsync(h, row_bytes, d, d_stride, row_bytes, c->batch, hipMemcpyDeviceToHost, c->stream);
+}
+
+// Front-end contract (vo_mi355x.h): a caller's point row with a NaN component enters the device as (+inf, +inf).  OpenCV's cvFloor makes
+// INT_MIN of a NaN (outside every level: status 0, err 0, no level entered, p1 not finite), while the tracker's saturating conversion makes 0 of
+// it and would track the image origin; +inf saturates to INT_MAX and is outside every level there too.  -> h itself when no row has a NaN
+// (the usual case: one pass over the floats), else a copy in c->pts_stage, which must stay untouched until the upload out of it has completed
+inline bool vo_row_has_nan(const float* row) { return row[0] != row[0] || row[1] != row[1]; }
+inline const float* vo_points_in(vo_ctx* c, const float* h, size_t n_rows) {
+  size_t i = 0;
+  while (i < n_rows && !vo_row_has_nan(h + 2 * i)) i++;
+  if (i == n_rows) return h;
+  c->pts_stage.assign(h, h + 2 * n_rows);
+  for (; i < n_rows; i++)
+    if (vo_row_has_nan(h + 2 * i)) c->pts_stage[2 * i] = c->pts_stage[2 * i + 1] = __builtin_inff();
+  return c->pts_stage.data();
 }
 
 // ---- the side-row stores (vo_side_rows; the four layouts: at the members of vo_ctx) ----

@@ -421,7 +421,9 @@ static int32_t klt_track_sync(vo_ctx* c, unsigned form, const float* p0, const f
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
   if (seeded) { const int32_t rg = vo_guess_reserve(c); if (rg != VO_OK) return rg; }
   const size_t off_in = vo_off_p(c), off_out = vo_off_p_next(c);
-  VO_HIP(c, rows_h2d(c, c->d_slab + off_in, c->slab_seq, p0, sizeof(float) * 2 * n));
+  const size_t n_rows = (size_t)n * c->batch;
+  const float* const p0_in = vo_points_in(c, p0, n_rows);        // NaN rows go in as (+inf, +inf): outside at every level, as the oracle has them
+  VO_HIP(c, rows_h2d(c, c->d_slab + off_in, c->slab_seq, p0_in, sizeof(float) * 2 * n));
   if (seeded) VO_HIP(c, vo_side_h2d(c, c->guess, 0, guess, n));
   { const int32_t r = vo_klt_enqueue(c, c->stream, n, prm, off_in, off_out, nullptr, form); if (r != VO_OK) return r; }
   VO_HIP(c, rows_d2h(c, p1, c->d_slab + off_out, c->slab_seq, sizeof(float) * 2 * n));
@@ -433,6 +435,12 @@ static int32_t klt_track_sync(vo_ctx* c, unsigned form, const float* p0, const f
   }
   if (iters) VO_HIP(c, iters_d2h(c, iters, n, prm->max_level + 1));
   VO_HIP(c, hipStreamSynchronize(c->stream));
+  if (p0_in != p0)                 // the oracle passes such a p0 through: p1 (and the backward track of that p1) is the caller's own NaN row
+    for (size_t i = 0; i < n_rows; i++)
+      if (vo_row_has_nan(p0 + 2 * i)) {
+        p1[2 * i] = p0[2 * i]; p1[2 * i + 1] = p0[2 * i + 1];
+        if (fb) { p0r[2 * i] = p0[2 * i]; p0r[2 * i + 1] = p0[2 * i + 1]; }
+      }
   return VO_OK;
 }
 
@@ -462,7 +470,8 @@ extern "C" int32_t vo_points_upload(vo_ctx* c, const float* p, int32_t n) {
   VO_CHECK(c, p && n >= 0 && n <= c->max_pts, VO_E_CAPACITY, "bad point set");
   VO_HIP(c, hipSetDevice(c->device));
   { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
-  if (n > 0) VO_HIP(c, rows_h2d(c, c->d_slab + vo_off_p(c), c->slab_seq, p, sizeof(float) * 2 * n));
+  // (NaN rows become (+inf, +inf) on the way in: the resident forms hand this set to the tracker and to the exclusion discs as it lies)
+  if (n > 0) VO_HIP(c, rows_h2d(c, c->d_slab + vo_off_p(c), c->slab_seq, vo_points_in(c, p, (size_t)n * c->batch), sizeof(float) * 2 * n));
   VO_HIP(c, hipStreamSynchronize(c->stream));
   c->n_resident = n;
   return VO_OK;

@@ -1280,6 +1280,8 @@ extern "C" int32_t vo_pipe_table_write(vo_ctx* c, int32_t which, const void* src
   VO_CHECK(c, c->pipe->enq == c->pipe->fetched, VO_E_STATE, "fetch the steps in flight first");
   VO_HIP(c, hipSetDevice(c->device));
   VO_HIP(c, hipStreamSynchronize(c->stream));
+  // K_UV rows are the tracker's p0 and the disc centres of the next step: NaN rows go in as (+inf, +inf) (vo_points_in; the copy is synchronous)
+  if (which == VO_PIPE_K_UV) src = vo_points_in(c, (const float*)src, c->pipe->tab_bytes[which] * c->batch / (2 * sizeof(float)));
   VO_HIP(c, hipMemcpy(c->pipe->tab[which], src, c->pipe->tab_bytes[which] * c->batch, hipMemcpyHostToDevice));
   return VO_OK;
 }

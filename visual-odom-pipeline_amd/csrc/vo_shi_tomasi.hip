@@ -126,7 +126,13 @@ __global__ void __launch_bounds__(256) k_st_discs(const float* __restrict__ pts,
   if (gid >= n * nrows) return;
   const int k = gid / nrows, dy = gid - k * nrows - radius;
   if (counts && k >= counts[blockIdx.y]) return;
-  const int cx = (int)pts[2 * k], cy = (int)pts[2 * k + 1];   // np.int32(): truncation toward zero
+  // A centre with a component that is NaN or not in [-2^31, 2^31) draws nothing: np.int32() makes INT_MIN of it on the reference's side and
+  // cv2.circle clips that away, while the conversion here would saturate (NaN -> 0: a disc at the origin; +-inf -> INT_MAX / INT_MIN: cx +- hw wraps
+  // and the span lands 2 GiB past the mask).  NaN fails the comparison; exactly -2^31 fails it too and draws nothing either way.
+  const float fx = pts[2 * k], fy = pts[2 * k + 1];
+  if (!(fabsf(fx) < 2147483648.f && fabsf(fy) < 2147483648.f)) return;
+  // now |cx|, |cy| <= 2^31 - 128 (the largest float below 2^31), and radius <= 31: cx +- hw and cy + dy cannot overflow
+  const int cx = (int)fx, cy = (int)fy;   // np.int32(): truncation toward zero
   const int y = cy + dy;
   if (y < 0 || y >= H) return;
   const int hw = rows.hw[dy < 0 ? -dy : dy];
