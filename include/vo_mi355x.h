@@ -466,6 +466,15 @@ int32_t vo_shi_tomasi(vo_ctx* ctx, const float* cur_pts, int32_t n_cur, int32_t 
 int32_t vo_shi_tomasi_resident(vo_ctx* ctx, int32_t n_cur, int32_t mask_radius,
                                const vo_st_params* prm);                      /* async; uses the resident points */
 int32_t vo_shi_tomasi_fetch(vo_ctx* ctx, float* out_pts, int32_t* n_out);     /* sync + copy out */
+/* Parameter rules, the same on every path that takes a vo_st_params (OpenCV asserts them): quality_level > 0 (NaN, 0 and -0.0 are refused),
+ * min_distance >= 0 (NaN and negatives are refused; any finite value and +inf are accepted -- a distance beyond the image diagonal yields
+ * exactly one corner, the strongest candidate), max_corners >= 0 (0 = all, at most 4096).  A refused call is VO_E_INVALID with nothing
+ * enqueued.  min_distance < 1 applies no distance rule; a fractional one is taken as it is (dx^2 + dy^2 < min_distance^2 in double).
+ * vo_shi_tomasi_resident_limit: vo_shi_tomasi_resident with a corner limit per sequence, limits [batch] on the host (copied before the call
+ * returns).  Sequence b ends with the first min(max(limits[b], 0), max_corners) corners of the unlimited call, in the same order, and n_out
+ * says so.  It is the closed loop's detection (the limit read on the device, the candidate list consumed in short rank-ordered chunks) as a
+ * call of its own; vo_tuning.st_host_limit makes it ignore the limits. */
+int32_t vo_shi_tomasi_resident_limit(vo_ctx* ctx, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm, const int32_t* limits);
 /* parity probes: min-eigenvalue map (h x w f32) and the mask actually used (h x w u8) of the last SYNCHRONOUS call
  * (vo_shi_tomasi).  The resident forms keep neither -- the map never leaves the kernel that forms it and the mask is handed
  * back clean for the next frame -- and eig_out / mask_out then return VO_E_STATE (vo_tuning.st_keep_eig makes the

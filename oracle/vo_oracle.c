@@ -524,7 +524,9 @@ int vo_oracle_good_features(const uint8_t* img, const uint8_t* mask, int w, int 
   qsort(cands, nc, sizeof(cand_t), cand_cmp);
   int ncorners = 0;
   if (min_distance >= 1) {
-    const int cell = (int)lrint(min_distance);
+    /* cvRound(minDistance); a cell beyond the image is one cell over all of it, and the clamp in double keeps 2^31 and +inf defined */
+    const double cell_d = rint(min_distance), cell_max = (double)(w > h ? w : h);
+    const int cell = (int)(cell_d < cell_max ? cell_d : cell_max);
     const int gw = (w + cell - 1) / cell, gh = (h + cell - 1) / cell;
     /* grid cells as linked lists */
     int* head = (int*)malloc((size_t)gw * gh * sizeof(int));

@@ -29,6 +29,17 @@ def test_library_exports_every_declared_symbol():
     assert _lib.load().vo_abi_version() == 4
 
 
+def test_the_limited_detection_is_declared_with_host_limits():
+    """vo_shi_tomasi_resident_limit(ctx, n_cur, mask_radius, prm, const int32_t* limits): the resident call's arguments + one limit per sequence"""
+    from vo_mi355x import _lib
+    txt = open(os.path.join(ROOT, "include", "vo_mi355x.h")).read()
+    assert re.search(r"int32_t vo_shi_tomasi_resident_limit\(vo_ctx\* ctx, int32_t n_cur, int32_t mask_radius, const vo_st_params\* prm, "
+                     r"const int32_t\* limits\);", txt)
+    res, args = _lib.SIGNATURES["vo_shi_tomasi_resident_limit"]
+    assert res is ctypes.c_int32 and args[:4] == _lib.SIGNATURES["vo_shi_tomasi_resident"][1] and args[4] is ctypes.POINTER(ctypes.c_int32)
+    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "vo_shi_tomasi_resident_limit")
+
+
 def test_struct_layouts_match_header():
     from vo_mi355x import _lib
     assert ctypes.sizeof(_lib.KltParams) == 32 and ctypes.sizeof(_lib.StParams) == 40

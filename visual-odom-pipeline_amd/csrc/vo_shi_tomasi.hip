@@ -23,8 +23,8 @@
 #include <type_traits>
 
 #define ST_CAND_CAP 16384        // keys sorted in LDS (128 KB of the CU's 160 KB)
-#define ST_GLOBAL_CAP (1 << 18)  // NMS candidates kept per sequence in HBM; above ST_CAND_CAP the selection works on the
-                                 // ST_CAND_CAP strongest (radix select) and is exact whenever it fills max_corners
+#define ST_GLOBAL_CAP (1 << 18)  // NMS candidates kept per sequence in HBM; above ST_CAND_CAP the selection consumes them in rank-ordered
+                                 // chunks (radix select).  More RAW candidates than this is the one VO_E_CAPACITY exit of the selection
 #define ST_CAND_STRIDE (ST_GLOBAL_CAP + ST_CAND_CAP)   // raw list (conservative threshold) | staging of one rank-ordered chunk
 #define ST_OUT_CAP 4096
 #define ST_MAX_RADIUS 31
@@ -42,6 +42,7 @@ struct vo_st_ws {
   vo_dev<float> d_blockmax;        // per-workgroup masked maxima of the eigenvalue pass
   float* d_out = nullptr;          // ST_OUT_CAP x 2; in the ctx slab (d_slab)
   vo_dev<float> d_pts;             // uploaded cur_pts (non-resident call)
+  vo_dev<int32_t> d_limit;         // [batch] per-sequence corner limits of vo_shi_tomasi_resident_limit
   int n_blockmax = 0;
   int last_max_corners = 0;
 };
@@ -1074,6 +1075,7 @@ static int32_t st_init(vo_ctx* c, hipStream_t q) {
     VO_HIP(c, s.d_blockmax.reserve((size_t)s.n_blockmax * B));
     s.d_out = vo_slab<float>(c, c->off_st_out);
     VO_HIP(c, s.d_pts.reserve(2 * (size_t)c->max_pts * B));
+    VO_HIP(c, s.d_limit.reserve(B));
     VO_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_st_select<ST_CAP_CLOSED_LOOP>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)st_sel_lds(ST_CAP_CLOSED_LOOP)));
     VO_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_st_select<ST_CAND_CAP>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1126,6 +1128,11 @@ extern "C" int32_t vo_st_default_params(vo_st_params* p) {
 int32_t vo_st_check_params(vo_ctx* c, const vo_st_params* prm) {
   VO_CHECK(c, prm->fast_threshold >= 0 && prm->fast_threshold <= 254, VO_E_INVALID, "fast_threshold must be 0 (off) or 1..254");
   VO_CHECK(c, !(prm->fast_threshold > 0 && prm->use_harris), VO_E_INVALID, "fast_threshold and use_harris exclude each other");
+  // OpenCV asserts qualityLevel > 0 && minDistance >= 0 && maxCorners >= 0.  A quality level that is not positive (NaN, -0.0) gives a threshold
+  // whose key has the sign bit set, above every candidate's; a NaN distance compares false with everything
+  VO_CHECK(c, prm->quality_level > 0.0, VO_E_INVALID, "quality_level must be > 0");
+  VO_CHECK(c, prm->min_distance >= 0.0, VO_E_INVALID, "min_distance must be >= 0 (+inf is allowed)");
+  VO_CHECK(c, prm->max_corners >= 0, VO_E_INVALID, "max_corners must be >= 0 (0 = all, at most 4096)");
   return VO_OK;
 }
 
@@ -1235,7 +1242,9 @@ static int32_t st_launch(vo_ctx* c, hipStream_t q, const float* d_pts, size_t pt
   st_note_flags(c, prm, keep, d_user_mask != nullptr);
   const int use_dist = prm->min_distance >= 1.0 ? 1 : 0;
   // grid cell: >= min_distance (3x3 neighbourhood then covers the exclusion radius), coarse enough to fit LDS
-  int cell = use_dist ? (int)ceil(prm->min_distance) : 1;
+  // (in double, clamped before the cast: a distance of 2^31 or more, +inf included, is one cell over the whole image)
+  const double cell_d = use_dist ? fmin(ceil(prm->min_distance), (double)(W > H ? W : H)) : 1.0;
+  int cell = (int)cell_d;
   if (cell < 1) cell = 1;
   while (((W + cell - 1) / cell) * ((H + cell - 1) / cell) > ST_MAX_CELLS) cell++;
   const int gw = (W + cell - 1) / cell, gh = (H + cell - 1) / cell;
@@ -1266,7 +1275,7 @@ static int32_t st_fetch(vo_ctx* c, float* out_pts, int32_t* n_out) {
                              sizeof(float) * 2 * (size_t)mc, B, hipMemcpyDeviceToHost, c->stream));
   VO_HIP(c, hipStreamSynchronize(c->stream));
   for (int b = 0; b < B; b++) {
-    if (sc[4 * b + 2] == 0xFFFFFFFFu) { n_out[b] = 0; return vo_fail(c, VO_E_CAPACITY, "shi_tomasi: the strongest NMS candidates the selection holds (16384; 4096 with a device-side corner limit) did not yield max_corners corners, or more than 262144 candidates"); }
+    if (sc[4 * b + 2] == 0xFFFFFFFFu) { n_out[b] = 0; return vo_fail(c, VO_E_CAPACITY, "shi_tomasi: the NMS stage appended more than 262144 raw candidates for one sequence (the list the selection reads holds no more)"); }
     n_out[b] = (int32_t)sc[4 * b + 2];
   }
   return VO_OK;
@@ -1316,6 +1325,24 @@ int32_t vo_shi_tomasi_resident_counts(vo_ctx* c, hipStream_t q, int32_t n_cur, i
   const bool dev_limit = !c->tune.st_host_limit;                                                           // (vo_tuning: A/B, read per call -- tests compare both)
   return st_launch(c, q, vo_slab<const float>(c, vo_off_p(c)), c->slab_seq, n_cur, mask_radius, nullptr, prm, d_counts,
                    c->tune.st_keep_eig != 0, dev_limit ? d_limit : nullptr);
+}
+
+// limits [batch] (host): sequence b gets the first min(max(limits[b], 0), max_corners) corners of the unlimited call -- the closed loop's path
+// (k_st_select with a device-side limit, the short-chunk instance up to max_corners = 2048) as a call of its own
+extern "C" int32_t vo_shi_tomasi_resident_limit(vo_ctx* c, int32_t n_cur, int32_t mask_radius, const vo_st_params* prm, const int32_t* limits) {
+  if (!c) return VO_E_INVALID;
+  VO_CHECK(c, limits, VO_E_INVALID, "null limits");
+  VO_CHECK(c, n_cur >= 0 && n_cur <= c->n_resident, VO_E_INVALID, "n_cur exceeds the resident point set");
+  vo_st_params def;
+  if (!prm) { vo_st_default_params(&def); prm = &def; }
+  { const int32_t rc = vo_st_check_params(c, prm); if (rc != VO_OK) return rc; }                          // (before the upload: a refused call enqueues nothing)
+  VO_HIP(c, hipSetDevice(c->device));
+  { const int32_t rq = vo_quiesce_side(c); if (rq != VO_OK) return rq; }
+  const int32_t r = st_init(c, c->stream);
+  if (r != VO_OK) return r;
+  // (pageable source: the copy is staged before the call returns, so the caller's array need not outlive it)
+  VO_HIP(c, hipMemcpyAsync(c->st->d_limit, limits, sizeof(int32_t) * (size_t)c->batch, hipMemcpyHostToDevice, c->stream));
+  return vo_shi_tomasi_resident_counts(c, c->stream, n_cur, mask_radius, prm, c->d_pt_counts, c->st->d_limit);
 }
 
 extern "C" int32_t vo_shi_tomasi_fetch(vo_ctx* c, float* out_pts, int32_t* n_out) {

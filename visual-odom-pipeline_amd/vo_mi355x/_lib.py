@@ -252,6 +252,7 @@ SIGNATURES = {
     "vo_st_default_params": (C.c_int32, [C.POINTER(StParams)]),
     "vo_shi_tomasi": (C.c_int32, [_ctx, _f32p, C.c_int32, C.c_int32, _u8p, C.POINTER(StParams), _f32p, _i32p]),
     "vo_shi_tomasi_resident": (C.c_int32, [_ctx, C.c_int32, C.c_int32, C.POINTER(StParams)]),
+    "vo_shi_tomasi_resident_limit": (C.c_int32, [_ctx, C.c_int32, C.c_int32, C.POINTER(StParams), _i32p]),
     "vo_shi_tomasi_fetch": (C.c_int32, [_ctx, _f32p, _i32p]),
     "vo_shi_tomasi_read": (C.c_int32, [_ctx, _f32p, _u8p, _i32p]),
     "vo_triangulate_dlt": (C.c_int32, [_ctx, _f32p, _f32p, _f32p, _f32p, C.c_int32, _f32p, _f64p, _f64p, _f64p,

@@ -574,10 +574,16 @@ class VoContext:
                                        ptr(n_out, C.c_int32)))
         return self._corners(out, n_out)
 
-    def shi_tomasi_resident(self, n_cur, mask_radius=7, params=None):
+    def shi_tomasi_resident(self, n_cur, mask_radius=7, params=None, limit=None):
+        """limit: None, or a corner limit per sequence (an int for all of them, or [batch] ints): sequence b keeps the first
+        min(max(limit[b], 0), max_corners) corners of the unlimited call (vo_shi_tomasi_resident_limit, the closed loop's detection)"""
         prm = params if params is not None else self.st_params()
+        if limit is None:
+            self._ck(self._L.vo_shi_tomasi_resident(self._h, n_cur, int(mask_radius), C.byref(prm)))
+        else:
+            lim = np.ascontiguousarray(np.broadcast_to(np.asarray(limit, np.int32).reshape(-1), (self.batch,)))
+            self._ck(self._L.vo_shi_tomasi_resident_limit(self._h, n_cur, int(mask_radius), C.byref(prm), ptr(lim, C.c_int32)))
         self._st_max_corners = prm.max_corners
-        self._ck(self._L.vo_shi_tomasi_resident(self._h, n_cur, int(mask_radius), C.byref(prm)))
 
     def shi_tomasi_fetch(self):
         mc = self._st_max_corners if self._st_max_corners > 0 else 4096
