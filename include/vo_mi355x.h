@@ -899,6 +899,78 @@ int32_t vo_align_default_params(vo_align_params* p);
 int32_t vo_sparse_align(vo_ctx* ctx, const double* K, const float* pts3d, int32_t n, const double* rvec0, const double* tvec0,
                         const vo_align_params* prm, double* rvec, double* tvec, uint8_t* used_mask, vo_align_stats* stats);
 
+/* ---- recursive depth filter for track candidates ------------------------------------------------
+ * The reference turns a candidate corner into a landmark by waiting min_track_length frames and triangulating two views by DLT
+ * (extractor.py triangulate_tracks): a candidate carries no depth and no uncertainty while it waits, and the frames between the first and
+ * the last view are thrown away.  The complement of vo_sparse_align in semi-direct VO is the depth filter (Forster et al., SVO, ICRA 2014,
+ * V; dense: Pizzoli et al., REMODE, ICRA 2014): every candidate (a SEED) holds a Gaussian over the inverse distance mu along its bearing
+ * and a Beta(a, b) over its inlier ratio (Vogiatzis and Hernandez 2011), and every later frame with a known pose contributes one
+ * measurement.  The algorithm is defined by tests/depth_model.py, in short:
+ *   seed      pixel (u, v) of the reference frame, bearing f = normalize(K^-1 (u, v, 1)), a 10 x 10 u8 patch centred on
+ *             floor((u, v) + 0.5) (inner 8 x 8: offsets -4..3); mu = 1 / depth_mean, z_range = 1 / depth_min, sigma2 = z_range^2 / 36,
+ *             a = b = 10; a patch that leaves the image, or a pixel that is not finite: ok = 0 and the seed is flagged diverged
+ *   update    against the store's CURRENT frame under x_cur = R x_ref + t of the seed's ref_id.  The exits in order: inactive (a state
+ *             value not finite, sigma2 <= 0, mu <= 0, a flag set, (u, v) outside the image, ref_id outside the pose list, a pose entry
+ *             not finite or beyond 1e15); the segment A, B, C = pi(X(1 / (mu + s))), pi(X(1 / max(mu - s, 1e-8))), pi(X(1 / mu)) with
+ *             s = sqrt(sigma2), X(d) = (R f) d + t: one of them not in front: invisible; n_steps = ceil(max |B - A|) > max_steps: long;
+ *             candidates k = 0..n_steps at floor(A + k (B - A) / n_steps + 0.5), scored where the 10 x 10 patch is inside the image by
+ *             S = 64 sum (p - q)^2 - (sum p - sum q)^2 (64 x ZMSSD, exact); smallest S, ties to the smallest k; none scored:
+ *             invisible; S > 64 max_score: outlier; n_steps < 2: no search, from floor(C + 0.5).  Then 1-D inverse-compositional
+ *             Gauss-Newton on (offset along the segment, mean difference) with the aligner's bilinear form (det H not positive, leaving
+ *             the image or no convergence: outlier); triangulation of [R f, -f_cur] (d_ref, d_cur) = -t by its normal equations
+ *             (determinant below 1e-6 |t|^2 or d_ref <= 0: degenerate); the measurement noise tau from px_noise pixels by the law of
+ *             sines; the moment-matched Gaussian x Beta update.  An outlier is b += 1.  Converged: sqrt(sigma2) < z_range / conv_ratio;
+ *             diverged: a / (a + b) < min_inlier; a flagged seed is inactive from the next call on
+ * The reference patch is not warped: the filter is for the short baselines of consecutive frames, as in REMODE.  Level 0 only.
+ * The per-pixel alignment arithmetic and its 64-pixel sums are float32 in a fixed order, everything else float64: a result does not
+ * depend on the batch position or on the call.  Against the model the kernel is held to 4 x what the model's own float32 switch moves
+ * each output (tests/test_gpu_depth.py).  One wave per seed, every sequence in one launch on the front-end stream; both calls are
+ * synchronous like vo_klt_track.
+ * vo_depth_seed_init: uv [batch][n][2] f32, depth_mean / depth_min [batch]; reads the store's current frame; seeds [batch][n],
+ * patches [batch][n][100] u8, ok_mask [batch][n] u8 (may be NULL) come back.
+ * vo_depth_update: K [batch][9] row-major; poses [batch][n_ref][6] (rvec, tvec as vo_pnp_ransac); seeds [batch][n] in and out;
+ * result [batch][n] u8 (VO_DEPTH_*), match_uv [batch][n][2] f32 (where the seed is in the current frame: the best candidate of an
+ * outlier without a match, else the last alignment step; NaN where none was reached), z [batch][n] f64 (the triangulated distance, else
+ * NaN), stats [batch]; prm NULL = the defaults; result, match_uv, z and stats may be NULL.
+ * Errors, nothing enqueued: no frame pushed or a step in flight: VO_E_STATE; n > max_pts: VO_E_CAPACITY; VO_E_INVALID for n < 0, a NULL
+ * required pointer, n_ref < 1, max_steps outside 1..128, max_iters < 1, max_score outside 0..4161600, an eps_align, px_noise,
+ * conv_ratio or min_inlier that is not finite or is negative, conv_ratio = 0 (every seed would be converged), a depth_mean or depth_min
+ * that is not finite and positive.  A ref_id outside 0..n_ref - 1 is the seed's VO_DEPTH_SKIP_INACTIVE, not an error.
+ * The three structures have no hidden padding: 32, 56 and 40 bytes. */
+typedef struct {
+  int32_t max_steps;         /* 128: the longest segment searched, in pixels (1..128) */
+  int32_t max_iters;         /* 10: alignment iterations */
+  int32_t max_score;         /* 300 * 64: the largest ZMSSD sum of a match, here an rms of 17 grey levels (0..4161600).  SVO's 2000 per pixel
+                                is for warped patches over wide baselines; without a warp it admits half-covered patches (EXPERIMENTS.md) */
+  float   eps_align;         /* 0.03 pixels */
+  float   px_noise;          /* 1 pixel */
+  float   conv_ratio;        /* 200 */
+  float   min_inlier;        /* 0.1 */
+  int32_t reserved;          /* 0 */
+} vo_depth_params;
+
+enum { VO_DEPTH_UPDATED = 0, VO_DEPTH_OUTLIER_NOMATCH = 1, VO_DEPTH_OUTLIER_ALIGN = 2, VO_DEPTH_SKIP_INVISIBLE = 3, VO_DEPTH_SKIP_LONG = 4,
+       VO_DEPTH_SKIP_DEGENERATE = 5, VO_DEPTH_SKIP_INACTIVE = 6 };
+/* vo_depth_seed.flags: the two flags, and from bit VO_DEPTH_OBS_SHIFT on the number of measurements (updates and outliers) taken */
+enum { VO_DEPTH_CONVERGED = 1, VO_DEPTH_DIVERGED = 2, VO_DEPTH_OBS_SHIFT = 8 };
+typedef struct {
+  double  mu, sigma2, a, b, z_range;
+  float   u, v;
+  int32_t ref_id;
+  int32_t flags;
+} vo_depth_seed;
+typedef struct {
+  int32_t counts[7];         /* seeds per result code of this call */
+  int32_t converged;         /* seeds flagged converged after it */
+  int32_t diverged;
+  int32_t reserved;
+} vo_depth_stats;
+int32_t vo_depth_default_params(vo_depth_params* p);
+int32_t vo_depth_seed_init(vo_ctx* ctx, const float* uv, int32_t n, const double* depth_mean, const double* depth_min, int32_t ref_id,
+                           vo_depth_seed* seeds, uint8_t* patches, uint8_t* ok_mask);
+int32_t vo_depth_update(vo_ctx* ctx, const double* K, const double* poses, int32_t n_ref, vo_depth_seed* seeds, const uint8_t* patches,
+                        int32_t n, const vo_depth_params* prm, uint8_t* result, float* match_uv, double* z, vo_depth_stats* stats);
+
 /* ---- SIFT features (SURVEY.md 8f "next" row 4, feature part) -----------------------------------
  * Replaces cv2.SIFT_create(nfeatures=1000).detect(img, mask) + .compute(img, kps) in
  * Extractor.extract(detector='custom', describe=True) (src/extractor/extractor.py:26-28, 114-122; the two bootstrap
@@ -1289,14 +1361,15 @@ int32_t vo_step_layout(vo_ctx* ctx, int32_t* layout, int32_t* gate_groups, int32
  * VO_PROF_HPOSE brackets the k_hpose launch of vo_homography_decompose and vo_homography_pose (tools/hpose_timing.py).
  * VO_PROF_SIM3_SOLVE / _SCORE / _SELECT / _FINISH bracket the k_s3_solve / k_s3_score / k_s3_select launch of every round of
  * vo_sim3_ransac and the k_s3_finish launch of vo_sim3_ransac and vo_sim3_fit (tools/sim3_timing.py).
- * VO_PROF_ALIGN brackets each k_align_level launch of vo_sparse_align, one per level (tools/align_timing.py). */
+ * VO_PROF_ALIGN brackets each k_align_level launch of vo_sparse_align, one per level (tools/align_timing.py).
+ * VO_PROF_DEPTH brackets the k_depth_update launch of vo_depth_update (tools/depth_timing.py). */
 enum { VO_PROF_FRAME = 0, VO_PROF_KLT = 1, VO_PROF_ST = 2, VO_PROF_DLT = 3, VO_PROF_BA = 4, VO_PROF_CLAHE_LUT = 5, VO_PROF_CLAHE_APPLY = 6,
        VO_PROF_HOM_SOLVE = 7, VO_PROF_HOM_SCORE = 8, VO_PROF_HOM_SELECT = 9, VO_PROF_HOM_FINISH = 10, VO_PROF_ORB_PYRAMID = 11,
        VO_PROF_ORB_CANDIDATES = 12, VO_PROF_ORB_RETAIN = 13, VO_PROF_ORB_DESCRIBE = 14,
        VO_PROF_FUND_SOLVE = 15, VO_PROF_FUND_SCORE = 16, VO_PROF_FUND_SELECT = 17, VO_PROF_FUND_FINISH = 18,
        VO_PROF_GMATCH_FORWARD = 19, VO_PROF_GMATCH_REVERSE = 20, VO_PROF_GMATCH_ACCEPT = 21, VO_PROF_HPOSE = 22,
        VO_PROF_SIM3_SOLVE = 23, VO_PROF_SIM3_SCORE = 24, VO_PROF_SIM3_SELECT = 25, VO_PROF_SIM3_FINISH = 26,
-       VO_PROF_ALIGN = 27, VO_PROF_COUNT = 28 };
+       VO_PROF_ALIGN = 27, VO_PROF_DEPTH = 28, VO_PROF_COUNT = 29 };
 int32_t vo_profile_enable(vo_ctx* ctx, int32_t region_mask);
 int32_t vo_profile_read(vo_ctx* ctx, int32_t region, double* total_ms, int32_t* count);
 /* diagnostic: shader-clock stamps (s_memtime deltas, cycles) of the phases of the last launch of a

@@ -356,6 +356,7 @@ extern "C" int32_t vo_ctx_destroy(vo_ctx* c) {
   vo_hpose_destroy(c);
   vo_sim3_destroy(c);
   vo_align_destroy(c);
+  vo_depth_destroy(c);
   vo_match_destroy(c);
   vo_sift_destroy(c);
   vo_st_destroy(c);

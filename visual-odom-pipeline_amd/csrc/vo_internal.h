@@ -163,6 +163,7 @@ struct vo_ctx {
   struct vo_hpose_ws* hpose = nullptr; // pose-from-homography workspace (vo_hpose.hip)
   struct vo_sim3_ws* sim3 = nullptr; // Sim(3) / rigid 3D-3D alignment workspace (vo_sim3.hip)
   struct vo_align_ws* align = nullptr; // sparse image alignment workspace (vo_align.hip)
+  struct vo_depth_ws* depth = nullptr; // depth filter workspace (vo_depth.hip)
   struct vo_trk_ws* trk = nullptr;   // device-resident track table (vo_tracks.hip)
   struct vo_pipe_ws* pipe = nullptr; // closed-loop Pipeline.step on the device (vo_pipeline.hip)
   const int32_t* d_pt_counts = nullptr;   // vo_tracks_* only (set by vo_tracks_seed, cleared by vo_trk_destroy): per-sequence number of live tracks the
@@ -414,6 +415,7 @@ void vo_fund_destroy(vo_ctx* c);
 void vo_hpose_destroy(vo_ctx* c);
 void vo_sim3_destroy(vo_ctx* c);
 void vo_align_destroy(vo_ctx* c);
+void vo_depth_destroy(vo_ctx* c);
 // vo_homography_ransac with work enqueued behind k_h4_finish on the same stream, in front of the one read-back (vo_homography_pose):
 // `enqueue` gets the search's device buffers -- points [batch][2][cap][2], the refined H of sequence b at d_H + b * h_stride (NaN
 // without a model), the winner's mask [batch][cap] -- and what it copies to pinned memory on q is complete when the call returns

@@ -137,6 +137,29 @@ class AlignStats(C.Structure):
                 ("chi2", C.c_float), ("zbar", C.c_float)]
 
 
+class DepthParams(C.Structure):
+    """vo_depth_params (32 bytes)"""
+    _fields_ = [("max_steps", C.c_int32), ("max_iters", C.c_int32), ("max_score", C.c_int32), ("eps_align", C.c_float), ("px_noise", C.c_float),
+                ("conv_ratio", C.c_float), ("min_inlier", C.c_float), ("reserved", C.c_int32)]
+
+
+class DepthSeed(C.Structure):
+    """vo_depth_seed (56 bytes); DEPTH_SEED_DTYPE is the same row as a numpy structured type"""
+    _fields_ = [("mu", C.c_double), ("sigma2", C.c_double), ("a", C.c_double), ("b", C.c_double), ("z_range", C.c_double), ("u", C.c_float),
+                ("v", C.c_float), ("ref_id", C.c_int32), ("flags", C.c_int32)]
+
+
+class DepthStats(C.Structure):
+    """vo_depth_stats (40 bytes)"""
+    _fields_ = [("counts", C.c_int32 * 7), ("converged", C.c_int32), ("diverged", C.c_int32), ("reserved", C.c_int32)]
+
+
+DEPTH_SEED_DTYPE = [("mu", "<f8"), ("sigma2", "<f8"), ("a", "<f8"), ("b", "<f8"), ("z_range", "<f8"), ("u", "<f4"), ("v", "<f4"),
+                    ("ref_id", "<i4"), ("flags", "<i4")]
+DEPTH_RESULTS = ("UPDATED", "OUTLIER_NOMATCH", "OUTLIER_ALIGN", "SKIP_INVISIBLE", "SKIP_LONG", "SKIP_DEGENERATE", "SKIP_INACTIVE")     # VO_DEPTH_*
+DEPTH_CONVERGED, DEPTH_DIVERGED, DEPTH_OBS_SHIFT = 1, 2, 8
+
+
 class HposeParams(C.Structure):
     _fields_ = [("ratio", C.c_double), ("threshold", C.c_double), ("hint", C.c_double * 3), ("min_off", C.c_int32), ("use_hint", C.c_int32)]
 
@@ -309,6 +332,10 @@ SIGNATURES = {
     "vo_sim3_fit": (C.c_int32, [_ctx, _f32p, _f32p, _u8p, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, C.POINTER(Sim3Stats)]),
     "vo_align_default_params": (C.c_int32, [C.POINTER(AlignParams)]),
     "vo_sparse_align": (C.c_int32, [_ctx, _f64p, _f32p, C.c_int32, _f64p, _f64p, C.POINTER(AlignParams), _f64p, _f64p, _u8p, C.POINTER(AlignStats)]),
+    "vo_depth_default_params": (C.c_int32, [C.POINTER(DepthParams)]),
+    "vo_depth_seed_init": (C.c_int32, [_ctx, _f32p, C.c_int32, _f64p, _f64p, C.c_int32, C.POINTER(DepthSeed), _u8p, _u8p]),
+    "vo_depth_update": (C.c_int32, [_ctx, _f64p, _f64p, C.c_int32, C.POINTER(DepthSeed), _u8p, C.c_int32, C.POINTER(DepthParams), _u8p, _f32p, _f64p,
+                                    C.POINTER(DepthStats)]),
     "vo_sift_detect_compute": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32, C.POINTER(SiftKp), _f32p, _i32p]),
     "vo_orb_default_params": (C.c_int32, [C.POINTER(OrbParams)]),
     "vo_orb_detect_compute": (C.c_int32, [_ctx, _u8p, C.c_int32, _u8p, C.POINTER(OrbParams), _i8p, C.c_int32, C.POINTER(OrbKp), _u8p, _i32p]),

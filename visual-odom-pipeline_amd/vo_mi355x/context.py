@@ -12,10 +12,39 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AlignParams, AlignStats, BaParams, BaStats, BriefParams, EssParams, EssStats, FundParams, FundStats, GMatchParams, HomParams, HomStats, HposeParams, HposeStats, KltParams, OrbKp, OrbParams, SiftKp, PnpParams, PnpStats, Sim3Params, Sim3Stats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
+from ._lib import AlignParams, AlignStats, BaParams, BaStats, BriefParams, DepthParams, DepthSeed, DepthStats, EssParams, EssStats, FundParams, FundStats, GMatchParams, HomParams, HomStats, HposeParams, HposeStats, KltParams, OrbKp, OrbParams, SiftKp, PnpParams, PnpStats, Sim3Params, Sim3Stats, StParams, SubpixParams, Tuning, VoError, as_c, ptr
 
 # vo_set_klt_predict modes (include/vo_mi355x.h)
 KLT_PREDICT_MODES = {"off": 0, "constant_velocity": 1}
+
+
+class DepthSeeds:
+    """What VoContext.depth_seeds returns and depth_update updates: seeds, a structured array of vo_depth_seed rows (mu, sigma2, a, b,
+    z_range, u, v, ref_id, flags); patches (.., 100) u8, the 10 x 10 reference patches; ok (..,) bool, False where no patch could be cut.
+    Extractor.init_seeds adds H_ref, the list of 4x4 reference poses ref_id indexes, and kps, the candidate keypoints; update_seeds K"""
+
+    def __init__(self, seeds, patches, ok, H_ref=None, kps=None, K=None):
+        self.seeds, self.patches, self.ok, self.H_ref, self.kps, self.K = seeds, patches, ok, H_ref, kps, K
+
+    def __len__(self):
+        return self.seeds.shape[-1]
+
+    @property
+    def converged(self):
+        return (self.seeds["flags"] & _lib.DEPTH_CONVERGED) != 0
+
+    @property
+    def diverged(self):
+        return (self.seeds["flags"] & _lib.DEPTH_DIVERGED) != 0
+
+    @property
+    def observations(self):
+        return self.seeds["flags"] >> _lib.DEPTH_OBS_SHIFT
+
+    @property
+    def depth_sigma(self):
+        """the standard deviation of each seed's distance along its bearing: sqrt(sigma2) / mu^2"""
+        return np.sqrt(self.seeds["sigma2"]) / self.seeds["mu"] ** 2
 
 
 class VoContext:
@@ -775,6 +804,7 @@ class VoContext:
     PROF_HPOSE = 22
     PROF_SIM3_SOLVE, PROF_SIM3_SCORE, PROF_SIM3_SELECT, PROF_SIM3_FINISH = range(23, 27)
     PROF_ALIGN = 27
+    PROF_DEPTH = 28
 
     def profile_enable(self, regions=(0, 1, 2, 3, 4)):
         """regions: iterable of PROF_* ids to time with hipEvent pairs on the ctx stream; () switches timing off"""
@@ -1255,6 +1285,54 @@ class VoContext:
         stats = [dict(status=s.status, n_used=s.n_used, levels_run=s.levels_run, flags=s.flags, iters=list(s.iters), chi2=s.chi2, zbar=s.zbar)
                  for s in st]
         return self._out(rv), self._out(tv), self._out(mask != 0), self._out(stats)
+
+    def depth_params(self, max_steps=128, max_iters=10, max_score=300 * 64, eps_align=0.03, px_noise=1.0, conv_ratio=200.0, min_inlier=0.1):
+        """vo_depth_params: max_steps the longest epipolar segment searched (pixels, 1..128); max_score the largest ZMSSD sum of a match;
+        eps_align / px_noise in pixels; converged at sqrt(sigma2) < z_range / conv_ratio, diverged at a / (a + b) < min_inlier"""
+        p = DepthParams()
+        self._L.vo_depth_default_params(C.byref(p))
+        p.max_steps, p.max_iters, p.max_score = int(max_steps), int(max_iters), int(max_score)
+        p.eps_align, p.px_noise, p.conv_ratio, p.min_inlier = eps_align, px_noise, conv_ratio, min_inlier
+        return p
+
+    def depth_seeds(self, uv, depth_mean, depth_min, ref_id=0):
+        """Depth-filter seeds at the pixels uv (n,2) of the store's CURRENT frame (vo_depth_seed_init; the algorithm:
+        tests/depth_model.py): inverse distance 1 / depth_mean with a standard deviation of a sixth of 1 / depth_min, and the 10 x 10
+        patches around the pixels.  depth_mean, depth_min: scalars (or (batch,)); ref_id: the row of depth_update's poses the seeds
+        refer to [leading batch dim if batch > 1] -> DepthSeeds (.seeds a structured array (n,), .patches (n,100) u8, .ok (n,) bool:
+        False where the patch leaves the image or the pixel is not finite; such a seed is flagged diverged)"""
+        B = self.batch
+        p = np.ascontiguousarray(uv, np.float32).reshape(B, -1, 2)
+        n = p.shape[1]
+        dm = np.ascontiguousarray(np.broadcast_to(np.asarray(depth_mean, np.float64).reshape(-1), (B,)))
+        dn = np.ascontiguousarray(np.broadcast_to(np.asarray(depth_min, np.float64).reshape(-1), (B,)))
+        seeds = np.zeros((B, n), _lib.DEPTH_SEED_DTYPE)
+        patches, ok = np.zeros((B, n, 100), np.uint8), np.zeros((B, n), np.uint8)
+        self._ck(self._L.vo_depth_seed_init(self._h, ptr(p, C.c_float), n, ptr(dm, C.c_double), ptr(dn, C.c_double), int(ref_id),
+                                            seeds.ctypes.data_as(C.POINTER(DepthSeed)), ptr(patches, C.c_uint8), ptr(ok, C.c_uint8)))
+        return DepthSeeds(self._out(seeds), self._out(patches), self._out(ok != 0))
+
+    def depth_update(self, K, poses, seeds, params=None):
+        """One depth-filter update of `seeds` (a DepthSeeds) against the store's CURRENT frame (vo_depth_update): a patch search along each
+        seed's epipolar segment, sub-pixel alignment, triangulation and the Gaussian x Beta update.  K (3,3); poses (n_ref,6) rvec, tvec
+        of x_cur = R x_ref + t, row seeds['ref_id'] for each seed [leading batch dim if batch > 1].  seeds.seeds is updated in place
+        -> result (n,) u8 (an index into DEPTH_RESULTS), match_uv (n,2) f32, z (n,) f64 (NaN where there is none), stats dict (counts
+        by result name, converged, diverged; a list of them if batch > 1)"""
+        B = self.batch
+        Kc = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (B, 3, 3)))
+        po = np.ascontiguousarray(poses, np.float64).reshape(B, -1, 6)
+        s = seeds.seeds.reshape(B, -1)
+        if not (s.flags["C_CONTIGUOUS"] and s.flags["WRITEABLE"] and np.shares_memory(s, seeds.seeds)):
+            raise ValueError("seeds.seeds must be a contiguous, writable array")
+        n = s.shape[1]
+        pt = np.ascontiguousarray(seeds.patches, np.uint8).reshape(B, n, 100)
+        prm = params if params is not None else self.depth_params()
+        res, match, z = np.zeros((B, n), np.uint8), np.zeros((B, n, 2), np.float32), np.zeros((B, n))
+        st = (DepthStats * B)()
+        self._ck(self._L.vo_depth_update(self._h, ptr(Kc, C.c_double), ptr(po, C.c_double), po.shape[1], s.ctypes.data_as(C.POINTER(DepthSeed)),
+                                         ptr(pt, C.c_uint8), n, C.byref(prm), ptr(res, C.c_uint8), ptr(match, C.c_float), ptr(z, C.c_double), st))
+        stats = [dict(dict(zip(_lib.DEPTH_RESULTS, list(x.counts))), converged=x.converged, diverged=x.diverged) for x in st]
+        return self._out(res), self._out(match), self._out(z), self._out(stats)
 
     def pnp_params(self, reproj_err=2.0, confidence=0.9999, max_iters=1000000, seed=0):
         prm = PnpParams()

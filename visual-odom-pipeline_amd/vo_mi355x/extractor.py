@@ -652,6 +652,76 @@ class Extractor:
             uv = np.stack([K[0, 0] * Y[:, 0] / z + K[0, 2], K[1, 1] * Y[:, 1] / z + K[1, 2]], 1)
         return uv.astype(np.float32)
 
+    # -- the depth filter: candidates that carry a depth and its uncertainty while they wait ---------------------------------------
+    def init_seeds(self, candidates, H_ref, depth_mean=None, depth_min=None, landmarks=None, im_ref=None):
+        """Depth-filter seeds (VoContext.depth_seeds; the algorithm: tests/depth_model.py) for the candidate keypoints at their newest
+        positions in the reference frame im_ref (None: _im_prev, the frame extend_tracks saw last), whose pose is H_ref (4x4,
+        x_cam = H x_world).  depth_mean / depth_min: the prior, scene depths; None: the mean and the smallest depth of `landmarks` in
+        that camera.  -> DepthSeeds that remember H_ref and the candidates; update_seeds moves them, seed_landmarks reads them."""
+        im_ref = self._im_prev if im_ref is None else im_ref
+        if im_ref is None:
+            raise RuntimeError("init_seeds needs the reference frame: pass im_ref=, or track a frame first")
+        if depth_mean is None or depth_min is None:
+            if not landmarks:
+                raise ValueError("init_seeds needs depth_mean and depth_min, or landmarks to take them from")
+            z = self._points_in_camera(H_ref, landmarks)[:, 2]
+            z = z[z > 0]
+            if not len(z):
+                raise ValueError("init_seeds: no landmark in front of the reference camera")
+            depth_mean = float(z.mean()) if depth_mean is None else depth_mean
+            depth_min = float(z.min()) if depth_min is None else depth_min
+        self._plain("init_seeds", im_ref)
+        self._ensure_cur(np.ascontiguousarray(im_ref, np.uint8))
+        uv = np.array([np.asarray(k.uv, np.float64).reshape(2) for k in candidates], np.float32).reshape(-1, 2)
+        s = self._ctx.depth_seeds(uv, depth_mean, depth_min, ref_id=0)
+        s.H_ref, s.kps = [np.array(H_ref, np.float64)], list(candidates)
+        return s
+
+    def update_seeds(self, K, seeds, H_cur, im_curr=None, **params):
+        """One depth-filter update (VoContext.depth_update) of `seeds` against im_curr (None: the frame the store holds) under its pose
+        H_cur (4x4, from align_frame, camera_pose or the bundle adjustment); the relative poses H_cur H_ref^-1 are formed in float64 on
+        the host.  params: VoContext.depth_params' keywords.  seeds are updated in place -> (result (n,) u8, match_uv (n,2), z (n,),
+        stats dict), as VoContext.depth_update"""
+        from .so3 import rodrigues_mat_to_vec
+        if im_curr is not None:
+            self._plain("update_seeds", im_curr)
+            self._ensure_cur(np.ascontiguousarray(im_curr, np.uint8))
+        H_cur = np.asarray(H_cur, np.float64)
+        poses = np.zeros((len(seeds.H_ref), 6))
+        for r, H_ref in enumerate(seeds.H_ref):
+            T = H_cur @ np.linalg.inv(H_ref)
+            poses[r, :3], poses[r, 3:] = np.asarray(rodrigues_mat_to_vec(T[:3, :3])).reshape(3), T[:3, 3]
+        seeds.K = np.array(K, np.float64).reshape(3, 3)
+        return self._ctx.depth_update(K, poses, seeds, self._ctx.depth_params(**params))
+
+    def seed_landmarks(self, seeds, which="converged", K=None, t_curr=None):
+        """The seeds that have converged (which="converged"; "active": every seed not flagged diverged; or a boolean mask) as Landmarks
+        in world coordinates, H_ref^-1 (f / mu), with their Keypoints -- shaped like triangulate_tracks' output, so a caller appends them
+        where it appends those.  K: None = the intrinsics update_seeds saw last; t_curr: the landmarks' t_latest (None: each
+        keypoint's newest frame).  -> (landmarks, their keypoints, the remaining candidates' keypoints).  seeds.depth_sigma holds
+        the standard deviation of each seed's distance along its bearing"""
+        K = seeds.K if K is None else K
+        if K is None:
+            raise ValueError("seed_landmarks needs K: no update_seeds call has given one yet")
+        K = np.asarray(K, np.float64).reshape(3, 3)
+        sd = seeds.seeds
+        if isinstance(which, str):
+            pick = {"converged": seeds.converged & ~seeds.diverged, "active": ~seeds.diverged}[which]
+        else:
+            pick = np.asarray(which, bool)
+        rows = np.nonzero(pick)[0]
+        x, y = (sd["u"][rows].astype(np.float64) - K[0, 2]) / K[0, 0], (sd["v"][rows].astype(np.float64) - K[1, 2]) / K[1, 1]
+        f = np.stack([x, y, np.ones(len(rows))], 1) / np.sqrt(x * x + y * y + 1.0)[:, None]
+        Xc = f / sd["mu"][rows][:, None]
+        P = np.empty((len(rows), 3))
+        for r in range(len(seeds.H_ref)):
+            m = sd["ref_id"][rows] == r
+            Hi = np.linalg.inv(seeds.H_ref[r])
+            P[m] = Xc[m] @ Hi[:3, :3].T + Hi[:3, 3]
+        kps = [seeds.kps[i] for i in rows]
+        lms = [Landmark(k.t_first + k.t_total - 1 if t_curr is None else t_curr, P[i].reshape(3, 1).copy(), k.des) for i, k in enumerate(kps)]
+        return lms, kps, [k for i, k in enumerate(seeds.kps) if not pick[i]]
+
     def bootstrap_check(self, K, list_1, list_2, threshold=1.0, max_h_ratio=0.8, seed=0):
         """Is this frame pair fit for the 2D-2D bootstrap?  One essential_ransac and one find_homography call at the same pixel threshold;
         -> dict e_inliers, h_inliers, h_ratio = h_inliers / max(e_inliers, 1), degenerate = h_ratio > max_h_ratio (COLMAP's
